@@ -301,6 +301,69 @@ class HostGather:
             pass
 
 
+DUMP_LIMIT = 64 << 20                                           # --dump-outputs: bytes of all .npy payloads together
+DUMP_SAMPLE = 1 << 21                                           # sampled output bytes (float32) and their positions (float64): 24 MiB
+DUMP_BLOCK = 1 << 20                                            # one checksum per MiB of output
+
+
+def _seeded_positions(n: int, k: int, seed: int):
+    """k sorted positions in [0, n), fixed by (n, k, seed): every position when n <= k."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=k, dtype=np.int64))
+
+
+def dump_outputs(out_dir: str, torch, parts, entry_off=None) -> dict:
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as .npy files in `out_dir`.  `parts` are the output's
+    uint8 tensors in archive order (one per gathered piece), `entry_off` the entry offsets a --framing none caller receives.  The output itself
+    can be GiBs, so it is written as
+      output_bytes.npy        float64 [1]       its length in bytes
+      output_block_sums.npy   float64 [blocks]  per MiB of output (each part on its own): sum over the block of (i + 1) * byte[i], exact in float64
+      output_sample_pos.npy   float64 [k]       positions of a seeded sample of the output (all of it when it is small)
+      output_sample.npy       float32 [k]       the bytes at those positions
+      entry_offsets.npy       float64 [n + 1]   --framing none only (a seeded sample of them past DUMP_SAMPLE entries, with entry_offsets_pos.npy)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = [int(p.numel()) for p in parts]
+    total = sum(sizes)
+    arrays = {"output_bytes": np.array([total], dtype=np.float64)}
+    w = torch.arange(1, DUMP_BLOCK + 1, dtype=torch.int64, device=parts[0].device) if parts else None
+    sums = []
+    for p in parts:
+        for lo in range(0, p.numel(), 16 * DUMP_BLOCK):       # 16 MiB at a time: the int64 products stay at 128 MiB
+            x = p[lo:lo + 16 * DUMP_BLOCK]
+            pad = -x.numel() % DUMP_BLOCK
+            if pad:
+                x = torch.cat([x, torch.zeros(pad, dtype=torch.uint8, device=x.device)])
+            sums.append((x.view(-1, DUMP_BLOCK).to(torch.int64) * w).sum(1).cpu().numpy())
+    arrays["output_block_sums"] = (np.concatenate(sums) if sums else np.zeros(0)).astype(np.float64)
+    pos = _seeded_positions(total, DUMP_SAMPLE, 1)
+    starts = np.cumsum([0] + sizes)
+    part_of = np.searchsorted(starts, pos, side="right") - 1
+    sample = np.empty(pos.size, dtype=np.float32)
+    for i, p in enumerate(parts):
+        sel = np.nonzero(part_of == i)[0]
+        if sel.size:
+            idx = torch.from_numpy(pos[sel] - starts[i]).to(p.device)
+            sample[sel] = p.index_select(0, idx).cpu().numpy().astype(np.float32)
+    arrays["output_sample_pos"] = pos.astype(np.float64)
+    arrays["output_sample"] = sample
+    if entry_off is not None:
+        eo = np.asarray(entry_off, dtype=np.float64)
+        if eo.size > DUMP_SAMPLE:
+            epos = _seeded_positions(eo.size, DUMP_SAMPLE, 2)
+            arrays["entry_offsets_pos"] = epos.astype(np.float64)
+            eo = eo[epos]
+        arrays["entry_offsets"] = eo
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {nbytes} bytes exceed the {DUMP_LIMIT} byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": nbytes}
+
+
 def launch_ranks(n: int, argv) -> int:
     """`python bench.py --gpus N` without a launcher: run the N ranks as children of this process through torch.distributed.run (the very command the
     driver uses), on a free port of 127.0.0.1.  Nothing here touches the GPU -- a process that has initialised HIP must not exec or fork GPU users --;
@@ -373,7 +436,12 @@ def main() -> None:
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)         # launch mechanics only (tests; no GPU)
     ap.add_argument("--launch-check-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-sample-mib", type=int, default=0, help="CPU baseline sample per core in MiB (0 = 256 zstd / 48 deflate; --solid: 1024 zstd / 192 deflate in all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: the whole archive / streams) as DIR/<name>.npy: "
+                         "its length, per-MiB checksums and a seeded sample of its bytes (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -429,6 +497,8 @@ def main() -> None:
     pieces = args.gather_pieces or (2 if world > 1 else 1)
     if args.framing != "archive" or pieces < 1 or n_files % pieces:
         pieces = 1
+    if args.dump_outputs and world == 1 and pieces > 2:
+        ap.error("--dump-outputs at one GPU needs --gather-pieces <= 2 (the two output buffers hold the last step's pieces)")
     n_piece = n_files // pieces
     shard = importlib.import_module("portable-network-archive_amd.shard")
     first_file = [lo for lo, _ in shard.piece_ranges(rank, world, pieces, n_piece)]
@@ -520,9 +590,12 @@ def main() -> None:
 
     lz_acc = [0.0, 0.0, 0.0, 0]                             # LZ stage ms, all stages ms, match-kernel ms, match-kernel launches
 
+    last_out = []                                             # (buffer, bytes, entry offsets) of every piece of the latest step: --dump-outputs
+
     def step():
         total_all = 0
         host_pos[0] = 0
+        last_out.clear()
         for h in range(pieces):
             b = cur[0]
             finish_gather(b)                                  # the gather that used this buffer two pieces ago
@@ -533,7 +606,9 @@ def main() -> None:
             elif args.framing == "solid":
                 total = ctx.create_solid_archive_device(names, src.data_ptr(), src_off, src_len, dst.data_ptr(), dst_cap, algo=algo, _cache=arg_cache[0], level=lvl)
             else:
-                total = ctx.compress_batch_device(src.data_ptr(), src_off, src_len, dst.data_ptr(), dst_cap, algo=algo, level=lvl)[-1]
+                dst_off = ctx.compress_batch_device(src.data_ptr(), src_off, src_len, dst.data_ptr(), dst_cap, algo=algo, level=lvl)
+                total = dst_off[-1]
+            last_out.append((b, total, dst_off if args.framing == "none" else None))
             tm = ctx.timing()
             lz_acc[0] += tm.ms_lz
             lz_acc[2] += tm.ms_lz_match
@@ -593,6 +668,14 @@ def main() -> None:
         step()
     dt, out_total = timed(args.steps)
     lz_ms, stage_ms, lzm_ms, lzm_launches = lz_acc
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below reuses the output buffers; N > 1: the archive as gathered on rank 0, else this process' buffers
+        if world > 1 and args.framing == "archive":
+            parts = [gather_out[h][:sum(piece_sizes[h])] for h in range(pieces)]
+        else:
+            parts = [dsts[b][:total] for b, total, _ in last_out]
+        dumped = dump_outputs(args.dump_outputs, torch, parts, last_out[0][2] if args.framing == "none" else None)
     if world > 1:
         o = torch.tensor([out_total], dtype=torch.int64, device=xdev)
         dist.all_reduce(o)
@@ -763,6 +846,8 @@ def main() -> None:
                               "GB_per_s": round(out_total / pieces / max(tm.ms_cipher, 1e-9) / 1e6, 1)}
         if gather_compare is not None:
             line["gather_compare"] = gather_compare
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if e2e is not None:
             line["end_to_end"] = e2e
         if world == 1 and not args.no_cpu_baseline:
