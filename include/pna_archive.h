@@ -46,7 +46,8 @@ void pna_archive_abort(pna_archive *a);
 
 /* pna create, non-solid or solid (cli/src/command/create.rs:575-635): compress the n entries on the GPU in one
  * batch (entry-parallel, like spawn_entry_results), then write them in index order.  algo PNA_ALGO_STORE works
- * without a GPU (ctx may be NULL). */
+ * without a GPU (ctx may be NULL).  solid, zstd or deflate: pna_gpu_create_solid_archive_host, which streams the
+ * inner entries to the device in windows -- bounded page-locked memory, inner entries of any size. */
 int  pna_create_archive(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
                         const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user);
 

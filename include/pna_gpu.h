@@ -271,11 +271,12 @@ int  pna_gpu_create_solid_archive_enc_device(pna_gpu_ctx *ctx, int algo, int lev
                                              const pna_gpu_cipher *cipher, void *d_dst, size_t dst_cap, uint64_t *archive_len,
                                              void *hip_stream);
 
-/* The same from host memory.  zstd: STREAMING, as SolidArchive::add_entry feeds its one encoder (lib/src/archive/write.rs:575-580): the serialised inner
- * entries reach the device in windows of `solid_win_mib` MiB (256) through two page-locked slots each way -- about four windows of page-locked memory
- * whatever the archive's size --, the sink receives the head, one piece per window, the tail; inner entries of ANY size (FDAT chunks of at most
- * 2^32 - 5 bytes, FlattenWriter's cut, lib/src/util/io.rs:60-77).  The bytes equal pna_gpu_create_solid_archive_device's.  deflate (one zlib stream
- * with one Adler-32) and option single_frame: the whole stream in flight at once, inner entries below 2 GiB. */
+/* The same from host memory, STREAMING for zstd and deflate, as SolidArchive::add_entry feeds its one encoder (lib/src/archive/write.rs:575-580): the
+ * serialised inner entries reach the device in windows of `solid_win_mib` MiB (256) through two page-locked slots each way -- about four windows of
+ * page-locked memory whatever the archive's size --, the sink receives the head, one piece per window, the tail; inner entries of ANY size (FDAT chunks
+ * of at most 2^32 - 5 bytes, FlattenWriter's cut, lib/src/util/io.rs:60-77).  deflate: one zlib stream over all windows, its Adler-32 carried from
+ * window to window on the device.  The bytes equal pna_gpu_create_solid_archive_device's.  n == 0 and zstd's option single_frame: the whole stream in
+ * flight at once, inner entries below 2 GiB. */
 int  pna_gpu_create_solid_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
                                        const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user);
 

@@ -7,6 +7,7 @@
 //   k_dplan   one thread per segment: dynamic vs stored per block, sizes.
 //   k_dwrite  one workgroup per block: payload (or stored blocks) + sync flush into the packed output.
 //   k_dfinal  one thread per entry: 78 9C header, Adler-32 trailer (combine over blocks), empty entries.
+//   k_dfold   one wave per run of a stream compressed in runs (solid windows): header / trailer by the run's place, Adler-32 carried in device memory.
 // Replaces miniz_oxide behind flate2::write::ZlibEncoder (lib/src/entry/write.rs:257-259).  Integer/bit work only.
 #include <hip/hip_runtime.h>
 #include "pna_dev.h"
@@ -701,6 +702,46 @@ __global__ void k_dfinal(const SegDesc *__restrict__ segs, const uint32_t *__res
     t[0] = (uint8_t)(B >> 8); t[1] = (uint8_t)B; t[2] = (uint8_t)(A >> 8); t[3] = (uint8_t)A;
 }
 
+// ------------------------------------------------------------------ k_dfold : one wave, one RUN of a zlib stream
+// The continuation form of k_dfinal for one zlib stream compressed in runs of whole segments (the windows of pna_gpu_create_solid_archive_host): the
+// run is the sub-batch's one entry, and its blocks fold into the stream's running Adler-32, carry = (A, B), which stays in device memory from run to run.
+// run bit 0 (DRUN_CONT): the run does not start the stream -- no zlib header, the carry holds the stream so far; bit 1 (DRUN_OPEN): it does not end the
+// stream -- the carry is stored, no trailer (k_dplan / k_dblock / k_dwrite take the same from the segments' flags).  Every lane folds a contiguous range
+// of blocks, then the 64 partial (A, B, len mod P) fold in lane order through shuffles: the combine is associative, not commutative.
+__device__ __forceinline__ void adler_fold(uint32_t &A, uint32_t &B, uint32_t &L, uint32_t a2, uint32_t b2, uint32_t l2) {
+    B = (uint32_t)(((uint64_t)B + b2 + (uint64_t)l2 * ((A + ADLER_P - 1) % ADLER_P)) % ADLER_P);
+    A = (A + a2 + ADLER_P - 1) % ADLER_P;
+    L = (L + l2) % ADLER_P;
+}
+__global__ __launch_bounds__(64)
+void k_dfold(const SegDesc *__restrict__ segs, const uint32_t *__restrict__ entry_seg, const uint32_t *__restrict__ blk_seg, uint32_t nblk,
+             const BlkInfo *__restrict__ blk, const uint64_t *__restrict__ seg_off, const uint64_t *__restrict__ seg_size, uint8_t *__restrict__ dst,
+             uint32_t *__restrict__ carry, uint32_t run, uint32_t stored_only) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t per = (nblk + 63) / 64, g0 = min(nblk, lane * per), g1 = min(nblk, g0 + per);
+    uint32_t A = 1, B = 0, L = 0;                                  // (1, 0, 0): the empty input
+    for (uint32_t g = g0; g < g1; g++) {
+        const SegDesc sd = segs[blk_seg[g]];
+        const uint32_t b0 = (g - sd.blk_base) << sd.blk_log, bsz = 1u << sd.blk_log;
+        const uint32_t n = sd.len - b0 < bsz ? sd.len - b0 : bsz;
+        const BlkInfo bi = blk[g];
+        adler_fold(A, B, L, bi.adler_a, bi.adler_b, n % ADLER_P);
+    }
+    for (uint32_t o = 1; o < 64; o <<= 1) {                         // lane i (i mod 2o == 0) takes in lane i + o: [i, i + o) || [i + o, i + 2o)
+        const uint32_t a2 = __shfl_down(A, o), b2 = __shfl_down(B, o), l2 = __shfl_down(L, o);
+        if ((lane & (2 * o - 1)) == 0) adler_fold(A, B, L, a2, b2, l2);
+    }
+    if (lane != 0) return;
+    const uint32_t s0 = entry_seg[0], s1 = entry_seg[1];
+    uint32_t cA = 1, cB = 0, cL = 0;
+    if (run & DRUN_CONT) { cA = carry[0]; cB = carry[1]; }
+    else { uint8_t *o = dst + seg_off[s0]; o[0] = 0x78; o[1] = stored_only ? 0x01 : 0x9C; }
+    adler_fold(cA, cB, cL, A, B, L);
+    if (run & DRUN_OPEN) { carry[0] = cA; carry[1] = cB; return; }
+    uint8_t *t = dst + seg_off[s1 - 1] + seg_size[s1 - 1] - 4;
+    t[0] = (uint8_t)(cB >> 8); t[1] = (uint8_t)cB; t[2] = (uint8_t)(cA >> 8); t[3] = (uint8_t)cA;
+}
+
 void k_scan_launch_big(const uint64_t *in, uint64_t *out, uint32_t n, hipStream_t st);
 
 void launch_deflate_stage1(const uint8_t *src, const SegDesc *segs, uint32_t nseg, const uint32_t *blk_seg, uint32_t nblk,
@@ -726,6 +767,14 @@ void launch_deflate_write(const uint8_t *src, const SegDesc *segs, const uint32_
                           uint8_t *dst, hipStream_t st, bool stored_only, bool small_blocks) {
     if (nblk) hipLaunchKernelGGL(k_dwrite, dim3(nblk), dim3(small_blocks ? 64 : 256), 0, st, src, segs, blk_seg, blk, seg_off, outc, dst);
     hipLaunchKernelGGL(k_dfinal, dim3((nentry + 255) / 256), dim3(256), 0, st, segs, entry_seg, nentry, blk, seg_off, seg_size, dst, stored_only ? 1u : 0u);
+}
+
+// the same for one RUN (window) of a zlib stream compressed in runs: the sub-batch's one entry, k_dfold in place of k_dfinal
+void launch_deflate_write_run(const uint8_t *src, const SegDesc *segs, const uint32_t *blk_seg, uint32_t nblk, const BlkInfo *blk,
+                              const uint64_t *seg_off, const uint64_t *seg_size, const uint8_t *outc, const uint32_t *entry_seg,
+                              uint8_t *dst, hipStream_t st, bool stored_only, bool small_blocks, uint32_t *adler_carry, uint32_t run) {
+    if (nblk) hipLaunchKernelGGL(k_dwrite, dim3(nblk), dim3(small_blocks ? 64 : 256), 0, st, src, segs, blk_seg, blk, seg_off, outc, dst);
+    hipLaunchKernelGGL(k_dfold, dim3(1), dim3(64), 0, st, segs, entry_seg, blk_seg, nblk, blk, seg_off, seg_size, dst, adler_carry, run, stored_only ? 1u : 0u);
 }
 
 } // namespace pna

@@ -36,6 +36,12 @@ void launch_deflate_stage1(const uint8_t *src, const SegDesc *segs, uint32_t nse
 void launch_deflate_write(const uint8_t *src, const SegDesc *segs, const uint32_t *blk_seg, uint32_t nblk, const BlkInfo *blk,
                           const uint64_t *seg_off, const uint64_t *seg_size, const uint8_t *outc, const uint32_t *entry_seg, uint32_t nentry,
                           uint8_t *dst, hipStream_t st, bool stored_only, bool small_blocks);
+// (k_deflate.hip) one window of a zlib stream compressed in windows: k_dwrite, then k_dfold (header / trailer by the window's place, the Adler-32 carry).
+// A weak reference: the sanitizer build of the host code (tests/san) links its own stand-ins for the launch layer and has none for it -- run_subbatch
+// refuses a deflate window when it is absent; the library always defines it.
+__attribute__((weak)) void launch_deflate_write_run(const uint8_t *src, const SegDesc *segs, const uint32_t *blk_seg, uint32_t nblk, const BlkInfo *blk,
+                                                    const uint64_t *seg_off, const uint64_t *seg_size, const uint8_t *outc, const uint32_t *entry_seg,
+                                                    uint8_t *dst, hipStream_t st, bool stored_only, bool small_blocks, uint32_t *adler_carry, uint32_t run);
 void launch_entropy_chunk(const SegDesc *segs, uint32_t s0, uint32_t ns, const uint32_t *blk_seg, uint32_t g0, uint32_t nb,
                           const uint64_t *seqs, const uint8_t *lits, BlkInfo *blk, SegTables *tabs, uint8_t *litc, uint8_t *seqc, uint32_t *seqw,
                           uint32_t flags, uint32_t blk_log, uint32_t *hist, hipStream_t st, hipEvent_t *ev, hipStream_t side, hipEvent_t fork, hipEvent_t join, bool single_block, const uint32_t *seq_hist);
@@ -235,6 +241,7 @@ struct pna_gpu_ctx {
     bool aes_ready = false;
     hipEvent_t ev_ci[2] = {};
     DevBuf solid_plain, solid_desc, solid_blob, solid_place;   // serialised inner entries of a solid archive
+    DevBuf solid_adler;                                        // deflate solid from host memory: the stream's Adler-32 carried from window to window
     DevBuf z_ents, z_frames, z_lit;                            // decoder descriptors, literal scratch
     DevBuf z_fx, z_blocks, z_tabs, z_seqs, z_hlist, z_slist, z_work, z_fb, z_cbase, z_apart;   // lane-parallel decoder workspace
     PinBuf h_desc, h_blob, h_segdst, h_segoff;
@@ -298,7 +305,10 @@ inline int fail(pna_gpu_ctx *c, int code, const char *what, hipError_t e = hipSu
 constexpr uint64_t CTR_UNIT = 256u << 10;                    // bytes of one CTR work unit (one workgroup)
 struct PlaceDescH { uint64_t src_off, dst_off; uint32_t len, pad; };   // = PlaceDesc of k_frame.hip (k_place / k_gather)
 struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cipher = nullptr; const uint8_t *ivs = nullptr; const pna_gpu_entry_meta *meta = nullptr;
-                  uint32_t max_chunk = 0; bool want_offsets = true; };   // FDAT chunks of at most this many bytes (FlattenWriter::max_chunk_size; 0 = the reference's default u32::MAX)
+                  uint32_t max_chunk = 0; bool want_offsets = true;      // FDAT chunks of at most this many bytes (FlattenWriter::max_chunk_size; 0 = the reference's default u32::MAX)
+                  // a solid stream compressed in windows (pna_gpu_create_solid_archive_host): the sub-batch is one window of a stream of stream_len bytes and
+                  // is planned as the whole stream; deflate: DRUN_* flags of the window's place in the stream, the stream's Adler-32 carry in device memory
+                  uint64_t stream_len = 0; uint32_t run = 0; uint32_t *adler_carry = nullptr; };
 struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4], ej0[4]; uint8_t ctr_iv[16]; };
 
 void set_call_level(pna_gpu_ctx *c, int algo, int level);

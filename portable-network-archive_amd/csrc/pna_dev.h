@@ -94,6 +94,9 @@ struct LzParseGrid { const SegDesc *segs_all; const uint32_t *blk_seg; uint32_t 
                      uint32_t *hist = nullptr; };    // hist (round 5; zstd, large batches): the segments' histogram counters (448 words each: k_entropy.hip HIST_WORDS) -- the parse kernel adds every block's sequence codes to words 256 .. 447 of its segment, so that k_stats reads the literals only
 constexpr uint32_t BLK_LOG_MIN = 13;   // smallest block of the latency mode (bounds: pna_gpu_bound)
 static_assert(sizeof(SegDesc) == 40, "SegDesc layout");
+// deflate, one zlib stream compressed in runs of whole segments (k_dfold): the run does not start the stream (no zlib header; the Adler-32 carry holds
+// the stream so far) / does not end it (its last segment ends in a sync flush, no BFINAL, no trailer)
+constexpr uint32_t DRUN_CONT = 1u, DRUN_OPEN = 2u;
 // sequences a block of 1 << blk_log bytes can hold: a match is >= MIN_MATCH bytes but for one front-cut match (>= 3 bytes) per 256-position parse region
 __host__ __device__ inline uint32_t seq_cap_of(uint32_t blk_log) {
     return blk_log >= PNA_BLK_LOG ? SEQ_CAP : ((((1u << blk_log) / MIN_MATCH + ((1u << blk_log) >> 8) + 256 + 255)) & ~255u);

@@ -84,7 +84,7 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->plan, &c->d_tail, &c->blk, &c->tabs, &c->seqs, &c->lits, &c->litc, &c->seqc, &c->seqw, &c->pbuf, &c->seg_size,
                       &c->seg_off, &c->stage_in, &c->stage_out, &c->z_words, &c->z_rep, &c->z_zxf, &c->z_spec, &c->z_big, &c->z_one, &c->ctab, &c->c_vocab, &c->c_cum, &c->c_phr,
-                      &c->gtab, &c->fr_desc, &c->fr_blob, &c->fr_segdst, &c->fr_entoff, &c->crc_tabs, &c->aes_tabs, &c->ci_units, &c->ci_ivs, &c->ci_keys, &c->ci_gcm, &c->ci_spread, &c->ci_spread_desc, &c->z_vp, &c->z_pb, &c->z_mode, &c->x_arc, &c->x_pk, &c->x_raw[0], &c->x_raw[1], &c->x_desc, &c->x_place, &c->x_flag, &c->x_tags, &c->x_plen, &c->aes_dtabs, &c->solid_plain, &c->solid_desc, &c->solid_blob, &c->solid_place, &c->z_ents, &c->z_frames, &c->z_lit, &c->z_fx, &c->z_blocks, &c->z_tabs, &c->z_seqs, &c->z_hlist, &c->z_slist, &c->z_work, &c->z_fb, &c->z_cbase, &c->z_apart}) b->release();
+                      &c->gtab, &c->fr_desc, &c->fr_blob, &c->fr_segdst, &c->fr_entoff, &c->crc_tabs, &c->aes_tabs, &c->ci_units, &c->ci_ivs, &c->ci_keys, &c->ci_gcm, &c->ci_spread, &c->ci_spread_desc, &c->z_vp, &c->z_pb, &c->z_mode, &c->x_arc, &c->x_pk, &c->x_raw[0], &c->x_raw[1], &c->x_desc, &c->x_place, &c->x_flag, &c->x_tags, &c->x_plen, &c->aes_dtabs, &c->solid_plain, &c->solid_desc, &c->solid_blob, &c->solid_place, &c->solid_adler, &c->z_ents, &c->z_frames, &c->z_lit, &c->z_fx, &c->z_blocks, &c->z_tabs, &c->z_seqs, &c->z_hlist, &c->z_slist, &c->z_work, &c->z_fb, &c->z_cbase, &c->z_apart}) b->release();
     for (auto &b : c->lent) (void)hipHostFree((void *)b.first);          // (buffers the host never gave back)
     c->lent.clear();
     for (PinBuf *b : {&c->h_entoff, &c->h_plan, &c->h_tail, &c->h_desc, &c->h_blob, &c->h_segdst, &c->h_segoff, &c->hp_in[0], &c->hp_in[1], &c->hp_in[2], &c->hp_in[3], &c->hp_out[0], &c->hp_out[1]}) b->release();
@@ -607,6 +607,11 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
         in_total += q.in_total; nseg_est += q.nseg_est; max_len = std::max(max_len, q.max_len); any_empty |= q.any_empty; n_short += q.n_short; n_mid += q.n_mid; max_mid = std::max(max_mid, q.max_mid);
         if (q.misaligned) return fail(c, PNA_E_INVAL, "entry offset not 16-byte aligned");
     }
+    if (fj && fj->stream_len) {
+        // one window of a solid stream: block size, latency form and units follow from the whole stream, as in its one-shot run, so that the window's
+        // segments are coded as they are there (a window is whole segments: the short ones are the stream's own)
+        in_total = fj->stream_len; nseg_est = (in_total + SEG_SIZE - 1) / SEG_SIZE; max_len = in_total;
+    }
     // an upper bound of every payload of the sub-batch when the entries are small and plain (k_frame's wave-per-entry form takes those; 0: no such bound)
     const uint32_t frame_max_payload = (fj && !fj->solid && !fj->cipher && max_len <= 16384) ? (uint32_t)std::min<size_t>(pna_gpu_bound(algo, (size_t)max_len), 0xFFFFFFFFu) : 0u;
     const bool latency = c->tun.latency_max_mib > 0 && in_total <= ((uint64_t)c->tun.latency_max_mib << 20) && nseg_est <= 1024 && !(c->call_flags & 0x100u);
@@ -667,6 +672,8 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     // option single_frame (zstd): an entry's segments form ONE frame -- the frame header in front of the first segment only, the last-block bit on the entry's
     // last block only (SegDesc::first bit 2 tells k_plan / k_write); the blocks are what they are in the frame-per-segment form
     const uint32_t sf_bit = (algo == PNA_ALGO_ZSTD && c->tun.single_frame) ? 4u : 0u;
+    // a window of a deflate stream (FrameJob::run): its first segment starts the stream only in the first window, its last one ends it only in the last
+    const uint32_t first_bit = (fj && (fj->run & DRUN_CONT)) ? 0u : 1u, last_bit = (fj && (fj->run & DRUN_OPEN)) ? 0u : 2u;
     {
         auto fill = [&](unsigned t, size_t a, size_t b) {
             uint32_t sg = pp[t].sg, bk = pp[t].bk, un = pp[t].un;
@@ -676,7 +683,7 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
                 if (len == 0) { segs[sg++] = SegDesc{off, 0, bk, (uint32_t)e, 3, 0, 0, blk_log, 0}; continue; }
                 for (uint64_t p = 0; p < len; p += SEG_SIZE) {
                     const uint32_t sl = (uint32_t)std::min<uint64_t>(SEG_SIZE, len - p);
-                    const SegDesc s{off + p, sl, bk, (uint32_t)e, (p == 0 ? 1u : 0u) | (p + SEG_SIZE >= len ? 2u : 0u) | sf_bit, 0, sl, blk_log, 0};
+                    const SegDesc s{off + p, sl, bk, (uint32_t)e, (p == 0 ? first_bit : 0u) | (p + SEG_SIZE >= len ? last_bit : 0u) | sf_bit, 0, sl, blk_log, 0};
                     const uint32_t nb = (sl + bsz - 1) >> blk_log;
                     for (uint32_t b2 = 0; b2 < nb; b2++) blk_seg[bk + b2] = sg;
                     bk += nb; segs[sg++] = s;
@@ -1087,7 +1094,13 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
         HIPCHK(c, hipMemcpyAsync(c->fr_segdst.p, segdst, (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, st));
         d_segdst = (const uint64_t *)c->fr_segdst.p; wbase = d_dst;
     } else if (!early_write && out_base + total > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
-    if (defl) launch_deflate_write(d_src, c->d_segs, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p,
+    if (defl && fj && fj->adler_carry) {
+        if (!launch_deflate_write_run) return fail(c, PNA_E_UNSUPPORTED, "deflate windows: this build has no k_dfold");
+        launch_deflate_write_run(d_src, c->d_segs, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p,
+                                 (const uint8_t *)c->litc.p, c->d_entry_seg, wbase, st, c->call_stored, /* a wave per block */ max_len <= 32768 && nseg >= 4096,
+                                 fj->adler_carry, fj->run);
+    }
+    else if (defl) launch_deflate_write(d_src, c->d_segs, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p,
                                    d_segdst, (const uint64_t *)c->seg_size.p, (const uint8_t *)c->litc.p, c->d_entry_seg,
                                    (uint32_t)(e1 - e0), wbase, st, c->call_stored, /* a wave per block */ max_len <= 32768 && nseg >= 4096);
     else launch_write(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p,

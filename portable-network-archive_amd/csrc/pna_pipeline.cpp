@@ -5,22 +5,24 @@
 #include <atomic>
 static void parallel_stage(uint8_t *dst, const void *const *src, const size_t *src_len, const uint64_t *off, size_t e0, size_t e1, unsigned threads);
 
-// `pna create --solid` from host memory (SolidArchive::add_entry streams the entries into ONE encoder, lib/src/archive/write.rs:575-580).
-// zstd: the serialised inner entries -- FHED | fSIZ | FDAT(data, crc) | FEND per entry, stored -- reach the device in WINDOWS of solid_win_mib MiB of that
-// stream (whole 1 MiB segments: every segment is a frame and an SDAT chunk of its own, so a window is compressed like the whole), through two page-locked
-// slots each way: ~4 windows of page-locked memory whatever the archive's size (round 4: the whole stream was staged, copied and held at once).  The host
-// writes the chunk framing and the entries' bytes where they stand in the stream while the device compresses the window before; the data chunks' CRC-32 are
-// the device's -- the raw CRC register of every piece of a chunk inside the window (k_frame's piece mode), chained by the host with CRC(A || B) =
+// `pna create --solid` from host memory (SolidArchive::add_entry streams the entries into ONE encoder, lib/src/archive/write.rs:575-580), zstd and deflate:
+// the serialised inner entries -- FHED | fSIZ | FDAT(data, crc) | FEND per entry, stored -- reach the device in WINDOWS of solid_win_mib MiB of that stream
+// (whole 1 MiB segments, every segment an SDAT chunk of its own), through two page-locked slots each way: ~4 windows of page-locked memory whatever the
+// archive's size (round 4: the whole stream was staged, copied and held at once).  A window is planned as the whole stream (FrameJob::stream_len: the
+// stream's block size and forms), so it is compressed exactly as it is inside the one-shot stream.  zstd: every segment is a frame.  deflate: the segments
+// are runs of blocks that end in a sync flush, and only three things tie the zlib stream together -- the 78 9C header in front of the stream's first
+// segment, BFINAL and the Adler-32 trailer on its last one, one Adler-32 over everything: the windows carry the segment flags of their place in the stream
+// (FrameJob::run) and fold their blocks into the stream's Adler-32, which stays in device memory from window to window (k_dfold).  The host writes the
+// chunk framing and the entries' bytes where they stand in the stream while the device compresses the window before; the data chunks' CRC-32 are the
+// device's -- the raw CRC register of every piece of a chunk inside the window (k_frame's piece mode), chained by the host with CRC(A || B) =
 // x^(8|B|) CRC(A) + CRC(B) for a chunk that spans windows, written into the window (k_crc_patch) before it is compressed.  An inner entry is cut into
 // FDAT chunks of at most 2^32 - 5 bytes like FlattenWriter's (lib/src/util/io.rs:60-77): any size goes through (the one-shot device path: below 2 GiB).
-// The archive equals pna_gpu_create_solid_archive_device's byte for byte.  deflate (one zlib stream with one Adler-32 over everything) and the
-// single_frame option keep the one-shot form below.
+// The archive equals pna_gpu_create_solid_archive_device's byte for byte.  No entries, and zstd's single_frame option, keep the one-shot form below.
 namespace {
 struct SolidSpan { uint64_t pos, len; uint32_t kind; uint32_t chunk; uint64_t a, b; };     // kind 0: blob[a ..), 1: entry a from byte b on, 2: the CRC of chunk `chunk`
 struct SolidChunk { uint32_t state = 0, crc = 0; uint64_t end = 0; bool started = false, done = false; };   // end: stream position behind the chunk's data
 }
-static int solid_stream_zstd(pna_gpu_ctx *c, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
-    const int algo = PNA_ALGO_ZSTD;
+static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
     set_call_level(c, algo, level);
     hipStream_t st = c->stream;
     // ---- the stream's layout
@@ -61,8 +63,11 @@ static int solid_stream_zstd(pna_gpu_ctx *c, int level, size_t n, const char *co
     const uint64_t wcap_in = std::min<uint64_t>(W, plain_len) + 8192;
     const uint64_t wcap_out = pna_gpu_bound(algo, (size_t)std::min<uint64_t>(W, plain_len)) + (std::min<uint64_t>(W, plain_len) / SEG_SIZE + 2) * 16 + 4096;
     int rc = ensure_crc(c); if (rc) return rc;
-    if (c->stage_in.ensure(2 * wcap_in + 64) || c->stage_out.ensure(2 * wcap_out + 64) || c->hp_in[0].ensure(wcap_in) || c->hp_in[1].ensure(wcap_in) ||
+    const uint64_t slot_in = (wcap_in + 255) & ~(uint64_t)255, slot_out = (wcap_out + 255) & ~(uint64_t)255;   // the two device slots each way
+    if (c->stage_in.ensure(2 * slot_in + 64) || c->stage_out.ensure(2 * slot_out + 64) || c->hp_in[0].ensure(wcap_in) || c->hp_in[1].ensure(wcap_in) ||
         c->hp_out[0].ensure(wcap_out) || c->hp_out[1].ensure(wcap_out)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
+    const bool defl = algo == PNA_ALGO_DEFLATE;
+    if (defl && c->solid_adler.ensure(64)) return fail(c, PNA_E_NOMEM, "solid workspace");                  // the stream's Adler-32 (A, B) between windows
     const CallTotalScope call_total(c, plain_len);                                            // every window picks the block size of the whole stream
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     const unsigned T = c->tun.stage_threads > 0 ? (unsigned)c->tun.stage_threads : std::min(8u, std::max(1u, hw / 2));
@@ -109,8 +114,8 @@ static int solid_stream_zstd(pna_gpu_ctx *c, int level, size_t n, const char *co
     for (uint64_t k = 0; k < nwin && rc == PNA_OK; k++) {
         Win &w = win[k & 1];
         const uint64_t wl = w.w1 - w.w0;
-        uint8_t *d_in = (uint8_t *)c->stage_in.p + (k & 1) * ((wcap_in + 255) & ~(uint64_t)255);
-        uint8_t *d_out = (uint8_t *)c->stage_out.p + (k & 1) * ((wcap_out + 255) & ~(uint64_t)255);
+        uint8_t *d_in = (uint8_t *)c->stage_in.p + (k & 1) * slot_in;
+        uint8_t *d_out = (uint8_t *)c->stage_out.p + (k & 1) * slot_out;
         HIPCHK(c, hipMemcpyAsync(d_in, c->hp_in[k & 1].p, wl + std::min<uint64_t>(64, wcap_in - wl), hipMemcpyHostToDevice, st));
         // the CRC registers of the window's pieces
         const size_t np = w.pieces.size();
@@ -151,6 +156,8 @@ static int solid_stream_zstd(pna_gpu_ctx *c, int level, size_t n, const char *co
         if (k + 1 < nwin) next = std::thread([&, k]() { assemble(k + 1, win[(k + 1) & 1]); });
         const uint64_t off0 = 0, len0 = wl; uint64_t offs[2] = {0, 0};
         FrameJob fj{nullptr, 1, nullptr, nullptr};
+        fj.stream_len = plain_len;
+        if (defl) { fj.run = (k > 0 ? DRUN_CONT : 0u) | (k + 1 < nwin ? DRUN_OPEN : 0u); fj.adler_carry = (uint32_t *)c->solid_adler.p; }
         rc = run_subbatch(c, algo, d_in, &off0, &len0, 0, 1, d_out, wcap_out, 0, offs, st, false, &fj);
         if (rc == PNA_OK && hipMemcpyAsync(c->hp_out[k & 1].p, d_out, offs[1], hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
         if (rc == PNA_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
@@ -172,13 +179,14 @@ extern "C" uint64_t pna_gpu_debug_pinned_bytes(pna_gpu_ctx *c) {
     return t;
 }
 
-// deflate / single_frame: one H2D of the entries, the device path, one D2H of the archive, handed to the sink in pieces of at most 16 MiB (the whole
-// stream is in flight at once: a zlib stream is one compression unit with one Adler-32)
+// no entries, or zstd's single_frame option (an entry's segments form ONE frame): one H2D of the entries, the device path, one D2H of the archive, handed
+// to the sink in pieces of at most 16 MiB
 extern "C" int pna_gpu_create_solid_archive_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                  const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
     if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    if (algo == PNA_ALGO_ZSTD && n && !c->tun.single_frame && c->tun.solid_win_mib > 0) return solid_stream_zstd(c, level, n, names, src, src_len, sink, user);
+    if (n && c->tun.solid_win_mib > 0 && (algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_ZSTD && !c->tun.single_frame)))
+        return solid_stream(c, algo, level, n, names, src, src_len, sink, user);
     std::vector<uint64_t> off(n + 1), len(n);
     uint64_t pos = 0;
     for (size_t i = 0; i < n; i++) { off[i] = pos; len[i] = src_len[i]; pos = (pos + src_len[i] + 15) & ~(uint64_t)15; }
