@@ -67,6 +67,20 @@ int  pna_create_archive_encrypted(pna_gpu_ctx *ctx, int algo, int level, size_t 
                                   const void *const *src, const size_t *src_len, const void *password, size_t password_len,
                                   int cipher_mode, uint32_t rounds, pna_sink_fn sink, void *user);
 
+/* pna create [--solid] --aes [ctr|cbc|gcm] with a choice of password hash: kdf PNA_KDF_ARGON2ID (the reference's default, lib/src/entry/options.rs:164:
+ * Argon2id with the argon2 crate's default parameters m = 19456 KiB, t = 2, p = 1; PHSF "$argon2id$v=19$m=19456,t=2,p=1$<salt>") or
+ * PNA_KDF_PBKDF2_SHA256 (`rounds`, 0 = 600 000), over a random 16-byte salt, one key per archive.  solid = 0: a fresh random IV per entry
+ * (pna_gpu_create_archive_enc_host); solid != 0: one cipher stream over the solid stream (pna_gpu_create_solid_archive_enc_host: CTR or GCM,
+ * CBC is PNA_E_UNSUPPORTED).  zstd / deflate. */
+#define PNA_KDF_ARGON2ID      0
+#define PNA_KDF_PBKDF2_SHA256 1
+/* The key (32 bytes) and the PHSF string of one of those password hashes over `salt` (what the entry point above does with its random salt). */
+int  pna_kdf_derive(int kdf, const void *password, size_t password_len, const void *salt, size_t salt_len, uint32_t rounds,
+                    uint8_t *key, char *phsf, size_t phsf_cap);
+int  pna_create_archive_encrypted_ex(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
+                                     const void *const *src, const size_t *src_len, const void *password, size_t password_len,
+                                     int cipher_mode, int kdf, uint32_t rounds, pna_sink_fn sink, void *user);
+
 /* `pna create --split`: re-frame ONE archive image into parts of at most max_part_bytes (SplitParts, lib/src/archive/split_parts.rs:
  * signature + AHED(archive number) ... [ANXT] AEND per part; chunks that fit keep their bytes, FDAT / SDAT chunks are cut at the budget
  * boundary and only the fragments get new CRCs).  sink(user, part_index, buf, len) receives the bytes of part `part_index` in order.

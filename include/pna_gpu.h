@@ -279,6 +279,16 @@ int  pna_gpu_create_solid_archive_enc_device(pna_gpu_ctx *ctx, int algo, int lev
  * flight at once, inner entries below 2 GiB. */
 int  pna_gpu_create_solid_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
                                        const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user);
+/* The same with a cipher, streaming too: the layouts of pna_gpu_create_solid_archive_enc_device (CTR: cipher->ivs ONE 16-byte IV; GCM: ONE
+ * salt(32) || nonce_prefix(7); NULL: drawn from the OS), and for the same IV / salt the same bytes, at every solid_win_mib, with inner entries of ANY
+ * size.  CTR: the keystream continues from window to window at the stream offset of the window's first compressed byte.  GCM STREAM: the segments are
+ * cut from the whole compressed stream (GcmEncryptWriter, lib/src/cipher/gcm.rs:45-90) -- each window but the last holds back, in device memory, the
+ * 1 .. gcm_segment_size bytes of its output not yet known to form a non-final segment and puts them in front of the next window's output.  Page-locked
+ * memory (pna_gpu_debug_pinned_bytes): about four windows, plus two GCM segments (the output slots hold the carry); device memory: one segment of carry
+ * on top of the plain form.  cipher == NULL or PNA_ENC_NONE: pna_gpu_create_solid_archive_host.  CBC and Camellia: PNA_E_UNSUPPORTED. */
+int  pna_gpu_create_solid_archive_enc_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
+                                           const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                           pna_sink_fn sink, void *user);
 
 /* Same archive from host memory with a bounded in-flight window: entries stream through two page-locked staging slots
  * (<= ~1 GiB of input each); staging of sub-batch k+1, the H2D copy, the kernels of sub-batch k and the D2H copy of

@@ -114,13 +114,13 @@ EXPORTS = [
     "pna_gpu_solid_archive_bound", "pna_gpu_solid_archive_enc_bound", "pna_gpu_create_solid_archive_device", "pna_gpu_create_solid_archive_host",
     "pna_gpu_create_archive_part_device", "pna_gpu_decompress_batch", "pna_gpu_decompress_batch_device",
     "pna_gpu_archive_enc_bound", "pna_gpu_create_archive_enc_device", "pna_gpu_cipher_apply_device", "pna_gpu_create_archive_enc_host",
-    "pna_gpu_create_solid_archive_enc_device", "pna_gpu_extract_archive_host", "pna_gpu_zstd_stream_frames_device",
+    "pna_gpu_create_solid_archive_enc_device", "pna_gpu_create_solid_archive_enc_host", "pna_gpu_extract_archive_host", "pna_gpu_zstd_stream_frames_device",
     "pna_gpu_zstd_decompress_open_device", "pna_gpu_inflate_open_device", "pna_gpu_create_archive_meta_device",
     "pna_gpu_create_archive_meta_host", "pna_gpu_stream_stats", "pna_bench_stream_threads",
     # include/pna_archive.h
     "pna_crc32", "pna_archive_new", "pna_archive_add_file", "pna_archive_add_dir", "pna_archive_add_solid",
     "pna_archive_inner_entry_bytes", "pna_archive_finalize", "pna_archive_abort", "pna_create_archive",
-    "pna_kdf_pbkdf2_sha256", "pna_create_archive_encrypted", "pna_kdf_argon2", "pna_split_archive", "pna_join_parts",
+    "pna_kdf_pbkdf2_sha256", "pna_create_archive_encrypted", "pna_create_archive_encrypted_ex", "pna_kdf_derive", "pna_kdf_argon2", "pna_split_archive", "pna_join_parts",
     "pna_archive_seek_to_end", "pna_archive_list_entries",
     # streaming entries, parts, append (include/pna_gpu.h)
     "pna_gpu_create_archive_part_host", "pna_gpu_create_archive_multi_host", "pna_gpu_append_archive_host", "pna_gpu_stream_entry_begin", "pna_gpu_stream_entry_write",
@@ -254,6 +254,14 @@ def load_library() -> ctypes.CDLL:
     L.pna_create_archive_encrypted.restype = ctypes.c_int
     L.pna_create_archive_encrypted.argtypes = [vp, ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
                                                ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_int, u32, SINK_FN, vp]
+    L.pna_create_archive_encrypted_ex.restype = ctypes.c_int
+    L.pna_create_archive_encrypted_ex.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
+                                                  ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_int, ctypes.c_int, u32, SINK_FN, vp]
+    L.pna_kdf_derive.restype = ctypes.c_int
+    L.pna_kdf_derive.argtypes = [ctypes.c_int, ctypes.c_char_p, sz, ctypes.c_char_p, sz, u32, ctypes.c_char_p, ctypes.c_char_p, sz]
+    L.pna_gpu_create_solid_archive_enc_host.restype = ctypes.c_int
+    L.pna_gpu_create_solid_archive_enc_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
+                                                        ctypes.POINTER(sz), ctypes.POINTER(CipherStruct), SINK_FN, vp]
     L.pna_archive_seek_to_end.restype = ctypes.c_int
     L.pna_archive_seek_to_end.argtypes = [ctypes.c_char_p, sz, u64p, ctypes.POINTER(ctypes.c_int)]
     L.pna_archive_list_entries.restype = ctypes.c_int
@@ -417,6 +425,33 @@ class Context:
                                                                     ctypes.c_void_p(d_dst), dst_cap, ctypes.byref(total),
                                                                     ctypes.c_void_p(stream) if stream else None))
         return total.value
+
+    def create_solid_archive_enc_host(self, names: Sequence[str], entries: Sequence[bytes], algo: int = ALGO_ZSTD, level: int = LEVEL_DEFAULT,
+                                      cipher: Optional[Cipher] = None) -> bytes:
+        """`pna create --solid` from host memory with the caller's key and IV (pna_gpu_create_solid_archive_enc_host): streamed in windows of
+        solid_win_mib MiB; CTR with one IV, GCM with one salt || nonce prefix; the bytes of create_solid_archive_device with the same cipher.
+        cipher None: create_archive(..., solid=True)."""
+        n = len(entries)
+        out = bytearray()
+
+        def _sink(_u, buf, k):
+            out.extend((ctypes.c_char * k).from_address(buf))
+            return 0
+        cb = SINK_FN(_sink)
+        bufs = [e if isinstance(e, (bytes, memoryview)) else bytes(e) for e in entries]
+        ptrs = []
+        for b in bufs:                                                  # bytes, or a writable / numpy-backed memoryview (no copy of large entries)
+            if isinstance(b, bytes):
+                ptrs.append(ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p))
+            else:
+                ptrs.append(ctypes.c_void_p(ctypes.addressof(ctypes.c_char.from_buffer(b)) if len(b) else 0))
+        a_names = (ctypes.c_char_p * max(n, 1))(*[s.encode() for s in names])
+        a_src = (ctypes.c_void_p * max(n, 1))(*ptrs)
+        a_len = (ctypes.c_size_t * max(n, 1))(*[len(e) for e in bufs])
+        cs = cipher.struct(1) if cipher is not None else None
+        self._check(self._L.pna_gpu_create_solid_archive_enc_host(self._h, algo, level, n, a_names, a_src, a_len,
+                                                                  ctypes.byref(cs) if cs is not None else None, cb, None))
+        return bytes(out)
 
     def decompress_batch(self, payloads: Sequence[bytes], raw_sizes: Sequence[int], algo: int = ALGO_ZSTD) -> List[bytes]:
         """decompress_reader for a batch of entries: payload i (concatenated FDAT bodies) -> raw_sizes[i] bytes."""
@@ -852,10 +887,30 @@ def kdf_pbkdf2_sha256(password: bytes, salt: bytes, rounds: int, key_len: int = 
     return key.raw, phsf.value.decode()
 
 
+KDFS = {"argon2id": 0, "pbkdf2": 1}      # include/pna_archive.h PNA_KDF_*
+
+
+def kdf_derive(kdf: str, password: bytes, salt: bytes, rounds: int = 0):
+    """The password hash of create_archive_encrypted(kdf=...) over a given salt (pna_kdf_derive): returns (key, PHSF string)."""
+    if kdf not in KDFS:
+        raise ValueError("kdf must be one of %s" % sorted(KDFS))
+    key = ctypes.create_string_buffer(32)
+    phsf = ctypes.create_string_buffer(256)
+    rc = load_library().pna_kdf_derive(KDFS[kdf], bytes(password), len(password), bytes(salt), len(salt), rounds, key, phsf, 256)
+    if rc:
+        raise PnaGpuError(rc, load_library().pna_gpu_strerror(rc).decode())
+    return key.raw, phsf.value.decode()
+
+
 def create_archive_encrypted(ctx: Context, names: Sequence[str], entries: Sequence[bytes], password: bytes, algo: int = ALGO_ZSTD,
-                             level: int = LEVEL_DEFAULT, mode: int = MODE_CTR, rounds: int = 0, cipher: Optional[Cipher] = None) -> bytes:
-    """`pna create --aes [ctr|cbc] --pbkdf2`: key derivation on the host, compression + cipher + framing on the device.
-    With `cipher` the caller supplies key / PHSF / IVs itself (pna_gpu_create_archive_enc_host)."""
+                             level: int = LEVEL_DEFAULT, mode: int = MODE_CTR, rounds: int = 0, cipher: Optional[Cipher] = None,
+                             solid: bool = False, kdf: str = "pbkdf2") -> bytes:
+    """`pna create [--solid] --aes [ctr|cbc|gcm] [--argon2 | --pbkdf2]`: key derivation on the host, compression + cipher + framing on the device.
+    kdf: "pbkdf2" (PBKDF2-SHA256, `rounds`, 0 = 600 000) or "argon2id" (m=19456, t=2, p=1, the reference's default).  solid: one cipher stream
+    over the solid stream, CTR or GCM (pna_gpu_create_solid_archive_enc_host).  With `cipher` the caller supplies key / PHSF / IVs itself
+    (pna_gpu_create_archive_enc_host, or the solid form: one IV / one salt || nonce prefix)."""
+    if kdf not in KDFS:
+        raise ValueError("kdf must be one of %s" % sorted(KDFS))
     L = load_library()
     n = len(entries)
     out = bytearray()
@@ -868,9 +923,15 @@ def create_archive_encrypted(ctx: Context, names: Sequence[str], entries: Sequen
     a_names = (ctypes.c_char_p * max(n, 1))(*[s.encode() for s in names])
     a_src = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
     a_len = (ctypes.c_size_t * max(n, 1))(*[len(e) for e in entries])
-    if cipher is not None:
+    if cipher is not None and solid:
+        cs = cipher.struct(1)
+        rc = L.pna_gpu_create_solid_archive_enc_host(ctx._h, algo, level, n, a_names, a_src, a_len, ctypes.byref(cs), cb, None)
+    elif cipher is not None:
         cs = cipher.struct(n)
         rc = L.pna_gpu_create_archive_enc_host(ctx._h, algo, level, n, a_names, a_src, a_len, ctypes.byref(cs), cb, None)
+    elif solid or kdf != "pbkdf2":
+        rc = L.pna_create_archive_encrypted_ex(ctx._h, algo, level, 1 if solid else 0, n, a_names, a_src, a_len, bytes(password), len(password),
+                                               mode, KDFS[kdf], rounds, cb, None)
     else:
         rc = L.pna_create_archive_encrypted(ctx._h, algo, level, n, a_names, a_src, a_len, bytes(password), len(password), mode, rounds, cb, None)
     if rc:

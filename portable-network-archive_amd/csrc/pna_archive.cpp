@@ -570,6 +570,41 @@ extern "C" int pna_create_archive_encrypted(pna_gpu_ctx *ctx, int algo, int leve
     return pna_gpu_create_archive_enc_host(ctx, algo, level, n, names, src, src_len, &ci, sink, user);
 }
 
+// The password hash of WriteOptions (hash(), lib/src/entry/write.rs:153-186): Argon2id by default (lib/src/entry/options.rs:164) with the argon2
+// crate's default parameters (m = 19456 KiB, t = 2, p = 1), or PBKDF2-SHA256; the PHSF is the PHC string without the hash,
+// "$argon2id$v=19$m=19456,t=2,p=1$<salt B64, no padding>" / "$pbkdf2-sha256$i=<rounds>,l=32$<salt>".
+extern "C" int pna_kdf_derive(int kdf, const void *password, size_t password_len, const void *salt, size_t salt_len, uint32_t rounds,
+                              uint8_t *key, char *phsf, size_t phsf_cap) {
+    if ((!password && password_len) || !salt || !salt_len || !key || !phsf) return PNA_E_INVAL;
+    if (kdf == PNA_KDF_PBKDF2_SHA256) return pna_kdf_pbkdf2_sha256(password, password_len, salt, salt_len, rounds ? rounds : 600000u, key, 32, phsf, phsf_cap);
+    if (kdf != PNA_KDF_ARGON2ID) return PNA_E_INVAL;
+    const std::string s = "$argon2id$v=19$m=19456,t=2,p=1$" + b64_nopad((const uint8_t *)salt, salt_len);
+    if (s.size() + 1 > phsf_cap) return PNA_E_DSTSIZE;
+    int rc = pna_kdf_argon2(2, password, password_len, salt, salt_len, 2, 19456, 1, key, 32);
+    if (rc) return rc;
+    memcpy(phsf, s.c_str(), s.size() + 1);
+    return PNA_OK;
+}
+
+// `pna create [--solid] --aes [ctr|cbc|gcm] --password ... [--argon2 | --pbkdf2]`: one key per archive over a fresh 16-byte salt
+// (SaltString::generate).  Solid archives: pna_gpu_create_solid_archive_enc_host; others: pna_gpu_create_archive_enc_host.
+extern "C" int pna_create_archive_encrypted_ex(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
+                                               const void *const *src, const size_t *src_len, const void *password, size_t password_len,
+                                               int cipher_mode, int kdf, uint32_t rounds, pna_sink_fn sink, void *user) {
+    if (!ctx) return PNA_E_NODEVICE;
+    if (!sink || (!password && password_len)) return PNA_E_INVAL;
+    uint8_t salt[16];
+    if (getrandom(salt, sizeof salt, 0) != (ssize_t)sizeof salt) return PNA_E_INVAL;
+    pna_gpu_cipher ci{};
+    ci.encryption = PNA_ENC_AES; ci.cipher_mode = cipher_mode; ci.ivs = nullptr;
+    char phsf[128];
+    int rc = pna_kdf_derive(kdf, password, password_len, salt, sizeof salt, rounds, ci.key, phsf, sizeof phsf);
+    if (rc) return rc;
+    ci.phsf = phsf;
+    if (solid) return pna_gpu_create_solid_archive_enc_host(ctx, algo, level, n, names, src, src_len, &ci, sink, user);
+    return pna_gpu_create_archive_enc_host(ctx, algo, level, n, names, src, src_len, &ci, sink, user);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Multipart archives (`pna create --split`): SplitParts, lib/src/archive/split_parts.rs.  The device paths produce ONE archive image;
 // this re-frames its chunk stream into parts of at most max_part_bytes: every part opens with the signature + AHED(archive number),

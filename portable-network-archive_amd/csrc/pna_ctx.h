@@ -242,6 +242,7 @@ struct pna_gpu_ctx {
     hipEvent_t ev_ci[2] = {};
     DevBuf solid_plain, solid_desc, solid_blob, solid_place;   // serialised inner entries of a solid archive
     DevBuf solid_adler;                                        // deflate solid from host memory: the stream's Adler-32 carried from window to window
+    DevBuf solid_carry;                                        // GCM solid from host memory: the tail of a window's output not yet cut into a segment
     DevBuf z_ents, z_frames, z_lit;                            // decoder descriptors, literal scratch
     DevBuf z_fx, z_blocks, z_tabs, z_seqs, z_hlist, z_slist, z_work, z_fb, z_cbase, z_apart;   // lane-parallel decoder workspace
     PinBuf h_desc, h_blob, h_segdst, h_segoff;
@@ -308,7 +309,15 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
                   uint32_t max_chunk = 0; bool want_offsets = true;      // FDAT chunks of at most this many bytes (FlattenWriter::max_chunk_size; 0 = the reference's default u32::MAX)
                   // a solid stream compressed in windows (pna_gpu_create_solid_archive_host): the sub-batch is one window of a stream of stream_len bytes and
                   // is planned as the whole stream; deflate: DRUN_* flags of the window's place in the stream, the stream's Adler-32 carry in device memory
-                  uint64_t stream_len = 0; uint32_t run = 0; uint32_t *adler_carry = nullptr; };
+                  uint64_t stream_len = 0; uint32_t run = 0; uint32_t *adler_carry = nullptr;
+                  // ... with a cipher: where the window stands in the cipher stream, updated by run_subbatch (SolidCipherRun)
+                  struct SolidCipherRun *crun = nullptr; };
+// The cipher state of a solid stream compressed in windows.  CTR: `pos`, the stream offset of the window's first compressed byte (the keystream
+// continues).  GCM STREAM: segments are cut from the whole compressed stream -- `seg`, the counter of the next segment; `carry` (carry_len bytes,
+// 1 .. G once the stream has begun, in device memory) the tail of the output before that is not yet known to be a non-final segment, placed in
+// front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  run_subbatch advances
+// pos, seg and carry_len past the window.
+struct SolidCipherRun { uint64_t pos = 0, seg = 0, carry_len = 0; uint8_t *carry = nullptr; bool final_win = false; };
 struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4], ej0[4]; uint8_t ctr_iv[16]; };
 
 void set_call_level(pna_gpu_ctx *c, int algo, int level);
@@ -421,6 +430,8 @@ void aes256_expand(const uint8_t key[32], AesKey &k);
 void aes256_dec_key(const AesKey &k, AesKey &d);
 void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]);
 int  resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs);
+void gcm_entry_material(const pna_gpu_cipher *ci, const uint8_t kc[32], const uint8_t phsf_hash[32], const uint8_t salt_prefix[39],
+                        uint32_t seg_size, const char *name, int compression, GcmMaterial &m);
 uint64_t chunk_limit(uint32_t max_chunk);
 size_t meta_len(const pna_gpu_entry_meta *m, size_t e);
 bool meta_blob_ok(const uint8_t *p, size_t n);

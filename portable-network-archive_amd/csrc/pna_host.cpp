@@ -815,7 +815,8 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
         if (e1 - e0 != 1) return fail(c, PNA_E_INVAL, "a solid stream is one entry");
         nunit = nseg;
         // (GCM: one SDAT chunk per GCM segment of the compressed stream -- at most the worst-case output / segment size + 1 of them)
-        const size_t ucap = gcm ? (size_t)(pna_gpu_bound(algo, (size_t)src_len[e0]) / gcm_seg) + 2 : nunit;
+        const uint64_t carry_in = fj->crun ? fj->crun->carry_len : 0;
+        const size_t ucap = gcm ? (size_t)((pna_gpu_bound(algo, (size_t)src_len[e0]) + carry_in) / gcm_seg) + 2 : nunit;
         if (c->h_desc.ensure(ucap * sizeof(FrameDesc)) || c->h_blob.ensure(ucap * 8 + 16) || c->h_segdst.ensure((size_t)(nseg + 1) * 8))
             return fail(c, PNA_E_NOMEM, "framing staging");
         fds = (FrameDesc *)c->h_desc.p; blob = (uint8_t *)c->h_blob.p; segdst = (uint64_t *)c->h_segdst.p;
@@ -941,6 +942,8 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     }
     uint64_t total = early_write ? 0 : seg_off[nseg];
     std::vector<CipherUnit> cunits;
+    uint64_t gcm_carry_in = 0, gcm_carry_in_len = 0, gcm_carry_out = 0;               // windowed GCM: where the carry goes in / the next one starts (0: none)
+    const uint64_t ctr_base = fj && fj->crun ? fj->crun->pos : 0;
     const uint64_t *d_segdst = (const uint64_t *)c->seg_off.p;
     uint8_t *wbase = d_dst + out_base;
     if (fj) {
@@ -955,12 +958,22 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
                 // gcm.rs:48-100): the head carries the stream header as its first SDAT chunk; here one SDAT chunk per GCM segment, ciphertext || tag.  The
                 // write kernels put the compressed stream down in one piece behind the first chunk header, segments k >= 1 then move forward by 28 k
                 // bytes (tag and CRC of the chunk before + their own chunk header), as a GCM entry of several segments does.
-                const uint64_t P = seg_off[nseg] - seg_off[0], G = gcm_seg;
-                const uint64_t K = P ? (P + G - 1) / G : 1;
-                if (K > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
+                // A window of a windowed stream (fj->crun): the carry of the window before goes in front of the window's output, segment counters
+                // start at crun->seg, and unless the window is the stream's last, the tail that does not yet form a non-final segment (1 .. G bytes)
+                // is held back as the next carry.
+                SolidCipherRun *cr = fj->crun;
+                const uint64_t C = cr ? cr->carry_len : 0, P = C + seg_off[nseg] - seg_off[0], G = gcm_seg, J = cr ? cr->seg : 0;
+                const bool last = !cr || cr->final_win;
+                const uint64_t K = last ? (P ? (P + G - 1) / G : (J ? 0 : 1)) : (P ? (P - 1) / G : 0);
+                const uint64_t E = last ? P : K * G;                                 // the bytes that go out in this window's segments
+                if (J + K > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
                 const uint64_t B = pos + 8;
-                for (uint32_t sg = 0; sg < nseg; sg++) segdst[sg] = B + (seg_off[sg] - seg_off[0]);
-                if (K > 1) spread_copy.emplace_back(B, P);
+                if (B + P + 16 > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");      // (the compact stream, carry included)
+                for (uint32_t sg = 0; sg < nseg; sg++) segdst[sg] = B + C + (seg_off[sg] - seg_off[0]);
+                if (C) { gcm_carry_in = B; gcm_carry_in_len = C; }
+                if (P > E) gcm_carry_out = B + E;
+                if (cr) { cr->seg = J + K; cr->carry_len = P - E; }
+                if (K > 1) spread_copy.emplace_back(B, E);
                 const GcmMaterial &gm = gmat[0];
                 for (uint64_t k = 0; k < K; k++) {
                     const uint64_t sl = std::min<uint64_t>(G, P - k * G), hk = pos + k * (G + 28), so_ = hk + 8;
@@ -972,7 +985,8 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
                     const uint32_t si = (uint32_t)gsegs.size();
                     uint8_t j0[16], eb[16];
                     memcpy(j0, gm.ctr_iv, 7);
-                    j0[7] = (uint8_t)(k >> 24); j0[8] = (uint8_t)(k >> 16); j0[9] = (uint8_t)(k >> 8); j0[10] = (uint8_t)k; j0[11] = k + 1 == K ? 1 : 0;
+                    const uint64_t q = J + k;                                    // the segment's counter in the stream
+                    j0[7] = (uint8_t)(q >> 24); j0[8] = (uint8_t)(q >> 16); j0[9] = (uint8_t)(q >> 8); j0[10] = (uint8_t)q; j0[11] = last && k + 1 == K ? 1 : 0;
                     j0[12] = 0; j0[13] = 0; j0[14] = 0; j0[15] = 1;
                     aes256_block_host(gm.rk, j0, eb);
                     GcmSeg gs; memcpy(gs.ctr_iv, j0, 16); gs.ctr_iv[15] = 2; gs.entry = 0;
@@ -986,8 +1000,8 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
                         for (uint64_t o = 0; o < sl; o += (1u << 20))
                             spread.push_back(SpreadPiece{spread_bytes + k * G + o, so_ + o, (uint32_t)std::min<uint64_t>(1u << 20, sl - o)});
                 }
-                if (K > 1) spread_bytes += (P + 15) & ~(uint64_t)15;
-                pos += P + 28 * K;
+                if (K > 1) spread_bytes += (E + 15) & ~(uint64_t)15;
+                pos += E + 28 * K;
                 nunit = (size_t)K; blob_len = 8 * (size_t)K;
             } else {
             for (uint32_t sg = 0; sg < nseg; sg++) {
@@ -997,12 +1011,13 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
                 memcpy(pf + 4, "SDAT", 4);
                 fds[sg] = FrameDesc{pos, (uint32_t)plen, 8u * sg, 8u, 0};
                 segdst[sg] = pos + 8;
-                if (fj->cipher)                                    // one cipher stream over all SDAT bodies: the keystream position runs on
+                if (fj->cipher)                                    // one cipher stream over all SDAT bodies: the keystream position runs on (over windows too)
                     for (uint64_t o = 0; o < plen; o += CTR_UNIT)
-                        cunits.push_back(CipherUnit{pos + 8 + o, (seg_off[sg] - seg_off[0]) + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, plen - o), 0u});
+                        cunits.push_back(CipherUnit{pos + 8 + o, ctr_base + (seg_off[sg] - seg_off[0]) + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, plen - o), 0u});
                 pos += 8 + plen + 4;
             }
             blob_len = 8 * (size_t)nseg;
+            if (fj->crun) fj->crun->pos += seg_off[nseg] - seg_off[0];
             }
         } else {
             // FlattenWriter cuts an entry's stream into FDAT chunks of max_chunk_size bytes, the last one holding the rest (lib/src/util/io.rs:60-77:
@@ -1106,6 +1121,9 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     else launch_write(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p,
                  (const SegTables *)c->tabs.p, d_segdst, (const uint8_t *)c->lits.p,
                  (const uint8_t *)c->litc.p, (const uint8_t *)c->seqc.p, wbase, any_empty, st, /* a wave per block */ max_len <= 32768 && nseg >= 4096);
+    // windowed GCM: the carry of the window before in front of the write kernels' output, then the new carry out of it (both before the spread)
+    if (gcm_carry_in) HIPCHK(c, hipMemcpyAsync(d_dst + gcm_carry_in, fj->crun->carry, gcm_carry_in_len, hipMemcpyDeviceToDevice, st));
+    if (gcm_carry_out) HIPCHK(c, hipMemcpyAsync(fj->crun->carry, d_dst + gcm_carry_out, fj->crun->carry_len, hipMemcpyDeviceToDevice, st));
     if (!spread.empty()) {
         // entries of several FDAT chunks / GCM segments: save the compact payloads, then put the pieces behind the first one at their places
         std::vector<PlaceDescH> pd(spread.size());

@@ -22,7 +22,8 @@ namespace {
 struct SolidSpan { uint64_t pos, len; uint32_t kind; uint32_t chunk; uint64_t a, b; };     // kind 0: blob[a ..), 1: entry a from byte b on, 2: the CRC of chunk `chunk`
 struct SolidChunk { uint32_t state = 0, crc = 0; uint64_t end = 0; bool started = false, done = false; };   // end: stream position behind the chunk's data
 }
-static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
+static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
+                        const pna_gpu_cipher *cipher, const uint8_t *ivs, pna_sink_fn sink, void *user) {
     set_call_level(c, algo, level);
     hipStream_t st = c->stream;
     // ---- the stream's layout
@@ -55,19 +56,33 @@ static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const cha
     const uint64_t plain_len = pos;
     // ---- the fixed chunks around the stream
     std::vector<uint8_t> head, tail;
-    frame_archive_head(head, 0); frame_solid_head(head, algo);
+    const bool gcm = cipher && cipher->cipher_mode == PNA_MODE_GCM;
+    const uint64_t G = gcm ? (cipher->gcm_segment_size ? cipher->gcm_segment_size : (1u << 20)) : 0;
+    frame_archive_head(head, 0);
+    if (gcm) {                                                  // the stream header is the stream's first SDAT chunk, as in the device form
+        GcmMaterial gm; uint8_t kc[32], ph[32];
+        hkdf_sha256_32(cipher->key, 32, nullptr, 0, "PNA-KC-v1", 9, kc);
+        sha256_bytes(cipher->phsf, strlen(cipher->phsf), nullptr, 0, ph);
+        gcm_entry_material(cipher, kc, ph, ivs, (uint32_t)G, nullptr, algo, gm);
+        frame_solid_head_enc(head, algo, cipher->encryption, cipher->cipher_mode, cipher->phsf, gm.header, 75);
+    } else if (cipher) frame_solid_head_enc(head, algo, cipher->encryption, cipher->cipher_mode, cipher->phsf, ivs, 16);
+    else frame_solid_head(head, algo);
     frame_solid_tail(tail); frame_archive_tail(tail);
     if (sink(user, head.data(), head.size()) != 0) return fail(c, PNA_E_SINK, "sink failed");
     const uint64_t W = std::max<uint64_t>(1, (uint64_t)c->tun.solid_win_mib) << 20;           // a multiple of SEG_SIZE
     const uint64_t nwin = (plain_len + W - 1) / W;
     const uint64_t wcap_in = std::min<uint64_t>(W, plain_len) + 8192;
-    const uint64_t wcap_out = pna_gpu_bound(algo, (size_t)std::min<uint64_t>(W, plain_len)) + (std::min<uint64_t>(W, plain_len) / SEG_SIZE + 2) * 16 + 4096;
+    uint64_t wcap_out = pna_gpu_bound(algo, (size_t)std::min<uint64_t>(W, plain_len)) + (std::min<uint64_t>(W, plain_len) / SEG_SIZE + 2) * 16 + 4096;
+    if (gcm) wcap_out += G + 28 * ((wcap_out + G) / G + 2);    // GCM: the carry in front, a tag and SDAT framing per segment
     int rc = ensure_crc(c); if (rc) return rc;
     const uint64_t slot_in = (wcap_in + 255) & ~(uint64_t)255, slot_out = (wcap_out + 255) & ~(uint64_t)255;   // the two device slots each way
     if (c->stage_in.ensure(2 * slot_in + 64) || c->stage_out.ensure(2 * slot_out + 64) || c->hp_in[0].ensure(wcap_in) || c->hp_in[1].ensure(wcap_in) ||
         c->hp_out[0].ensure(wcap_out) || c->hp_out[1].ensure(wcap_out)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
     const bool defl = algo == PNA_ALGO_DEFLATE;
     if (defl && c->solid_adler.ensure(64)) return fail(c, PNA_E_NOMEM, "solid workspace");                  // the stream's Adler-32 (A, B) between windows
+    if (gcm && c->solid_carry.ensure(G + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");              // the GCM carry between windows
+    SolidCipherRun crun;
+    crun.carry = (uint8_t *)c->solid_carry.p;
     const CallTotalScope call_total(c, plain_len);                                            // every window picks the block size of the whole stream
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     const unsigned T = c->tun.stage_threads > 0 ? (unsigned)c->tun.stage_threads : std::min(8u, std::max(1u, hw / 2));
@@ -155,8 +170,9 @@ static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const cha
         std::thread next;
         if (k + 1 < nwin) next = std::thread([&, k]() { assemble(k + 1, win[(k + 1) & 1]); });
         const uint64_t off0 = 0, len0 = wl; uint64_t offs[2] = {0, 0};
-        FrameJob fj{nullptr, 1, nullptr, nullptr};
+        FrameJob fj{nullptr, 1, cipher, ivs};
         fj.stream_len = plain_len;
+        if (cipher) { crun.final_win = k + 1 == nwin; fj.crun = &crun; }
         if (defl) { fj.run = (k > 0 ? DRUN_CONT : 0u) | (k + 1 < nwin ? DRUN_OPEN : 0u); fj.adler_carry = (uint32_t *)c->solid_adler.p; }
         rc = run_subbatch(c, algo, d_in, &off0, &len0, 0, 1, d_out, wcap_out, 0, offs, st, false, &fj);
         if (rc == PNA_OK && hipMemcpyAsync(c->hp_out[k & 1].p, d_out, offs[1], hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
@@ -181,24 +197,20 @@ extern "C" uint64_t pna_gpu_debug_pinned_bytes(pna_gpu_ctx *c) {
 
 // no entries, or zstd's single_frame option (an entry's segments form ONE frame): one H2D of the entries, the device path, one D2H of the archive, handed
 // to the sink in pieces of at most 16 MiB
-extern "C" int pna_gpu_create_solid_archive_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
-                                                 const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
-    if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n && c->tun.solid_win_mib > 0 && (algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_ZSTD && !c->tun.single_frame)))
-        return solid_stream(c, algo, level, n, names, src, src_len, sink, user);
+static int solid_one_shot(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
+                          const pna_gpu_cipher *cipher, pna_sink_fn sink, void *user) {
     std::vector<uint64_t> off(n + 1), len(n);
     uint64_t pos = 0;
     for (size_t i = 0; i < n; i++) { off[i] = pos; len[i] = src_len[i]; pos = (pos + src_len[i] + 15) & ~(uint64_t)15; }
     off[n] = pos;
-    const size_t cap = pna_gpu_solid_archive_bound(algo, n, names, len.data());
+    const size_t cap = pna_gpu_solid_archive_enc_bound(algo, n, names, len.data(), cipher);
     if (c->stage_in.ensure(pos + 8192) || c->stage_out.ensure(cap + 64) || c->hp_in[0].ensure(pos + 64) || c->hp_out[0].ensure(cap + 64))
         return fail(c, PNA_E_NOMEM, "staging allocation failed");
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     parallel_stage((uint8_t *)c->hp_in[0].p, src, src_len, off.data(), 0, n, std::min(8u, std::max(1u, hw / 2)));
     if (pos) HIPCHK(c, hipMemcpyAsync(c->stage_in.p, c->hp_in[0].p, pos, hipMemcpyHostToDevice, c->stream));
     uint64_t total = 0;
-    int rc = pna_gpu_create_solid_archive_device(c, algo, level, n, names, c->stage_in.p, off.data(), len.data(), c->stage_out.p, cap + 64, &total, nullptr);
+    int rc = pna_gpu_create_solid_archive_enc_device(c, algo, level, n, names, c->stage_in.p, off.data(), len.data(), cipher, c->stage_out.p, cap + 64, &total, nullptr);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->hp_out[0].p, c->stage_out.p, total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -207,6 +219,35 @@ extern "C" int pna_gpu_create_solid_archive_host(pna_gpu_ctx *c, int algo, int l
         if (sink(user, (const uint8_t *)c->hp_out[0].p + p, k) != 0) return fail(c, PNA_E_SINK, "sink failed");
     }
     return PNA_OK;
+}
+static bool solid_windowed(const pna_gpu_ctx *c, int algo, size_t n) {
+    return n && c->tun.solid_win_mib > 0 && (algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_ZSTD && !c->tun.single_frame));
+}
+extern "C" int pna_gpu_create_solid_archive_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                                 const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
+    if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, nullptr, nullptr, sink, user);
+    return solid_one_shot(c, algo, level, n, names, src, src_len, nullptr, sink, user);
+}
+// The same with a cipher (into_solid_archive, lib/src/archive/write.rs:443-470): CTR -- one keystream over all SDAT bodies, continued from window to
+// window at the stream offset of the window's first compressed byte; GCM STREAM -- segments cut from the whole compressed stream, each window holding
+// back in device memory the tail that is not yet known to be a non-final segment (SolidCipherRun).  The archive equals
+// pna_gpu_create_solid_archive_enc_device's for the same IV / salt.
+extern "C" int pna_gpu_create_solid_archive_enc_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                                     const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                                     pna_sink_fn sink, void *user) {
+    if (!cipher || cipher->encryption == PNA_ENC_NONE) return pna_gpu_create_solid_archive_host(c, algo, level, n, names, src, src_len, sink, user);
+    if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
+    std::vector<uint8_t> own_ivs;
+    const uint8_t *ivs = nullptr;
+    int rc = resolve_ivs(c, cipher, 1, own_ivs, &ivs); if (rc) return rc;
+    if (cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    HIPCHK(c, hipSetDevice(c->device));
+    pna_gpu_cipher ci = *cipher; ci.ivs = ivs;                  // (IVs drawn here: the one-shot form must not draw others)
+    if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, &ci, ivs, sink, user);
+    return solid_one_shot(c, algo, level, n, names, src, src_len, &ci, sink, user);
 }
 
 // ---------------------------------------------------------------------------------------------------------
