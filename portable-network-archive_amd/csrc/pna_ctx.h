@@ -37,7 +37,7 @@ void launch_deflate_write(const uint8_t *src, const SegDesc *segs, const uint32_
                           const uint64_t *seg_off, const uint64_t *seg_size, const uint8_t *outc, const uint32_t *entry_seg, uint32_t nentry,
                           uint8_t *dst, hipStream_t st, bool stored_only, bool small_blocks);
 // (k_deflate.hip) one window of a zlib stream compressed in windows: k_dwrite, then k_dfold (header / trailer by the window's place, the Adler-32 carry).
-// A weak reference: the sanitizer build of the host code (tests/san) links its own stand-ins for the launch layer and has none for it -- run_subbatch
+// A weak reference: the sanitizer build of the host code (tests/san) links its own stand-ins for the launch layer and has none for it -- write_stage
 // refuses a deflate window when it is absent; the library always defines it.
 __attribute__((weak)) void launch_deflate_write_run(const uint8_t *src, const SegDesc *segs, const uint32_t *blk_seg, uint32_t nblk, const BlkInfo *blk,
                                                     const uint64_t *seg_off, const uint64_t *seg_size, const uint8_t *outc, const uint32_t *entry_seg,
@@ -156,10 +156,8 @@ struct Tuning {
                                      // until then 32 768 = 4 GiB per run, and the 10 GiB headline paid three kernel tails per stage -- one run: 74.7 -> 73.5 ms; a workspace that cannot be had is halved, as before)
     long lz_split_min = 0;           // PNA_LZ_SPLIT_MIN: shortest run (segments) that takes the split form (0: every run; shorter ones take the one-kernel form)
     long lz_pbuf_fail = 0;           // PNA_LZ_PBUF_FAIL: testing -- behave as if the words workspace could not be allocated
-    long pipeline_chunks = 1;        // PNA_PIPELINE_CHUNKS: zstd entropy stage of chunk k next to the LZ stage of chunk k + 1 (measured: slower)
     long max_chunk_size = 0;         // PNA_MAX_CHUNK_SIZE: FlattenWriter::max_chunk_size of the archive entry points without such a parameter (0 = the reference's default, u32::MAX)
     long sub_mib = 256;              // PNA_SUB_MIB: largest sub-batch (input bytes) of the bounded host pipeline
-    long sub_ramp_down = 0;          // PNA_SUB_RAMP_DOWN: sub-batches shrink towards the end of the input (measured: no gain)
     long stage_threads = 0;          // PNA_STAGE_THREADS: host threads that stage entries into page-locked memory (0: min(8, cores / 2))
     long extract_win_mib = 1024;     // PNA_EXTRACT_WIN_MIB: archive bytes per window of the extract driver
     long solid_win_mib = 256;        // PNA_SOLID_WIN_MIB: pna_gpu_create_solid_archive_host takes the serialised inner entries through in windows of this many MiB (page-locked memory: ~4 windows)
@@ -253,9 +251,8 @@ struct pna_gpu_ctx {
     DevBuf dp_in[4], dp_out[2];
     hipStream_t cp_in = nullptr, cp_out = nullptr;
     uint64_t call_total = 0;                          // input bytes of the whole call that run_subbatch's sub-batch belongs to (0: the sub-batch is the call): decides the block size
-    hipStream_t aux = nullptr;                        // entropy stage of chunk c runs here while k_lz works on chunk c+1
-    static constexpr int MAXCH = 8;
-    hipEvent_t ev_lz[MAXCH + 1] = {}, ev_en[MAXCH][4] = {}, ev_join = nullptr, ev_fork = nullptr;
+    hipStream_t aux = nullptr;                        // zstd's literal coder next to the sequence coder (option lit_beside_seq)
+    hipEvent_t ev_lz[2] = {}, ev_en[4] = {}, ev_join = nullptr, ev_fork = nullptr;   // around the LZ stage, the entropy stage's parts; aux's fork and join
     hipEvent_t ev_in[4] = {}, ev_out[2] = {};
     bool crc_ready = false;
     bool corpus_ready = false;
@@ -310,15 +307,18 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
                   // a solid stream compressed in windows (pna_gpu_create_solid_archive_host): the sub-batch is one window of a stream of stream_len bytes and
                   // is planned as the whole stream; deflate: DRUN_* flags of the window's place in the stream, the stream's Adler-32 carry in device memory
                   uint64_t stream_len = 0; uint32_t run = 0; uint32_t *adler_carry = nullptr;
-                  // ... with a cipher: where the window stands in the cipher stream, updated by run_subbatch (SolidCipherRun)
+                  // ... with a cipher: where the window stands in the cipher stream, updated by layout_solid (SolidCipherRun)
                   struct SolidCipherRun *crun = nullptr; };
 // The cipher state of a solid stream compressed in windows.  CTR: `pos`, the stream offset of the window's first compressed byte (the keystream
 // continues).  GCM STREAM: segments are cut from the whole compressed stream -- `seg`, the counter of the next segment; `carry` (carry_len bytes,
 // 1 .. G once the stream has begun, in device memory) the tail of the output before that is not yet known to be a non-final segment, placed in
-// front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  run_subbatch advances
+// front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  layout_solid advances
 // pos, seg and carry_len past the window.
 struct SolidCipherRun { uint64_t pos = 0, seg = 0, carry_len = 0; uint8_t *carry = nullptr; bool final_win = false; };
 struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4], ej0[4]; uint8_t ctr_iv[16]; };
+struct GcmCallKeys { uint8_t kc[32], phsf_hash[32]; };
+// GCM STREAM segment size of a cipher job (0: the reference's DEFAULT_SEGMENT_SIZE, 1 MiB)
+inline uint32_t gcm_seg_size(const pna_gpu_cipher *ci) { return ci->gcm_segment_size ? ci->gcm_segment_size : (1u << 20); }
 
 void set_call_level(pna_gpu_ctx *c, int algo, int level);
 inline size_t plan_blocks(const pna_gpu_ctx *c, uint64_t len) {
@@ -326,7 +326,7 @@ inline size_t plan_blocks(const pna_gpu_ctx *c, uint64_t len) {
 }
 // Block size of a batch whose entries are all small: the per-block arrays have the block size as their stride, so a batch of 4 KiB entries on 128 KiB
 // blocks would spend 32 times the memory (and a sub-batch per 131 072 entries) that 8 KiB blocks need.  Entries of up to 64 KiB: the power of two that
-// holds the largest (>= 8 KiB); anything larger: 128 KiB.  (Latency mode, for small batches of large entries, chooses on top of this in run_subbatch.)
+// holds the largest (>= 8 KiB); anything larger: 128 KiB.  (Latency mode, for small batches of large entries, chooses on top of this in plan_geometry.)
 // The input bytes of the whole call for the duration of a scope (pna_gpu_ctx::call_total: run_subbatch picks the block size by the call, not by its sub-batches)
 // A scope opened while another is open on the context (an entry point that cuts its call into parts or pieces and runs each through another entry point: the
 // multi-context create, the host form of compress_batch) leaves the outer total in place -- every part then picks the block size of the WHOLE call, so the
@@ -345,13 +345,6 @@ inline uint32_t blk_log_for_longest(const pna_gpu_ctx *c, uint64_t mx) {
     uint32_t lg = BLK_LOG_MIN;
     while (((uint64_t)1 << lg) < mx) lg++;
     return lg;
-}
-template <class L>
-inline uint32_t small_entry_blk_log(const pna_gpu_ctx *c, const L *src_len, size_t e0, size_t e1) {
-    if (c->tun.blk_log) return (uint32_t)c->tun.blk_log;
-    uint64_t mx = 0;
-    for (size_t e = e0; e < e1; e++) mx = std::max<uint64_t>(mx, src_len[e]);
-    return blk_log_for_longest(c, mx);
 }
 // The per-entry host loops of a sub-batch of 10^5 .. 10^6 small entries (plan, bounds, record prefixes) run on several threads over CONTIGUOUS index
 // ranges: fn(t, a, b) for thread t and its range [a, b) of [0, n); the caller's thread takes the first range.
@@ -414,9 +407,9 @@ inline void plan_call_longest(pna_gpu_ctx *c, uint64_t longest) {           // p
 }
 template <class L>
 inline void plan_call(pna_gpu_ctx *c, const L *src_len, size_t n) {
-    c->plan_log = small_entry_blk_log(c, src_len, 0, n);
-    const uint64_t per_block = (uint64_t)seq_cap_of(c->plan_log) * 16 + ((uint64_t)3 << c->plan_log) + 64;
-    c->max_blocks = (size_t)std::max<uint64_t>(1024, (96ull << 30) / per_block);
+    uint64_t mx = 0;
+    if (!c->tun.blk_log) for (size_t e = 0; e < n; e++) mx = std::max<uint64_t>(mx, src_len[e]);     // (a forced block size needs no longest entry)
+    plan_call_longest(c, mx);
 }
 
 
@@ -430,8 +423,11 @@ void aes256_expand(const uint8_t key[32], AesKey &k);
 void aes256_dec_key(const AesKey &k, AesKey &d);
 void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]);
 int  resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs);
-void gcm_entry_material(const pna_gpu_cipher *ci, const uint8_t kc[32], const uint8_t phsf_hash[32], const uint8_t salt_prefix[39],
-                        uint32_t seg_size, const char *name, int compression, GcmMaterial &m);
+GcmCallKeys gcm_call_keys(const pna_gpu_cipher *ci);
+void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const uint8_t salt_prefix[39], uint32_t seg_size, const char *name, int compression,
+                        GcmMaterial &m);
+void gcm_solid_material(const pna_gpu_cipher *ci, const uint8_t salt_prefix[39], int compression, GcmMaterial &m);
+void solid_archive_head(std::vector<uint8_t> &head, int compression, const pna_gpu_cipher *ci, const uint8_t *ivs);
 uint64_t chunk_limit(uint32_t max_chunk);
 size_t meta_len(const pna_gpu_entry_meta *m, size_t e);
 bool meta_blob_ok(const uint8_t *p, size_t n);

@@ -5,13 +5,13 @@
 static const TuningName TUNING_NAMES[] = {
     {"lz_split", "PNA_LZ_SPLIT", &Tuning::lz_split, 0, 2}, {"lz_split_blocks", "PNA_LZ_SPLIT_BLOCKS", &Tuning::lz_split_blocks, 8, 1 << 17},
     {"lz_split_min", "PNA_LZ_SPLIT_MIN", &Tuning::lz_split_min, 0, 1 << 30}, {"lz_pbuf_fail", "PNA_LZ_PBUF_FAIL", &Tuning::lz_pbuf_fail, 0, 1},
-    {"pipeline_chunks", "PNA_PIPELINE_CHUNKS", &Tuning::pipeline_chunks, 1, 8}, {"max_chunk_size", "PNA_MAX_CHUNK_SIZE", &Tuning::max_chunk_size, 0, 0xFFFFFFFFl},
+    {"max_chunk_size", "PNA_MAX_CHUNK_SIZE", &Tuning::max_chunk_size, 0, 0xFFFFFFFFl},
     {"sub_mib", "PNA_SUB_MIB", &Tuning::sub_mib, 16, 16384}, {"stage_threads", "PNA_STAGE_THREADS", &Tuning::stage_threads, 0, 64},
     {"extract_win_mib", "PNA_EXTRACT_WIN_MIB", &Tuning::extract_win_mib, 1, 1 << 20}, {"batch_piece_mib", "PNA_BATCH_PIECE_MIB", &Tuning::batch_piece_mib, 0, 1 << 20}, {"solid_win_mib", "PNA_SOLID_WIN_MIB", &Tuning::solid_win_mib, 1, 1 << 16},
     {"inflate_serial", "PNA_INFLATE_SERIAL", &Tuning::inflate_serial, 0, 1}, {"zdec_serial", "PNA_ZDEC_SERIAL", &Tuning::zdec_serial, 0, 1}, {"zdec_dbg", "PNA_ZDEC_DBG", &Tuning::zdec_dbg, 0, 15},
     {"blk_log", "PNA_BLK_LOG", &Tuning::blk_log, 0, PNA_BLK_LOG}, {"unit_log", "PNA_LZ_UNIT_LOG", &Tuning::unit_log, 0, 20},
     {"latency_max_mib", "PNA_LATENCY_MAX_MIB", &Tuning::latency_max_mib, 0, 1 << 20}, {"hist_by_block", "PNA_HIST_BY_BLOCK", &Tuning::hist_by_block, -1, 1},
-    {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1}, {"sub_ramp_down", "PNA_SUB_RAMP_DOWN", &Tuning::sub_ramp_down, 0, 1},
+    {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
 };
 
 extern "C" const char *pna_gpu_strerror(int code) {
@@ -84,7 +84,7 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->plan, &c->d_tail, &c->blk, &c->tabs, &c->seqs, &c->lits, &c->litc, &c->seqc, &c->seqw, &c->pbuf, &c->seg_size,
                       &c->seg_off, &c->stage_in, &c->stage_out, &c->z_words, &c->z_rep, &c->z_zxf, &c->z_spec, &c->z_big, &c->z_one, &c->ctab, &c->c_vocab, &c->c_cum, &c->c_phr,
-                      &c->gtab, &c->fr_desc, &c->fr_blob, &c->fr_segdst, &c->fr_entoff, &c->crc_tabs, &c->aes_tabs, &c->ci_units, &c->ci_ivs, &c->ci_keys, &c->ci_gcm, &c->ci_spread, &c->ci_spread_desc, &c->z_vp, &c->z_pb, &c->z_mode, &c->x_arc, &c->x_pk, &c->x_raw[0], &c->x_raw[1], &c->x_desc, &c->x_place, &c->x_flag, &c->x_tags, &c->x_plen, &c->aes_dtabs, &c->solid_plain, &c->solid_desc, &c->solid_blob, &c->solid_place, &c->solid_adler, &c->z_ents, &c->z_frames, &c->z_lit, &c->z_fx, &c->z_blocks, &c->z_tabs, &c->z_seqs, &c->z_hlist, &c->z_slist, &c->z_work, &c->z_fb, &c->z_cbase, &c->z_apart}) b->release();
+                      &c->gtab, &c->fr_desc, &c->fr_blob, &c->fr_segdst, &c->fr_entoff, &c->crc_tabs, &c->aes_tabs, &c->ci_units, &c->ci_ivs, &c->ci_keys, &c->ci_gcm, &c->ci_spread, &c->ci_spread_desc, &c->z_vp, &c->z_pb, &c->z_mode, &c->x_arc, &c->x_pk, &c->x_raw[0], &c->x_raw[1], &c->x_desc, &c->x_place, &c->x_flag, &c->x_tags, &c->x_plen, &c->aes_dtabs, &c->solid_plain, &c->solid_desc, &c->solid_blob, &c->solid_place, &c->solid_adler, &c->solid_carry, &c->z_ents, &c->z_frames, &c->z_lit, &c->z_fx, &c->z_blocks, &c->z_tabs, &c->z_seqs, &c->z_hlist, &c->z_slist, &c->z_work, &c->z_fb, &c->z_cbase, &c->z_apart}) b->release();
     for (auto &b : c->lent) (void)hipHostFree((void *)b.first);          // (buffers the host never gave back)
     c->lent.clear();
     for (PinBuf *b : {&c->h_entoff, &c->h_plan, &c->h_tail, &c->h_desc, &c->h_blob, &c->h_segdst, &c->h_segoff, &c->hp_in[0], &c->hp_in[1], &c->hp_in[2], &c->hp_in[3], &c->hp_out[0], &c->hp_out[1]}) b->release();
@@ -94,7 +94,7 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     for (auto &e : c->ev_lz) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->lzm_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_ci) if (e) (void)hipEventDestroy(e);
-    for (auto &r : c->ev_en) for (auto &e : r) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_en) if (e) (void)hipEventDestroy(e);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->aux) (void)hipStreamDestroy(c->aux);
@@ -171,7 +171,6 @@ extern "C" int pna_gpu_last_timing(const pna_gpu_ctx *c, pna_gpu_timing *out) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// One sub-batch: entries [e0, e1) -> segments -> kernels; output appended at d_dst + out_base.
 // ---- CRC-32 tables of the framing kernel (k_frame.hip explains the algebra)
 uint32_t crc_gf2_mulmod(uint32_t a, uint32_t b);
 uint32_t crc_gf2_xpow(uint64_t e);
@@ -333,17 +332,17 @@ void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]) {
 // the FHED chunk and the PHSF string, round keys, hash subkey, E(K, J0) of the (single, final) segment 0 and its first counter block.
 // (the stream key is bound to the header chunk of the entry that carries the stream: FHED of a normal entry, SHED of a solid one -- entry_context,
 // lib/src/cipher/aead.rs:167-190; name == nullptr: the solid entry's SHED)
-void gcm_entry_material(const pna_gpu_cipher *ci, const uint8_t kc[32], const uint8_t phsf_hash[32], const uint8_t salt_prefix[39],
-                               uint32_t seg_size, const char *name, int compression, GcmMaterial &m) {
+void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const uint8_t salt_prefix[39], uint32_t seg_size, const char *name, int compression,
+                        GcmMaterial &m) {
     memcpy(m.header, salt_prefix, 39);
     m.header[39] = (uint8_t)(seg_size >> 24); m.header[40] = (uint8_t)(seg_size >> 16); m.header[41] = (uint8_t)(seg_size >> 8); m.header[42] = (uint8_t)seg_size;
-    memcpy(m.header + 43, kc, 32);
+    memcpy(m.header + 43, keys.kc, 32);
     const std::vector<uint8_t> fh = name ? frame_fhed_bytes(name, compression, ci->encryption, PNA_MODE_GCM)
                                          : std::vector<uint8_t>{0, 0, (uint8_t)compression, (uint8_t)ci->encryption, (uint8_t)PNA_MODE_GCM};
     uint8_t info[88];
     memcpy(info, "PNA-STREAM-v1", 13);
     sha256_bytes(name ? "FHED" : "SHED", 4, fh.data(), fh.size(), info + 13);
-    memcpy(info + 45, phsf_hash, 32);
+    memcpy(info + 45, keys.phsf_hash, 32);
     memcpy(info + 77, salt_prefix + 32, 7);
     memcpy(info + 84, m.header + 39, 4);
     uint8_t ks[32];
@@ -359,6 +358,27 @@ void gcm_entry_material(const pna_gpu_cipher *ci, const uint8_t kc[32], const ui
         m.ej0[i] = ((uint32_t)eb[4 * i] << 24) | ((uint32_t)eb[4 * i + 1] << 16) | ((uint32_t)eb[4 * i + 2] << 8) | eb[4 * i + 3];
     }
     memcpy(m.ctr_iv, j0, 16); m.ctr_iv[15] = 2;                                           // first data block: counter 2
+}
+// what the GCM STREAMs of a call share: the key confirmation (key_confirmation, aead.rs:161-163) and the hash of the PHSF string
+GcmCallKeys gcm_call_keys(const pna_gpu_cipher *ci) {
+    GcmCallKeys k;
+    hkdf_sha256_32(ci->key, 32, nullptr, 0, "PNA-KC-v1", 9, k.kc);
+    sha256_bytes(ci->phsf, strlen(ci->phsf), nullptr, 0, k.phsf_hash);
+    return k;
+}
+// ... the material of a solid archive's one stream (bound to its SHED chunk)
+void gcm_solid_material(const pna_gpu_cipher *ci, const uint8_t salt_prefix[39], int compression, GcmMaterial &m) {
+    gcm_entry_material(ci, gcm_call_keys(ci), salt_prefix, gcm_seg_size(ci), nullptr, compression, m);
+}
+// The head of a solid archive: signature + AHED, then SHED; with a cipher PHSF and the stream's first write, a chunk of its own -- the IV (CTR) or
+// the stream header (GCM: salt || nonce prefix || segment size || key confirmation, 75 bytes)
+void solid_archive_head(std::vector<uint8_t> &head, int compression, const pna_gpu_cipher *ci, const uint8_t *ivs) {
+    frame_archive_head(head, 0);
+    if (!ci) { frame_solid_head(head, compression); return; }
+    if (ci->cipher_mode != PNA_MODE_GCM) { frame_solid_head_enc(head, compression, ci->encryption, ci->cipher_mode, ci->phsf, ivs, 16); return; }
+    GcmMaterial gm;
+    gcm_solid_material(ci, ivs, compression, gm);
+    frame_solid_head_enc(head, compression, ci->encryption, ci->cipher_mode, ci->phsf, gm.header, 75);
 }
 // the per-entry IVs of a cipher job: the caller's, or random ones (random::random_vec(block_size) per entry, lib/src/entry/write.rs:108-112)
 int resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs) {
@@ -419,6 +439,13 @@ static void splice_meta(std::vector<uint8_t> &pre, const pna_gpu_entry_meta *m, 
 // stream, so runs share it) --, shorter ones and PNA_F_LZ_FUSED / PNA_LZ_SPLIT=0 the one-kernel form (k_lz<MODE 0>, no pbuf);
 // PNA_F_LZ_WAVEPARSE / PNA_LZ_SPLIT=2: the split form as k_lz<MODE 1> + k_lz<MODE 2> (testing).  All forms give the same bytes.  If pbuf
 // cannot be had, the run is halved down to 1 024 blocks, then fused.
+// The end of a run of segments from `a` on: the first segment before s1 whose blocks no longer fit `run_blocks` blocks from a's first one (block bases grow
+// with the index: a binary search -- 10^6 small entries made the linear walk a millisecond)
+static uint32_t run_end(const SegDesc *segs, uint32_t nseg_all, uint32_t nblk, uint32_t a, uint32_t s1, uint32_t bps, uint32_t run_blocks) {
+    uint32_t b = a + 1, hi = s1;
+    while (b < hi) { const uint32_t mid = b + (hi - b) / 2; if ((mid < nseg_all ? segs[mid].blk_base : nblk) - segs[a].blk_base + bps <= run_blocks) b = mid + 1; else hi = mid; }
+    return b;
+}
 // The SHORT segments among [s0, s1) behind a launch of the one-kernel form, which skips them (pna_dev.h SMALL_SEG): k_lzms + the parse kernel over their blocks, through
 // the words workspace, in runs of blocks as the split form's
 static int lz_small_pass(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, uint32_t nseg_all, uint32_t s0, uint32_t s1, uint32_t nblk, uint4 *ctab,
@@ -427,11 +454,7 @@ static int lz_small_pass(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *se
     const uint32_t bps = 1u << (20 - segs[s0].blk_log);
     for (uint32_t a = s0; a < s1;) {
         const uint32_t b0 = segs[a].blk_base;
-        uint32_t b = a + 1;
-        {   // the first segment behind `a` whose blocks no longer fit the run (block bases grow with the index: a binary search -- 10^6 small entries made the linear walk a millisecond)
-            uint32_t hi = s1;
-            while (b < hi) { const uint32_t mid = b + (hi - b) / 2; if ((mid < nseg_all ? segs[mid].blk_base : nblk) - b0 + bps <= run_blocks) b = mid + 1; else hi = mid; }
-        }
+        const uint32_t b = run_end(segs, nseg_all, nblk, a, s1, bps, run_blocks);
         const uint32_t b1 = b < nseg_all ? segs[b].blk_base : nblk;
         if (c->pbuf.ensure(((size_t)std::max<uint32_t>(b1 - b0, 1) << segs[a].blk_log) * 4)) {
             (void)hipGetLastError();
@@ -476,11 +499,7 @@ static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, u
     const uint32_t min_segs = gt ? 0u : (uint32_t)c->tun.lz_split_min;
     for (uint32_t a = s0; a < s1 && !fused;) {
         const uint32_t b0 = segs[a].blk_base;
-        uint32_t b = a + 1;
-        {   // the first segment behind `a` whose blocks no longer fit the run (block bases grow with the index: a binary search -- 10^6 small entries made the linear walk a millisecond)
-            uint32_t hi = s1;
-            while (b < hi) { const uint32_t mid = b + (hi - b) / 2; if ((mid < nseg_all ? segs[mid].blk_base : nblk) - b0 + bps <= split_blocks) b = mid + 1; else hi = mid; }
-        }
+        const uint32_t b = run_end(segs, nseg_all, nblk, a, s1, bps, split_blocks);
         const uint32_t b1 = b < nseg_all ? segs[b].blk_base : nblk;
         if (b - a < min_segs && !waveparse) { s0 = a; s1 = b; fused_tail = b < s1_all; break; }
         if ((c->tun.lz_pbuf_fail && !gt) /* testing: as if the allocation failed */ || c->pbuf.ensure(((size_t)std::max<uint32_t>(b1 - b0, 1) << segs[a].blk_log) * 4) ||
@@ -537,32 +556,20 @@ static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, u
 }
 
 // stage times of a finished sub-batch from its events (the stream has been waited for)
-static int collect_timing(pna_gpu_ctx *c, bool defl, int nch, uint32_t nseg, uint32_t nblk, bool with_cipher) {
+static int collect_timing(pna_gpu_ctx *c, bool defl, uint32_t nseg, uint32_t nblk, bool with_cipher) {
     float ms[6] = {0, 0, 0, 0, 0, 0}, msf = 0;
     (void)hipEventElapsedTime(&msf, c->ev[6], c->ev[7]);
     c->timing.ms_frame += msf;
     float mc = 0;                                             // the cipher kernels run inside the "pack" interval: report them apart
     if (with_cipher) { (void)hipEventElapsedTime(&mc, c->ev_ci[0], c->ev_ci[1]); c->timing.ms_cipher += mc; c->timing.ms_pack -= mc; }
     if (defl) {
-        (void)hipEventElapsedTime(&ms[0], c->ev[0], c->ev[1]);
-        (void)hipEventElapsedTime(&ms[1], c->ev[1], c->ev[2]);
-        (void)hipEventElapsedTime(&ms[2], c->ev[2], c->ev[3]);
-        (void)hipEventElapsedTime(&ms[3], c->ev[3], c->ev[4]);
-        (void)hipEventElapsedTime(&ms[4], c->ev[4], c->ev[5]);
-        (void)hipEventElapsedTime(&ms[5], c->ev[5], c->ev[6]);
+        for (int i = 0; i < 6; i++) (void)hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]);
     } else {
-        // k_lz: first launch to last completion on the main stream; the entropy stages are summed over the chunks on the
-        // auxiliary stream (with more than one chunk they overlap k_lz and add up to more than the wall time); "pack" = from the
-        // end of the last chunk's entropy stage to the end of the write kernels (plan + scan + layout + write)
-        (void)hipEventElapsedTime(&ms[0], c->ev_lz[0], c->ev_lz[nch]);
-        for (int k = 0; k < nch; k++) {
-            float a = 0, b2 = 0, d = 0;
-            (void)hipEventElapsedTime(&a, c->ev_en[k][0], c->ev_en[k][1]);
-            (void)hipEventElapsedTime(&b2, c->ev_en[k][1], c->ev_en[k][2]);
-            (void)hipEventElapsedTime(&d, c->ev_en[k][2], c->ev_en[k][3]);
-            ms[1] += a; ms[2] += b2; ms[3] += d;
-        }
-        (void)hipEventElapsedTime(&ms[4], c->ev_en[nch - 1][3], c->ev[6]);
+        // k_lz: first launch to last completion; the entropy stage's statistics, literal and sequence parts; "pack" = from the end of the
+        // entropy stage to the end of the write kernels (plan + scan + layout + write)
+        (void)hipEventElapsedTime(&ms[0], c->ev_lz[0], c->ev_lz[1]);
+        for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&ms[1 + i], c->ev_en[i], c->ev_en[i + 1]);
+        (void)hipEventElapsedTime(&ms[4], c->ev_en[3], c->ev[6]);
     }
     c->timing.ms_lz += ms[0]; c->timing.ms_stats += ms[1]; c->timing.ms_lit += ms[2]; c->timing.ms_seq += ms[3];
     c->timing.ms_pack += ms[4] + ms[5];
@@ -571,51 +578,37 @@ static int collect_timing(pna_gpu_ctx *c, bool defl, int nch, uint32_t nseg, uin
     return PNA_OK;
 }
 
-int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
-                        size_t e0, size_t e1, uint8_t *d_dst, size_t dst_cap, uint64_t out_base, uint64_t *dst_off,
-                        hipStream_t st, bool timed, const FrameJob *fj) {
-    // LATENCY MODE: a small batch -- the CompressionWriter seam with a handful of writers in flight, one entry of
-    // `pna_gpu_compress_batch` -- has fewer segments than the chip has CUs, and its time is the length of the per-segment and per-block serial
-    // chains (one workgroup walks a segment's 256 tiles; one lane codes a block's sequences).  Such a batch is cut finer: blocks of 8 .. 64 KiB
-    // inside the same frames (blk_log), and the LZ stage runs one workgroup per UNIT of 1 << unit_log bytes whose table is pre-warmed with
-    // everything before it (lz_prewarm), which gives the very matches of the segment-long walk.  Both follow from the batch's size alone
-    // (and pna_gpu_set_option), are reported by pna_gpu_last_timing, and are parameters of the oracle's model.
-    // option trace: the HOST's time line of the sub-batch (what it does before and next to the kernels), printed when the call ends
-    const auto t_host0 = std::chrono::steady_clock::now();
-    std::vector<std::pair<const char *, double>> host_marks;
-    auto mark = [&](const char *what) { if (c->tun.trace) host_marks.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count()); };
-    auto print_marks = [&]() { if (c->tun.trace && !host_marks.empty()) { fprintf(stderr, "[pna sub-batch] %zu entries, host:", e1 - e0); for (auto &m : host_marks) fprintf(stderr, "  %s %.2f", m.first, m.second); fprintf(stderr, " ms\n"); } };
-    const size_t ne_all = e1 - e0;
-    const unsigned host_nt = host_loop_threads(ne_all);
-    struct PlanPart { uint64_t in_total = 0, nseg_est = 0, max_len = 0, n_short = 0, n_mid = 0, max_mid = 0; uint32_t sg = 0, bk = 0, un = 0; bool misaligned = false, any_empty = false; };
-    std::vector<PlanPart> pp(host_nt);
-    par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
-        PlanPart q;
-        for (size_t e = e0 + a; e < e0 + b; e++) {
-            const uint64_t len = src_len[e];
-            q.in_total += len; q.nseg_est += len ? (len + SEG_SIZE - 1) / SEG_SIZE : 1; q.max_len = std::max<uint64_t>(q.max_len, len);
-            q.misaligned |= (src_off[e] & 15) != 0; q.any_empty |= len == 0;
-            // SHORT segments (pna_dev.h SMALL_SEG): an entry of at most that many bytes, or the last segment of a longer one
-            const uint64_t last = len ? ((len - 1) & (SEG_SIZE - 1)) + 1 : 0;
-            q.n_short += (last > 0 && last <= SMALL_SEG) ? 1u : 0u; if (last > SMALL_SEG && last <= MID_SEG) { q.n_mid++; q.max_mid = std::max(q.max_mid, last); }
-        }
-        pp[t] = q;
-    });
-    uint64_t in_total = 0, nseg_est = 0, max_len = 0, n_short = 0, n_mid = 0, max_mid = 0;
-    bool any_empty = false;
-    for (const PlanPart &q : pp) {
-        in_total += q.in_total; nseg_est += q.nseg_est; max_len = std::max(max_len, q.max_len); any_empty |= q.any_empty; n_short += q.n_short; n_mid += q.n_mid; max_mid = std::max(max_mid, q.max_mid);
-        if (q.misaligned) return fail(c, PNA_E_INVAL, "entry offset not 16-byte aligned");
-    }
-    if (fj && fj->stream_len) {
-        // one window of a solid stream: block size, latency form and units follow from the whole stream, as in its one-shot run, so that the window's
-        // segments are coded as they are there (a window is whole segments: the short ones are the stream's own)
-        in_total = fj->stream_len; nseg_est = (in_total + SEG_SIZE - 1) / SEG_SIZE; max_len = in_total;
-    }
-    // an upper bound of every payload of the sub-batch when the entries are small and plain (k_frame's wave-per-entry form takes those; 0: no such bound)
-    const uint32_t frame_max_payload = (fj && !fj->solid && !fj->cipher && max_len <= 16384) ? (uint32_t)std::min<size_t>(pna_gpu_bound(algo, (size_t)max_len), 0xFFFFFFFFu) : 0u;
+// ---- One sub-batch, in stages (run_subbatch below is their driver): plan -> compress -> prefixes -> layout (device, or host after a wait for the
+// segment sizes) -> write + carry + spread -> cipher -> frame + offsets + timing.
+// The arguments of one run_subbatch call, which every stage reads
+struct SubBatch { pna_gpu_ctx *c; int algo; const uint8_t *d_src; const uint64_t *src_off, *src_len; size_t e0, e1;
+                  uint8_t *d_dst; size_t dst_cap; uint64_t out_base; uint64_t *dst_off; hipStream_t st; bool timed; const FrameJob *fj; };
+// option trace: the HOST's time line of the sub-batch (what it does before and next to the kernels), printed when the call ends
+struct HostMarks {
+    bool on; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    std::vector<std::pair<const char *, double>> marks;
+    void mark(const char *what) { if (on) marks.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
+    void print(size_t ne) const { if (on && !marks.empty()) { fprintf(stderr, "[pna sub-batch] %zu entries, host:", ne); for (auto &m : marks) fprintf(stderr, "  %s %.2f", m.first, m.second); fprintf(stderr, " ms\n"); } }
+};
+// The plan of a sub-batch (plan_subbatch): its geometry, its forms, and the host's copy of the tables it uploaded
+struct SubPlan {
+    uint32_t blk_log = PNA_BLK_LOG, unit_log = 20, nseg = 0, nblk = 0, nunits = 0;
+    uint64_t max_len = 0;                    // the longest entry (a window of a solid stream: the whole stream)
+    bool latency = false, unit_mode = false, single_block = false, hist_on = false, seq_hist = false, any_empty = false;
+    uint32_t small_fl = 0;                   // launch flags of the short segments' geometry (k_lzms)
+    bool wave_blk = false;                   // many small entries: deflate's stage 1 runs a wave per segment, the write kernels a wave per block
+    uint32_t frame_max_payload = 0;          // an upper bound of every payload when the entries are small and plain (k_frame's wave-per-entry form; 0: none)
+    const SegDesc *segs = nullptr; const uint32_t *entry_first_seg = nullptr;
+};
+// LATENCY MODE: a small batch -- the CompressionWriter seam with a handful of writers in flight, one entry of
+// `pna_gpu_compress_batch` -- has fewer segments than the chip has CUs, and its time is the length of the per-segment and per-block serial
+// chains (one workgroup walks a segment's 256 tiles; one lane codes a block's sequences).  Such a batch is cut finer: blocks of 8 .. 64 KiB
+// inside the same frames (blk_log), and the LZ stage runs one workgroup per UNIT of 1 << unit_log bytes whose table is pre-warmed with
+// everything before it (lz_prewarm), which gives the very matches of the segment-long walk.  Both follow from the batch's size alone
+// (and pna_gpu_set_option), are reported by pna_gpu_last_timing, and are parameters of the oracle's model.
+static void plan_geometry(const pna_gpu_ctx *c, int algo, uint64_t in_total, uint64_t nseg_est, SubPlan &p) {
     const bool latency = c->tun.latency_max_mib > 0 && in_total <= ((uint64_t)c->tun.latency_max_mib << 20) && nseg_est <= 1024 && !(c->call_flags & 0x100u);
-    uint32_t blk_log = blk_log_for_longest(c, max_len), unit_log = 20;
+    uint32_t blk_log = blk_log_for_longest(c, p.max_len), unit_log = 20;
     if (blk_log == PNA_BLK_LOG && algo != PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & 0x100u) && !(latency && in_total <= (64ull << 20))) {
         // deflate beyond 64 MiB of input: whole segments, and 64 KiB blocks up to 384 MiB of the call's input (96 / 192 / 256 MiB: 1.78 / 2.19 / 2.52 -> 1.66 / 1.99 / 2.20 ms;
         // ratio 2.540 -> 2.536: every dynamic block repeats the code description, so the blocks stay larger than zstd's)
@@ -642,9 +635,44 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     }
     if (c->tun.unit_log) unit_log = (uint32_t)std::max<long>(c->tun.unit_log, blk_log);
     if (unit_log < blk_log) unit_log = blk_log;
-    const uint32_t bsz = 1u << blk_log;
-    // The plan: counted first, then written straight into the page-locked blob that travels to the device in one copy (several threads for the
-    // batches of 10^5 .. 10^6 small entries, where this loop is a tenth of the call).  Layout: [segs | units | blk_seg | entry_first_seg].
+    p.latency = latency; p.blk_log = blk_log; p.unit_log = unit_log;
+}
+// The plan: the geometry, then the segment, unit, block -> segment and entry -> first segment tables, counted first and then written straight into
+// the page-locked blob that travels to the device in one copy (several threads for the batches of 10^5 .. 10^6 small entries, where these loops are a
+// tenth of the call), the workspace for the kernels.  A sub-batch without segments leaves p.nseg = 0 and queues nothing.
+static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
+    pna_gpu_ctx *c = sb.c; const int algo = sb.algo; const FrameJob *fj = sb.fj;
+    const uint64_t *src_off = sb.src_off, *src_len = sb.src_len; const size_t e0 = sb.e0, ne_all = sb.e1 - sb.e0;
+    const unsigned host_nt = host_loop_threads(ne_all);
+    struct PlanPart { uint64_t in_total = 0, nseg_est = 0, max_len = 0, n_short = 0, n_mid = 0, max_mid = 0; uint32_t sg = 0, bk = 0, un = 0; bool misaligned = false, any_empty = false; };
+    std::vector<PlanPart> pp(host_nt);
+    par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
+        PlanPart q;
+        for (size_t e = e0 + a; e < e0 + b; e++) {
+            const uint64_t len = src_len[e];
+            q.in_total += len; q.nseg_est += len ? (len + SEG_SIZE - 1) / SEG_SIZE : 1; q.max_len = std::max<uint64_t>(q.max_len, len);
+            q.misaligned |= (src_off[e] & 15) != 0; q.any_empty |= len == 0;
+            // SHORT segments (pna_dev.h SMALL_SEG): an entry of at most that many bytes, or the last segment of a longer one
+            const uint64_t last = len ? ((len - 1) & (SEG_SIZE - 1)) + 1 : 0;
+            q.n_short += (last > 0 && last <= SMALL_SEG) ? 1u : 0u; if (last > SMALL_SEG && last <= MID_SEG) { q.n_mid++; q.max_mid = std::max(q.max_mid, last); }
+        }
+        pp[t] = q;
+    });
+    uint64_t in_total = 0, nseg_est = 0, max_len = 0, n_short = 0, n_mid = 0, max_mid = 0;
+    bool any_empty = false;
+    for (const PlanPart &q : pp) {
+        in_total += q.in_total; nseg_est += q.nseg_est; max_len = std::max(max_len, q.max_len); any_empty |= q.any_empty; n_short += q.n_short; n_mid += q.n_mid; max_mid = std::max(max_mid, q.max_mid);
+        if (q.misaligned) return fail(c, PNA_E_INVAL, "entry offset not 16-byte aligned");
+    }
+    if (fj && fj->stream_len) {
+        // one window of a solid stream: block size, latency form and units follow from the whole stream, as in its one-shot run, so that the window's
+        // segments are coded as they are there (a window is whole segments: the short ones are the stream's own)
+        in_total = fj->stream_len; nseg_est = (in_total + SEG_SIZE - 1) / SEG_SIZE; max_len = in_total;
+    }
+    p.max_len = max_len; p.any_empty = any_empty;
+    p.frame_max_payload = (fj && !fj->solid && !fj->cipher && max_len <= 16384) ? (uint32_t)std::min<size_t>(pna_gpu_bound(algo, (size_t)max_len), 0xFFFFFFFFu) : 0u;
+    plan_geometry(c, algo, in_total, nseg_est, p);
+    const uint32_t blk_log = p.blk_log, unit_log = p.unit_log, bsz = 1u << blk_log;
     // first segment / block / unit of every range of entries (the ranges of par_ranges): counted per range, then a prefix sum over the ranges
     par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
         uint32_t sg = 0, bk = 0, un = 0;
@@ -660,9 +688,9 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     });
     uint32_t nseg = 0, nblk = 0, nunits = 0;
     for (PlanPart &q : pp) { const uint32_t a = q.sg, b = q.bk, u = q.un; q.sg = nseg; q.bk = nblk; q.un = nunits; nseg += a; nblk += b; nunits += u; }
-
     if (nseg == 0) return PNA_OK;
-    mark("counted");
+    hm.mark("counted");
+    // Layout of the blob: [segs | units | blk_seg | entry_first_seg]
     const size_t o_units = ((size_t)nseg * sizeof(SegDesc) + 15) & ~(size_t)15, o_blkseg = (o_units + (size_t)nunits * sizeof(SegDesc) + 15) & ~(size_t)15,
                  o_entry = (o_blkseg + (size_t)(nblk + 1) * 4 + 15) & ~(size_t)15, plan_bytes = o_entry + (ne_all + 2) * 4;
     if (c->plan.ensure(plan_bytes) || c->h_plan.ensure(plan_bytes)) return fail(c, PNA_E_NOMEM, "workspace allocation failed");
@@ -674,27 +702,24 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     const uint32_t sf_bit = (algo == PNA_ALGO_ZSTD && c->tun.single_frame) ? 4u : 0u;
     // a window of a deflate stream (FrameJob::run): its first segment starts the stream only in the first window, its last one ends it only in the last
     const uint32_t first_bit = (fj && (fj->run & DRUN_CONT)) ? 0u : 1u, last_bit = (fj && (fj->run & DRUN_OPEN)) ? 0u : 2u;
-    {
-        auto fill = [&](unsigned t, size_t a, size_t b) {
-            uint32_t sg = pp[t].sg, bk = pp[t].bk, un = pp[t].un;
-            for (size_t e = e0 + a; e < e0 + b; e++) {
-                entry_first_seg[e - e0] = sg;
-                const uint64_t len = src_len[e], off = src_off[e];
-                if (len == 0) { segs[sg++] = SegDesc{off, 0, bk, (uint32_t)e, 3, 0, 0, blk_log, 0}; continue; }
-                for (uint64_t p = 0; p < len; p += SEG_SIZE) {
-                    const uint32_t sl = (uint32_t)std::min<uint64_t>(SEG_SIZE, len - p);
-                    const SegDesc s{off + p, sl, bk, (uint32_t)e, (p == 0 ? first_bit : 0u) | (p + SEG_SIZE >= len ? last_bit : 0u) | sf_bit, 0, sl, blk_log, 0};
-                    const uint32_t nb = (sl + bsz - 1) >> blk_log;
-                    for (uint32_t b2 = 0; b2 < nb; b2++) blk_seg[bk + b2] = sg;
-                    bk += nb; segs[sg++] = s;
-                    if (unit_log < 20)
-                        for (uint32_t u = 0; u < sl; u += 1u << unit_log) { SegDesc us = s; us.u0 = u; us.u1 = std::min<uint32_t>(sl, u + (1u << unit_log)); units[un++] = us; }
-                }
+    par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
+        uint32_t sg = pp[t].sg, bk = pp[t].bk, un = pp[t].un;
+        for (size_t e = e0 + a; e < e0 + b; e++) {
+            entry_first_seg[e - e0] = sg;
+            const uint64_t len = src_len[e], off = src_off[e];
+            if (len == 0) { segs[sg++] = SegDesc{off, 0, bk, (uint32_t)e, 3, 0, 0, blk_log, 0}; continue; }
+            for (uint64_t q = 0; q < len; q += SEG_SIZE) {
+                const uint32_t sl = (uint32_t)std::min<uint64_t>(SEG_SIZE, len - q);
+                const SegDesc s{off + q, sl, bk, (uint32_t)e, (q == 0 ? first_bit : 0u) | (q + SEG_SIZE >= len ? last_bit : 0u) | sf_bit, 0, sl, blk_log, 0};
+                const uint32_t nb = (sl + bsz - 1) >> blk_log;
+                for (uint32_t b2 = 0; b2 < nb; b2++) blk_seg[bk + b2] = sg;
+                bk += nb; segs[sg++] = s;
+                if (unit_log < 20)
+                    for (uint32_t u = 0; u < sl; u += 1u << unit_log) { SegDesc us = s; us.u0 = u; us.u1 = std::min<uint32_t>(sl, u + (1u << unit_log)); units[un++] = us; }
             }
-        };
-        par_ranges(ne_all, host_nt, fill);
-        entry_first_seg[ne_all] = nseg;
-    }
+        }
+    });
+    entry_first_seg[ne_all] = nseg;
     const bool unit_mode = unit_log < 20 && nunits > 0;
     c->last_blk_log = blk_log; c->last_units = unit_mode ? nunits : 0;
     // zstd entropy stage, two forms: statistics per block (k_hist) + tables + three-lane state chains (k_seqa) + token-parallel packing (k_seqb) while
@@ -714,473 +739,466 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
         (algo == PNA_ALGO_ZSTD && c->seqw.ensure(hist_on ? (size_t)(nblk + 1) * seq_cap_of(blk_log) * 8 : 64)) ||
         c->seg_size.ensure((size_t)nseg * 8) || c->seg_off.ensure(((size_t)nseg + 1 + 2 * ((size_t)nseg / 4096 + 2)) * 8))       // (+ the scratch of the hierarchical scan)
         return fail(c, PNA_E_NOMEM, "workspace allocation failed");
-    {
-        uint8_t *hp = (uint8_t *)c->h_plan.p, *dp = (uint8_t *)c->plan.p;
-        c->d_segs = (SegDesc *)dp; c->d_units = (SegDesc *)(dp + o_units); c->d_blk_seg = (uint32_t *)(dp + o_blkseg); c->d_entry_seg = (uint32_t *)(dp + o_entry);
-        c->d_hist = (uint32_t *)((uint8_t *)c->blk.p + o_hist);
-        HIPCHK(c, hipMemcpyAsync(dp, hp, plan_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemsetAsync(c->blk.p, 0, blk_bytes, st));                     // BlkInfo of every block and, behind them, the segments' histogram counters
-    }
+    uint8_t *hp = (uint8_t *)c->h_plan.p, *dp = (uint8_t *)c->plan.p;
+    c->d_segs = (SegDesc *)dp; c->d_units = (SegDesc *)(dp + o_units); c->d_blk_seg = (uint32_t *)(dp + o_blkseg); c->d_entry_seg = (uint32_t *)(dp + o_entry);
+    c->d_hist = (uint32_t *)((uint8_t *)c->blk.p + o_hist);
+    HIPCHK(c, hipMemcpyAsync(dp, hp, plan_bytes, hipMemcpyHostToDevice, sb.st));
+    HIPCHK(c, hipMemsetAsync(c->blk.p, 0, blk_bytes, sb.st));                     // BlkInfo of every block and, behind them, the segments' histogram counters
+    // the short segments' geometry (k_lzms): a launch flag tells the large geometry's kernels to skip them; a sub-batch of short segments only launches none of those
+    p.small_fl = (c->tun.small_geometry && (n_short || n_mid))
+        ? (FLAG_HAS_SMALL | (n_short ? FLAG_TIER1 : 0u) | (n_mid ? FLAG_TIER2 | ((max_mid <= 8192 ? 0u : (max_mid <= 12288 ? 1u : 2u)) << FLAG_T2_SHIFT) : 0u) | (max_len <= MID_SEG ? FLAG_ALL_SMALL : 0u)) : 0u;
+    p.nseg = nseg; p.nblk = nblk; p.nunits = nunits; p.unit_mode = unit_mode; p.single_block = single_block; p.hist_on = hist_on; p.seq_hist = seq_hist;
+    p.wave_blk = max_len <= 32768 && nseg >= 4096;
+    p.segs = segs; p.entry_first_seg = entry_first_seg;
+    return PNA_OK;
+}
+// The kernel chains of the codec: LZ stage, then deflate's stage 1 (codes, sizes, offsets) or zstd's entropy stage and k_plan -- every segment's
+// compressed size and offset in c->seg_size / c->seg_off.
+static int compress_subbatch(const SubBatch &sb, const SubPlan &p) {
+    pna_gpu_ctx *c = sb.c; const uint8_t *d_src = sb.d_src; const hipStream_t st = sb.st; const bool timed = sb.timed;
+    const uint32_t nseg = p.nseg, nblk = p.nblk, nunits = p.nunits, blk_log = p.blk_log;
     c->lzm_used = 0; c->lzm_nl.clear();
     c->lzp_hist = nullptr; c->lzp_hist_all = false;
-    const bool defl = algo == PNA_ALGO_DEFLATE;
-    // the short segments' geometry (k_lzms): a launch flag tells the large geometry's kernels to skip them; a sub-batch of short segments only launches none of those
-    const uint32_t small_fl = (c->tun.small_geometry && (n_short || n_mid))
-        ? (FLAG_HAS_SMALL | (n_short ? FLAG_TIER1 : 0u) | (n_mid ? FLAG_TIER2 | ((max_mid <= 8192 ? 0u : (max_mid <= 12288 ? 1u : 2u)) << FLAG_T2_SHIFT) : 0u) | (max_len <= MID_SEG ? FLAG_ALL_SMALL : 0u)) : 0u;
-    mark("plan queued");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-    int nch = 1;
-    if (defl) {
-        const uint32_t dfl = (c->call_flags & (F_LAZY | F_ADOPT | F_INS2 | F_STRONG | 0x300u)) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | FLAG_LEN36 | small_fl;
+    if (sb.algo == PNA_ALGO_DEFLATE) {
+        const uint32_t dfl = (c->call_flags & (F_LAZY | F_ADOPT | F_INS2 | F_STRONG | 0x300u)) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | FLAG_LEN36 | p.small_fl;
         if (c->call_stored) { }                                // deflate level 0 = Compression::none(): stored blocks only, no match finder, no codes
-        else if (unit_mode) {
+        else if (p.unit_mode) {
             if (!(dfl & FLAG_ALL_SMALL)) launch_lz(d_src, c->d_units, nunits, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (uint4 *)c->ctab.p, dfl, 32768u, 258u, st, nullptr, 0, nullptr, nullptr, nullptr);
-            if (dfl & FLAG_HAS_SMALL) { const int rc = lz_small_pass(c, d_src, segs, nseg, 0, nseg, nblk, (uint4 *)c->ctab.p, dfl, 258u, st); if (rc) return rc; }
+            if (dfl & FLAG_HAS_SMALL) { const int rc = lz_small_pass(c, d_src, p.segs, nseg, 0, nseg, nblk, (uint4 *)c->ctab.p, dfl, 258u, st); if (rc) return rc; }
         }
-        else { const int rc = lz_stage(c, d_src, segs, nseg, 0, nseg, nblk, (uint4 *)c->ctab.p, dfl, 32768u, 258u, st, timed); if (rc) return rc; }
+        else { const int rc = lz_stage(c, d_src, p.segs, nseg, 0, nseg, nblk, (uint4 *)c->ctab.p, dfl, 32768u, 258u, st, timed); if (rc) return rc; }
         if (timed) HIPCHK(c, hipEventRecord(c->ev[1], st));
         launch_deflate_stage1(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const uint64_t *)c->seqs.p,
                               (const uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (const uint4 *)c->ctab.p, (DeflTables *)c->tabs.p, (uint8_t *)c->litc.p,
                               (uint64_t *)c->seg_size.p, (uint64_t *)c->seg_off.p, st, timed ? &c->ev[2] : nullptr, c->call_flags, c->call_stored,
-                              /* a wave per segment: many small entries */ max_len <= 32768 && nseg >= 4096);
+                              /* a wave per segment: many small entries */ p.wave_blk);
     } else {
-        // zstd: the segments go through k_lz in chunks on `st`; the entropy stage of a finished chunk runs on the auxiliary
-        // stream next to the following chunk's k_lz (latency-bound kernels hide in the issue slots k_lz leaves free)
+        // zstd: everything stays on `st` -- a hand-over to the auxiliary stream and back costs ~45 us of idle device, a tenth of a small batch --, except the
+        // literal coder of large batches, which runs on the auxiliary stream next to the sequence coder (option lit_beside_seq)
         if (!c->aux) {
             { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // (lowest priority: what runs here fills in beside the main stream's kernels)
               HIPCHK(c, hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, lo)); }
             for (auto &e : c->ev_lz) HIPCHK(c, hipEventCreate(&e));
-            for (auto &r : c->ev_en) for (auto &e : r) HIPCHK(c, hipEventCreate(&e));
+            for (auto &e : c->ev_en) HIPCHK(c, hipEventCreate(&e));
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         }
-        // Measured (10 000 x 1 MiB): 4 chunks 111.8 ms vs 108.9 ms unchunked -- k_seq's duration is set by the length of one
-        // block's tANS chain, not by the number of blocks, so every chunk pays it in full and the co-resident waves slow k_lz
-        // by 12 %.  The chunked form therefore stays off unless PNA_PIPELINE_CHUNKS asks for it.
-        nch = (int)c->tun.pipeline_chunks; if (nch < 1) nch = 1; if (nch > pna_gpu_ctx::MAXCH) nch = pna_gpu_ctx::MAXCH; if ((uint32_t)nch > nseg || latency) nch = 1;
         HIPCHK(c, hipEventRecord(c->ev_lz[0], st));
-        for (int k = 0; k < nch; k++) {
-            const uint32_t s0 = (uint32_t)((uint64_t)nseg * k / nch), s1 = (uint32_t)((uint64_t)nseg * (k + 1) / nch);
-            const uint32_t g0 = segs[s0].blk_base, g1 = s1 < nseg ? segs[s1].blk_base : nblk;
-            const uint32_t zfl = (c->call_flags & 0x3FFu) | (c->call_w32 ? (c->call_w16 ? FLAG_W16 : FLAG_W32) : 0u) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | (c->call_gtab ? 0u : FLAG_LEN36) | (c->call_tab3 ? FLAG_TAB3 : 0u) | ((c->call_tab3 && !c->call_w16 && c->tun.far1) ? FLAG_FAR1 : 0u) | (c->call_strong2 ? FLAG_STRONG2 : 0u) | small_fl;
-            const uint32_t zmax = (c->call_flags & F_FAR) ? (c->call_gtab ? MAX_OFF : MAX_OFF_W3) : NEAR_OFF;   // (3-byte words keep 19 bits of offset)
-            if (unit_mode) {
-                // (nch == 1: one launch over all units; the strong set: split form over the units, tables in global memory)
-                const bool gt = c->call_gtab;
-                const LzParseGrid pgu{c->d_segs, c->d_blk_seg, nblk};
-                if (gt && (c->pbuf.ensure(((size_t)nblk << blk_log) * 4) || c->gtab.ensure((size_t)nunits << (lz_gtab_log() + 2)))) return fail(c, PNA_E_NOMEM, "no room for the strong level set's hash tables");
-                if (gt || !(zfl & FLAG_ALL_SMALL))
-                launch_lz(d_src, c->d_units, nunits, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, nullptr, zfl,
-                          zmax, 0xFFFFFFFFu, st, gt ? (uint32_t *)c->pbuf.p : nullptr, 0, nullptr, gt ? (uint32_t *)c->gtab.p : nullptr, gt ? &pgu : nullptr);
-                if (!gt && (zfl & FLAG_HAS_SMALL)) { const int rc = lz_small_pass(c, d_src, segs, nseg, 0, nseg, nblk, nullptr, zfl, 0xFFFFFFFFu, st); if (rc) return rc; }   // (the split form above takes them itself)
-            }
-            else {
-                c->lzp_hist = (seq_hist && nch == 1) ? c->d_hist : nullptr; c->lzp_hist_all = c->lzp_hist != nullptr;
-                const int rc = lz_stage(c, d_src, segs, nseg, s0, s1, nblk, nullptr, zfl, zmax, 0xFFFFFFFFu, st, timed); if (rc) return rc;
-            }
-            // (one chunk: everything stays on `st` -- a hand-over to the auxiliary stream and back costs ~45 us of idle device, a tenth of a small batch)
-            hipStream_t est = nch > 1 ? c->aux : st;
-            HIPCHK(c, hipEventRecord(c->ev_lz[k + 1], st));
-            if (nch > 1) HIPCHK(c, hipStreamWaitEvent(c->aux, c->ev_lz[k + 1], 0));
-            HIPCHK(c, hipEventRecord(c->ev_en[k][0], est));
-            launch_entropy_chunk(c->d_segs, s0, s1 - s0, c->d_blk_seg, g0, g1 - g0, (const uint64_t *)c->seqs.p,
-                                 (const uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (SegTables *)c->tabs.p, (uint8_t *)c->litc.p, (uint8_t *)c->seqc.p,
-                                 (uint32_t *)c->seqw.p, c->call_flags, blk_log, hist_on ? c->d_hist : nullptr, est, &c->ev_en[k][1],
-                                 (nch == 1 && c->tun.lit_beside_seq) ? c->aux : nullptr, c->ev_fork, c->ev_join, single_block, c->lzp_hist_all ? c->d_hist : nullptr);
+        const uint32_t zfl = (c->call_flags & 0x3FFu) | (c->call_w32 ? (c->call_w16 ? FLAG_W16 : FLAG_W32) : 0u) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | (c->call_gtab ? 0u : FLAG_LEN36) | (c->call_tab3 ? FLAG_TAB3 : 0u) | ((c->call_tab3 && !c->call_w16 && c->tun.far1) ? FLAG_FAR1 : 0u) | (c->call_strong2 ? FLAG_STRONG2 : 0u) | p.small_fl;
+        const uint32_t zmax = (c->call_flags & F_FAR) ? (c->call_gtab ? MAX_OFF : MAX_OFF_W3) : NEAR_OFF;   // (3-byte words keep 19 bits of offset)
+        if (p.unit_mode) {
+            // (one launch over all units; the strong set: split form over the units, tables in global memory)
+            const bool gt = c->call_gtab;
+            const LzParseGrid pgu{c->d_segs, c->d_blk_seg, nblk};
+            if (gt && (c->pbuf.ensure(((size_t)nblk << blk_log) * 4) || c->gtab.ensure((size_t)nunits << (lz_gtab_log() + 2)))) return fail(c, PNA_E_NOMEM, "no room for the strong level set's hash tables");
+            if (gt || !(zfl & FLAG_ALL_SMALL))
+            launch_lz(d_src, c->d_units, nunits, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, nullptr, zfl,
+                      zmax, 0xFFFFFFFFu, st, gt ? (uint32_t *)c->pbuf.p : nullptr, 0, nullptr, gt ? (uint32_t *)c->gtab.p : nullptr, gt ? &pgu : nullptr);
+            if (!gt && (zfl & FLAG_HAS_SMALL)) { const int rc = lz_small_pass(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, 0xFFFFFFFFu, st); if (rc) return rc; }   // (the split form above takes them itself)
         }
-        if (nch > 1) { HIPCHK(c, hipEventRecord(c->ev_join, c->aux)); HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0)); }
+        else {
+            c->lzp_hist = p.seq_hist ? c->d_hist : nullptr; c->lzp_hist_all = c->lzp_hist != nullptr;
+            const int rc = lz_stage(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, zmax, 0xFFFFFFFFu, st, timed); if (rc) return rc;
+        }
+        HIPCHK(c, hipEventRecord(c->ev_lz[1], st));
+        HIPCHK(c, hipEventRecord(c->ev_en[0], st));
+        launch_entropy_chunk(c->d_segs, 0, nseg, c->d_blk_seg, 0, nblk, (const uint64_t *)c->seqs.p,
+                             (const uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (SegTables *)c->tabs.p, (uint8_t *)c->litc.p, (uint8_t *)c->seqc.p,
+                             (uint32_t *)c->seqw.p, c->call_flags, blk_log, p.hist_on ? c->d_hist : nullptr, st, &c->ev_en[1],
+                             c->tun.lit_beside_seq ? c->aux : nullptr, c->ev_fork, c->ev_join, p.single_block, c->lzp_hist_all ? c->d_hist : nullptr);
         if (timed) HIPCHK(c, hipEventRecord(c->ev[4], st));
         launch_plan(c->d_segs, nseg, (BlkInfo *)c->blk.p, (const SegTables *)c->tabs.p, (uint64_t *)c->seg_size.p,
                     (uint64_t *)c->seg_off.p, c->call_flags, st);
         if (timed) HIPCHK(c, hipEventRecord(c->ev[5], st));
     }
     HIPCHK(c, hipGetLastError());
-    // while the kernels run: the name-dependent part of every entry record (FHED and fSIZ chunks with their CRCs)
-    mark("kernels queued");
-    uint64_t layout_need = 0; bool layout_over = false;         // the sub-batch's worst-case size with its prefixes; an entry whose worst case exceeds one FDAT chunk
+    return PNA_OK;
+}
+// The framing of a sub-batch as the host lays it out: descriptors and prefixes for k_frame in the page-locked staging (c->h_desc, h_blob, h_segdst),
+// and what the cipher stage and the spread of entries of several FDAT chunks / GCM segments need
+struct SubLayout {
     FrameDesc *fds = nullptr; uint8_t *blob = nullptr; uint64_t *segdst = nullptr; size_t blob_len = 0;
-    const bool solid = fj && fj->solid;
-    const bool gcm = fj && fj->cipher && fj->cipher->cipher_mode == PNA_MODE_GCM;
-    const uint32_t gcm_seg = gcm ? (fj->cipher->gcm_segment_size ? fj->cipher->gcm_segment_size : (1u << 20)) : 0u;   // default = the reference's DEFAULT_SEGMENT_SIZE (1 MiB)
+    size_t nunit = 0;                                        // framed units: entries, FDAT chunks, or the SDAT chunks of the solid stream
+    uint64_t layout_need = 0; bool layout_over = false;      // the sub-batch's worst-case size with its prefixes; an entry whose worst case exceeds one FDAT chunk
+    uint64_t total = 0;                                      // archive bytes of the sub-batch
     std::vector<GcmMaterial> gmat; std::vector<GcmEntry> gents;
     // GCM STREAM segments of this sub-batch, in order (an entry has ceil(payload / segment_size) of them, at least one): counter-mode IV
-    // (nonce || 2) and the entry they belong to; `spread`: pieces of the compact payload that move to their place between the tags
-    struct GcmSeg { uint8_t ctr_iv[16]; uint32_t entry; };
-    std::vector<GcmSeg> gsegs;
+    // (nonce || 2) and the round keys of the stream they belong to; `spread`: pieces of the compact payload that move to their place between the tags
+    std::vector<uint8_t> giv; std::vector<AesKey> gkeys;
     struct SpreadPiece { uint64_t src, dst; uint32_t len; };
     std::vector<SpreadPiece> spread; uint64_t spread_bytes = 0;
     std::vector<std::pair<uint64_t, uint64_t>> spread_copy;     // (archive offset, length) of the compact payloads to save first
-    size_t nunit = e1 - e0;                                    // framed units: entries, or the segments of the solid stream
-    if (solid) {
+    std::vector<CipherUnit> cunits;
+    uint64_t carry_in = 0, carry_in_len = 0, carry_out = 0;     // windowed GCM: where the carry goes in / the next one starts (0: none)
+    // bytes [from, from + len) of the compact payload being laid out move to `dst`, in pieces of at most 1 MiB
+    void move(uint64_t from, uint64_t dst, uint64_t len) {
+        for (uint64_t o = 0; o < len; o += (1u << 20)) spread.push_back(SpreadPiece{spread_bytes + from + o, dst + o, (uint32_t)std::min<uint64_t>(1u << 20, len - o)});
+    }
+    // ... which is saved first: the `len` bytes at archive offset `at` (the pieces of the next payload come from behind it)
+    void save(uint64_t at, uint64_t len) { spread_copy.emplace_back(at, len); spread_bytes += (len + 15) & ~(uint64_t)15; }
+    // GCM STREAM segments first .. first + K - 1 of a stream (GcmEncryptWriter, lib/src/cipher/gcm.rs:48-100): `plen` compact payload bytes from archive
+    // offset `base` on, cut into segments of G bytes (the last one the rest); segment k goes to base + k * stride, its tag behind it, and only the stream's
+    // last segment -- the last of these if `final_last` -- carries nonce flag 1.  Appends every segment's counter IV, CTR units and tag descriptor and, for
+    // K > 1, the spread that moves segments k >= 1 to their places.
+    void gcm_segments(const GcmMaterial &gm, uint64_t first, uint64_t K, bool final_last, uint64_t plen, uint64_t G, uint64_t base, uint64_t stride) {
+        for (uint64_t k = 0; k < K; k++) {
+            const uint64_t sl = std::min<uint64_t>(G, plen - k * G), so = base + k * stride, q = first + k;     // q: the segment's counter in the stream
+            const uint32_t si = (uint32_t)gkeys.size();
+            uint8_t j0[16], eb[16];
+            memcpy(j0, gm.ctr_iv, 7);                                  // nonce prefix
+            j0[7] = (uint8_t)(q >> 24); j0[8] = (uint8_t)(q >> 16); j0[9] = (uint8_t)(q >> 8); j0[10] = (uint8_t)q; j0[11] = final_last && k + 1 == K ? 1 : 0;
+            j0[12] = 0; j0[13] = 0; j0[14] = 0; j0[15] = 1;
+            aes256_block_host(gm.rk, j0, eb);
+            j0[15] = 2;                                                // the first data block
+            giv.insert(giv.end(), j0, j0 + 16); gkeys.push_back(gm.rk);
+            for (uint64_t o = 0; o < sl; o += CTR_UNIT) cunits.push_back(CipherUnit{so + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
+            GcmEntry ge{so, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+            memcpy(ge.h, gm.h, 16);
+            for (int w = 0; w < 4; w++) ge.ej0[w] = ((uint32_t)eb[4 * w] << 24) | ((uint32_t)eb[4 * w + 1] << 16) | ((uint32_t)eb[4 * w + 2] << 8) | eb[4 * w + 3];
+            gents.push_back(ge);
+            if (k >= 1) move(k * G, so, sl);
+        }
+        if (K > 1) save(base, std::min(plen, K * G));
+    }
+};
+// While the kernels run: the staging of the framing and the name-dependent part of every entry record (FHED and fSIZ chunks with their CRCs); GCM
+// STREAM: every stream's key material.
+static int frame_prefixes(const SubBatch &sb, const SubPlan &p, SubLayout &L) {
+    pna_gpu_ctx *c = sb.c; const int algo = sb.algo; const FrameJob *fj = sb.fj; const uint64_t *src_len = sb.src_len; const size_t e0 = sb.e0, e1 = sb.e1;
+    const bool gcm = fj->cipher && fj->cipher->cipher_mode == PNA_MODE_GCM;
+    const uint32_t gcm_seg = gcm ? gcm_seg_size(fj->cipher) : 0u;
+    if (fj->solid) {
         if (e1 - e0 != 1) return fail(c, PNA_E_INVAL, "a solid stream is one entry");
-        nunit = nseg;
+        L.nunit = p.nseg;
         // (GCM: one SDAT chunk per GCM segment of the compressed stream -- at most the worst-case output / segment size + 1 of them)
         const uint64_t carry_in = fj->crun ? fj->crun->carry_len : 0;
-        const size_t ucap = gcm ? (size_t)((pna_gpu_bound(algo, (size_t)src_len[e0]) + carry_in) / gcm_seg) + 2 : nunit;
-        if (c->h_desc.ensure(ucap * sizeof(FrameDesc)) || c->h_blob.ensure(ucap * 8 + 16) || c->h_segdst.ensure((size_t)(nseg + 1) * 8))
+        const size_t ucap = gcm ? (size_t)((pna_gpu_bound(algo, (size_t)src_len[e0]) + carry_in) / gcm_seg) + 2 : L.nunit;
+        if (c->h_desc.ensure(ucap * sizeof(FrameDesc)) || c->h_blob.ensure(ucap * 8 + 16) || c->h_segdst.ensure((size_t)(p.nseg + 1) * 8))
             return fail(c, PNA_E_NOMEM, "framing staging");
-        fds = (FrameDesc *)c->h_desc.p; blob = (uint8_t *)c->h_blob.p; segdst = (uint64_t *)c->h_segdst.p;
-        if (gcm) {
-            gmat.resize(1);
-            uint8_t kc[32], ph[32];
-            hkdf_sha256_32(fj->cipher->key, 32, nullptr, 0, "PNA-KC-v1", 9, kc);
-            sha256_bytes(fj->cipher->phsf, strlen(fj->cipher->phsf), nullptr, 0, ph);
-            gcm_entry_material(fj->cipher, kc, ph, fj->ivs, gcm_seg, nullptr, algo, gmat[0]);
-        }
-    } else if (fj) {
-        std::vector<uint8_t> tmp;
-        // bounds, one pass over the entries on the host-loop threads: the prefixes' worst case per range of entries (a range's prefixes are written
-        // from its bound offset on, so the ranges need no compaction pass afterwards), the extra FDAT chunks (every chunk behind an entry's first needs a
-        // descriptor and 8 prefix bytes: at most one per max_chunk_size bytes of the worst-case output), and what the device-side layout must know --
-        // whether every worst-case payload fits one chunk, and the worst-case size of the sub-batch
-        struct FramePart { size_t bound = 0, extra = 0; uint64_t need = 0; bool over = false; };
-        std::vector<FramePart> fp(host_nt);
-        const uint64_t CHb = chunk_limit(fj->max_chunk);
-        par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
-            FramePart q;
-            for (size_t e = e0 + a; e < e0 + b; e++) {
-                const size_t pb = (fj->cipher ? frame_entry_prefix_enc_bound(fj->names[e], fj->cipher->phsf) : frame_entry_prefix_bound(fj->names[e])) + meta_len(fj->meta, e);
-                const uint64_t wb = pna_gpu_bound(algo, (size_t)src_len[e]);
-                q.bound += pb; q.extra += (size_t)((wb + 64 + 16 * (src_len[e] >> 12)) / CHb); q.need += pb + wb + 16; q.over |= wb > CHb;
-            }
-            fp[t] = q;
-        });
-        size_t bound = 0, extra_chunks = 0;
-        for (FramePart &q : fp) { const size_t b = q.bound; q.bound = bound; bound += b; extra_chunks += q.extra; layout_need += q.need; layout_over |= q.over; }
-        if (c->h_desc.ensure(((e1 - e0) + extra_chunks + 1) * sizeof(FrameDesc)) || c->h_blob.ensure(bound + 8 * extra_chunks + 16) || c->h_segdst.ensure((size_t)(nseg + 1) * 8))
-            return fail(c, PNA_E_NOMEM, "framing staging");
-        fds = (FrameDesc *)c->h_desc.p; blob = (uint8_t *)c->h_blob.p; segdst = (uint64_t *)c->h_segdst.p;
-        if (gcm) {
-            // GCM STREAM: per entry a stream header, an HKDF stream key bound to its FHED chunk, round keys, hash subkey, E(K, J0);
-            // a few host threads share the entries (SHA-256 / HKDF / key schedule: a few microseconds each) while k_lz runs
-            gmat.resize(e1 - e0);
-            uint8_t kc[32], ph[32];
-            hkdf_sha256_32(fj->cipher->key, 32, nullptr, 0, "PNA-KC-v1", 9, kc);               // key_confirmation, aead.rs:161-163
-            sha256_bytes(fj->cipher->phsf, strlen(fj->cipher->phsf), nullptr, 0, ph);
-            const unsigned nt = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (e1 - e0) / 256));
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < nt; t++)
-                th.emplace_back([&, t]() {
-                    for (size_t e = e0 + t; e < e1; e += nt)
-                        gcm_entry_material(fj->cipher, kc, ph, fj->ivs + 39 * e, gcm_seg, fj->names[e], algo, gmat[e - e0]);
-                });
-            for (auto &x : th) x.join();
-        }
-        if (!fj->cipher && !fj->meta) {
-            // plain entries: the prefixes are written straight into the staging blob, every range of entries back to back from the range's bound offset
-            // (the few unused bytes between two ranges travel with the blob; nothing refers to them)
-            par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
-                size_t at = fp[t].bound;
-                for (size_t i = a; i < b; i++) {
-                    const size_t pl = frame_entry_prefix_into(blob + at, fj->names[e0 + i], algo, src_len[e0 + i]);
-                    fds[i] = FrameDesc{0, 0, (uint32_t)at, (uint32_t)pl, 0};
-                    at += pl;
-                }
-            });
-            blob_len = bound;
-        } else
-        for (size_t e = e0; e < e1; e++) {
-            tmp.clear();
-            if (gcm) frame_entry_prefix_enc(tmp, fj->names[e], algo, src_len[e], fj->cipher->encryption, PNA_MODE_GCM, fj->cipher->phsf, gmat[e - e0].header, 75);
-            else if (fj->cipher) frame_entry_prefix_enc(tmp, fj->names[e], algo, src_len[e], fj->cipher->encryption, fj->cipher->cipher_mode, fj->cipher->phsf, fj->ivs + 16 * e, 16);
-            else frame_entry_prefix(tmp, fj->names[e], algo, src_len[e], 0);
-            splice_meta(tmp, fj->meta, e);
-            memcpy(blob + blob_len, tmp.data(), tmp.size());
-            fds[e - e0] = FrameDesc{0, 0, (uint32_t)blob_len, (uint32_t)tmp.size(), 0};
-            blob_len += tmp.size();
-        }
-    }
-    // Plain file entries of one FDAT chunk each (no cipher; the worst case of every payload below the chunk limit and of the whole sub-batch below the
-    // destination's capacity): the archive layout is computed on the device (k_layout) and the host never waits in the middle of the sub-batch.
-    mark("prefixes built");
-    const bool dev_layout = fj && !solid && !fj->cipher && c->tun.dev_layout != 0 && !layout_over && out_base + layout_need + 16 <= dst_cap;
-    if (dev_layout) {
-        const size_t ne = e1 - e0;
-        if (c->fr_desc.ensure(ne * sizeof(FrameDesc)) || c->fr_blob.ensure(blob_len + 16) || c->fr_segdst.ensure((size_t)(nseg + 1) * 8) ||
-            c->fr_entoff.ensure((ne + 2 + 2 * (ne / 1024 + 2)) * 8) || c->h_entoff.ensure((ne + 2) * 8)) return fail(c, PNA_E_NOMEM, "framing workspace");
-        int rcc = ensure_crc(c); if (rcc) return rcc;
-        HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, fds, ne * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, blob, blob_len, hipMemcpyHostToDevice, st));
-        uint64_t *d_ent = (uint64_t *)c->fr_entoff.p;
-        launch_layout((FrameDesc *)c->fr_desc.p, (uint8_t *)c->fr_blob.p, c->d_entry_seg, (const uint64_t *)c->seg_off.p, (uint32_t)ne, nseg, out_base,
-                      (uint64_t *)c->fr_segdst.p, d_ent, d_ent + ne + 1, st);
-        if (defl) launch_deflate_write(d_src, c->d_segs, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p, (const uint64_t *)c->fr_segdst.p, (const uint64_t *)c->seg_size.p,
-                                       (const uint8_t *)c->litc.p, c->d_entry_seg, (uint32_t)ne, d_dst, st, c->call_stored, /* a wave per block */ max_len <= 32768 && nseg >= 4096);
-        else launch_write(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p, (const SegTables *)c->tabs.p, (const uint64_t *)c->fr_segdst.p,
-                          (const uint8_t *)c->lits.p, (const uint8_t *)c->litc.p, (const uint8_t *)c->seqc.p, d_dst, any_empty, st, /* a wave per block */ max_len <= 32768 && nseg >= 4096);
-        if (timed) HIPCHK(c, hipEventRecord(c->ev[6], st));
-        launch_frame((const FrameDesc *)c->fr_desc.p, (uint32_t)ne, (const uint8_t *)c->fr_blob.p, (const CrcTabs *)c->crc_tabs.p,
-                     d_dst, (uint64_t)dst_cap & ~(uint64_t)15, frame_fend_crc(), "FDAT", true, st, frame_max_payload);
-        if (timed) HIPCHK(c, hipEventRecord(c->ev[7], st));
-        // the entry offsets (when the caller wants them) and the sub-batch's length travel back behind the kernels: the call's one wait
-        uint64_t *h_ent = (uint64_t *)c->h_entoff.p;
-        if (fj->want_offsets) HIPCHK(c, hipMemcpyAsync(h_ent, d_ent, (ne + 2) * 8, hipMemcpyDeviceToHost, st));
-        else HIPCHK(c, hipMemcpyAsync(h_ent + ne, d_ent + ne, 16, hipMemcpyDeviceToHost, st));
-        mark("framing queued");
-        HIPCHK(c, hipStreamSynchronize(st));
-        mark("device done"); print_marks();
-        HIPCHK(c, hipGetLastError());
-        if (fj->want_offsets) memcpy(dst_off + e0, h_ent, ne * 8);
-        dst_off[e1] = h_ent[ne];
-        c->last_nblk = nblk;
-        if (timed) {
-            int rct = collect_timing(c, defl, nch, nseg, nblk, false);
-            if (rct) return rct;
-        }
+        L.fds = (FrameDesc *)c->h_desc.p; L.blob = (uint8_t *)c->h_blob.p; L.segdst = (uint64_t *)c->h_segdst.p;
+        if (gcm) { L.gmat.resize(1); gcm_solid_material(fj->cipher, fj->ivs, algo, L.gmat[0]); }
         return PNA_OK;
     }
+    const size_t ne_all = e1 - e0;
+    const unsigned host_nt = host_loop_threads(ne_all);
+    L.nunit = ne_all;
+    // bounds, one pass over the entries on the host-loop threads: the prefixes' worst case per range of entries (a range's prefixes are written
+    // from its bound offset on, so the ranges need no compaction pass afterwards), the extra FDAT chunks (every chunk behind an entry's first needs a
+    // descriptor and 8 prefix bytes: at most one per max_chunk_size bytes of the worst-case output), and what the device-side layout must know --
+    // whether every worst-case payload fits one chunk, and the worst-case size of the sub-batch
+    struct FramePart { size_t bound = 0, extra = 0; uint64_t need = 0; bool over = false; };
+    std::vector<FramePart> fp(host_nt);
+    const uint64_t CHb = chunk_limit(fj->max_chunk);
+    par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
+        FramePart q;
+        for (size_t e = e0 + a; e < e0 + b; e++) {
+            const size_t pb = (fj->cipher ? frame_entry_prefix_enc_bound(fj->names[e], fj->cipher->phsf) : frame_entry_prefix_bound(fj->names[e])) + meta_len(fj->meta, e);
+            const uint64_t wb = pna_gpu_bound(algo, (size_t)src_len[e]);
+            q.bound += pb; q.extra += (size_t)((wb + 64 + 16 * (src_len[e] >> 12)) / CHb); q.need += pb + wb + 16; q.over |= wb > CHb;
+        }
+        fp[t] = q;
+    });
+    size_t bound = 0, extra_chunks = 0;
+    for (FramePart &q : fp) { const size_t bq = q.bound; q.bound = bound; bound += bq; extra_chunks += q.extra; L.layout_need += q.need; L.layout_over |= q.over; }
+    if (c->h_desc.ensure((ne_all + extra_chunks + 1) * sizeof(FrameDesc)) || c->h_blob.ensure(bound + 8 * extra_chunks + 16) || c->h_segdst.ensure((size_t)(p.nseg + 1) * 8))
+        return fail(c, PNA_E_NOMEM, "framing staging");
+    FrameDesc *fds = L.fds = (FrameDesc *)c->h_desc.p; uint8_t *blob = L.blob = (uint8_t *)c->h_blob.p; L.segdst = (uint64_t *)c->h_segdst.p;
+    if (gcm) {
+        // GCM STREAM: per entry a stream header, an HKDF stream key bound to its FHED chunk, round keys, hash subkey, E(K, J0);
+        // a few host threads share the entries (SHA-256 / HKDF / key schedule: a few microseconds each) while k_lz runs
+        L.gmat.resize(ne_all);
+        const GcmCallKeys keys = gcm_call_keys(fj->cipher);
+        const unsigned nt = (unsigned)std::min<size_t>(8, std::max<size_t>(1, ne_all / 256));
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nt; t++)
+            th.emplace_back([&, t]() {
+                for (size_t e = e0 + t; e < e1; e += nt)
+                    gcm_entry_material(fj->cipher, keys, fj->ivs + 39 * e, gcm_seg, fj->names[e], algo, L.gmat[e - e0]);
+            });
+        for (auto &x : th) x.join();
+    }
+    if (!fj->cipher && !fj->meta) {
+        // plain entries: the prefixes are written straight into the staging blob, every range of entries back to back from the range's bound offset
+        // (the few unused bytes between two ranges travel with the blob; nothing refers to them)
+        par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
+            size_t at = fp[t].bound;
+            for (size_t i = a; i < b; i++) {
+                const size_t pl = frame_entry_prefix_into(blob + at, fj->names[e0 + i], algo, src_len[e0 + i]);
+                fds[i] = FrameDesc{0, 0, (uint32_t)at, (uint32_t)pl, 0};
+                at += pl;
+            }
+        });
+        L.blob_len = bound;
+        return PNA_OK;
+    }
+    std::vector<uint8_t> tmp;
+    for (size_t e = e0; e < e1; e++) {
+        tmp.clear();
+        if (gcm) frame_entry_prefix_enc(tmp, fj->names[e], algo, src_len[e], fj->cipher->encryption, PNA_MODE_GCM, fj->cipher->phsf, L.gmat[e - e0].header, 75);
+        else if (fj->cipher) frame_entry_prefix_enc(tmp, fj->names[e], algo, src_len[e], fj->cipher->encryption, fj->cipher->cipher_mode, fj->cipher->phsf, fj->ivs + 16 * e, 16);
+        else frame_entry_prefix(tmp, fj->names[e], algo, src_len[e], 0);
+        splice_meta(tmp, fj->meta, e);
+        memcpy(blob + L.blob_len, tmp.data(), tmp.size());
+        fds[e - e0] = FrameDesc{0, 0, (uint32_t)L.blob_len, (uint32_t)tmp.size(), 0};
+        L.blob_len += tmp.size();
+    }
+    return PNA_OK;
+}
+// The host layout of a solid stream (seg_off: the segment offsets, waited for): one SDAT chunk per segment (= per zstd frame / per run of deflate
+// blocks): [len "SDAT" | payload | crc]; with GCM one per GCM segment.  `pos`: where the stream's chunks start, then where they end.
+static int layout_solid(const SubBatch &sb, const SubPlan &p, const uint64_t *seg_off, SubLayout &L, uint64_t &pos) {
+    pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const uint32_t nseg = p.nseg;
+    auto sdat = [&](size_t k, uint64_t at, uint64_t cl) {           // the header of SDAT chunk k at archive offset `at`, `cl` bytes of data
+        uint8_t *pf = L.blob + 8 * k;
+        pf[0] = (uint8_t)(cl >> 24); pf[1] = (uint8_t)(cl >> 16); pf[2] = (uint8_t)(cl >> 8); pf[3] = (uint8_t)cl;
+        memcpy(pf + 4, "SDAT", 4);
+        L.fds[k] = FrameDesc{at, (uint32_t)cl, (uint32_t)(8 * k), 8u, 0};
+    };
+    sb.dst_off[sb.e0] = pos;
+    if (!fj->cipher || fj->cipher->cipher_mode != PNA_MODE_GCM) {
+        const uint64_t ctr_base = fj->crun ? fj->crun->pos : 0;
+        for (uint32_t sg = 0; sg < nseg; sg++) {
+            const uint64_t plen = seg_off[sg + 1] - seg_off[sg];
+            sdat(sg, pos, plen);
+            L.segdst[sg] = pos + 8;
+            if (fj->cipher)                                    // one cipher stream over all SDAT bodies: the keystream position runs on (over windows too)
+                for (uint64_t o = 0; o < plen; o += CTR_UNIT)
+                    L.cunits.push_back(CipherUnit{pos + 8 + o, ctr_base + (seg_off[sg] - seg_off[0]) + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, plen - o), 0u});
+            pos += 8 + plen + 4;
+        }
+        L.blob_len = 8 * (size_t)nseg;
+        if (fj->crun) fj->crun->pos += seg_off[nseg] - seg_off[0];
+        return PNA_OK;
+    }
+    // GCM STREAM over the solid stream (into_solid_archive takes any cipher, lib/src/archive/write.rs:443-470; GcmEncryptWriter, lib/src/cipher/
+    // gcm.rs:48-100): the head carries the stream header as its first SDAT chunk; here one SDAT chunk per GCM segment, ciphertext || tag.  The
+    // write kernels put the compressed stream down in one piece behind the first chunk header, segments k >= 1 then move forward by 28 k
+    // bytes (tag and CRC of the chunk before + their own chunk header), as a GCM entry of several segments does.
+    // A window of a windowed stream (fj->crun): the carry of the window before goes in front of the window's output, segment counters
+    // start at crun->seg, and unless the window is the stream's last, the tail that does not yet form a non-final segment (1 .. G bytes)
+    // is held back as the next carry.
+    SolidCipherRun *cr = fj->crun;
+    const uint64_t C = cr ? cr->carry_len : 0, P = C + seg_off[nseg] - seg_off[0], G = gcm_seg_size(fj->cipher), J = cr ? cr->seg : 0;
+    const bool last = !cr || cr->final_win;
+    const uint64_t K = last ? (P ? (P + G - 1) / G : (J ? 0 : 1)) : (P ? (P - 1) / G : 0);
+    const uint64_t E = last ? P : K * G;                                 // the bytes that go out in this window's segments
+    if (J + K > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
+    const uint64_t B = pos + 8;
+    if (B + P + 16 > sb.dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");      // (the compact stream, carry included)
+    for (uint32_t sg = 0; sg < nseg; sg++) L.segdst[sg] = B + C + (seg_off[sg] - seg_off[0]);
+    if (C) { L.carry_in = B; L.carry_in_len = C; }
+    if (P > E) L.carry_out = B + E;
+    if (cr) { cr->seg = J + K; cr->carry_len = P - E; }
+    for (uint64_t k = 0; k < K; k++) sdat((size_t)k, pos + k * (G + 28), std::min<uint64_t>(G, P - k * G) + 16);
+    L.gcm_segments(L.gmat[0], J, K, last, P, G, B, G + 28);
+    pos += E + 28 * K;
+    L.nunit = (size_t)K; L.blob_len = 8 * (size_t)K;
+    return PNA_OK;
+}
+// The host layout of file entries (seg_off: the segment offsets, waited for): [prefix | payload | crc | FEND] per entry; the write kernels put every
+// segment straight at its final place, k_frame adds the rest (no second copy of the payload).
+// FlattenWriter cuts an entry's stream into FDAT chunks of max_chunk_size bytes, the last one holding the rest (lib/src/util/io.rs:60-77:
+// the open chunk is topped up before a new one starts; FileEntryBuilder::max_chunk_size, lib/src/entry/builder/file.rs:105-112; default
+// u32::MAX, lib/src/chunk.rs:28).  The write kernels put an entry's payload down in one piece behind the first FDAT header; for an entry of
+// K > 1 chunks the payload is saved to a scratch buffer and chunks 1 .. K - 1 move forward by 12 k bytes (CRC of the chunk before +
+// their own length / type), k_frame then takes one descriptor per chunk.  The same pass serves the GCM STREAM layout below.
+static int layout_entries(const SubBatch &sb, const SubPlan &p, const uint64_t *seg_off, SubLayout &L, uint64_t &pos) {
+    pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const size_t e0 = sb.e0, e1 = sb.e1;
+    const uint64_t CH = chunk_limit(fj->max_chunk);
+    std::vector<FrameDesc> units; units.reserve(e1 - e0);
+    const int mode = fj->cipher ? fj->cipher->cipher_mode : -1;
+    const bool cbc = mode == PNA_MODE_CBC, gcm = mode == PNA_MODE_GCM, ctr = mode == PNA_MODE_CTR;
+    const uint64_t G = gcm ? gcm_seg_size(fj->cipher) : 0;
+    for (size_t e = e0; e < e1; e++) {
+        const uint32_t s0 = p.entry_first_seg[e - e0], s1 = p.entry_first_seg[e - e0 + 1];
+        const FrameDesc f0 = L.fds[e - e0];                // prefix of the entry: FHED | fSIZ | ... | first FDAT header
+        sb.dst_off[e] = pos;
+        const uint64_t p0 = pos + f0.prefix_len;           // where the payload starts
+        uint64_t plen = seg_off[s1] - seg_off[s0];         // the entry's compressed stream, then what the cipher makes of it
+        for (uint32_t sg = s0; sg < s1; sg++) L.segdst[sg] = p0 + (seg_off[sg] - seg_off[s0]);
+        if (cbc) {
+            // CBC chains the whole entry (one lane) and appends the PKCS#7 padding block, in place
+            L.cunits.push_back(CipherUnit{p0, 0, (uint32_t)plen, (uint32_t)(e - e0)});
+            plen = (plen / 16 + 1) * 16;
+            if (plen > CH) return fail(c, PNA_E_UNSUPPORTED, "CBC entry beyond one FDAT chunk");
+        } else if (gcm) {
+            // GCM STREAM: the payload in segments of segment_size bytes, every segment followed by its 16-byte tag; all but the last carry nonce
+            // flag 0, the last one (possibly full, possibly empty) flag 1; counters 0, 1, ...  Segments k >= 1 move forward by 16 k bytes before the cipher runs.
+            const uint64_t K = plen ? (plen + G - 1) / G : 1;
+            if (K > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
+            if (plen + 16 * K > CH) return fail(c, PNA_E_UNSUPPORTED, "GCM entry beyond one FDAT chunk");
+            L.gcm_segments(L.gmat[e - e0], 0, K, true, plen, G, p0, G + 16);
+            plen += 16 * K;
+        }
+        // the FDAT chunks: CH bytes each, the last one the rest (an empty payload is one empty chunk)
+        const uint64_t K = plen ? (plen + CH - 1) / CH : 1;
+        for (uint64_t k = 0; k < K; k++) {
+            const uint64_t cl = std::min<uint64_t>(CH, plen - k * CH), cstart = p0 + k * (CH + 12);   // the chunk's data in the archive
+            FrameDesc u;
+            if (k == 0) { u = f0; u.arc_off = pos; }
+            else { u.prefix_off = (uint32_t)L.blob_len; u.prefix_len = 8; u.arc_off = cstart - 8; memcpy(L.blob + L.blob_len + 4, "FDAT", 4); L.blob_len += 8; }
+            uint8_t *lenf = &L.blob[u.prefix_off + u.prefix_len - 8];  // FDAT chunk length, big-endian
+            lenf[0] = (uint8_t)(cl >> 24); lenf[1] = (uint8_t)(cl >> 16); lenf[2] = (uint8_t)(cl >> 8); lenf[3] = (uint8_t)cl;
+            u.payload_len = (uint32_t)cl; u.pad = k + 1 < K ? 2u : 0u;
+            units.push_back(u);
+            if (k >= 1) L.move(k * CH, cstart, cl);
+            if (ctr)                                       // CTR keeps the length and may be cut anywhere: the keystream position runs on over the chunks
+                for (uint64_t o = 0; o < cl; o += CTR_UNIT)
+                    L.cunits.push_back(CipherUnit{cstart + o, k * CH + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, cl - o), (uint32_t)(e - e0)});
+        }
+        if (K > 1) L.save(p0, plen);
+        pos += f0.prefix_len + plen + 12 * (K - 1) + 4 + 12;
+    }
+    L.nunit = units.size();
+    memcpy(L.fds, units.data(), L.nunit * sizeof(FrameDesc));
+    return PNA_OK;
+}
+// The write kernels: every segment's output at wbase + segdst[segment] (a deflate window of a solid stream: k_dwrite, then k_dfold); windowed GCM: the
+// carry of the window before in front of their output, then the new carry out of it; entries of several FDAT chunks / GCM segments: the compact
+// payloads saved, then the pieces behind the first one put at their places
+static int write_stage(const SubBatch &sb, const SubPlan &p, const SubLayout &L, const uint64_t *d_segdst, uint8_t *wbase) {
+    pna_gpu_ctx *c = sb.c; const hipStream_t st = sb.st; uint8_t *d_dst = sb.d_dst;
+    if (sb.algo == PNA_ALGO_DEFLATE && sb.fj && sb.fj->adler_carry) {
+        if (!launch_deflate_write_run) return fail(c, PNA_E_UNSUPPORTED, "deflate windows: this build has no k_dfold");
+        launch_deflate_write_run(sb.d_src, c->d_segs, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p,
+                                 (const uint8_t *)c->litc.p, c->d_entry_seg, wbase, st, c->call_stored, /* a wave per block */ p.wave_blk, sb.fj->adler_carry, sb.fj->run);
+    }
+    else if (sb.algo == PNA_ALGO_DEFLATE) launch_deflate_write(sb.d_src, c->d_segs, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p,
+                                                               (const uint8_t *)c->litc.p, c->d_entry_seg, (uint32_t)(sb.e1 - sb.e0), wbase, st, c->call_stored, p.wave_blk);
+    else launch_write(sb.d_src, c->d_segs, p.nseg, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, (const SegTables *)c->tabs.p, d_segdst, (const uint8_t *)c->lits.p,
+                      (const uint8_t *)c->litc.p, (const uint8_t *)c->seqc.p, wbase, p.any_empty, st, /* a wave per block */ p.wave_blk);
+    if (L.carry_in) HIPCHK(c, hipMemcpyAsync(d_dst + L.carry_in, sb.fj->crun->carry, L.carry_in_len, hipMemcpyDeviceToDevice, st));
+    if (L.carry_out) HIPCHK(c, hipMemcpyAsync(sb.fj->crun->carry, d_dst + L.carry_out, sb.fj->crun->carry_len, hipMemcpyDeviceToDevice, st));
+    if (L.spread.empty()) return PNA_OK;
+    std::vector<PlaceDescH> pd(L.spread.size());
+    for (size_t i = 0; i < L.spread.size(); i++) pd[i] = PlaceDescH{L.spread[i].src, L.spread[i].dst, L.spread[i].len, 0};
+    if (c->ci_spread.ensure(L.spread_bytes + 64) || c->ci_spread_desc.ensure(pd.size() * sizeof(PlaceDescH) + 16)) return fail(c, PNA_E_NOMEM, "chunk workspace");
+    uint64_t sp = 0;
+    for (auto &cp : L.spread_copy) { HIPCHK(c, hipMemcpyAsync((uint8_t *)c->ci_spread.p + sp, d_dst + cp.first, cp.second, hipMemcpyDeviceToDevice, st)); sp += (cp.second + 15) & ~(uint64_t)15; }
+    HIPCHK(c, hipMemcpyAsync(c->ci_spread_desc.p, pd.data(), pd.size() * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
+    launch_gather(c->ci_spread_desc.p, (uint32_t)pd.size(), (const uint8_t *)c->ci_spread.p, d_dst, st);
+    HIPCHK(c, hipStreamSynchronize(st));                      // pd goes out of scope
+    return PNA_OK;
+}
+// Plain file entries of one FDAT chunk each (no cipher; the worst case of every payload below the chunk limit and of the whole sub-batch below the
+// destination's capacity): the archive layout is computed on the device (k_layout) and the host never waits in the middle of the sub-batch.
+static int layout_device(const SubBatch &sb, const SubPlan &p, const SubLayout &L, HostMarks &hm) {
+    pna_gpu_ctx *c = sb.c; const hipStream_t st = sb.st; const size_t ne = sb.e1 - sb.e0;
+    if (c->fr_desc.ensure(ne * sizeof(FrameDesc)) || c->fr_blob.ensure(L.blob_len + 16) || c->fr_segdst.ensure((size_t)(p.nseg + 1) * 8) ||
+        c->fr_entoff.ensure((ne + 2 + 2 * (ne / 1024 + 2)) * 8) || c->h_entoff.ensure((ne + 2) * 8)) return fail(c, PNA_E_NOMEM, "framing workspace");
+    int rc = ensure_crc(c); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, L.fds, ne * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, L.blob, L.blob_len, hipMemcpyHostToDevice, st));
+    uint64_t *d_ent = (uint64_t *)c->fr_entoff.p;
+    launch_layout((FrameDesc *)c->fr_desc.p, (uint8_t *)c->fr_blob.p, c->d_entry_seg, (const uint64_t *)c->seg_off.p, (uint32_t)ne, p.nseg, sb.out_base,
+                  (uint64_t *)c->fr_segdst.p, d_ent, d_ent + ne + 1, st);
+    rc = write_stage(sb, p, L, (const uint64_t *)c->fr_segdst.p, sb.d_dst); if (rc) return rc;       // (no carry, no spread: entries of one chunk)
+    if (sb.timed) HIPCHK(c, hipEventRecord(c->ev[6], st));
+    launch_frame((const FrameDesc *)c->fr_desc.p, (uint32_t)ne, (const uint8_t *)c->fr_blob.p, (const CrcTabs *)c->crc_tabs.p,
+                 sb.d_dst, (uint64_t)sb.dst_cap & ~(uint64_t)15, frame_fend_crc(), "FDAT", true, st, p.frame_max_payload);
+    if (sb.timed) HIPCHK(c, hipEventRecord(c->ev[7], st));
+    // the entry offsets (when the caller wants them) and the sub-batch's length travel back behind the kernels: the call's one wait
+    uint64_t *h_ent = (uint64_t *)c->h_entoff.p;
+    if (sb.fj->want_offsets) HIPCHK(c, hipMemcpyAsync(h_ent, d_ent, (ne + 2) * 8, hipMemcpyDeviceToHost, st));
+    else HIPCHK(c, hipMemcpyAsync(h_ent + ne, d_ent + ne, 16, hipMemcpyDeviceToHost, st));
+    hm.mark("framing queued");
+    HIPCHK(c, hipStreamSynchronize(st));
+    hm.mark("device done"); hm.print(ne);
+    HIPCHK(c, hipGetLastError());
+    if (sb.fj->want_offsets) memcpy(sb.dst_off + sb.e0, h_ent, ne * 8);
+    sb.dst_off[sb.e1] = h_ent[ne];
+    c->last_nblk = p.nblk;
+    return sb.timed ? collect_timing(c, sb.algo == PNA_ALGO_DEFLATE, p.nseg, p.nblk, false) : PNA_OK;
+}
+// The cipher stage over the laid-out payloads, in place, before k_frame takes their CRC-32: CTR, CBC, or GCM STREAM (CTR under per-segment keys + tags)
+static int cipher_stage(const SubBatch &sb, const SubLayout &L) {
+    pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const hipStream_t st = sb.st; const size_t e0 = sb.e0, e1 = sb.e1;
+    const bool gcm = fj->cipher->cipher_mode == PNA_MODE_GCM;
+    if (fj->solid && fj->cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
+    int rc = ensure_aes(c); if (rc) return rc;
+    if (c->ci_units.ensure(L.cunits.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure((e1 - e0) * 16 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+    AesKey key; aes256_expand(fj->cipher->key, key);
+    HIPCHK(c, hipMemcpyAsync(c->ci_units.p, L.cunits.data(), L.cunits.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
+    if (gcm) {
+        if (c->ci_keys.ensure(L.gkeys.size() * sizeof(AesKey) + 16) || c->ci_gcm.ensure(L.gents.size() * sizeof(GcmEntry) + 16) || c->ci_ivs.ensure(L.giv.size() + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+        HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, L.giv.data(), L.giv.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, L.gkeys.data(), L.gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ci_gcm.p, L.gents.data(), L.gents.size() * sizeof(GcmEntry), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));                  // (the copies read host vectors)
+    } else HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, fj->ivs + 16 * e0, (e1 - e0) * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->ev_ci[0], st));
+    const CipherUnit *units = (const CipherUnit *)c->ci_units.p; const uint32_t nu = (uint32_t)L.cunits.size(); const uint8_t *ivs = (const uint8_t *)c->ci_ivs.p;
+    if (fj->cipher->cipher_mode == PNA_MODE_CBC) launch_aes_cbc_enc(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, st);
+    else launch_aes_ctr(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, gcm ? (const AesKey *)c->ci_keys.p : nullptr, st);   // (GCM: per-segment keys)
+    if (gcm) launch_gcm_tag((const GcmEntry *)c->ci_gcm.p, (uint32_t)L.gents.size(), sb.d_dst, st);
+    HIPCHK(c, hipEventRecord(c->ev_ci[1], st));
+    return PNA_OK;
+}
+// One sub-batch: entries [e0, e1) -> segments -> kernels; output appended at d_dst + out_base.
+int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                 size_t e0, size_t e1, uint8_t *d_dst, size_t dst_cap, uint64_t out_base, uint64_t *dst_off,
+                 hipStream_t st, bool timed, const FrameJob *fj) {
+    const SubBatch sb{c, algo, d_src, src_off, src_len, e0, e1, d_dst, dst_cap, out_base, dst_off, st, timed, fj};
+    HostMarks hm{c->tun.trace != 0};
+    SubPlan p;
+    int rc = plan_subbatch(sb, hm, p);
+    if (rc || p.nseg == 0) return rc;
+    hm.mark("plan queued");
+    rc = compress_subbatch(sb, p); if (rc) return rc;
+    hm.mark("kernels queued");
+    SubLayout L;
+    if (fj) { rc = frame_prefixes(sb, p, L); if (rc) return rc; }
+    hm.mark("prefixes built");
+    if (fj && !fj->solid && !fj->cipher && c->tun.dev_layout != 0 && !L.layout_over && out_base + L.layout_need + 16 <= dst_cap) return layout_device(sb, p, L, hm);
     // the output offsets are needed on the host before the write pass can be bounds-checked
-    if (c->h_segoff.ensure((size_t)(nseg + 1) * 8)) return fail(c, PNA_E_NOMEM, "offset staging");
+    if (c->h_segoff.ensure((size_t)(p.nseg + 1) * 8)) return fail(c, PNA_E_NOMEM, "offset staging");
     const uint64_t *seg_off = (const uint64_t *)c->h_segoff.p;
     // (plain batches whose destination holds the worst case of every entry need no check against the sizes found: the write kernels go out
     // at once, the offsets travel behind them and the one wait is the call's last -- a wait in the middle of a small batch is a tenth of it)
     bool early_write = !fj;
     if (early_write) { uint64_t need = out_base; for (size_t e = e0; e < e1; e++) need += pna_gpu_bound(algo, (size_t)src_len[e]); early_write = need <= dst_cap; }
     if (!early_write) {
-        HIPCHK(c, hipMemcpyAsync(c->h_segoff.p, c->seg_off.p, (size_t)(nseg + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(c->h_segoff.p, c->seg_off.p, (size_t)(p.nseg + 1) * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
+        L.total = seg_off[p.nseg];
     }
-    uint64_t total = early_write ? 0 : seg_off[nseg];
-    std::vector<CipherUnit> cunits;
-    uint64_t gcm_carry_in = 0, gcm_carry_in_len = 0, gcm_carry_out = 0;               // windowed GCM: where the carry goes in / the next one starts (0: none)
-    const uint64_t ctr_base = fj && fj->crun ? fj->crun->pos : 0;
     const uint64_t *d_segdst = (const uint64_t *)c->seg_off.p;
     uint8_t *wbase = d_dst + out_base;
     if (fj) {
-        // archive layout of this sub-batch: [prefix | payload | crc | FEND] per entry; the write kernels put every
-        // segment straight at its final place, k_frame adds the rest (no second copy of the payload)
+        // the host layout, checked against the destination; its descriptors, prefixes and segment destinations to the device
         uint64_t pos = out_base;
-        if (solid) {
-            // solid stream: one SDAT chunk per segment (= per zstd frame / per run of deflate blocks): [len "SDAT" | payload | crc]
-            dst_off[e0] = pos;
-            if (gcm) {
-                // GCM STREAM over the solid stream (into_solid_archive takes any cipher, lib/src/archive/write.rs:443-470; GcmEncryptWriter, lib/src/cipher/
-                // gcm.rs:48-100): the head carries the stream header as its first SDAT chunk; here one SDAT chunk per GCM segment, ciphertext || tag.  The
-                // write kernels put the compressed stream down in one piece behind the first chunk header, segments k >= 1 then move forward by 28 k
-                // bytes (tag and CRC of the chunk before + their own chunk header), as a GCM entry of several segments does.
-                // A window of a windowed stream (fj->crun): the carry of the window before goes in front of the window's output, segment counters
-                // start at crun->seg, and unless the window is the stream's last, the tail that does not yet form a non-final segment (1 .. G bytes)
-                // is held back as the next carry.
-                SolidCipherRun *cr = fj->crun;
-                const uint64_t C = cr ? cr->carry_len : 0, P = C + seg_off[nseg] - seg_off[0], G = gcm_seg, J = cr ? cr->seg : 0;
-                const bool last = !cr || cr->final_win;
-                const uint64_t K = last ? (P ? (P + G - 1) / G : (J ? 0 : 1)) : (P ? (P - 1) / G : 0);
-                const uint64_t E = last ? P : K * G;                                 // the bytes that go out in this window's segments
-                if (J + K > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
-                const uint64_t B = pos + 8;
-                if (B + P + 16 > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");      // (the compact stream, carry included)
-                for (uint32_t sg = 0; sg < nseg; sg++) segdst[sg] = B + C + (seg_off[sg] - seg_off[0]);
-                if (C) { gcm_carry_in = B; gcm_carry_in_len = C; }
-                if (P > E) gcm_carry_out = B + E;
-                if (cr) { cr->seg = J + K; cr->carry_len = P - E; }
-                if (K > 1) spread_copy.emplace_back(B, E);
-                const GcmMaterial &gm = gmat[0];
-                for (uint64_t k = 0; k < K; k++) {
-                    const uint64_t sl = std::min<uint64_t>(G, P - k * G), hk = pos + k * (G + 28), so_ = hk + 8;
-                    uint8_t *pf = blob + 8 * (size_t)k;
-                    const uint64_t cl = sl + 16;
-                    pf[0] = (uint8_t)(cl >> 24); pf[1] = (uint8_t)(cl >> 16); pf[2] = (uint8_t)(cl >> 8); pf[3] = (uint8_t)cl;
-                    memcpy(pf + 4, "SDAT", 4);
-                    fds[k] = FrameDesc{hk, (uint32_t)cl, (uint32_t)(8 * k), 8u, 0};
-                    const uint32_t si = (uint32_t)gsegs.size();
-                    uint8_t j0[16], eb[16];
-                    memcpy(j0, gm.ctr_iv, 7);
-                    const uint64_t q = J + k;                                    // the segment's counter in the stream
-                    j0[7] = (uint8_t)(q >> 24); j0[8] = (uint8_t)(q >> 16); j0[9] = (uint8_t)(q >> 8); j0[10] = (uint8_t)q; j0[11] = last && k + 1 == K ? 1 : 0;
-                    j0[12] = 0; j0[13] = 0; j0[14] = 0; j0[15] = 1;
-                    aes256_block_host(gm.rk, j0, eb);
-                    GcmSeg gs; memcpy(gs.ctr_iv, j0, 16); gs.ctr_iv[15] = 2; gs.entry = 0;
-                    gsegs.push_back(gs);
-                    for (uint64_t o = 0; o < sl; o += CTR_UNIT) cunits.push_back(CipherUnit{so_ + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
-                    GcmEntry ge{so_, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-                    memcpy(ge.h, gm.h, 16);
-                    for (int w = 0; w < 4; w++) ge.ej0[w] = ((uint32_t)eb[4 * w] << 24) | ((uint32_t)eb[4 * w + 1] << 16) | ((uint32_t)eb[4 * w + 2] << 8) | eb[4 * w + 3];
-                    gents.push_back(ge);
-                    if (k >= 1)
-                        for (uint64_t o = 0; o < sl; o += (1u << 20))
-                            spread.push_back(SpreadPiece{spread_bytes + k * G + o, so_ + o, (uint32_t)std::min<uint64_t>(1u << 20, sl - o)});
-                }
-                if (K > 1) spread_bytes += (E + 15) & ~(uint64_t)15;
-                pos += E + 28 * K;
-                nunit = (size_t)K; blob_len = 8 * (size_t)K;
-            } else {
-            for (uint32_t sg = 0; sg < nseg; sg++) {
-                const uint64_t plen = seg_off[sg + 1] - seg_off[sg];
-                uint8_t *pf = blob + 8 * (size_t)sg;
-                pf[0] = (uint8_t)(plen >> 24); pf[1] = (uint8_t)(plen >> 16); pf[2] = (uint8_t)(plen >> 8); pf[3] = (uint8_t)plen;
-                memcpy(pf + 4, "SDAT", 4);
-                fds[sg] = FrameDesc{pos, (uint32_t)plen, 8u * sg, 8u, 0};
-                segdst[sg] = pos + 8;
-                if (fj->cipher)                                    // one cipher stream over all SDAT bodies: the keystream position runs on (over windows too)
-                    for (uint64_t o = 0; o < plen; o += CTR_UNIT)
-                        cunits.push_back(CipherUnit{pos + 8 + o, ctr_base + (seg_off[sg] - seg_off[0]) + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, plen - o), 0u});
-                pos += 8 + plen + 4;
-            }
-            blob_len = 8 * (size_t)nseg;
-            if (fj->crun) fj->crun->pos += seg_off[nseg] - seg_off[0];
-            }
-        } else {
-            // FlattenWriter cuts an entry's stream into FDAT chunks of max_chunk_size bytes, the last one holding the rest (lib/src/util/io.rs:60-77:
-            // the open chunk is topped up before a new one starts; FileEntryBuilder::max_chunk_size, lib/src/entry/builder/file.rs:105-112; default
-            // u32::MAX, lib/src/chunk.rs:28).  The write kernels put an entry's payload down in one piece behind the first FDAT header; for an entry of
-            // K > 1 chunks the payload is saved to a scratch buffer and chunks 1 .. K - 1 move forward by 12 k bytes (CRC of the chunk before +
-            // their own length / type), k_frame then takes one descriptor per chunk.  The same pass serves the GCM STREAM layout below.
-            const uint64_t CH = chunk_limit(fj->max_chunk);
-            std::vector<FrameDesc> units; units.reserve(e1 - e0);
-            const bool cbc = fj->cipher && fj->cipher->cipher_mode == PNA_MODE_CBC;
-            const bool ctr = fj->cipher && !cbc && !gcm;
-            for (size_t e = e0; e < e1; e++) {
-                const uint32_t s0 = entry_first_seg[e - e0], s1 = entry_first_seg[e - e0 + 1];
-                const FrameDesc f0 = fds[e - e0];                  // prefix of the entry: FHED | fSIZ | ... | first FDAT header
-                dst_off[e] = pos;
-                const uint64_t p0 = pos + f0.prefix_len;           // where the payload starts
-                uint64_t plen = seg_off[s1] - seg_off[s0];         // the entry's compressed stream, then what the cipher makes of it
-                for (uint32_t sg = s0; sg < s1; sg++) segdst[sg] = p0 + (seg_off[sg] - seg_off[s0]);
-                if (cbc) {
-                    // CBC chains the whole entry (one lane) and appends the PKCS#7 padding block, in place
-                    cunits.push_back(CipherUnit{p0, 0, (uint32_t)plen, (uint32_t)(e - e0)});
-                    plen = (plen / 16 + 1) * 16;
-                    if (plen > CH) return fail(c, PNA_E_UNSUPPORTED, "CBC entry beyond one FDAT chunk");
-                } else if (gcm) {
-                    // GCM STREAM (GcmEncryptWriter, lib/src/cipher/gcm.rs:48-100): the payload in segments of segment_size bytes, every
-                    // segment followed by its 16-byte tag; all but the last carry nonce flag 0, the last one (possibly full, possibly
-                    // empty) flag 1; counters 0, 1, ...  Segments k >= 1 move forward by 16 k bytes before the cipher runs.
-                    const uint64_t K = plen ? (plen + gcm_seg - 1) / gcm_seg : 1;
-                    if (K > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
-                    if (plen + 16 * K > CH) return fail(c, PNA_E_UNSUPPORTED, "GCM entry beyond one FDAT chunk");
-                    const GcmMaterial &gm = gmat[e - e0];
-                    if (K > 1) { spread_copy.emplace_back(p0, plen); }
-                    for (uint64_t k = 0; k < K; k++) {
-                        const uint64_t sl = std::min<uint64_t>(gcm_seg, plen - k * gcm_seg), so_ = p0 + k * ((uint64_t)gcm_seg + 16);
-                        const uint32_t si = (uint32_t)gsegs.size();
-                        uint8_t j0[16], eb[16];
-                        memcpy(j0, gm.ctr_iv, 7);                                  // nonce prefix
-                        j0[7] = (uint8_t)(k >> 24); j0[8] = (uint8_t)(k >> 16); j0[9] = (uint8_t)(k >> 8); j0[10] = (uint8_t)k; j0[11] = k + 1 == K ? 1 : 0;
-                        j0[12] = 0; j0[13] = 0; j0[14] = 0; j0[15] = 1;
-                        aes256_block_host(gm.rk, j0, eb);
-                        GcmSeg gs; memcpy(gs.ctr_iv, j0, 16); gs.ctr_iv[15] = 2; gs.entry = (uint32_t)(e - e0);
-                        gsegs.push_back(gs);
-                        for (uint64_t o = 0; o < sl; o += CTR_UNIT)
-                            cunits.push_back(CipherUnit{so_ + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
-                        GcmEntry ge{so_, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-                        memcpy(ge.h, gm.h, 16);
-                        for (int w = 0; w < 4; w++) ge.ej0[w] = ((uint32_t)eb[4 * w] << 24) | ((uint32_t)eb[4 * w + 1] << 16) | ((uint32_t)eb[4 * w + 2] << 8) | eb[4 * w + 3];
-                        gents.push_back(ge);
-                        if (k >= 1)
-                            for (uint64_t o = 0; o < sl; o += (1u << 20))
-                                spread.push_back(SpreadPiece{spread_bytes + k * gcm_seg + o, so_ + o, (uint32_t)std::min<uint64_t>(1u << 20, sl - o)});
-                    }
-                    if (K > 1) spread_bytes += (plen + 15) & ~(uint64_t)15;
-                    plen += 16 * K;
-                }
-                // the FDAT chunks: CH bytes each, the last one the rest (an empty payload is one empty chunk)
-                const uint64_t K = plen ? (plen + CH - 1) / CH : 1;
-                if (K > 1) spread_copy.emplace_back(p0, plen);
-                for (uint64_t k = 0; k < K; k++) {
-                    const uint64_t cl = std::min<uint64_t>(CH, plen - k * CH), cstart = p0 + k * (CH + 12);   // the chunk's data in the archive
-                    FrameDesc u;
-                    if (k == 0) { u = f0; u.arc_off = pos; }
-                    else { u.prefix_off = (uint32_t)blob_len; u.prefix_len = 8; u.arc_off = cstart - 8; memcpy(blob + blob_len + 4, "FDAT", 4); blob_len += 8; }
-                    uint8_t *lenf = &blob[u.prefix_off + u.prefix_len - 8];  // FDAT chunk length, big-endian
-                    lenf[0] = (uint8_t)(cl >> 24); lenf[1] = (uint8_t)(cl >> 16); lenf[2] = (uint8_t)(cl >> 8); lenf[3] = (uint8_t)cl;
-                    u.payload_len = (uint32_t)cl; u.pad = k + 1 < K ? 2u : 0u;
-                    units.push_back(u);
-                    if (k >= 1)
-                        for (uint64_t o = 0; o < cl; o += (1u << 20))
-                            spread.push_back(SpreadPiece{spread_bytes + k * CH + o, cstart + o, (uint32_t)std::min<uint64_t>(1u << 20, cl - o)});
-                    if (ctr)                                       // CTR keeps the length and may be cut anywhere: the keystream position runs on over the chunks
-                        for (uint64_t o = 0; o < cl; o += CTR_UNIT)
-                            cunits.push_back(CipherUnit{cstart + o, k * CH + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, cl - o), (uint32_t)(e - e0)});
-                }
-                if (K > 1) spread_bytes += (plen + 15) & ~(uint64_t)15;
-                pos += f0.prefix_len + plen + 12 * (K - 1) + 4 + 12;
-            }
-            nunit = units.size();
-            memcpy(fds, units.data(), nunit * sizeof(FrameDesc));
-        }
-        segdst[nseg] = pos;
-        total = pos - out_base;
+        rc = fj->solid ? layout_solid(sb, p, seg_off, L, pos) : layout_entries(sb, p, seg_off, L, pos); if (rc) return rc;
+        L.segdst[p.nseg] = pos;
+        L.total = pos - out_base;
         if (pos + 16 > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
-        if (c->fr_desc.ensure(nunit * sizeof(FrameDesc)) || c->fr_blob.ensure(blob_len + 16) || c->fr_segdst.ensure((size_t)(nseg + 1) * 8))
+        if (c->fr_desc.ensure(L.nunit * sizeof(FrameDesc)) || c->fr_blob.ensure(L.blob_len + 16) || c->fr_segdst.ensure((size_t)(p.nseg + 1) * 8))
             return fail(c, PNA_E_NOMEM, "framing workspace");
-        int rc = ensure_crc(c); if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, fds, nunit * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, blob, blob_len, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->fr_segdst.p, segdst, (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, st));
+        rc = ensure_crc(c); if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, L.fds, L.nunit * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, L.blob, L.blob_len, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->fr_segdst.p, L.segdst, (size_t)(p.nseg + 1) * 8, hipMemcpyHostToDevice, st));
         d_segdst = (const uint64_t *)c->fr_segdst.p; wbase = d_dst;
-    } else if (!early_write && out_base + total > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
-    if (defl && fj && fj->adler_carry) {
-        if (!launch_deflate_write_run) return fail(c, PNA_E_UNSUPPORTED, "deflate windows: this build has no k_dfold");
-        launch_deflate_write_run(d_src, c->d_segs, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p,
-                                 (const uint8_t *)c->litc.p, c->d_entry_seg, wbase, st, c->call_stored, /* a wave per block */ max_len <= 32768 && nseg >= 4096,
-                                 fj->adler_carry, fj->run);
-    }
-    else if (defl) launch_deflate_write(d_src, c->d_segs, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p,
-                                   d_segdst, (const uint64_t *)c->seg_size.p, (const uint8_t *)c->litc.p, c->d_entry_seg,
-                                   (uint32_t)(e1 - e0), wbase, st, c->call_stored, /* a wave per block */ max_len <= 32768 && nseg >= 4096);
-    else launch_write(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const BlkInfo *)c->blk.p,
-                 (const SegTables *)c->tabs.p, d_segdst, (const uint8_t *)c->lits.p,
-                 (const uint8_t *)c->litc.p, (const uint8_t *)c->seqc.p, wbase, any_empty, st, /* a wave per block */ max_len <= 32768 && nseg >= 4096);
-    // windowed GCM: the carry of the window before in front of the write kernels' output, then the new carry out of it (both before the spread)
-    if (gcm_carry_in) HIPCHK(c, hipMemcpyAsync(d_dst + gcm_carry_in, fj->crun->carry, gcm_carry_in_len, hipMemcpyDeviceToDevice, st));
-    if (gcm_carry_out) HIPCHK(c, hipMemcpyAsync(fj->crun->carry, d_dst + gcm_carry_out, fj->crun->carry_len, hipMemcpyDeviceToDevice, st));
-    if (!spread.empty()) {
-        // entries of several FDAT chunks / GCM segments: save the compact payloads, then put the pieces behind the first one at their places
-        std::vector<PlaceDescH> pd(spread.size());
-        for (size_t i = 0; i < spread.size(); i++) pd[i] = PlaceDescH{spread[i].src, spread[i].dst, spread[i].len, 0};
-        if (c->ci_spread.ensure(spread_bytes + 64) || c->ci_spread_desc.ensure(pd.size() * sizeof(PlaceDescH) + 16)) return fail(c, PNA_E_NOMEM, "chunk workspace");
-        uint64_t sp = 0;
-        for (auto &cp : spread_copy) { HIPCHK(c, hipMemcpyAsync((uint8_t *)c->ci_spread.p + sp, d_dst + cp.first, cp.second, hipMemcpyDeviceToDevice, st)); sp += (cp.second + 15) & ~(uint64_t)15; }
-        HIPCHK(c, hipMemcpyAsync(c->ci_spread_desc.p, pd.data(), pd.size() * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
-        launch_gather(c->ci_spread_desc.p, (uint32_t)pd.size(), (const uint8_t *)c->ci_spread.p, d_dst, st);
-        HIPCHK(c, hipStreamSynchronize(st));                      // pd goes out of scope
-    }
-    if (fj && fj->cipher) {
-        if (solid && fj->cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
-        int rc = ensure_aes(c); if (rc) return rc;
-        if (c->ci_units.ensure(cunits.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure((e1 - e0) * 16 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
-        AesKey key; aes256_expand(fj->cipher->key, key);
-        HIPCHK(c, hipMemcpyAsync(c->ci_units.p, cunits.data(), cunits.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
-        std::vector<uint8_t> giv; std::vector<AesKey> gkeys;
-        if (gcm) {
-            giv.resize(gsegs.size() * 16); gkeys.resize(gsegs.size());
-            for (size_t i = 0; i < gsegs.size(); i++) { memcpy(&giv[16 * i], gsegs[i].ctr_iv, 16); gkeys[i] = gmat[gsegs[i].entry].rk; }
-            if (c->ci_keys.ensure(gkeys.size() * sizeof(AesKey) + 16) || c->ci_gcm.ensure(gents.size() * sizeof(GcmEntry) + 16) || c->ci_ivs.ensure(giv.size() + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
-            HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, giv.data(), giv.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, gkeys.data(), gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->ci_gcm.p, gents.data(), gents.size() * sizeof(GcmEntry), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));                  // the host vectors above go out of scope
-        } else HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, fj->ivs + 16 * e0, (e1 - e0) * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipEventRecord(c->ev_ci[0], st));
-        if (gcm) {
-            launch_aes_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)cunits.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, d_dst, key, (const AesKey *)c->ci_keys.p, st);
-            launch_gcm_tag((const GcmEntry *)c->ci_gcm.p, (uint32_t)gents.size(), d_dst, st);
-        } else if (fj->cipher->cipher_mode == PNA_MODE_CTR)
-            launch_aes_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)cunits.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, d_dst, key, nullptr, st);
-        else
-            launch_aes_cbc_enc((const CipherUnit *)c->ci_units.p, (uint32_t)cunits.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, d_dst, key, st);
-        HIPCHK(c, hipEventRecord(c->ev_ci[1], st));
-    }
+    } else if (!early_write && out_base + L.total > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
+    rc = write_stage(sb, p, L, d_segdst, wbase); if (rc) return rc;
+    if (fj && fj->cipher) { rc = cipher_stage(sb, L); if (rc) return rc; }
+    // k_frame over the framed units; the offsets (early_write: the segment offsets travel back behind the kernels) and, timed, the stage times.  The call
+    // waits here: the staging buffers are reused by the next sub-batch.
     if (timed) HIPCHK(c, hipEventRecord(c->ev[6], st));
-    if (fj) launch_frame((const FrameDesc *)c->fr_desc.p, (uint32_t)nunit, (const uint8_t *)c->fr_blob.p, (const CrcTabs *)c->crc_tabs.p,
-                         d_dst, (uint64_t)dst_cap & ~(uint64_t)15, frame_fend_crc(), solid ? "SDAT" : "FDAT", !solid, st, frame_max_payload);
+    if (fj) launch_frame((const FrameDesc *)c->fr_desc.p, (uint32_t)L.nunit, (const uint8_t *)c->fr_blob.p, (const CrcTabs *)c->crc_tabs.p,
+                         d_dst, (uint64_t)dst_cap & ~(uint64_t)15, frame_fend_crc(), fj->solid ? "SDAT" : "FDAT", !fj->solid, st, p.frame_max_payload);
     if (timed) HIPCHK(c, hipEventRecord(c->ev[7], st));
     HIPCHK(c, hipGetLastError());
     if (early_write) {
-        HIPCHK(c, hipMemcpyAsync(c->h_segoff.p, c->seg_off.p, (size_t)(nseg + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(c->h_segoff.p, c->seg_off.p, (size_t)(p.nseg + 1) * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
-        total = seg_off[nseg];
+        L.total = seg_off[p.nseg];
     }
-    if (!fj) for (size_t e = e0; e < e1; e++) dst_off[e] = out_base + seg_off[entry_first_seg[e - e0]];
-    dst_off[e1] = out_base + total;
-    c->last_nblk = nblk;
-    if (fj && !timed) HIPCHK(c, hipStreamSynchronize(st));        // the staging buffers are reused by the next sub-batch
-    if (timed) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        int rct = collect_timing(c, defl, nch, nseg, nblk, fj && fj->cipher);
-        if (rct) return rct;
-    }
-    return PNA_OK;
+    if (!fj) for (size_t e = e0; e < e1; e++) dst_off[e] = out_base + seg_off[p.entry_first_seg[e - e0]];
+    dst_off[e1] = out_base + L.total;
+    c->last_nblk = p.nblk;
+    if (fj || timed) HIPCHK(c, hipStreamSynchronize(st));
+    return timed ? collect_timing(c, algo == PNA_ALGO_DEFLATE, p.nseg, p.nblk, fj && fj->cipher) : PNA_OK;
 }
 
 extern "C" int pna_gpu_compress_batch_device(pna_gpu_ctx *c, int algo, int level, size_t n, const void *d_src,
@@ -1248,7 +1266,7 @@ extern "C" size_t pna_gpu_archive_enc_bound(int algo, size_t n, const char *cons
     if (cipher && cipher->encryption != PNA_ENC_NONE && cipher->phsf) {
         b += n * (12 + strlen(cipher->phsf) + 12 + 75 + 16);   // PHSF, FDAT(iv | stream header), CBC padding / the final GCM tag
         if (cipher->cipher_mode == PNA_MODE_GCM) {               // one more tag per full stream segment of the (bounded) payload
-            const uint64_t seg = cipher->gcm_segment_size ? cipher->gcm_segment_size : (1u << 20);
+            const uint64_t seg = gcm_seg_size(cipher);
             for (size_t i = 0; i < n; i++) b += 16 * (pna_gpu_bound(algo, (size_t)src_len[i]) / seg);
         }
     }
@@ -1419,7 +1437,7 @@ extern "C" size_t pna_gpu_solid_archive_enc_bound(int algo, size_t n, const char
     if (!cipher || cipher->encryption == PNA_ENC_NONE) return b;
     b += 12 + (cipher->phsf ? strlen(cipher->phsf) : 0) + 12 + 75 + 64;          // PHSF chunk, the chunk of the IV / stream header
     if (cipher->cipher_mode == PNA_MODE_GCM) {
-        const uint64_t seg = cipher->gcm_segment_size ? cipher->gcm_segment_size : (1u << 20);
+        const uint64_t seg = gcm_seg_size(cipher);
         b += 28 * (size_t)(b / seg + 2);                                            // tag + chunk framing per GCM segment
     }
     return b;
@@ -1488,15 +1506,7 @@ extern "C" int pna_gpu_create_solid_archive_enc_device(pna_gpu_ctx *c, int algo,
     // ---- 2 + 3. one entry -> SDAT chunks, between the fixed chunks
     c->timing = pna_gpu_timing{};
     std::vector<uint8_t> head, tail;
-    frame_archive_head(head, 0);
-    if (cipher && cipher->cipher_mode == PNA_MODE_GCM) {
-        // the stream header (salt || nonce prefix || segment size || key confirmation: 75 bytes) is the stream's first write, a chunk of its own
-        GcmMaterial gm; uint8_t kc[32], ph[32];
-        hkdf_sha256_32(cipher->key, 32, nullptr, 0, "PNA-KC-v1", 9, kc);
-        sha256_bytes(cipher->phsf, strlen(cipher->phsf), nullptr, 0, ph);
-        gcm_entry_material(cipher, kc, ph, ivs, cipher->gcm_segment_size ? cipher->gcm_segment_size : (1u << 20), nullptr, algo, gm);
-        frame_solid_head_enc(head, algo, cipher->encryption, cipher->cipher_mode, cipher->phsf, gm.header, 75);
-    } else if (cipher) frame_solid_head_enc(head, algo, cipher->encryption, cipher->cipher_mode, cipher->phsf, ivs, 16); else frame_solid_head(head, algo);
+    solid_archive_head(head, algo, cipher, ivs);
     frame_solid_tail(tail); frame_archive_tail(tail);
     if (head.size() + tail.size() + 64 > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
     HIPCHK(c, hipMemcpyAsync(d_dst, head.data(), head.size(), hipMemcpyHostToDevice, st));

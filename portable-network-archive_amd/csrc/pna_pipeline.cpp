@@ -57,16 +57,8 @@ static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const cha
     // ---- the fixed chunks around the stream
     std::vector<uint8_t> head, tail;
     const bool gcm = cipher && cipher->cipher_mode == PNA_MODE_GCM;
-    const uint64_t G = gcm ? (cipher->gcm_segment_size ? cipher->gcm_segment_size : (1u << 20)) : 0;
-    frame_archive_head(head, 0);
-    if (gcm) {                                                  // the stream header is the stream's first SDAT chunk, as in the device form
-        GcmMaterial gm; uint8_t kc[32], ph[32];
-        hkdf_sha256_32(cipher->key, 32, nullptr, 0, "PNA-KC-v1", 9, kc);
-        sha256_bytes(cipher->phsf, strlen(cipher->phsf), nullptr, 0, ph);
-        gcm_entry_material(cipher, kc, ph, ivs, (uint32_t)G, nullptr, algo, gm);
-        frame_solid_head_enc(head, algo, cipher->encryption, cipher->cipher_mode, cipher->phsf, gm.header, 75);
-    } else if (cipher) frame_solid_head_enc(head, algo, cipher->encryption, cipher->cipher_mode, cipher->phsf, ivs, 16);
-    else frame_solid_head(head, algo);
+    const uint64_t G = gcm ? gcm_seg_size(cipher) : 0;
+    solid_archive_head(head, algo, cipher, ivs);                // (GCM: the stream header is the stream's first SDAT chunk, as in the device form)
     frame_solid_tail(tail); frame_archive_tail(tail);
     if (sink(user, head.data(), head.size()) != 0) return fail(c, PNA_E_SINK, "sink failed");
     const uint64_t W = std::max<uint64_t>(1, (uint64_t)c->tun.solid_win_mib) << 20;           // a multiple of SEG_SIZE
@@ -451,7 +443,7 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
     //   * sub-batch sizes grow from 64 MiB to `sub_mib` (default 256 MiB) at the start: the first kernels start after 2 ms instead of 20, and
     //     what is left to do when the last input byte has arrived is the work of one sub-batch.  256 MiB is the smallest size whose kernels
     //     (1.2 ms of fixed costs + 1 ms per 85 MiB) keep up with its H2D copy (1 ms per 53 MiB); shrinking sizes at the end only makes the
-    //     kernels fall behind the copies (measured: option sub_ramp_down).
+    //     kernels fall behind the copies (measured, LAB_LOG.md).
     const uint64_t SUBMAX = (uint64_t)c->tun.sub_mib << 20, SUBMIN = std::min<uint64_t>(64ull << 20, SUBMAX);
     struct Sub { size_t e0, e1; uint64_t in_bytes, out_cap; };
     std::vector<Sub> subs;
@@ -469,7 +461,7 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
             const uint64_t l = src_len[i], wb = pna_gpu_bound(algo, (size_t)l);
             tot += l; mx = std::max(mx, l);
             uint64_t cap = (cipher ? frame_entry_prefix_enc_bound(names[i], cipher->phsf) + 16 : frame_entry_prefix_bound(names[i])) + meta_len(meta, i) + wb + 16;
-            if (cipher && cipher->cipher_mode == PNA_MODE_GCM) cap += 16 * (wb / (cipher->gcm_segment_size ? cipher->gcm_segment_size : (1u << 20)));   // a tag per full stream segment
+            if (cipher && cipher->cipher_mode == PNA_MODE_GCM) cap += 16 * (wb / gcm_seg_size(cipher));   // a tag per full stream segment
             // a CRC + a header per further FDAT chunk once max_chunk_size cuts the payload (the term of pna_gpu_archive_chunked_bound: without it data
             // that does not compress overran the sub-batch's device buffer by 12 bytes per chunk -- PNA_E_DSTSIZE for a 2 MiB random entry at mcs = 1000)
             cap += 12 * (uint64_t)((wb + 64 + 16 * (l >> 12)) / chunk_limit(max_chunk) + 1);
@@ -481,12 +473,9 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
     plan_call_longest(c, longest);
     const auto t_caps = std::chrono::steady_clock::now();
     {
-        uint64_t done = 0, target = SUBMIN;
+        uint64_t target = SUBMIN;
         for (size_t e = 0; e < n;) {
-            const uint64_t rest = in_total - done;
-            uint64_t want = std::min(target, SUBMAX);
-            if (c->tun.sub_ramp_down && rest < 2 * want) want = std::max(SUBMIN, rest / 2);   // (option) ramp down: half of what is left, not below the minimum
-            (void)rest;
+            const uint64_t want = std::min(target, SUBMAX);
             Sub sb{e, e, 0, 64}; uint64_t pos = 0; size_t blocks = 0;
             while (sb.e1 < n) {
                 const size_t i = sb.e1; const uint64_t l = src_len[i];
@@ -494,7 +483,7 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
                 if (i > sb.e0 && (pos + l > want || blocks + nb > c->max_blocks)) break;
                 off[i] = pos; len64[i] = l; pos = (pos + l + 15) & ~(uint64_t)15; blocks += nb;
                 sb.out_cap += ecap[i];
-                done += l; sb.e1++;
+                sb.e1++;
             }
             sb.in_bytes = pos; subs.push_back(sb); e = sb.e1;
             target = std::min(SUBMAX, target * 2);

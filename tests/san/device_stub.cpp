@@ -1,6 +1,7 @@
 // tests/san/device_stub.cpp -- TEST INFRASTRUCTURE: the launch layer of libpna_gpu.so on the CPU for the sanitizer builds.
 // The zstd write path is stubbed with a trivially valid encoder (every segment = one frame of RAW blocks; the empty entry = the
-// reference's 9-byte frame), the framing kernel (prefix + CRC-32 + FEND) is restated bytewise; everything else aborts: the sanitizer
+// reference's 9-byte frame), the framing kernels (prefix + CRC-32 + FEND, the pieces' raw CRC registers, the CRC patches) are restated bytewise, the
+// cipher kernels by keyed hashes that fold in everything the host hands them; everything else aborts: the sanitizer
 // driver exercises the HOST code around the kernels, not the codecs (those are checked against the oracle on the GPU).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -99,8 +100,6 @@ void launch_zxxh(ZFrame *, uint32_t, const uint8_t *, const uint8_t *, hipStream
 void launch_zscan(const ZEntry *, uint32_t, const uint8_t *, ZFrame *, ZFrameX *, hipStream_t) { nostub("zscan"); }
 void launch_zcount(const ZEntry *, uint32_t, const uint8_t *, uint32_t *, hipStream_t) { nostub("zcount"); }
 void launch_zlist(const uint8_t *, uint64_t, uint64_t, uint64_t, void *, uint32_t, uint64_t *, hipStream_t) { nostub("zlist"); }
-void launch_frame_pieces(const FrameDesc *, uint32_t, const CrcTabs *, const uint8_t *, uint64_t, const char[4], uint32_t *, hipStream_t) { nostub("frame_pieces"); }
-void launch_crc_patch(const void *, uint32_t, uint8_t *, hipStream_t) { nostub("crc_patch"); }
 void launch_zparse(ZFrame *, ZFrameX *, uint32_t, const uint8_t *, ZBlock *, ZTables *, uint32_t *, uint32_t *, void *, hipStream_t) { nostub("zparse"); }
 void launch_zstreams(uint32_t, uint32_t, const uint32_t *, const uint32_t *, const void *, ZBlock *, const ZFrame *, const ZTables *, const uint8_t *, uint8_t *, uint64_t *, hipStream_t) { nostub("zstreams"); }
 void launch_inflate(ZFrame *, ZFrameX *, uint32_t, const uint8_t *, ZBlock *, uint8_t *, uint64_t *, const uint32_t *, hipStream_t) { nostub("inflate"); }
@@ -111,10 +110,63 @@ void launch_vinflate(ZFrame *, ZFrameX *, uint32_t, const void *, uint32_t, uint
 void launch_iadler(ZFrame *, const ZFrameX *, const ZBlock *, uint32_t, const uint32_t *, uint32_t, const uint8_t *, void *, hipStream_t) { nostub("iadler"); }
 void launch_zexec(ZFrame *, const ZFrameX *, uint32_t, ZBlock *, const uint8_t *, const uint8_t *, const uint64_t *, uint8_t *, hipStream_t) { nostub("zexec"); }
 void launch_zexec_groups(ZFrame *, const ZFrameX *, uint32_t, ZBlock *, const void *, uint32_t, const uint8_t *, const uint8_t *, const uint64_t *, uint8_t *, hipStream_t) { nostub("zexec"); }
-void launch_gcm_tag(const GcmEntry *, uint32_t, uint8_t *, hipStream_t) { nostub("gcm"); }
 void launch_gcm_verify(const GcmEntry *, uint32_t, const uint8_t *, const uint8_t *, uint32_t *, hipStream_t) { nostub("gcm"); }
 void launch_aes_cbc_dec(const CipherUnit *, uint32_t, const uint8_t *, const AesDecTabs *, uint8_t *, const AesKey &, uint32_t *, hipStream_t) { nostub("aes"); }
-void launch_aes_ctr(const CipherUnit *, uint32_t, const uint8_t *, const AesTabs *, uint8_t *, const AesKey &, const AesKey *, hipStream_t) { nostub("aes"); }
-void launch_aes_cbc_enc(const CipherUnit *, uint32_t, const uint8_t *, const AesTabs *, uint8_t *, const AesKey &, hipStream_t) { nostub("aes"); }
+// Pieces of chunks (k_frame's piece mode, FrameDesc::pad bit 8 = a later piece): the raw CRC-32 register of "FDAT" || piece with the folded initial value
+// (first piece) or of the piece's bytes from register 0 (later piece); pna_crc32(c, ..) = ~register(~c, ..)
+void launch_frame_pieces(const FrameDesc *fd, uint32_t n, const CrcTabs *, const uint8_t *buf, uint64_t, const char ty[4], uint32_t *states, hipStream_t) {
+    for (uint32_t i = 0; i < n; i++) {
+        const FrameDesc &d = fd[i];
+        const uint8_t *pay = buf + d.arc_off + d.prefix_len;
+        states[i] = (d.pad & 8) ? ~pna_crc32(0xFFFFFFFFu, pay, d.payload_len) : ~pna_crc32(pna_crc32(0, ty, 4), pay, d.payload_len);
+    }
+}
+struct CrcPatch { int64_t off; uint32_t crc, mask; };
+void launch_crc_patch(const void *patches, uint32_t n, uint8_t *dst, hipStream_t) {
+    for (uint32_t i = 0; i < n; i++) {
+        const CrcPatch &q = ((const CrcPatch *)patches)[i];
+        for (int j = 0; j < 4; j++) if ((q.mask >> j) & 1) dst[q.off + j] = (uint8_t)(q.crc >> (24 - 8 * j));
+    }
+}
+// The cipher stage: no AES, but every byte written depends on everything the host hands the kernels -- the unit's offset (where it writes) and stream
+// position, its IV, the round keys (the call's, or GCM's per-segment ones) -- and a GCM tag on the segment's bytes, length, hash subkey and E(K, J0).
+static uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31);
+}
+static uint64_t fold(uint64_t h, const void *p, size_t n) {
+    for (size_t i = 0; i < n; i++) h = (h ^ ((const uint8_t *)p)[i]) * 0x100000001B3ull;
+    return mix64(h);
+}
+void launch_aes_ctr(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *, uint8_t *buf, const AesKey &key, const AesKey *keys, hipStream_t) {
+    for (uint32_t i = 0; i < n; i++) {
+        const CipherUnit &u = units[i];
+        const uint64_t seed = fold(fold(0xC7Bull, ivs + 16 * (size_t)u.iv_idx, 16), keys ? keys[u.iv_idx].rk : key.rk, sizeof key.rk);
+        for (uint32_t j = 0; j < u.len; j++) { const uint64_t p = u.pos + j; buf[u.off + j] ^= (uint8_t)(mix64(seed + (p >> 3)) >> (8 * (p & 7))); }
+    }
+}
+void launch_aes_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *, uint8_t *buf, const AesKey &key, hipStream_t) {
+    const uint64_t kh = fold(0xCBCull, key.rk, sizeof key.rk);
+    for (uint32_t i = 0; i < n; i++) {                          // PKCS#7 padding, then every block XORed with a hash of the block before (the IV first)
+        const CipherUnit &u = units[i];
+        uint8_t *p = buf + u.off;
+        const uint32_t padded = (u.len / 16 + 1) * 16;
+        memset(p + u.len, (int)(padded - u.len), padded - u.len);
+        uint8_t prev[16]; memcpy(prev, ivs + 16 * (size_t)u.iv_idx, 16);
+        for (uint32_t b = 0; b < padded; b += 16) {
+            const uint64_t h0 = fold(kh, prev, 16), h1 = mix64(h0 + 1);
+            for (int j = 0; j < 16; j++) p[b + j] ^= (uint8_t)((j < 8 ? h0 : h1) >> (8 * (j & 7)));
+            memcpy(prev, p + b, 16);
+        }
+    }
+}
+void launch_gcm_tag(const GcmEntry *ents, uint32_t n, uint8_t *buf, hipStream_t) {
+    for (uint32_t i = 0; i < n; i++) {
+        const GcmEntry &g = ents[i];
+        uint64_t h = fold(fold(fold(0x6C3ull, &g.len, 4), &g.pad, 4), g.h, 16);          // (not `off`: a buffer offset, it picks the bytes)
+        h = fold(fold(h, g.ej0, 16), buf + g.off, g.len);
+        const uint64_t h1 = mix64(h + 1);
+        for (int j = 0; j < 16; j++) buf[g.off + g.len + j] = (uint8_t)((j < 8 ? h : h1) >> (8 * (j & 7)));
+    }
+}
 void launch_corpus(int, uint64_t, uint64_t, uint64_t, uint64_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *, hipStream_t) { nostub("corpus"); }
 } // namespace pna

@@ -182,6 +182,106 @@ static void test_pipeline_and_append(pna_gpu_ctx *c) {
     CHECK(pna_gpu_stream_entry_begin(c, PNA_ALGO_ZSTD, 3, "x", "garbage", 7, 0, vec_sink, &rec, &w) == PNA_E_INVAL);
 }
 
+// Framing matrix: archives of every framing form the encode core lays out -- plain, metadata, several FDAT chunks, device / host layout, part flags,
+// CTR / CBC / GCM (several segments per entry, an empty entry), solid on the device and windowed from host memory -- with fixed IVs and salts.  Each one
+// is walked (every chunk CRC) and its CRC-32 compared with the value recorded when the matrix was written: any change in what the host hands the
+// (stubbed) kernels changes the bytes.
+static Bytes chunk(const char ty[4], const Bytes &body) {
+    Bytes o = {(uint8_t)(body.size() >> 24), (uint8_t)(body.size() >> 16), (uint8_t)(body.size() >> 8), (uint8_t)body.size()};
+    o.insert(o.end(), ty, ty + 4); o.insert(o.end(), body.begin(), body.end());
+    const uint32_t crc = pna_crc32(pna_crc32(0, ty, 4), body.data(), body.size());
+    for (int s = 24; s >= 0; s -= 8) o.push_back((uint8_t)(crc >> s));
+    return o;
+}
+static void framing_case(const char *what, const Bytes &arc, uint32_t want, const Bytes *whole = nullptr) {   // whole: a part, walked inside an archive
+    std::vector<Chunk> ch;
+    const bool ok = walk(whole ? *whole : arc, ch);
+    const uint32_t got = pna_crc32(0, arc.data(), arc.size());
+    printf("framing %-28s %8zu bytes crc %08x\n", what, arc.size(), got);
+    if (!ok || got != want) { fprintf(stderr, "framing %s: %s (crc %08x, recorded %08x)\n", what, ok ? "bytes changed" : "malformed archive", got, want); g_fail++; }
+}
+static void test_framing_matrix() {
+    pna_gpu_ctx *c = nullptr;
+    CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK);
+    if (!c) return;
+    // entries: empty, small, one segment, several segments (the last one short), in one 16-byte aligned device buffer
+    const size_t lens[] = {0, 5000, 70000, 1 << 20, (1 << 20) + (1 << 19) + 333, 12345};
+    const size_t n = sizeof lens / sizeof lens[0];
+    std::vector<uint64_t> off(n), len(n); std::vector<std::string> nm(n); std::vector<const char *> names(n);
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) { off[i] = at; len[i] = lens[i]; at = (at + lens[i] + 15) & ~(uint64_t)15; nm[i] = "m/" + std::to_string(i) + ".bin"; names[i] = nm[i].c_str(); }
+    Bytes src(at + 64, 0);
+    for (size_t i = 0; i < n; i++) { const Bytes t = text(lens[i], 7000 + (uint32_t)i); if (!t.empty()) memcpy(&src[off[i]], t.data(), t.size()); }
+    uint8_t ivs[6 * 39];
+    for (size_t i = 0; i < sizeof ivs; i++) ivs[i] = (uint8_t)(i * 37 + 11);
+    pna_gpu_cipher ctr = {PNA_ENC_AES, PNA_MODE_CTR, {0}, "$pbkdf2-sha256$i=100,l=32$c2FsdA$aGFzaA", ivs, 0};
+    for (int i = 0; i < 32; i++) ctr.key[i] = (uint8_t)(3 * i + 1);
+    pna_gpu_cipher cbc = ctr; cbc.cipher_mode = PNA_MODE_CBC;
+    pna_gpu_cipher gcm = ctr; gcm.cipher_mode = PNA_MODE_GCM; gcm.gcm_segment_size = 65536;
+    // metadata: an extra chunk in front of fSIZ and a facet behind it, on some entries
+    const Bytes ex = chunk("tEST", Bytes{1, 2, 3}), fa = chunk("mTIM", Bytes{0, 0, 0, 0, 0x5F, 0, 0, 1});
+    std::vector<const void *> exv(n, ex.data()), fav(n, fa.data()); std::vector<size_t> exl(n, 0), fal(n, 0);
+    exl[1] = exl[3] = ex.size(); fal[1] = fal[2] = fal[5] = fa.size();
+    const pna_gpu_entry_meta meta = {exv.data(), exl.data(), fav.data(), fal.data()};
+    auto dev = [&](const char *what, const pna_gpu_cipher *ci, const pna_gpu_entry_meta *m, uint32_t mcs, uint32_t parts, uint32_t want) {
+        const size_t cap = pna_gpu_archive_chunked_bound(PNA_ALGO_ZSTD, n, names.data(), len.data(), ci, mcs) + 4096;
+        Bytes dst(cap + 16); uint8_t *d = dst.data() + ((16 - ((uintptr_t)dst.data() & 15)) & 15);
+        std::vector<uint64_t> eoff(n + 1); uint64_t alen = 0;
+        const int rc = pna_gpu_create_archive_chunked_device(c, PNA_ALGO_ZSTD, 3, n, names.data(), src.data(), off.data(), len.data(), ci, m, mcs, d, cap,
+                                                             eoff.data(), &alen, parts, nullptr);
+        CHECK(rc == PNA_OK && eoff[n] <= alen);
+        Bytes arc(d, d + (rc == PNA_OK ? alen : 0));
+        if (parts == (PNA_PART_HEAD | PNA_PART_TAIL)) { framing_case(what, arc, want); return; }
+        Bytes empty; pna_archive *a = nullptr;                   // a part: walked between the head and the tail of an empty archive
+        CHECK(pna_archive_new(vec_sink, &empty, 0, &a) == PNA_OK && pna_archive_finalize(a) == PNA_OK && empty.size() > 12);
+        Bytes whole(empty.begin(), empty.end() - (parts & PNA_PART_HEAD ? empty.size() : 12));
+        whole.insert(whole.end(), arc.begin(), arc.end());
+        if (!(parts & PNA_PART_TAIL)) whole.insert(whole.end(), empty.end() - 12, empty.end());
+        framing_case(what, arc, want, &whole);
+    };
+    for (long dl = 0; dl <= 1; dl++) {
+        CHECK(pna_gpu_set_option(c, "dev_layout", dl) == PNA_OK);
+        dev(dl ? "plain dev_layout=1" : "plain dev_layout=0", nullptr, nullptr, 0, PNA_PART_HEAD | PNA_PART_TAIL, 0x8aa4a34fu);
+        dev(dl ? "meta dev_layout=1" : "meta dev_layout=0", nullptr, &meta, 0, PNA_PART_HEAD | PNA_PART_TAIL, 0xe08d0a72u);
+        dev(dl ? "chunked dev_layout=1" : "chunked dev_layout=0", nullptr, nullptr, 300000, PNA_PART_HEAD | PNA_PART_TAIL, 0xa3b88b24u);
+        dev(dl ? "part head dev_layout=1" : "part head dev_layout=0", nullptr, nullptr, 0, PNA_PART_HEAD, 0xb18d2166u);
+        dev(dl ? "part tail dev_layout=1" : "part tail dev_layout=0", nullptr, nullptr, 0, PNA_PART_TAIL, 0x9037bfb1u);
+    }
+    dev("ctr", &ctr, nullptr, 0, PNA_PART_HEAD | PNA_PART_TAIL, 0x67bd3d58u);
+    dev("ctr chunked meta", &ctr, &meta, 200000, PNA_PART_HEAD | PNA_PART_TAIL, 0x6f1409eau);
+    dev("cbc", &cbc, nullptr, 0, PNA_PART_HEAD | PNA_PART_TAIL, 0xeab93cf6u);
+    dev("gcm", &gcm, nullptr, 0, PNA_PART_HEAD | PNA_PART_TAIL, 0x0cd7fb94u);
+    dev("gcm meta", &gcm, &meta, 0, PNA_PART_HEAD | PNA_PART_TAIL, 0x7ffab2e6u);
+    // solid on the device: plain, CTR, GCM (one IV / salt)
+    auto solid_dev = [&](const char *what, const pna_gpu_cipher *ci, uint32_t want) {
+        const size_t cap = pna_gpu_solid_archive_enc_bound(PNA_ALGO_ZSTD, n, names.data(), len.data(), ci) + 4096;
+        Bytes dst(cap + 16); uint8_t *d = dst.data() + ((16 - ((uintptr_t)dst.data() & 15)) & 15);
+        uint64_t alen = 0;
+        CHECK(pna_gpu_create_solid_archive_enc_device(c, PNA_ALGO_ZSTD, 3, n, names.data(), src.data(), off.data(), len.data(), ci, d, cap, &alen, nullptr) == PNA_OK);
+        framing_case(what, Bytes(d, d + alen), want);
+    };
+    solid_dev("solid device", nullptr, 0x316d41edu);
+    solid_dev("solid device ctr", &ctr, 0xa9278512u);
+    solid_dev("solid device gcm", &gcm, 0xa3c3d9cau);
+    // solid from host memory in windows of 1 and 2 MiB: plain, CTR, GCM
+    std::vector<const void *> hsrc(n); std::vector<size_t> hlen(n);
+    Bytes big = text(3 << 20, 99);
+    for (size_t i = 0; i < n; i++) { hsrc[i] = &src[off[i]]; hlen[i] = lens[i]; }
+    hsrc.push_back(big.data()); hlen.push_back(big.size()); names.push_back("m/big.bin");
+    for (long w = 1; w <= 2; w++) {
+        CHECK(pna_gpu_set_option(c, "solid_win_mib", w) == PNA_OK);
+        const pna_gpu_cipher *cs[3] = {nullptr, &ctr, &gcm}; const char *cn[3] = {"plain", "ctr", "gcm"};
+        const uint32_t want[3] = {0xb815dc24u, 0x217ff317u, 0xfd55fdb1u};                 // (the same for both window sizes)
+        for (int k = 0; k < 3; k++) {
+            Bytes arc;
+            CHECK(pna_gpu_create_solid_archive_enc_host(c, PNA_ALGO_ZSTD, 3, n + 1, names.data(), hsrc.data(), hlen.data(), cs[k], vec_sink, &arc) == PNA_OK);
+            const std::string what = "solid host win=" + std::to_string(w) + " " + cn[k];
+            framing_case(what.c_str(), arc, want[k]);
+        }
+    }
+    pna_gpu_shutdown(c);
+}
+
 int main() {
     pna_gpu_ctx *c = nullptr;
     CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK);
@@ -191,6 +291,7 @@ int main() {
     test_batch(c);
     test_streams(c);
     test_pipeline_and_append(c);
+    test_framing_matrix();
     pna_gpu_shutdown(c);
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("san_driver: all checks passed\n");
