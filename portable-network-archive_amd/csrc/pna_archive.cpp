@@ -7,7 +7,7 @@
 #include <vector>
 #include <algorithm>
 #include <sys/random.h>
-#include "../../include/pna_archive.h"
+#include "pna_ctx.h"
 
 namespace {
 
@@ -26,9 +26,28 @@ struct CrcTables {
 };
 const CrcTables &crc_tables() { static CrcTables T; return T; }
 
-void put_be32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
-
 } // namespace
+
+namespace pna {
+extern const uint8_t PNA_SIGNATURE[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};        // lib/src/format/signature.rs:6
+void put_be32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
+uint32_t rd_be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+// One chunk of a chunk stream (read_chunk, lib/src/io.rs:117-149): length BE | type | body | crc BE.  The chunk at `pos` goes to `out` and `pos` moves
+// behind it; the stream's end is not an error here, the callers decide what ends a walk.  No CRC is checked: chunk_crc_ok does that.
+int next_chunk(const uint8_t *buf, size_t len, size_t &pos, PnaChunk &out) {
+    if (pos > len || len - pos < 12) return CHUNK_SHORT_HEADER;
+    const uint32_t l = rd_be32(buf + pos);
+    if (len - pos - 12 < l) return CHUNK_SHORT_BODY;
+    out = PnaChunk{pos, l, buf + pos + 4, buf + pos + 8};
+    pos += 12 + (size_t)l;
+    return CHUNK_OK;
+}
+// write_chunk (lib/src/io.rs:183-197): the 8 bytes in front of a chunk's body (length BE | type) and the 4 behind it (CRC-32 of type || body, BE)
+static void chunk_frame(const void *ty, const void *data, size_t len, uint8_t head[8], uint8_t tail[4]) {
+    put_be32(head, (uint32_t)len); memcpy(head + 4, ty, 4); put_be32(tail, pna_crc32(pna_crc32(0, ty, 4), data, len));
+}
+bool chunk_crc_ok(const PnaChunk &ch) { return pna_crc32(pna_crc32(0, ch.type, 4), ch.data, ch.len) == rd_be32(ch.data + ch.len); }
+} // namespace pna
 
 extern "C" uint32_t pna_crc32(uint32_t crc, const void *buf, size_t len) {
     const CrcTables &T = crc_tables();
@@ -52,9 +71,7 @@ struct pna_archive {
     // write_chunk: length BE | type | data | crc32(type||data) BE -- lib/src/io.rs:183-197
     int chunk(const char ty[4], const void *data, size_t len) {
         if (len > 0xFFFFFFFFull) return err = PNA_E_INVAL;
-        uint8_t head[8]; put_be32(head, (uint32_t)len); memcpy(head + 4, ty, 4);
-        uint32_t crc = pna_crc32(pna_crc32(0, ty, 4), data, len);
-        uint8_t tail[4]; put_be32(tail, crc);
+        uint8_t head[8], tail[4]; chunk_frame(ty, data, len, head, tail);
         emit(head, 8); emit(data, len); return emit(tail, 4);
     }
 };
@@ -100,15 +117,13 @@ static size_t fsiz(uint64_t raw, uint8_t out[16]) {        // u128 BE, leading z
 // ---- pieces of the entry record used by the in-HBM framing path (pna_gpu_create_archive_device, pna_host.cpp)
 namespace pna {
 static void put_chunk(std::vector<uint8_t> &o, const char ty[4], const uint8_t *data, size_t len) {
-    uint8_t head[8]; put_be32(head, (uint32_t)len); memcpy(head + 4, ty, 4);
-    uint8_t tail[4]; put_be32(tail, pna_crc32(pna_crc32(0, ty, 4), data, len));
+    uint8_t head[8], tail[4]; chunk_frame(ty, data, len, head, tail);
     o.insert(o.end(), head, head + 8); if (len) o.insert(o.end(), data, data + len); o.insert(o.end(), tail, tail + 4);
 }
 // signature + AHED -- lib/src/archive/write.rs (write_header), lib/src/archive/header.rs:27-39
 void frame_archive_head(std::vector<uint8_t> &o, uint32_t archive_number) {
-    static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};
     uint8_t ahed[8] = {0, 0, 0, 0, 0, 0, 0, 0}; put_be32(ahed + 4, archive_number);
-    o.insert(o.end(), sig, sig + 8); put_chunk(o, "AHED", ahed, 8);
+    o.insert(o.end(), PNA_SIGNATURE, PNA_SIGNATURE + 8); put_chunk(o, "AHED", ahed, 8);
 }
 void frame_archive_tail(std::vector<uint8_t> &o) { put_chunk(o, "AEND", nullptr, 0); }
 // FHED | fSIZ | FDAT length + type: everything of a file entry that precedes its payload (NormalEntry::write_chunks_to, lib/src/entry.rs:895-911)
@@ -194,9 +209,8 @@ uint32_t frame_fend_crc() { return pna_crc32(0, "FEND", 4); }
 extern "C" int pna_archive_new(pna_sink_fn sink, void *user, uint32_t archive_number, pna_archive **out) {
     if (!sink || !out) return PNA_E_INVAL;
     pna_archive *a = new pna_archive{sink, user, 0};
-    static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};     // lib/src/format/signature.rs:6
     uint8_t ahed[8] = {0, 0, 0, 0, 0, 0, 0, 0}; put_be32(ahed + 4, archive_number);     // lib/src/archive/header.rs:27-39
-    a->emit(sig, 8); a->chunk("AHED", ahed, 8);
+    a->emit(PNA_SIGNATURE, 8); a->chunk("AHED", ahed, 8);
     if (a->err) { int e = a->err; delete a; return e; }
     *out = a; return PNA_OK;
 }
@@ -370,6 +384,11 @@ std::string b64_nopad(const uint8_t *p, size_t n) {
 } // namespace
 
 namespace pna {
+bool b64_decode_nopad(const std::string &s, std::vector<uint8_t> &out) {       // the salt of a PHSF string: the inverse of b64_nopad
+    uint32_t acc = 0; int bits = 0;
+    for (char ch : s) { const char *q = ch ? strchr(B64, ch) : nullptr; if (!q) return false; acc = (acc << 6) | (uint32_t)(q - B64); bits += 6; if (bits >= 8) { bits -= 8; out.push_back((uint8_t)(acc >> bits)); } }
+    return true;
+}
 void sha256_bytes(const void *a, size_t an, const void *b, size_t bn, uint8_t out[32]) { Sha256 s; s.init(); s.update(a, an); if (bn) s.update(b, bn); s.final(out); }
 // HKDF-SHA-256 with one output block (RFC 5869): hkdf_sha256, lib/src/cipher/aead.rs:151-157
 void hkdf_sha256_32(const void *ikm, size_t ikm_len, const void *salt, size_t salt_len, const void *info, size_t info_len, uint8_t okm[32]) {
@@ -615,15 +634,13 @@ struct PartOut {
     pna_part_sink_fn sink; void *user; uint32_t part = 0; int err = 0;
     void emit(const void *p, size_t n) { if (!err && n && sink(user, part, p, n) != 0) err = PNA_E_SINK; }
     void header() {
-        static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};
         uint8_t c[20]; put_be32(c, 8); memcpy(c + 4, "AHED", 4); memset(c + 8, 0, 4); put_be32(c + 12, part);
         put_be32(c + 16, pna_crc32(0, c + 4, 12));
-        emit(sig, 8); emit(c, 20);
+        emit(PNA_SIGNATURE, 8); emit(c, 20);
     }
-    void empty_chunk(const char ty[4]) { uint8_t c[12]; put_be32(c, 0); memcpy(c + 4, ty, 4); put_be32(c + 8, pna_crc32(0, ty, 4)); emit(c, 12); }
+    void empty_chunk(const char ty[4]) { uint8_t c[12]; chunk_frame(ty, nullptr, 0, c, c + 8); emit(c, 12); }
     void fresh_chunk(const uint8_t *ty, const uint8_t *data, size_t n) {
-        uint8_t h[8], t[4]; put_be32(h, (uint32_t)n); memcpy(h + 4, ty, 4);
-        put_be32(t, pna_crc32(pna_crc32(0, ty, 4), data, n));
+        uint8_t h[8], t[4]; chunk_frame(ty, data, n, h, t);
         emit(h, 8); emit(data, n); emit(t, 4);
     }
 };
@@ -634,8 +651,7 @@ extern "C" int pna_split_archive(const void *archive, size_t len, size_t max_par
     const size_t MINC = 12, OVER = 8 + 20 + 2 * MINC;          // MIN_CHUNK_BYTES_SIZE, SPLIT_ARCHIVE_OVERHEAD_BYTES (split_parts.rs:14-23)
     if (max_part_bytes < OVER + MINC) return PNA_E_INVAL;      // MIN_SPLIT_PART_BYTES
     const uint8_t *a = (const uint8_t *)archive;
-    static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};
-    if (len < 8 + 20 + 12 || memcmp(a, sig, 8) != 0 || memcmp(a + 12, "AHED", 4) != 0) return PNA_E_INVAL;
+    if (len < 8 + 20 + 12 || memcmp(a, PNA_SIGNATURE, 8) != 0 || memcmp(a + 12, "AHED", 4) != 0) return PNA_E_INVAL;
     const size_t budget = max_part_bytes - OVER;
     size_t remaining = budget;
     PartOut o{sink, user};
@@ -648,37 +664,34 @@ extern "C" int pna_split_archive(const void *archive, size_t len, size_t max_par
     };
     size_t pos = 8 + 20; bool ended = false;
     while (pos < len && !o.err) {
-        if (len - pos < 12) return PNA_E_INVAL;
-        const uint32_t dl = ((uint32_t)a[pos] << 24) | ((uint32_t)a[pos + 1] << 16) | ((uint32_t)a[pos + 2] << 8) | a[pos + 3];
-        const uint8_t *ty = a + pos + 4, *data = a + pos + 8;
-        if (len - pos - 12 < dl) return PNA_E_INVAL;
-        const size_t clen = MINC + dl;
-        if (memcmp(ty, "AEND", 4) == 0) { ended = true; break; }
-        if (memcmp(ty, "ANXT", 4) == 0) return PNA_E_INVAL;     // already a part of a multipart archive
-        const bool stream = memcmp(ty, "FDAT", 4) == 0 || memcmp(ty, "SDAT", 4) == 0;
-        if (clen <= remaining) { o.emit(a + pos, clen); remaining -= clen; }
+        PnaChunk ch;
+        if (next_chunk(a, len, pos, ch)) return PNA_E_INVAL;
+        const size_t clen = MINC + ch.len, at = ch.off;
+        if (memcmp(ch.type, "AEND", 4) == 0) { ended = true; break; }
+        if (memcmp(ch.type, "ANXT", 4) == 0) return PNA_E_INVAL;     // already a part of a multipart archive
+        const bool stream = memcmp(ch.type, "FDAT", 4) == 0 || memcmp(ch.type, "SDAT", 4) == 0;
+        if (clen <= remaining) { o.emit(a + at, clen); remaining -= clen; }
         else if (!stream) {
             if (clen > budget) return PNA_E_INVAL;              // chunk_does_not_fit_error
             int rc = roll_over(); if (rc) return rc;
-            o.emit(a + pos, clen); remaining -= clen;
+            o.emit(a + at, clen); remaining -= clen;
         } else if (clen <= budget && remaining <= MINC) {
             int rc = roll_over(); if (rc) return rc;
-            o.emit(a + pos, clen); remaining -= clen;
+            o.emit(a + at, clen); remaining -= clen;
         } else {
-            const uint8_t *rest = data; size_t rl = dl; bool first = true;
+            const uint8_t *rest = ch.data; size_t rl = ch.len; bool first = true;
             for (;;) {
                 if (MINC + rl <= remaining) {
-                    if (first) o.emit(a + pos, clen); else o.fresh_chunk(ty, rest, rl);   // (cannot be `first` here, kept for symmetry)
+                    if (first) o.emit(a + at, clen); else o.fresh_chunk(ch.type, rest, rl);   // (cannot be `first` here, kept for symmetry)
                     remaining -= MINC + rl; break;
                 }
                 if (remaining > MINC) {
                     const size_t take = remaining - MINC;
-                    o.fresh_chunk(ty, rest, take); rest += take; rl -= take; remaining -= MINC + take; first = false;
+                    o.fresh_chunk(ch.type, rest, take); rest += take; rl -= take; remaining -= MINC + take; first = false;
                 } else if (budget <= MINC) return PNA_E_INVAL;
                 int rc = roll_over(); if (rc) return rc;
             }
         }
-        pos += clen;
     }
     if (!ended) return o.err ? o.err : PNA_E_INVAL;
     o.empty_chunk("AEND");                                      // finalize_archive: the last part has no ANXT
@@ -691,37 +704,31 @@ extern "C" int pna_split_archive(const void *archive, size_t len, size_t max_par
 // bodies are concatenated by the entry reader anyway).
 extern "C" int pna_join_parts(const void *const *parts, const size_t *part_len, size_t n, pna_sink_fn sink, void *user) {
     if (!parts || !part_len || !sink || n == 0) return PNA_E_INVAL;
-    static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};
     auto out = [&](const void *p, size_t k) { return k == 0 || sink(user, p, k) == 0; };
     for (size_t k = 0; k < n; k++) {
         const uint8_t *a = (const uint8_t *)parts[k]; const size_t len = part_len[k];
-        if (!a || len < 8 + 20 + 12 || memcmp(a, sig, 8) != 0 || memcmp(a + 12, "AHED", 4) != 0) return PNA_E_INVAL;
-        const uint32_t num = ((uint32_t)a[20] << 24) | ((uint32_t)a[21] << 16) | ((uint32_t)a[22] << 8) | a[23];      // AHED body: major, minor, 0, 0, archive number
-        if (num != k || pna_crc32(0, a + 12, 12) != (((uint32_t)a[24] << 24) | ((uint32_t)a[25] << 16) | ((uint32_t)a[26] << 8) | a[27])) return PNA_E_INVAL;
+        if (!a || len < 8 + 20 + 12 || memcmp(a, PNA_SIGNATURE, 8) != 0 || memcmp(a + 12, "AHED", 4) != 0) return PNA_E_INVAL;
+        if (rd_be32(a + 20) != k || pna_crc32(0, a + 12, 12) != rd_be32(a + 24)) return PNA_E_INVAL;      // AHED body: major, minor, 0, 0, archive number
         if (k == 0 && !out(a, 28)) return PNA_E_SINK;
         size_t pos = 28; bool has_next = false, ended = false;
         while (pos < len) {
-            if (len - pos < 12) return PNA_E_INVAL;
-            const uint32_t dl = ((uint32_t)a[pos] << 24) | ((uint32_t)a[pos + 1] << 16) | ((uint32_t)a[pos + 2] << 8) | a[pos + 3];
-            if (len - pos - 12 < dl) return PNA_E_INVAL;
-            const uint8_t *ty = a + pos + 4;
-            if (memcmp(ty, "AEND", 4) == 0) { ended = true; break; }
-            if (memcmp(ty, "ANXT", 4) == 0) has_next = true;
-            else { if (has_next) return PNA_E_INVAL; if (!out(a + pos, 12 + (size_t)dl)) return PNA_E_SINK; }
-            pos += 12 + (size_t)dl;
+            PnaChunk ch;
+            if (next_chunk(a, len, pos, ch)) return PNA_E_INVAL;
+            if (memcmp(ch.type, "AEND", 4) == 0) { ended = true; break; }
+            if (memcmp(ch.type, "ANXT", 4) == 0) has_next = true;
+            else { if (has_next) return PNA_E_INVAL; if (!out(a + ch.off, 12 + (size_t)ch.len)) return PNA_E_SINK; }
         }
         if (!ended || has_next != (k + 1 < n)) return PNA_E_INVAL;
     }
-    uint8_t c[12]; put_be32(c, 0); memcpy(c + 4, "AEND", 4); put_be32(c + 8, pna_crc32(0, "AEND", 4));
+    uint8_t c[12]; chunk_frame("AEND", nullptr, 0, c, c + 8);
     return out(c, 12) ? PNA_OK : PNA_E_SINK;
 }
 
 
 // ---- `pna append` / `pna update` plumbing on the host (include/pna_archive.h)
 static bool pna_image_header_ok(const uint8_t *a, size_t len) {
-    static const uint8_t sig[8] = {0x89, 0x50, 0x4E, 0x41, 0x0D, 0x0A, 0x1A, 0x0A};
     // signature, then AHED as the first chunk (Archive::read_header, lib/src/archive/read.rs:26-44)
-    return len >= 8 + 12 + 8 && memcmp(a, sig, 8) == 0 && memcmp(a + 12, "AHED", 4) == 0 && a[8] == 0 && a[9] == 0 && a[10] == 0 && a[11] == 8;
+    return len >= 8 + 12 + 8 && memcmp(a, PNA_SIGNATURE, 8) == 0 && memcmp(a + 12, "AHED", 4) == 0 && a[8] == 0 && a[9] == 0 && a[10] == 0 && a[11] == 8;
 }
 extern "C" int pna_archive_seek_to_end(const void *archive, size_t len, uint64_t *aend_off, int *has_next) {
     if (!archive || !aend_off) return PNA_E_INVAL;
@@ -730,12 +737,10 @@ extern "C" int pna_archive_seek_to_end(const void *archive, size_t len, uint64_t
     if (has_next) *has_next = 0;
     size_t pos = 8;
     for (;;) {
-        if (len - pos < 12) return PNA_E_INVAL;                                   // truncated: UnexpectedEof
-        const uint64_t l = ((uint64_t)a[pos] << 24) | ((uint64_t)a[pos + 1] << 16) | ((uint64_t)a[pos + 2] << 8) | a[pos + 3];
-        if (len - pos - 12 < l) return PNA_E_INVAL;
-        if (memcmp(a + pos + 4, "AEND", 4) == 0) { *aend_off = pos; return PNA_OK; }
-        if (memcmp(a + pos + 4, "ANXT", 4) == 0 && has_next) *has_next = 1;
-        pos += 12 + (size_t)l;
+        PnaChunk ch;
+        if (next_chunk(a, len, pos, ch)) return PNA_E_INVAL;                 // truncated: UnexpectedEof
+        if (memcmp(ch.type, "AEND", 4) == 0) { *aend_off = ch.off; return PNA_OK; }
+        if (memcmp(ch.type, "ANXT", 4) == 0 && has_next) *has_next = 1;
     }
 }
 extern "C" int pna_archive_list_entries(const void *archive, size_t len, pna_raw_entry_fn cb, void *user) {
@@ -745,18 +750,16 @@ extern "C" int pna_archive_list_entries(const void *archive, size_t len, pna_raw
     size_t pos = 8, idx = 0, start = 0, name_off = 0, name_len = 0;
     int open = 0, kind = 0;                                                       // 1: inside FHED..FEND, 2: inside SHED..SEND
     for (;;) {
-        if (len - pos < 12) return PNA_E_INVAL;
-        const uint64_t l = ((uint64_t)a[pos] << 24) | ((uint64_t)a[pos + 1] << 16) | ((uint64_t)a[pos + 2] << 8) | a[pos + 3];
-        if (len - pos - 12 < l) return PNA_E_INVAL;
-        const uint8_t *ty = a + pos + 4;
+        PnaChunk ch;
+        if (next_chunk(a, len, pos, ch)) return PNA_E_INVAL;
+        const uint8_t *ty = ch.type;
         if (!open) {
             if (memcmp(ty, "AEND", 4) == 0) return PNA_OK;
-            if (memcmp(ty, "FHED", 4) == 0) { if (l < 6) return PNA_E_INVAL; open = 1; start = pos; kind = a[pos + 8 + 2]; name_off = pos + 8 + 6; name_len = (size_t)l - 6; }
-            else if (memcmp(ty, "SHED", 4) == 0) { open = 2; start = pos; kind = -1; name_off = pos; name_len = 0; }
+            if (memcmp(ty, "FHED", 4) == 0) { if (ch.len < 6) return PNA_E_INVAL; open = 1; start = ch.off; kind = ch.data[2]; name_off = ch.off + 8 + 6; name_len = (size_t)ch.len - 6; }
+            else if (memcmp(ty, "SHED", 4) == 0) { open = 2; start = ch.off; kind = -1; name_off = ch.off; name_len = 0; }
         } else if ((open == 1 && memcmp(ty, "FEND", 4) == 0) || (open == 2 && memcmp(ty, "SEND", 4) == 0)) {
-            if (cb(user, idx++, (const char *)a + name_off, name_len, kind, start, pos + 12 + l - start) != 0) return PNA_E_SINK;
+            if (cb(user, idx++, (const char *)a + name_off, name_len, kind, start, pos - start) != 0) return PNA_E_SINK;
             open = 0;
         }
-        pos += 12 + (size_t)l;
     }
 }

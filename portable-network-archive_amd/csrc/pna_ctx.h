@@ -96,6 +96,15 @@ int launch_zexec_par(ZxFrame *zf, const ZxFrame &h, const ZBlock *blocks, const 
 void launch_zexec(ZFrame *frames, const ZFrameX *fx, uint32_t n, ZBlock *blocks, const uint8_t *src, const uint8_t *lit_scratch,
                   const uint64_t *seqs, uint8_t *dst, hipStream_t st);
 std::string pna_sanitize_name(const char *name, size_t n);
+// the chunk stream of an archive (pna_archive.cpp): the signature, big-endian words, one chunk at a time
+extern const uint8_t PNA_SIGNATURE[8];
+void put_be32(uint8_t *p, uint32_t v);
+uint32_t rd_be32(const uint8_t *p);
+struct PnaChunk { size_t off; uint32_t len; const uint8_t *type, *data; };      // off: where the chunk starts; its CRC follows the body
+enum { CHUNK_OK = 0, CHUNK_SHORT_HEADER, CHUNK_SHORT_BODY };
+int  next_chunk(const uint8_t *buf, size_t len, size_t &pos, PnaChunk &out);
+bool chunk_crc_ok(const PnaChunk &ch);
+bool b64_decode_nopad(const std::string &s, std::vector<uint8_t> &out);
 void frame_inner_entry_empty(std::vector<uint8_t> &o, const char *name);
 void frame_solid_head(std::vector<uint8_t> &o, int compression);
 void frame_solid_head_enc(std::vector<uint8_t> &o, int compression, int encryption, int cipher_mode, const char *phsf, const uint8_t *prefix, size_t prefix_len);
@@ -315,7 +324,7 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
 // front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  layout_solid advances
 // pos, seg and carry_len past the window.
 struct SolidCipherRun { uint64_t pos = 0, seg = 0, carry_len = 0; uint8_t *carry = nullptr; bool final_win = false; };
-struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4], ej0[4]; uint8_t ctr_iv[16]; };
+struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4]; };     // a stream's header, round keys and hash subkey
 struct GcmCallKeys { uint8_t kc[32], phsf_hash[32]; };
 // GCM STREAM segment size of a cipher job (0: the reference's DEFAULT_SEGMENT_SIZE, 1 MiB)
 inline uint32_t gcm_seg_size(const pna_gpu_cipher *ci) { return ci->gcm_segment_size ? ci->gcm_segment_size : (1u << 20); }
@@ -423,7 +432,9 @@ void aes256_expand(const uint8_t key[32], AesKey &k);
 void aes256_dec_key(const AesKey &k, AesKey &d);
 void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]);
 int  resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs);
-GcmCallKeys gcm_call_keys(const pna_gpu_cipher *ci);
+GcmCallKeys gcm_call_keys(const uint8_t key[32], const char *phsf, size_t phsf_len);
+void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], AesKey &rk, uint32_t h[4]);
+void gcm_segment(const GcmMaterial &m, uint32_t counter, bool fin, GcmEntry &ge, uint8_t iv[16]);
 void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const uint8_t salt_prefix[39], uint32_t seg_size, const char *name, int compression,
                         GcmMaterial &m);
 void gcm_solid_material(const pna_gpu_cipher *ci, const uint8_t salt_prefix[39], int compression, GcmMaterial &m);

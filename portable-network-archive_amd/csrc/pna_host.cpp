@@ -100,6 +100,9 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->cp_in) (void)hipStreamDestroy(c->cp_in);
     if (c->cp_out) (void)hipStreamDestroy(c->cp_out);
+    if (c->x_cp) (void)hipStreamDestroy(c->x_cp);
+    for (auto &e : c->x_ev) if (e) (void)hipEventDestroy(e);
+    if (c->x_done) (void)hipEventDestroy(c->x_done);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -328,47 +331,52 @@ void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]) {
         t[i] = (sb(s[i]) | (sb(s[(i + 1) & 3] >> 8) << 8) | (sb(s[(i + 2) & 3] >> 16) << 16) | (sb(s[(i + 3) & 3] >> 24) << 24)) ^ k.rk[56 + i];
     for (int i = 0; i < 4; i++) { out[4 * i] = (uint8_t)t[i]; out[4 * i + 1] = (uint8_t)(t[i] >> 8); out[4 * i + 2] = (uint8_t)(t[i] >> 16); out[4 * i + 3] = (uint8_t)(t[i] >> 24); }
 }
-// GCM STREAM material of one entry (lib/src/entry/write.rs:81-107 to_hashed; lib/src/cipher/aead.rs): stream header, stream key bound to
-// the FHED chunk and the PHSF string, round keys, hash subkey, E(K, J0) of the (single, final) segment 0 and its first counter block.
-// (the stream key is bound to the header chunk of the entry that carries the stream: FHED of a normal entry, SHED of a solid one -- entry_context,
-// lib/src/cipher/aead.rs:167-190; name == nullptr: the solid entry's SHED)
+// The stream key of a GCM STREAM (derive_stream_key, lib/src/cipher/aead.rs:184-199), bound to the PHSF string and to the header chunk of the entry
+// that carries the stream: FHED or SHED (entry_context, aead.rs:167-190).  `header`: salt || nonce prefix || segment size of the stream header.
+void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], AesKey &rk, uint32_t h[4]) {
+    uint8_t info[88], ks[32];
+    memcpy(info, "PNA-STREAM-v1", 13);
+    sha256_bytes(htype, 4, hbody.data(), hbody.size(), info + 13);
+    memcpy(info + 45, phsf_hash, 32);
+    memcpy(info + 77, header + 32, 11);
+    hkdf_sha256_32(master, 32, header, 32, info, 88, ks);
+    aes256_expand(ks, rk);
+    uint8_t zero[16] = {0}, hb[16];
+    aes256_block_host(rk, zero, hb);
+    for (int i = 0; i < 4; i++) h[i] = rd_be32(hb + 4 * i);
+}
+// Segment `counter` of a stream (segment_nonce, lib/src/cipher/gcm.rs): J0 = nonce prefix || counter || final flag || 0 0 0 1.  Gives the tag
+// descriptor's H and E(K, J0) and the counter-mode IV of the segment's first data block (counter 2).
+void gcm_segment(const GcmMaterial &m, uint32_t counter, bool fin, GcmEntry &ge, uint8_t iv[16]) {
+    uint8_t j0[16], eb[16];
+    memcpy(j0, m.header + 32, 7); put_be32(j0 + 7, counter); j0[11] = fin ? 1 : 0;
+    put_be32(j0 + 12, 1);
+    aes256_block_host(m.rk, j0, eb);
+    memcpy(ge.h, m.h, 16);
+    for (int i = 0; i < 4; i++) ge.ej0[i] = rd_be32(eb + 4 * i);
+    memcpy(iv, j0, 16); iv[15] = 2;
+}
+// GCM STREAM material of one entry (lib/src/entry/write.rs:81-107 to_hashed; lib/src/cipher/aead.rs): stream header, round keys and hash subkey of
+// the stream key (name == nullptr: the solid entry's SHED)
 void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const uint8_t salt_prefix[39], uint32_t seg_size, const char *name, int compression,
                         GcmMaterial &m) {
     memcpy(m.header, salt_prefix, 39);
-    m.header[39] = (uint8_t)(seg_size >> 24); m.header[40] = (uint8_t)(seg_size >> 16); m.header[41] = (uint8_t)(seg_size >> 8); m.header[42] = (uint8_t)seg_size;
+    put_be32(m.header + 39, seg_size);
     memcpy(m.header + 43, keys.kc, 32);
     const std::vector<uint8_t> fh = name ? frame_fhed_bytes(name, compression, ci->encryption, PNA_MODE_GCM)
                                          : std::vector<uint8_t>{0, 0, (uint8_t)compression, (uint8_t)ci->encryption, (uint8_t)PNA_MODE_GCM};
-    uint8_t info[88];
-    memcpy(info, "PNA-STREAM-v1", 13);
-    sha256_bytes(name ? "FHED" : "SHED", 4, fh.data(), fh.size(), info + 13);
-    memcpy(info + 45, keys.phsf_hash, 32);
-    memcpy(info + 77, salt_prefix + 32, 7);
-    memcpy(info + 84, m.header + 39, 4);
-    uint8_t ks[32];
-    hkdf_sha256_32(ci->key, 32, salt_prefix, 32, info, 88, ks);
-    aes256_expand(ks, m.rk);
-    uint8_t zero[16] = {0}, hb[16], j0[16], eb[16];
-    aes256_block_host(m.rk, zero, hb);
-    memcpy(j0, salt_prefix + 32, 7); j0[7] = j0[8] = j0[9] = j0[10] = 0; j0[11] = 1;      // segment_nonce(prefix, 0, final)
-    j0[12] = 0; j0[13] = 0; j0[14] = 0; j0[15] = 1;
-    aes256_block_host(m.rk, j0, eb);
-    for (int i = 0; i < 4; i++) {
-        m.h[i] = ((uint32_t)hb[4 * i] << 24) | ((uint32_t)hb[4 * i + 1] << 16) | ((uint32_t)hb[4 * i + 2] << 8) | hb[4 * i + 3];
-        m.ej0[i] = ((uint32_t)eb[4 * i] << 24) | ((uint32_t)eb[4 * i + 1] << 16) | ((uint32_t)eb[4 * i + 2] << 8) | eb[4 * i + 3];
-    }
-    memcpy(m.ctr_iv, j0, 16); m.ctr_iv[15] = 2;                                           // first data block: counter 2
+    gcm_stream_key(ci->key, m.header, name ? "FHED" : "SHED", fh, keys.phsf_hash, m.rk, m.h);
 }
-// what the GCM STREAMs of a call share: the key confirmation (key_confirmation, aead.rs:161-163) and the hash of the PHSF string
-GcmCallKeys gcm_call_keys(const pna_gpu_cipher *ci) {
+// what the GCM STREAMs under one key and PHSF string share: the key confirmation (key_confirmation, aead.rs:161-163) and the hash of the PHSF string
+GcmCallKeys gcm_call_keys(const uint8_t key[32], const char *phsf, size_t phsf_len) {
     GcmCallKeys k;
-    hkdf_sha256_32(ci->key, 32, nullptr, 0, "PNA-KC-v1", 9, k.kc);
-    sha256_bytes(ci->phsf, strlen(ci->phsf), nullptr, 0, k.phsf_hash);
+    hkdf_sha256_32(key, 32, nullptr, 0, "PNA-KC-v1", 9, k.kc);
+    sha256_bytes(phsf, phsf_len, nullptr, 0, k.phsf_hash);
     return k;
 }
 // ... the material of a solid archive's one stream (bound to its SHED chunk)
 void gcm_solid_material(const pna_gpu_cipher *ci, const uint8_t salt_prefix[39], int compression, GcmMaterial &m) {
-    gcm_entry_material(ci, gcm_call_keys(ci), salt_prefix, gcm_seg_size(ci), nullptr, compression, m);
+    gcm_entry_material(ci, gcm_call_keys(ci->key, ci->phsf, strlen(ci->phsf)), salt_prefix, gcm_seg_size(ci), nullptr, compression, m);
 }
 // The head of a solid archive: signature + AHED, then SHED; with a cipher PHSF and the stream's first write, a chunk of its own -- the IV (CTR) or
 // the stream header (GCM: salt || nonce prefix || segment size || key confirmation, 75 bytes)
@@ -410,22 +418,17 @@ size_t meta_len(const pna_gpu_entry_meta *m, size_t e) {
 bool meta_blob_ok(const uint8_t *p, size_t n) {
     size_t pos = 0;
     while (pos < n) {
-        if (n - pos < 12) return false;
-        const uint32_t dl = ((uint32_t)p[pos] << 24) | ((uint32_t)p[pos + 1] << 16) | ((uint32_t)p[pos + 2] << 8) | p[pos + 3];
-        if (n - pos - 12 < dl) return false;
-        const uint8_t *ty = p + pos + 4;
-        for (const char *own : {"FHED", "FDAT", "FEND", "fSIZ", "PHSF", "SHED", "SDAT", "SEND", "AHED", "AEND", "ANXT"}) if (memcmp(ty, own, 4) == 0) return false;
-        const uint8_t *cp = p + pos + 8 + dl;
-        if (pna_crc32(0, ty, 4 + (size_t)dl) != (((uint32_t)cp[0] << 24) | ((uint32_t)cp[1] << 16) | ((uint32_t)cp[2] << 8) | cp[3])) return false;
-        pos += 12 + (size_t)dl;
+        PnaChunk ch;
+        if (next_chunk(p, n, pos, ch)) return false;
+        for (const char *own : {"FHED", "FDAT", "FEND", "fSIZ", "PHSF", "SHED", "SDAT", "SEND", "AHED", "AEND", "ANXT"}) if (memcmp(ch.type, own, 4) == 0) return false;
+        if (!chunk_crc_ok(ch)) return false;
     }
     return true;
 }
 // prefix = FHED | fSIZ | rest  ->  FHED | extra | fSIZ | facets | rest   (NormalEntry::write_chunks_to, lib/src/entry.rs:895-911)
 static void splice_meta(std::vector<uint8_t> &pre, const pna_gpu_entry_meta *m, size_t e) {
     if (!meta_len(m, e)) return;
-    const size_t c0 = 12 + ((size_t)pre[0] << 24 | (size_t)pre[1] << 16 | (size_t)pre[2] << 8 | pre[3]);
-    const size_t c1 = 12 + ((size_t)pre[c0] << 24 | (size_t)pre[c0 + 1] << 16 | (size_t)pre[c0 + 2] << 8 | pre[c0 + 3]);
+    const size_t c0 = 12 + (size_t)rd_be32(pre.data()), c1 = 12 + (size_t)rd_be32(pre.data() + c0);
     std::vector<uint8_t> out(pre.begin(), pre.begin() + c0);
     if (m->extra && m->extra_len && m->extra_len[e]) out.insert(out.end(), (const uint8_t *)m->extra[e], (const uint8_t *)m->extra[e] + m->extra_len[e]);
     out.insert(out.end(), pre.begin() + c0, pre.begin() + c0 + c1);
@@ -845,17 +848,11 @@ struct SubLayout {
         for (uint64_t k = 0; k < K; k++) {
             const uint64_t sl = std::min<uint64_t>(G, plen - k * G), so = base + k * stride, q = first + k;     // q: the segment's counter in the stream
             const uint32_t si = (uint32_t)gkeys.size();
-            uint8_t j0[16], eb[16];
-            memcpy(j0, gm.ctr_iv, 7);                                  // nonce prefix
-            j0[7] = (uint8_t)(q >> 24); j0[8] = (uint8_t)(q >> 16); j0[9] = (uint8_t)(q >> 8); j0[10] = (uint8_t)q; j0[11] = final_last && k + 1 == K ? 1 : 0;
-            j0[12] = 0; j0[13] = 0; j0[14] = 0; j0[15] = 1;
-            aes256_block_host(gm.rk, j0, eb);
-            j0[15] = 2;                                                // the first data block
-            giv.insert(giv.end(), j0, j0 + 16); gkeys.push_back(gm.rk);
-            for (uint64_t o = 0; o < sl; o += CTR_UNIT) cunits.push_back(CipherUnit{so + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
             GcmEntry ge{so, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-            memcpy(ge.h, gm.h, 16);
-            for (int w = 0; w < 4; w++) ge.ej0[w] = ((uint32_t)eb[4 * w] << 24) | ((uint32_t)eb[4 * w + 1] << 16) | ((uint32_t)eb[4 * w + 2] << 8) | eb[4 * w + 3];
+            uint8_t iv[16];
+            gcm_segment(gm, (uint32_t)q, final_last && k + 1 == K, ge, iv);
+            giv.insert(giv.end(), iv, iv + 16); gkeys.push_back(gm.rk);
+            for (uint64_t o = 0; o < sl; o += CTR_UNIT) cunits.push_back(CipherUnit{so + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
             gents.push_back(ge);
             if (k >= 1) move(k * G, so, sl);
         }
@@ -908,7 +905,7 @@ static int frame_prefixes(const SubBatch &sb, const SubPlan &p, SubLayout &L) {
         // GCM STREAM: per entry a stream header, an HKDF stream key bound to its FHED chunk, round keys, hash subkey, E(K, J0);
         // a few host threads share the entries (SHA-256 / HKDF / key schedule: a few microseconds each) while k_lz runs
         L.gmat.resize(ne_all);
-        const GcmCallKeys keys = gcm_call_keys(fj->cipher);
+        const GcmCallKeys keys = gcm_call_keys(fj->cipher->key, fj->cipher->phsf, strlen(fj->cipher->phsf));
         const unsigned nt = (unsigned)std::min<size_t>(8, std::max<size_t>(1, ne_all / 256));
         std::vector<std::thread> th;
         for (unsigned t = 0; t < nt; t++)
@@ -951,7 +948,7 @@ static int layout_solid(const SubBatch &sb, const SubPlan &p, const uint64_t *se
     pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const uint32_t nseg = p.nseg;
     auto sdat = [&](size_t k, uint64_t at, uint64_t cl) {           // the header of SDAT chunk k at archive offset `at`, `cl` bytes of data
         uint8_t *pf = L.blob + 8 * k;
-        pf[0] = (uint8_t)(cl >> 24); pf[1] = (uint8_t)(cl >> 16); pf[2] = (uint8_t)(cl >> 8); pf[3] = (uint8_t)cl;
+        put_be32(pf, cl);
         memcpy(pf + 4, "SDAT", 4);
         L.fds[k] = FrameDesc{at, (uint32_t)cl, (uint32_t)(8 * k), 8u, 0};
     };
@@ -1039,7 +1036,7 @@ static int layout_entries(const SubBatch &sb, const SubPlan &p, const uint64_t *
             if (k == 0) { u = f0; u.arc_off = pos; }
             else { u.prefix_off = (uint32_t)L.blob_len; u.prefix_len = 8; u.arc_off = cstart - 8; memcpy(L.blob + L.blob_len + 4, "FDAT", 4); L.blob_len += 8; }
             uint8_t *lenf = &L.blob[u.prefix_off + u.prefix_len - 8];  // FDAT chunk length, big-endian
-            lenf[0] = (uint8_t)(cl >> 24); lenf[1] = (uint8_t)(cl >> 16); lenf[2] = (uint8_t)(cl >> 8); lenf[3] = (uint8_t)cl;
+            put_be32(lenf, cl);
             u.payload_len = (uint32_t)cl; u.pad = k + 1 < K ? 2u : 0u;
             units.push_back(u);
             if (k >= 1) L.move(k * CH, cstart, cl);

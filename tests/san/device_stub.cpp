@@ -1,7 +1,8 @@
 // tests/san/device_stub.cpp -- TEST INFRASTRUCTURE: the launch layer of libpna_gpu.so on the CPU for the sanitizer builds.
 // The zstd write path is stubbed with a trivially valid encoder (every segment = one frame of RAW blocks; the empty entry = the
-// reference's 9-byte frame), the framing kernels (prefix + CRC-32 + FEND, the pieces' raw CRC registers, the CRC patches) are restated bytewise, the
-// cipher kernels by keyed hashes that fold in everything the host hands them; everything else aborts: the sanitizer
+// reference's 9-byte frame), the framing kernels (prefix + CRC-32 + FEND, the pieces' raw CRC registers, the CRC patches, the read side's CRC check)
+// are restated bytewise, the cipher kernels by keyed hashes that fold in everything the host hands them (CBC decryption: the exact inverse of the
+// stub's encryption); everything else aborts: the sanitizer
 // driver exercises the HOST code around the kernels, not the codecs (those are checked against the oracle on the GPU).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -9,6 +10,8 @@
 #include <vector>
 #include "pna_dev.h"
 #include "../../include/pna_archive.h"
+
+void aes256_expand(const uint8_t key[32], pna::AesKey &k);      // the host code's key schedule (pna_host.cpp)
 
 namespace pna {
 [[noreturn]] static void nostub(const char *what) { fprintf(stderr, "device_stub: %s is not stubbed\n", what); abort(); }
@@ -90,7 +93,16 @@ void launch_deflate_stage1(const uint8_t *, const SegDesc *, uint32_t, const uin
                            uint8_t *, uint64_t *, uint64_t *, hipStream_t, hipEvent_t *, uint32_t, bool, bool) { nostub("deflate"); }
 void launch_deflate_write(const uint8_t *, const SegDesc *, const uint32_t *, uint32_t, const BlkInfo *, const uint64_t *, const uint64_t *, const uint8_t *, const uint32_t *,
                           uint32_t, uint8_t *, hipStream_t, bool, bool) { nostub("deflate"); }
-void launch_frame_verify(const FrameDesc *, uint32_t, const CrcTabs *, const uint8_t *, uint64_t, const char[4], uint32_t *, hipStream_t, uint32_t) { nostub("frame_verify"); }
+// The read side's CRC check (k_frame in verify mode) over whole chunks: verify[0] counts mismatches, verify[1] keeps the lowest failing descriptor index
+void launch_frame_verify(const FrameDesc *fd, uint32_t n, const CrcTabs *, const uint8_t *buf, uint64_t, const char ty[4], uint32_t *verify, hipStream_t, uint32_t) {
+    for (uint32_t i = 0; i < n; i++) {
+        const FrameDesc &d = fd[i];
+        if (d.pad & 4) nostub("frame_verify (pieces)");
+        const uint8_t *pay = buf + d.arc_off + d.prefix_len, *q = pay + d.payload_len;
+        const uint32_t stored = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+        if (pna_crc32(pna_crc32(0, ty, 4), pay, d.payload_len) != stored) { verify[0]++; if (i < verify[1]) verify[1] = i; }
+    }
+}
 void launch_zdec(ZFrame *, uint32_t, const uint8_t *, uint8_t *, uint8_t *, uint32_t, hipStream_t) { nostub("zdec"); }
 void launch_zparse_big_a(ZFrame *, ZFrameX *, const uint32_t *, uint32_t, const uint8_t *, ZBlock *, uint32_t *, void *, hipStream_t) { nostub("zparse"); }
 void launch_zparse_big_b(ZFrame *, ZFrameX *, uint32_t, const uint8_t *, ZBlock *, ZTables *, uint32_t *, uint32_t *, void *, const uint32_t *, hipStream_t) { nostub("zparse"); }
@@ -111,7 +123,6 @@ void launch_iadler(ZFrame *, const ZFrameX *, const ZBlock *, uint32_t, const ui
 void launch_zexec(ZFrame *, const ZFrameX *, uint32_t, ZBlock *, const uint8_t *, const uint8_t *, const uint64_t *, uint8_t *, hipStream_t) { nostub("zexec"); }
 void launch_zexec_groups(ZFrame *, const ZFrameX *, uint32_t, ZBlock *, const void *, uint32_t, const uint8_t *, const uint8_t *, const uint64_t *, uint8_t *, hipStream_t) { nostub("zexec"); }
 void launch_gcm_verify(const GcmEntry *, uint32_t, const uint8_t *, const uint8_t *, uint32_t *, hipStream_t) { nostub("gcm"); }
-void launch_aes_cbc_dec(const CipherUnit *, uint32_t, const uint8_t *, const AesDecTabs *, uint8_t *, const AesKey &, uint32_t *, hipStream_t) { nostub("aes"); }
 // Pieces of chunks (k_frame's piece mode, FrameDesc::pad bit 8 = a later piece): the raw CRC-32 register of "FDAT" || piece with the folded initial value
 // (first piece) or of the piece's bytes from register 0 (later piece); pna_crc32(c, ..) = ~register(~c, ..)
 void launch_frame_pieces(const FrameDesc *fd, uint32_t n, const CrcTabs *, const uint8_t *buf, uint64_t, const char ty[4], uint32_t *states, hipStream_t) {
@@ -157,6 +168,42 @@ void launch_aes_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs,
             for (int j = 0; j < 16; j++) p[b + j] ^= (uint8_t)((j < 8 ? h0 : h1) >> (8 * (j & 7)));
             memcpy(prev, p + b, 16);
         }
+    }
+}
+// The encryption round keys behind a decryption schedule.  aes256_dec_key (pna_host.cpp) builds the equivalent inverse cipher's schedule: the
+// encryption round keys in reverse order, d.rk[4 r + c] = InvMixColumns(k.rk[4 (14 - r) + c]) for rounds 1 .. 13, rounds 0 and 14 swapped as they
+// are.  AES-256's round keys 0 and 1 are the key itself: round 0 is d.rk[56 .. 59], round 1 is MixColumns(d.rk[52 .. 55]); the expansion gives the
+// rest.  (The stub's CBC encryption folds the encryption schedule, and its bytes are pinned by the framing matrix.)
+static AesKey enc_key_of(const AesKey &dk) {
+    auto x2 = [](uint8_t a) { return (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1B : 0)); };
+    uint8_t key[32];
+    for (int c4 = 0; c4 < 4; c4++) {
+        uint8_t a[4];
+        for (int j = 0; j < 4; j++) { key[4 * c4 + j] = (uint8_t)(dk.rk[56 + c4] >> (8 * j)); a[j] = (uint8_t)(dk.rk[52 + c4] >> (8 * j)); }
+        for (int j = 0; j < 4; j++) key[16 + 4 * c4 + j] = x2(a[j]) ^ x2(a[(j + 1) & 3]) ^ a[(j + 1) & 3] ^ a[(j + 2) & 3] ^ a[(j + 3) & 3];
+    }
+    AesKey ek; ::aes256_expand(key, ek);
+    return ek;
+}
+// the exact inverse of launch_aes_cbc_enc, in place; plain_len: a unit's plaintext length, 0xFFFFFFFF on a bad length or PKCS#7 padding (k_aes_cbc_dec)
+void launch_aes_cbc_dec(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesDecTabs *, uint8_t *buf, const AesKey &dkey, uint32_t *plain_len, hipStream_t) {
+    const AesKey ek = enc_key_of(dkey);
+    const uint64_t kh = fold(0xCBCull, ek.rk, sizeof ek.rk);
+    for (uint32_t i = 0; i < n; i++) {
+        const CipherUnit &u = units[i];
+        if (u.len == 0 || (u.len & 15)) { plain_len[i] = 0xFFFFFFFFu; continue; }
+        uint8_t *p = buf + u.off;
+        uint8_t prev[16]; memcpy(prev, ivs + 16 * (size_t)u.iv_idx, 16);
+        for (uint32_t b = 0; b < u.len; b += 16) {
+            uint8_t ct[16]; memcpy(ct, p + b, 16);
+            const uint64_t h0 = fold(kh, prev, 16), h1 = mix64(h0 + 1);
+            for (int j = 0; j < 16; j++) p[b + j] ^= (uint8_t)((j < 8 ? h0 : h1) >> (8 * (j & 7)));
+            memcpy(prev, ct, 16);
+        }
+        const uint32_t pad = p[u.len - 1];
+        bool ok = pad >= 1 && pad <= 16;
+        for (uint32_t k = 0; ok && k < pad; k++) ok = p[u.len - 1 - k] == pad;
+        plain_len[i] = ok ? u.len - pad : 0xFFFFFFFFu;
     }
 }
 void launch_gcm_tag(const GcmEntry *ents, uint32_t n, uint8_t *buf, hipStream_t) {

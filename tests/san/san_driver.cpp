@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -282,6 +283,165 @@ static void test_framing_matrix() {
     pna_gpu_shutdown(c);
 }
 
+// Extract matrix: archives through pna_gpu_extract_archive_host -- stored entries (the decoders are not stubbed), solid streams, CTR / CBC under
+// PBKDF2 and Argon2id PHSF strings, and the archives it must refuse.  Each case records the return code, the error text, the number of entries
+// handed out and one CRC-32 over every callback's (index, name, kind, length, data), compared with the values recorded when the matrix was written.
+struct XOut { size_t n = 0; uint32_t crc = 0; };
+static int xsink(void *u, size_t index, const char *name, int kind, const void *data, size_t len) {
+    XOut *o = (XOut *)u;
+    const uint64_t il[2] = {index, len}; const int32_t k = kind;
+    o->crc = pna_crc32(o->crc, il, sizeof il); o->crc = pna_crc32(o->crc, name, strlen(name) + 1); o->crc = pna_crc32(o->crc, &k, sizeof k);
+    o->crc = pna_crc32(o->crc, data, data ? len : 0); o->n++;
+    return 0;
+}
+static Bytes cat(std::initializer_list<Bytes> parts) { Bytes o; for (const Bytes &p : parts) o.insert(o.end(), p.begin(), p.end()); return o; }
+static Bytes str(const std::string &s) { return Bytes(s.begin(), s.end()); }
+static Bytes fhed_body(int kind, int comp, int enc, int mode, const std::string &name) { return cat({Bytes{0, 0, (uint8_t)kind, (uint8_t)comp, (uint8_t)enc, (uint8_t)mode}, str(name)}); }
+static Bytes fsiz_body(uint64_t v) { Bytes b; for (int s = 56; s >= 0; s -= 8) if (!b.empty() || (uint8_t)(v >> s) || s == 0) b.push_back((uint8_t)(v >> s)); return b; }
+static void test_extract_matrix() {
+    pna_gpu_ctx *c = nullptr;
+    CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK);
+    if (!c) return;
+    const char *pw = "password";
+    auto xcase = [&](const char *what, const Bytes &arc, const char *pass, int want_rc, const char *want_err, size_t want_n, uint32_t want_crc) {
+        XOut o;
+        const int rc = pna_gpu_extract_archive_host(c, arc.data(), arc.size(), pass, pass ? strlen(pass) : 0, xsink, &o);
+        const std::string err = rc ? pna_gpu_last_error(c) : "";
+        printf("extract %-28s rc %d n %zu crc %08x %s\n", what, rc, o.n, o.crc, err.c_str());
+        if (rc != want_rc || err != want_err || o.n != want_n || o.crc != want_crc) {
+            fprintf(stderr, "extract %s: rc %d \"%s\" n %zu crc %08x (recorded %d \"%s\" %zu %08x)\n", what, rc, err.c_str(), o.n, o.crc, want_rc, want_err, want_n, want_crc);
+            g_fail++;
+        }
+    };
+    auto writer = [](const std::function<void(pna_archive *)> &fill) {
+        Bytes out; pna_archive *a = nullptr;
+        CHECK(pna_archive_new(vec_sink, &out, 0, &a) == PNA_OK);
+        if (a) { fill(a); CHECK(pna_archive_finalize(a) == PNA_OK); }
+        return out;
+    };
+    auto inner = [](const char *name, const Bytes &d) {
+        Bytes b(pna_archive_inner_entry_bytes(name, d.data(), d.size(), nullptr, 0));
+        CHECK(pna_archive_inner_entry_bytes(name, d.data(), d.size(), b.data(), b.size()) == b.size());
+        return b;
+    };
+    const Bytes t1 = text(5000, 1), t2 = text(70000, 2), t3 = text(300, 3);
+    Bytes head; { pna_archive *a = nullptr; CHECK(pna_archive_new(vec_sink, &head, 0, &a) == PNA_OK); pna_archive_abort(a); }   // signature + AHED
+    const Bytes aend = chunk("AEND", {}), fend = chunk("FEND", {});
+    // ---- plain stored entries
+    const Bytes plain = writer([&](pna_archive *a) {
+        CHECK(pna_archive_add_file(a, "empty", 0, 0, nullptr, 0, 0) == PNA_OK);
+        CHECK(pna_archive_add_dir(a, "d/sub") == PNA_OK);
+        CHECK(pna_archive_add_file(a, "d/sub/t2", 0, (int64_t)t2.size(), t2.data(), t2.size(), 9000) == PNA_OK);
+        CHECK(pna_archive_add_file(a, "nosize", 0, -1, t1.data(), t1.size(), 0) == PNA_OK);
+    });
+    xcase("plain", plain, nullptr, 0, "", 4, 0x8653a76du);
+    const Bytes unsanitised = cat({head, chunk("FHED", fhed_body(0, 0, 0, 1, "/abs/./x/../y")), chunk("FDAT", t3), fend,
+                                   chunk("FHED", fhed_body(0, 0, 0, 1, "../../up")), chunk("fSIZ", fsiz_body(t3.size())), chunk("FDAT", t3), fend, aend});
+    xcase("names sanitised", unsanitised, nullptr, 0, "", 2, 0x7265ca23u);
+    const Bytes big1 = text(700000, 4), big2 = text(900000, 5);
+    const Bytes windows = writer([&](pna_archive *a) {
+        CHECK(pna_archive_add_file(a, "w1", 0, (int64_t)big1.size(), big1.data(), big1.size(), 200000) == PNA_OK);
+        CHECK(pna_archive_add_file(a, "w2", 0, (int64_t)big2.size(), big2.data(), big2.size(), 0) == PNA_OK);
+        CHECK(pna_archive_add_file(a, "w3", 0, (int64_t)t2.size(), t2.data(), t2.size(), 0) == PNA_OK);
+        CHECK(pna_archive_add_file(a, "w4", 0, (int64_t)big1.size(), big1.data(), big1.size(), 0) == PNA_OK);
+    });
+    CHECK(pna_gpu_set_option(c, "extract_win_mib", 1) == PNA_OK);
+    xcase("windows of 1 MiB", windows, nullptr, 0, "", 4, 0xd6f865fbu);
+    xcase("plain, windows of 1 MiB", plain, nullptr, 0, "", 4, 0x8653a76du);
+    CHECK(pna_gpu_set_option(c, "extract_win_mib", 1024) == PNA_OK);
+    xcase("windows of 1 GiB", windows, nullptr, 0, "", 4, 0xd6f865fbu);
+    // ---- stored solid streams: between entries, alone (the deferred hand-out), inner records of several FDAT chunks
+    const Bytes istream = cat({inner("s/a", t1), inner("s/empty", {}), inner("s/../b", t2)});
+    const Bytes multi_fdat = cat({chunk("FHED", fhed_body(0, 0, 0, 1, "s/multi")), chunk("fSIZ", fsiz_body(t2.size())),
+                                  chunk("FDAT", Bytes(t2.begin(), t2.begin() + 1000)), chunk("FDAT", Bytes(t2.begin() + 1000, t2.begin() + 1001)),
+                                  chunk("FDAT", Bytes(t2.begin() + 1001, t2.end())), fend});
+    auto solid_of = [&](const Bytes &st) {
+        return writer([&](pna_archive *a) {
+            const void *pcs[3] = {st.data(), st.data() + 7, st.data() + 4000}; const size_t pl[3] = {7, 3993, st.size() - 4000};
+            CHECK(pna_archive_add_solid(a, 0, pcs, pl, 3) == PNA_OK);
+        });
+    };
+    const Bytes between = writer([&](pna_archive *a) {
+        CHECK(pna_archive_add_file(a, "before", 0, (int64_t)t1.size(), t1.data(), t1.size(), 0) == PNA_OK);
+        const void *pcs[2] = {istream.data(), istream.data() + 100}; const size_t pl[2] = {100, istream.size() - 100};
+        CHECK(pna_archive_add_solid(a, 0, pcs, pl, 2) == PNA_OK);
+        CHECK(pna_archive_add_file(a, "after", 0, (int64_t)t3.size(), t3.data(), t3.size(), 0) == PNA_OK);
+        const void *pc2[1] = {istream.data()}; const size_t pl2[1] = {istream.size()};
+        CHECK(pna_archive_add_solid(a, 0, pc2, pl2, 1) == PNA_OK);
+    });
+    xcase("solid between entries", between, nullptr, 0, "", 8, 0xbe48525cu);
+    xcase("solid alone", solid_of(istream), nullptr, 0, "", 3, 0x6deabe0fu);
+    xcase("solid inner FDAT chunks", solid_of(cat({istream, multi_fdat})), nullptr, 0, "", 4, 0x3070098cu);
+    // ---- encrypted stored entries: CTR / CBC, PBKDF2 and Argon2id, two PHSF strings (two key groups), a CTR solid stream
+    uint8_t kp[32], ka[32]; char phsf_p[128];
+    CHECK(pna_kdf_pbkdf2_sha256(pw, strlen(pw), "saltsaltsaltsalt", 16, 100, kp, 32, phsf_p, sizeof phsf_p) == PNA_OK);
+    const std::string phsf_a = "$argon2id$v=19$m=64,t=1,p=1$c2FsdHNhbHRzYWx0c2FsdA";     // B64 of "saltsaltsaltsalt"
+    CHECK(pna_kdf_argon2(2, pw, strlen(pw), "saltsaltsaltsalt", 16, 1, 64, 1, ka, 32) == PNA_OK);
+    auto encrypt = [&](const uint8_t key[32], int mode, const Bytes &plain_, uint8_t seed) {     // IV || ciphertext
+        uint8_t iv[16]; for (int i = 0; i < 16; i++) iv[i] = (uint8_t)(seed * 31 + i);
+        const size_t clen = mode == PNA_MODE_CBC ? (plain_.size() / 16 + 1) * 16 : plain_.size();
+        Bytes buf(clen + 16, 0); if (!plain_.empty()) memcpy(buf.data(), plain_.data(), plain_.size());
+        pna_gpu_cipher ci{}; ci.encryption = PNA_ENC_AES; ci.cipher_mode = mode; memcpy(ci.key, key, 32); ci.phsf = ""; ci.ivs = iv;
+        const uint64_t off = 0, len = plain_.size();
+        CHECK(pna_gpu_cipher_apply_device(c, &ci, 0, 1, buf.data(), &off, &len, nullptr) == PNA_OK);
+        Bytes o(iv, iv + 16); o.insert(o.end(), buf.begin(), buf.begin() + clen);
+        return o;
+    };
+    auto enc_entry = [&](const char *name, const uint8_t key[32], const std::string &phsf, int mode, const Bytes &d, uint8_t seed) {
+        const Bytes ct = encrypt(key, mode, d, seed);
+        const size_t cut = ct.size() / 3;                                   // the IV and the data in pieces of their own
+        return cat({chunk("FHED", fhed_body(0, 0, PNA_ENC_AES, mode, name)), chunk("fSIZ", fsiz_body(d.size())), chunk("PHSF", str(phsf)),
+                    chunk("FDAT", Bytes(ct.begin(), ct.begin() + 16)), chunk("FDAT", Bytes(ct.begin() + 16, ct.begin() + 16 + cut)),
+                    chunk("FDAT", Bytes(ct.begin() + 16 + cut, ct.end())), fend});
+    };
+    const Bytes enc_pbkdf2 = cat({head, enc_entry("e/ctr", kp, phsf_p, PNA_MODE_CTR, t2, 1), enc_entry("e/cbc", kp, phsf_p, PNA_MODE_CBC, t1, 2),
+                                  enc_entry("e/cbc-empty", kp, phsf_p, PNA_MODE_CBC, {}, 3), enc_entry("e/ctr2", kp, phsf_p, PNA_MODE_CTR, t3, 4), aend});
+    xcase("ctr + cbc pbkdf2", enc_pbkdf2, pw, 0, "", 4, 0x3751c832u);
+    const Bytes enc_argon = cat({head, enc_entry("e/cbc", ka, phsf_a, PNA_MODE_CBC, t2, 5), enc_entry("e/ctr", ka, phsf_a, PNA_MODE_CTR, t1, 6), aend});
+    xcase("ctr + cbc argon2id", enc_argon, pw, 0, "", 2, 0x9e63dc80u);
+    const Bytes two_phsf = cat({head, enc_entry("k/1", kp, phsf_p, PNA_MODE_CTR, t1, 7), enc_entry("k/2", ka, phsf_a, PNA_MODE_CTR, t3, 8),
+                                enc_entry("k/3", kp, phsf_p, PNA_MODE_CBC, t2, 9), aend});
+    xcase("two PHSF strings", two_phsf, pw, 0, "", 3, 0xc9fa9303u);
+    const Bytes sct = encrypt(ka, PNA_MODE_CTR, istream, 10);
+    const Bytes solid_ctr = cat({head, chunk("SHED", Bytes{0, 0, 0, PNA_ENC_AES, PNA_MODE_CTR}), chunk("PHSF", str(phsf_a)), chunk("SDAT", Bytes(sct.begin(), sct.begin() + 16)),
+                                 chunk("SDAT", Bytes(sct.begin() + 16, sct.begin() + 500)), chunk("SDAT", Bytes(sct.begin() + 500, sct.end())), chunk("SEND", {}), aend});
+    xcase("solid ctr argon2id", solid_ctr, pw, 0, "", 3, 0x6deabe0fu);
+    const Bytes cbc_only = cat({head, enc_entry("e/cbc", kp, phsf_p, PNA_MODE_CBC, t2, 11), aend});
+    xcase("cbc wrong password", cbc_only, "passw0rd", -2, "CBC: bad length or padding (wrong password or damaged data)", 0, 0x00000000u);
+    // ---- refusals
+    const Bytes one = writer([&](pna_archive *a) { CHECK(pna_archive_add_file(a, "one", 0, (int64_t)t1.size(), t1.data(), t1.size(), 0) == PNA_OK); });
+    const size_t fdat_at = one.size() - 12 - 12 - 4 - t1.size();          // FDAT body: in front of its CRC, FEND and AEND
+    xcase("truncated chunk header", Bytes(one.begin(), one.end() - 5), nullptr, -2, "truncated chunk header", 0, 0x00000000u);
+    xcase("truncated chunk body", cat({Bytes(one.begin(), one.end() - 12), Bytes{0, 0, 3, 0, 'F', 'D', 'A', 'T'}, Bytes(40, 1)}), nullptr, -2, "truncated chunk body", 0, 0x00000000u);
+    { Bytes b = one; b[8 + 20 + 8 + 2] ^= 1; xcase("chunk CRC mismatch", b, nullptr, -2, "chunk CRC mismatch", 0, 0x00000000u); }
+    { Bytes b = one; b[fdat_at + 100] ^= 1; xcase("FDAT CRC mismatch", b, nullptr, -2, "data chunk CRC mismatch (1 FDAT / SDAT chunks)", 0, 0x00000000u); }
+    { Bytes b = between; b[b.size() - 40] ^= 1; xcase("SDAT CRC mismatch", b, nullptr, -2, "data chunk CRC mismatch (1 FDAT / SDAT chunks)", 5, 0xe47aa3cfu); }
+    const Bytes xbad = chunk("XBAD", Bytes{1}), xanc = chunk("xanc", Bytes{2});
+    xcase("critical chunk between entries", cat({Bytes(one.begin(), one.end() - 12), xanc, xbad, aend}), nullptr, -2, "unknown critical chunk between entries", 0, 0x00000000u);
+    xcase("critical chunk in an entry", cat({head, chunk("FHED", fhed_body(0, 0, 0, 1, "x")), xanc, xbad, fend, aend}), nullptr, -2, "unknown critical chunk", 0, 0x00000000u);
+    xcase("critical chunk in a solid entry", cat({head, chunk("SHED", Bytes{0, 0, 0, 0, 1}), xanc, xbad, chunk("SEND", {}), aend}), nullptr, -2, "unknown critical chunk in a solid entry", 0, 0x00000000u);
+    xcase("bad SHED", cat({head, chunk("SHED", Bytes{0, 0, 0, 0}), chunk("SEND", {}), aend}), nullptr, -2, "bad solid header", 0, 0x00000000u);
+    xcase("ANXT", cat({Bytes(one.begin(), one.end() - 12), chunk("ANXT", {}), aend}), nullptr, -7, "multipart archives are not read by this driver", 0, 0x00000000u);
+    xcase("no AEND", Bytes(one.begin(), one.end() - 12), nullptr, -2, "archive not terminated by AEND", 0, 0x00000000u);
+    xcase("stored fSIZ differs", cat({Bytes(one.begin(), one.end() - 12), chunk("FHED", fhed_body(0, 0, 0, 1, "short")), chunk("fSIZ", fsiz_body(t3.size() + 1)),
+                                      chunk("FDAT", t3), fend, aend}), nullptr, -2, "stored entry: fSIZ differs from the data length", 1, 0xace9736au);
+    xcase("xz", cat({head, chunk("FHED", fhed_body(0, 3, 0, 1, "xz")), chunk("FDAT", t3), fend, aend}), nullptr, -7, "compression method not decoded on the device (xz)", 0, 0x00000000u);
+    xcase("encrypted, no password", enc_pbkdf2, nullptr, -2, "encrypted entry and no password", 0, 0x00000000u);
+    xcase("camellia", cat({head, chunk("FHED", fhed_body(0, 0, PNA_ENC_CAMELLIA, PNA_MODE_CTR, "cam")), chunk("PHSF", str(phsf_p)), chunk("FDAT", t3), fend, aend}), pw, -7, "only AES entries are decrypted by this driver", 0, 0x00000000u);
+    auto phsf_case = [&](const char *what, const std::string &phsf, int want_rc, const char *want_err) {
+        xcase(what, cat({head, enc_entry("p", kp, phsf, PNA_MODE_CTR, t3, 12), aend}), pw, want_rc, want_err, 0, 0);
+    };
+    phsf_case("malformed PHSF", "$pbkdf2-sha256$i=100,l=32", -2, "malformed PHSF");
+    phsf_case("malformed argon2 PHSF", "$argon2id$v=19$m=64,t=x,p=1$c2FsdA", -2, "malformed argon2 parameter in PHSF");
+    phsf_case("argon2 cost above the cap", "$argon2id$v=19$m=4194305,t=1,p=1$c2FsdA", -7, "argon2 cost beyond the accepted maximum (m <= 4 GiB, t <= 64, p <= 256)");
+    phsf_case("pbkdf2 rounds above the cap", "$pbkdf2-sha256$i=10000001,l=32$c2FsdA", -7, "pbkdf2 round count beyond the accepted maximum (10 000 000)");
+    phsf_case("unknown password hash", "$scrypt$ln=4,r=8,p=1$c2FsdA", -7, "password hash other than argon2 / pbkdf2-sha256");
+    xcase("inner entry not stored", solid_of(cat({istream, chunk("FHED", fhed_body(0, 2, 0, 1, "z")), fend})), nullptr, -7, "solid stream: inner entry that is not stored", 0, 0x00000000u);
+    xcase("dangling inner chunks", solid_of(cat({istream, chunk("FHED", fhed_body(0, 0, 0, 1, "open")), chunk("FDAT", t3)})), nullptr, -2, "solid stream: dangling chunks", 0, 0x00000000u);
+    xcase("inner FDAT CRC mismatch", [&] { Bytes st = istream; st[st.size() - 40] ^= 1; return solid_of(st); }(), nullptr, -2, "solid stream: inner FDAT CRC mismatch", 0, 0x00000000u);
+    pna_gpu_shutdown(c);
+}
+
 int main() {
     pna_gpu_ctx *c = nullptr;
     CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK);
@@ -292,6 +452,7 @@ int main() {
     test_streams(c);
     test_pipeline_and_append(c);
     test_framing_matrix();
+    test_extract_matrix();
     pna_gpu_shutdown(c);
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("san_driver: all checks passed\n");
