@@ -332,6 +332,16 @@ int  pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *ctx, const void *d_src, ui
 int  pna_gpu_inflate_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
                                  uint64_t dst_cap, uint64_t *raw_len, void *hip_stream);
 
+/* The decoded size of one such stream (algo: PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE or PNA_ALGO_STORE), measured on the device before it is decoded, so that
+ * the open decoders above can be given exactly the room it needs.  No output buffer is used; the scratch grows with src_len, not with the size.
+ * GUARANTEE: *size is never below what the stream decodes to.  *exact = 1: *size IS that size -- always for zlib streams (their blocks are walked and
+ * counted: k_inflate's count pass, one wave per chunk between block starts) and for zstd frames that carry Frame_Content_Size (this library's);
+ * *exact = 0: an upper bound -- a zstd frame without a content size (what the reference's solid writer emits) counts its raw and RLE blocks exactly and
+ * each compressed block as Block_Maximum_Size (min(window, 128 KiB)).  The open decoders report the true size.  PNA_E_INVAL for bytes that are not a
+ * well-formed stream (truncated, reserved block types, a content size its blocks contradict, a corrupt zlib block); no read leaves the stream's bytes (zlib:
+ * its aligned 4-byte words).  PNA_E_UNSUPPORTED: zlib streams of 4 GiB of compressed bytes and more, or of more than 4 GiB of content without dynamic blocks to split them at. */
+int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, int *exact, void *hip_stream);
+
 /* Read-side driver for archives in host memory (normal and solid entries): `pna extract` / `pna verify` (cli/src/command/extract.rs:594-640,
  * verify.rs:140-188; Archive::read_header + entries, lib/src/archive/read.rs:22-66; read_chunk's mandatory CRC check, lib/src/io.rs:117-149;
  * decrypt_reader / decompress_reader, lib/src/entry/read.rs:59-104,171-190).  The chunk walk and the small chunks' CRCs are host work;
@@ -341,7 +351,9 @@ int  pna_gpu_inflate_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t s
  * DataKind::to_byte(): 0 file, 1 directory, ...); `data` is valid during the call.  PNA_E_INVAL: structural damage, CRC mismatch, corrupt
  * stream, wrong password (GCM key confirmation, CBC padding), authentication failure; PNA_E_UNSUPPORTED: multipart archives, xz,
  * Camellia, solid streams with inner entries that are not stored.  Solid entries (SHED [PHSF] SDAT* SEND; plain or AES CTR / CBC / GCM):
- * SDAT CRCs and the inner FDAT CRCs on the device, the stream is decoded without a recorded size (frames counted first). */
+ * SDAT CRCs and the inner FDAT CRCs on the device.  A solid stream or an entry without fSIZ has no recorded size: it is measured first
+ * (pna_gpu_open_size_device), decoded into device memory of that size and copied once to host memory (an N-GiB solid stream: N GiB of host memory,
+ * besides the archive); PNA_E_NOMEM, naming the size, when the device cannot hold it. */
 /* `name` is the entry's PATH as the reference's reader exposes it (EntryHeader::path(), lib/src/entry/header.rs:91-94): the FHED name
  * normalised and reduced to its normal components (EntryName::sanitize, lib/src/entry/name.rs:148-156 -- no root, no "." / ".."), so a
  * callback that writes files below an output directory cannot be led outside it by a crafted archive.  FHED names that are not valid

@@ -115,7 +115,7 @@ EXPORTS = [
     "pna_gpu_create_archive_part_device", "pna_gpu_decompress_batch", "pna_gpu_decompress_batch_device",
     "pna_gpu_archive_enc_bound", "pna_gpu_create_archive_enc_device", "pna_gpu_cipher_apply_device", "pna_gpu_create_archive_enc_host",
     "pna_gpu_create_solid_archive_enc_device", "pna_gpu_create_solid_archive_enc_host", "pna_gpu_extract_archive_host", "pna_gpu_zstd_stream_frames_device",
-    "pna_gpu_zstd_decompress_open_device", "pna_gpu_inflate_open_device", "pna_gpu_create_archive_meta_device",
+    "pna_gpu_zstd_decompress_open_device", "pna_gpu_inflate_open_device", "pna_gpu_open_size_device", "pna_gpu_create_archive_meta_device",
     "pna_gpu_create_archive_meta_host", "pna_gpu_stream_stats", "pna_bench_stream_threads",
     # include/pna_archive.h
     "pna_crc32", "pna_archive_new", "pna_archive_add_file", "pna_archive_add_dir", "pna_archive_add_solid",
@@ -243,6 +243,8 @@ def load_library() -> ctypes.CDLL:
                                                    ctypes.POINTER(sz), ctypes.POINTER(CipherStruct), ctypes.POINTER(MetaStruct), SINK_FN, vp]
     L.pna_gpu_extract_archive_host.restype = ctypes.c_int
     L.pna_gpu_extract_archive_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ENTRY_FN, vp]
+    L.pna_gpu_open_size_device.restype = ctypes.c_int
+    L.pna_gpu_open_size_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.POINTER(ctypes.c_int), vp]
     L.pna_kdf_pbkdf2_sha256.restype = ctypes.c_int
     L.pna_kdf_pbkdf2_sha256.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, u32, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
     L.pna_split_archive.restype = ctypes.c_int
@@ -394,6 +396,14 @@ class Context:
                                                               ctypes.c_void_p(d_dst), dst_cap, a_out, ctypes.byref(total), part,
                                                               ctypes.c_void_p(stream) if stream else None))
         return total.value, (list(a_out) if want_offsets else None)      # the list conversion costs milliseconds for 10^5 entries
+
+    def open_size_device(self, d_src: int, src_off: int, src_len: int, algo: int = ALGO_ZSTD, stream: int = 0):
+        """The decoded size of one zstd / zlib / stored stream in device memory whose size is recorded nowhere (pna_gpu_open_size_device):
+        (size, exact) -- exact False: a proven upper bound (zstd frames without a content size)."""
+        size, exact = ctypes.c_uint64(), ctypes.c_int()
+        self._check(self._L.pna_gpu_open_size_device(self._h, algo, ctypes.c_void_p(d_src), src_off, src_len, ctypes.byref(size), ctypes.byref(exact),
+                                                     ctypes.c_void_p(stream) if stream else None))
+        return size.value, bool(exact.value)
 
     def cipher_apply_device(self, cipher: Cipher, d_buf: int, off: Sequence[int], length: Sequence[int], decrypt: bool = False,
                             stream: int = 0) -> None:

@@ -1525,6 +1525,74 @@ void launch_zlist(const uint8_t *src, uint64_t base, uint64_t len, uint64_t ip0,
     hipLaunchKernelGGL(k_zlist, dim3(1), dim3(64), 0, st, src, base, len, ip0, (ZListItem *)items, cap, hdr);
 }
 
+// ------------------------------------------------------------------ k_zsize : the decoded size of ONE payload, without decoding it
+// The same walk as k_zlist (every frame, skippable ones skipped), down to the block headers (RFC 8878 3.1.1.2): a frame with Frame_Content_Size counts
+// that (checked against its blocks: no less than its raw / RLE content, no more than the bound below); one without it counts its raw and RLE blocks
+// exactly and every compressed block as Block_Maximum_Size = min(Window_Size, 128 KiB) -- a proven upper bound, tight for compressible data (a 3-byte
+// RLE block header covers up to 128 KiB).  Nothing is read at or behind `len`.  out[0] = size (or bound), out[1] = 1 when exact, out[2] = 1 when the
+// bytes are not a sequence of well-formed frames (truncated, reserved bits or block types, sizes that contradict each other), out[3] = frames, out[4] = the
+// last frame's share of out[0] (the decoder plans a stream of this library's 1 MiB frames from out[3] and out[4]).
+__global__ void k_zsize(const uint8_t *__restrict__ src, uint64_t base, uint64_t len, unsigned long long *__restrict__ out) {
+    if (blockIdx.x || threadIdx.x) return;
+    const uint8_t *p = src + base;
+    uint64_t ip = 0, total = 0, nfr = 0, last = 0;
+    uint32_t exact = 1, bad = 0;
+    while (ip < len && !bad) {
+        if (len - ip < 4) { bad = 1; break; }
+        const uint32_t magic = p[ip] | (p[ip + 1] << 8) | (p[ip + 2] << 16) | ((uint32_t)p[ip + 3] << 24);
+        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
+            if (len - ip < 8) { bad = 1; break; }
+            const uint64_t sz = (uint64_t)p[ip + 4] | ((uint64_t)p[ip + 5] << 8) | ((uint64_t)p[ip + 6] << 16) | ((uint64_t)p[ip + 7] << 24);
+            if (sz > len - ip - 8) { bad = 1; break; }
+            ip += 8 + sz;
+            continue;
+        }
+        if (magic != 0xFD2FB528u || len - ip < 5) { bad = 1; break; }
+        const uint32_t fhd = p[ip + 4];
+        const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3, cksum = (fhd >> 2) & 1;
+        if (fhd & 8) { bad = 1; break; }                                    // reserved bit
+        uint64_t q = ip + 5, wsize = 0;
+        if (!single) {
+            if (q >= len) { bad = 1; break; }
+            const uint32_t wd = p[q++];
+            const uint64_t wbase = 1ull << (10 + (wd >> 3));
+            wsize = wbase + (wbase >> 3) * (wd & 7);
+        }
+        q += dict == 0 ? 0 : (dict == 1 ? 1 : (dict == 2 ? 2 : 4));
+        const uint32_t fb = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
+        if (q > len || len - q < fb) { bad = 1; break; }
+        uint64_t fcs = 0;
+        for (uint32_t i = 0; i < fb; i++) fcs |= (uint64_t)p[q + i] << (8 * i);
+        if (fb == 2) fcs += 256;
+        q += fb;
+        if (single) wsize = fcs;
+        const uint64_t bms = wsize < (128u << 10) ? wsize : (128u << 10);
+        uint64_t ex = 0, bnd = 0;                                           // raw + RLE content; compressed blocks' bound
+        for (;;) {
+            if (len - q < 3) { bad = 1; break; }
+            const uint32_t bh = p[q] | (p[q + 1] << 8) | ((uint32_t)p[q + 2] << 16);
+            const uint32_t type = (bh >> 1) & 3, size = bh >> 3;
+            q += 3;
+            if (type == 3) { bad = 1; break; }
+            const uint64_t body = type == 1 ? 1u : size;
+            if (body > len - q) { bad = 1; break; }
+            if (type == 2) bnd += bms; else ex += size;
+            q += body;
+            if (bh & 1) break;
+        }
+        if (bad) break;
+        if (cksum) { if (len - q < 4) { bad = 1; break; } q += 4; }
+        if (fb) { if (fcs < ex || fcs - ex > bnd) { bad = 1; break; } last = fcs; }
+        else { last = ex + bnd; if (bnd) exact = 0; }
+        total += last;
+        ip = q; nfr++;
+    }
+    out[0] = total; out[1] = exact; out[2] = bad; out[3] = nfr; out[4] = last;
+}
+void launch_zsize(const uint8_t *src, uint64_t base, uint64_t len, unsigned long long *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_zsize, dim3(1), dim3(64), 0, st, src, base, len, out);
+}
+
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_zscan, dim3((n + 63) / 64), dim3(64), 0, st, ents, n, src, frames, fx);
 }

@@ -69,6 +69,9 @@ void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st);
 void launch_zcount(const ZEntry *ents, uint32_t n, const uint8_t *src, uint32_t *counts, hipStream_t st);
 void launch_zlist(const uint8_t *src, uint64_t base, uint64_t len, uint64_t ip0, void *items, uint32_t cap, uint64_t *hdr, hipStream_t st);   // items: {off, len, fcs} x cap (24 B each)
+// (k_zdec.hip) the decoded size of one zstd payload from its frame and block headers: out = {size or bound, exact, malformed, frames, last frame's share}.  A weak reference like
+// launch_deflate_write_run: the sanitizer build has no stand-in for it, pna_gpu_open_size_device refuses zstd there.
+__attribute__((weak)) void launch_zsize(const uint8_t *src, uint64_t base, uint64_t len, unsigned long long *out, hipStream_t st);
 void launch_zparse(ZFrame *frames, ZFrameX *fx, uint32_t n, const uint8_t *src, ZBlock *blocks, ZTables *tabs, uint32_t *huf_list, uint32_t *seq_list,
                    void *work, hipStream_t st);
 void launch_zparse_big_a(ZFrame *frames, ZFrameX *fx, const uint32_t *big_list, uint32_t nbig, const uint8_t *src, ZBlock *blocks, uint32_t *one_list, void *work, hipStream_t st);
@@ -76,6 +79,11 @@ void launch_zparse_big_b(ZFrame *frames, ZFrameX *fx, uint32_t nblocks, const ui
                          void *work, const uint32_t *one_list, hipStream_t st);
 void launch_zstreams(uint32_t n_huf, uint32_t n_seq, const uint32_t *huf_list, const uint32_t *seq_list, const void *work, ZBlock *blocks,
                      const ZFrame *frames, const ZTables *tabs, const uint8_t *src, uint8_t *lit_scratch, uint64_t *seqs, hipStream_t st);
+// pna_decode.cpp: the measurement behind pna_gpu_open_size_device (zstd: also its frames and the last frame's share of the size), and the open zstd
+// decode planned from it -- frames of 1 MiB but the last, which gets `last` bytes of room (the rest of `cap` only if the stream is not of that shape)
+struct OpenSize { uint64_t size = 0; int exact = 0; uint64_t frames = 0, last = 0; };
+int open_size(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, OpenSize *out, hipStream_t st);
+int zstd_open_decode_planned(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, const OpenSize &m, uint64_t *got, hipStream_t st);
 struct ISChunkH { uint64_t start_bit, end_bit, lit_base, out_base, rec_base, end_found, mtot; uint32_t nlit, nrec, status, adler; };   // = ISChunk of k_inflate.hip
 static_assert(sizeof(ISChunkH) == 72, "ISChunk layout");
 void launch_ispec(const uint8_t *src, uint64_t src_off, uint64_t src_len, uint32_t cbytes, uint32_t nchunks, uint64_t *start, hipStream_t st);

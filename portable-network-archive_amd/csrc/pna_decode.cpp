@@ -28,51 +28,35 @@ static int zx_windows(pna_gpu_ctx *c, const ZxFrame &h, hipStream_t st, std::vec
 // Read side, Compression::Deflate: one zlib stream per entry (flate2::read::ZlibDecoder, lib/src/entry/read.rs:178-179).
 // k_inflate turns each stream into literals + (run, length, distance) records, k_zoff / k_zexec execute them, k_iadler_* check
 // the Adler-32 trailer.
-// A LARGE stream the lane-per-piece decoder cannot take (a foreign encoder's: no sync flush behind every 128 KiB -- what the reference itself writes for a large
-// deflate entry): block starts found by trial (k_ispec), one wave per chunk between two of them (k_inflate's chunk mode: COUNT, prefix sums here, EMIT), one ZBlock per
-// chunk.  *ok = false: something did not fit (no chunk starts found, a chunk's walk did not end where the next begins, sizes that do not add up) -- the serial walk
-// takes the stream, nothing is lost but time.  The records are executed by k_zexec_par afterwards (the caller).
 static constexpr uint32_t SPEC_CHUNK = 16384;
-static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, const ZFrameX &x, const void *d_src, hipStream_t st, uint32_t *nblk_out, bool *ok,
-                               bool open, uint64_t *out_len) {
-    *ok = false;
-    const uint32_t nch = (uint32_t)((fr.src_len + SPEC_CHUNK - 1) / SPEC_CHUNK);
-    if (nch < 4 || nch > x.blk_cap) return PNA_OK;
-    if (c->z_spec.ensure((size_t)nch * (8 + sizeof(ISChunkH)) + 64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
-    uint64_t *d_start = (uint64_t *)c->z_spec.p;
-    ISChunkH *d_chunks = (ISChunkH *)((uint8_t *)c->z_spec.p + (size_t)nch * 8);
-    std::vector<uint64_t> start(nch);
-    launch_ispec((const uint8_t *)d_src, fr.src_off, fr.src_len, SPEC_CHUNK, nch, d_start, st);
-    HIPCHK(c, hipMemcpyAsync(start.data(), d_start, (size_t)nch * 8, hipMemcpyDeviceToHost, st));
+// One walk of k_inflate's chunk mode over the chunks ch[idx[0 ..]] (idx empty: all of them) of stream f (its ZFrame / ZFrameX on the device): count pass
+// (emit = 0: only the chunk descriptors are written) or emit pass.
+static int run_chunks(pna_gpu_ctx *c, uint32_t f, std::vector<ISChunkH> &ch, const std::vector<uint32_t> &idx, uint32_t emit, ISChunkH *d_chunks, const void *d_src,
+                      ZBlock *blocks, uint8_t *lit, uint64_t *seqs, hipStream_t st) {
+    const uint32_t cnt = idx.empty() ? (uint32_t)ch.size() : (uint32_t)idx.size();
+    std::vector<ISChunkH> sub;
+    if (!idx.empty()) { sub.resize(cnt); for (uint32_t i = 0; i < cnt; i++) sub[i] = ch[idx[i]]; }
+    ISChunkH *hp = idx.empty() ? ch.data() : sub.data();
+    HIPCHK(c, hipMemcpyAsync(d_chunks, hp, (size_t)cnt * sizeof(ISChunkH), hipMemcpyHostToDevice, st));
+    launch_inflate_chunks((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, f, d_chunks, cnt, emit, (const uint8_t *)d_src, blocks, lit, seqs, st);
+    HIPCHK(c, hipMemcpyAsync(hp, d_chunks, (size_t)cnt * sizeof(ISChunkH), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    std::vector<ISChunkH> ch;
-    for (uint32_t k = 0; k < nch; k++)
-        if (start[k] != ~0ull) { ISChunkH h{}; h.start_bit = start[k]; h.end_bit = ~0ull; if (!ch.empty()) ch.back().end_bit = start[k]; ch.push_back(h); }
+    if (!idx.empty()) for (uint32_t i = 0; i < cnt; i++) ch[idx[i]] = sub[i];
+    return PNA_OK;
+}
+// The count pass over the chunks `ch` of stream f, false block starts repaired; *ok = false: a chunk's walk failed, the chain is broken or there were too many
+// false starts (`why` says which).
+// A walk that runs past its chunk's end says the NEXT chunk's start was not a block start (a well-formed header by chance: one in a few 10^9 bit positions --
+// seen in a 445 MB stream, five of them in a 2 GB one): that chunk is dropped, its predecessor runs on to the start behind it and is counted again -- only it:
+// the other chunks' counts stand (second half of round 4; before, every repair was a walk over the whole stream, one false start at a time).  A dropped chunk's
+// own walk says nothing about the chunk behind it, which is judged in the next round by its new predecessor.
+static int count_chunks(pna_gpu_ctx *c, uint32_t f, std::vector<ISChunkH> &ch, ISChunkH *d_chunks, const void *d_src, ZBlock *blocks, uint8_t *lit, uint64_t *seqs,
+                        hipStream_t st, const std::function<void(const char *, uint64_t, uint64_t)> &why, bool *ok) {
+    *ok = false;
     uint32_t m = (uint32_t)ch.size();
-    auto why = [&](const char *what, uint64_t a, uint64_t b) { if (c->tun.trace) fprintf(stderr, "[pna inflate] stream %u of %llu B not decoded in chunks: %s (%llu, %llu)\n", f, (unsigned long long)fr.src_len, what, (unsigned long long)a, (unsigned long long)b); };
-    if (m < 4) { why("too few block starts found", m, nch); return PNA_OK; }                                      // (stored data, or blocks of more than a chunk each: not worth the two passes)
-    // one walk over the chunks ch[idx[0 ..]] (idx empty: all of them): count pass (emit = 0) or emit pass
-    auto run = [&](uint32_t emit, const std::vector<uint32_t> &idx) -> int {
-        const uint32_t cnt = idx.empty() ? m : (uint32_t)idx.size();
-        std::vector<ISChunkH> sub;
-        if (!idx.empty()) { sub.resize(cnt); for (uint32_t i = 0; i < cnt; i++) sub[i] = ch[idx[i]]; }
-        ISChunkH *hp = idx.empty() ? ch.data() : sub.data();
-        HIPCHK(c, hipMemcpyAsync(d_chunks, hp, (size_t)cnt * sizeof(ISChunkH), hipMemcpyHostToDevice, st));
-        launch_inflate_chunks((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, f, d_chunks, cnt, emit, (const uint8_t *)d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p,
-                              (uint64_t *)c->z_seqs.p, st);
-        HIPCHK(c, hipMemcpyAsync(hp, d_chunks, (size_t)cnt * sizeof(ISChunkH), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (!idx.empty()) for (uint32_t i = 0; i < cnt; i++) ch[idx[i]] = sub[i];
-        return PNA_OK;
-    };
-    // A walk that runs past its chunk's end says the NEXT chunk's start was not a block start (a well-formed header by chance: one in a few 10^9 bit positions --
-    // seen in a 445 MB stream, five of them in a 2 GB one): that chunk is dropped, its predecessor runs on to the start behind it and is counted again -- only it:
-    // the other chunks' counts stand (second half of round 4; before, every repair was a walk over the whole stream, one false start at a time).  A dropped chunk's
-    // own walk says nothing about the chunk behind it, which is judged in the next round by its new predecessor.
-    int rc = PNA_OK;
     std::vector<uint32_t> todo;                                      // (empty: everything)
     for (int round = 0;; round++) {
-        rc = run(0, todo); if (rc) return rc;
+        const int rc = run_chunks(c, f, ch, todo, 0, d_chunks, d_src, blocks, lit, seqs, st); if (rc) return rc;
         std::vector<ISChunkH> keep; keep.reserve(m);
         todo.clear();
         bool prev_dropped = false;
@@ -90,20 +74,56 @@ static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, con
         ch.swap(keep); m = (uint32_t)ch.size();
         for (uint32_t i : todo) { ISChunkH &h = ch[i]; const uint64_t sb = h.start_bit; h = ISChunkH{}; h.start_bit = sb; h.end_bit = i + 1 < m ? ch[i + 1].start_bit : ~0ull; }
     }
-    uint64_t lit = 0, out = 0, rec = 0;
     for (uint32_t k = 0; k < m; k++) {
         const ISChunkH &h = ch[k];
         if (h.status) { why("a chunk's walk failed: chunk, status", k, h.status); return PNA_OK; }
         if (k + 1 < m && h.end_found != ch[k + 1].start_bit) { why("the chain is broken behind chunk: end found, next start", h.end_found, ch[k + 1].start_bit); return PNA_OK; }   // a false start, or a stream this scheme does not fit
-        lit += h.nlit; out += (uint64_t)h.nlit + h.mtot; rec += h.nrec;
     }
+    *ok = true;
+    return PNA_OK;
+}
+// block starts of a stream by trial (k_ispec): one chunk per start found, each running up to the next (nch chunks of SPEC_CHUNK bytes searched)
+static int find_chunks(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, uint32_t nch, uint64_t *d_start, std::vector<ISChunkH> &ch, hipStream_t st) {
+    std::vector<uint64_t> start(nch);
+    launch_ispec((const uint8_t *)d_src, src_off, src_len, SPEC_CHUNK, nch, d_start, st);
+    HIPCHK(c, hipMemcpyAsync(start.data(), d_start, (size_t)nch * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    ch.clear();
+    for (uint32_t k = 0; k < nch; k++)
+        if (start[k] != ~0ull) { ISChunkH h{}; h.start_bit = start[k]; h.end_bit = ~0ull; if (!ch.empty()) ch.back().end_bit = start[k]; ch.push_back(h); }
+    return PNA_OK;
+}
+
+// A LARGE stream the lane-per-piece decoder cannot take (a foreign encoder's: no sync flush behind every 128 KiB -- what the reference itself writes for a large
+// deflate entry): block starts found by trial (k_ispec), one wave per chunk between two of them (k_inflate's chunk mode: COUNT, prefix sums here, EMIT), one ZBlock per
+// chunk.  *ok = false: something did not fit (no chunk starts found, a chunk's walk did not end where the next begins, sizes that do not add up) -- the serial walk
+// takes the stream, nothing is lost but time.  The records are executed by k_zexec_par afterwards (the caller).
+static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, const ZFrameX &x, const void *d_src, hipStream_t st, uint32_t *nblk_out, bool *ok,
+                               bool open, uint64_t *out_len) {
+    *ok = false;
+    const uint32_t nch = (uint32_t)((fr.src_len + SPEC_CHUNK - 1) / SPEC_CHUNK);
+    if (nch < 4 || nch > x.blk_cap) return PNA_OK;
+    if (c->z_spec.ensure((size_t)nch * (8 + sizeof(ISChunkH)) + 64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
+    uint64_t *d_start = (uint64_t *)c->z_spec.p;
+    ISChunkH *d_chunks = (ISChunkH *)((uint8_t *)c->z_spec.p + (size_t)nch * 8);
+    std::vector<ISChunkH> ch;
+    int rc = find_chunks(c, d_src, fr.src_off, fr.src_len, nch, d_start, ch, st); if (rc) return rc;
+    uint32_t m = (uint32_t)ch.size();
+    auto why = [&](const char *what, uint64_t a, uint64_t b) { if (c->tun.trace) fprintf(stderr, "[pna inflate] stream %u of %llu B not decoded in chunks: %s (%llu, %llu)\n", f, (unsigned long long)fr.src_len, what, (unsigned long long)a, (unsigned long long)b); };
+    if (m < 4) { why("too few block starts found", m, nch); return PNA_OK; }                                      // (stored data, or blocks of more than a chunk each: not worth the two passes)
+    bool counted = false;
+    rc = count_chunks(c, f, ch, d_chunks, d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p, st, why, &counted); if (rc) return rc;
+    if (!counted) return PNA_OK;
+    m = (uint32_t)ch.size();
+    uint64_t lit = 0, out = 0, rec = 0;
+    for (uint32_t k = 0; k < m; k++) { const ISChunkH &h = ch[k]; lit += h.nlit; out += (uint64_t)h.nlit + h.mtot; rec += h.nrec; }
     if (open ? out > fr.dst_len : out != fr.dst_len) { why("sizes do not add up: output, expected", out, fr.dst_len); return PNA_OK; }   // (open: dst_len is the room)
     *out_len = out;
     if (rec > x.seq_cap) { why("more records than room: records, room", rec, x.seq_cap); return PNA_OK; }
     if ((ch[m - 1].end_found + 7) / 8 != fr.src_len) { why("the last chunk does not end with the stream: end bit, stream bytes", ch[m - 1].end_found, fr.src_len); return PNA_OK; }
     lit = out = rec = 0;
     for (uint32_t k = 0; k < m; k++) { ISChunkH &h = ch[k]; h.lit_base = lit; h.out_base = out; h.rec_base = rec; lit += h.nlit; out += (uint64_t)h.nlit + h.mtot; rec += h.nrec; }
-    rc = run(1, std::vector<uint32_t>()); if (rc) return rc;
+    rc = run_chunks(c, f, ch, std::vector<uint32_t>(), 1, d_chunks, d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p, st); if (rc) return rc;
     for (uint32_t k = 0; k < m; k++) if (ch[k].status) { why("a chunk's second walk failed: chunk, status", k, ch[k].status); return PNA_OK; }
     *nblk_out = m; *ok = true;
     return PNA_OK;
@@ -267,9 +287,77 @@ extern "C" int pna_gpu_inflate_open_device(pna_gpu_ctx *c, const void *d_src, ui
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The decoded size of one stream whose size is recorded nowhere, measured before it is decoded: no output buffer, scratch by the compressed length.
+// zlib: k_inflate's chunk mode in its count pass (emit = 0: nothing but the chunk descriptors is written) between block starts found by trial (k_ispec --
+// this library's sync-flush pieces and a foreign encoder's dynamic blocks alike), one wave per chunk, false starts repaired; one wave over the whole stream
+// when there are fewer than four starts (small streams, stored or fixed-code blocks) or the chain does not hold.  The count is exact.
+static int inflate_measure(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, hipStream_t st) {
+    if (src_len > 0xFFFFFFFFull) return fail(c, PNA_E_UNSUPPORTED, "zlib streams of 4 GiB of compressed bytes and more are not measured");
+    const uint32_t nch = src_len >= 8ull * SPEC_CHUNK ? (uint32_t)((src_len + SPEC_CHUNK - 1) / SPEC_CHUNK) : 1u;
+    if (c->z_spec.ensure((size_t)nch * (8 + sizeof(ISChunkH)) + 64) || c->z_frames.ensure(sizeof(ZFrame)) || c->z_fx.ensure(sizeof(ZFrameX)))
+        return fail(c, PNA_E_NOMEM, "measurement workspace");
+    uint64_t *d_start = (uint64_t *)c->z_spec.p;
+    ISChunkH *d_chunks = (ISChunkH *)((uint8_t *)c->z_spec.p + (size_t)nch * 8);
+    uint8_t *none = (uint8_t *)c->z_spec.p;                              // (the count pass writes no literals, records or blocks)
+    static const ZFrame fr0{0, 0, 0, ~0ull, 0, 0};                        // dst_len: no limit
+    ZFrame fr = fr0; fr.src_off = src_off; fr.src_len = src_len;
+    ZFrameX x{}; x.seq_cap = 0xFFFFFFFFu;
+    HIPCHK(c, hipMemcpyAsync(c->z_frames.p, &fr, sizeof fr, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->z_fx.p, &x, sizeof x, hipMemcpyHostToDevice, st));
+    std::vector<ISChunkH> ch;
+    int rc = PNA_OK;
+    if (nch >= 8) { rc = find_chunks(c, d_src, src_off, src_len, nch, d_start, ch, st); if (rc) return rc; }
+    auto why = [&](const char *what, uint64_t a, uint64_t b) { if (c->tun.trace) fprintf(stderr, "[pna inflate] stream of %llu B measured by one wave: %s (%llu, %llu)\n", (unsigned long long)src_len, what, (unsigned long long)a, (unsigned long long)b); };
+    bool ok = false;
+    if (ch.size() >= 4) { rc = count_chunks(c, 0, ch, d_chunks, d_src, (ZBlock *)none, none, (uint64_t *)none, st, why, &ok); if (rc) return rc; }
+    if (!ok) {                                                            // one wave over the whole stream: its verdict stands
+        ch.assign(1, ISChunkH{}); ch[0].end_bit = ~0ull;
+        rc = run_chunks(c, 0, ch, std::vector<uint32_t>(), 0, d_chunks, d_src, (ZBlock *)none, none, (uint64_t *)none, st); if (rc) return rc;
+        if (ch[0].status == 2) return fail(c, PNA_E_UNSUPPORTED, "zlib stream with a preset dictionary, or of more than 4 GiB of content and no block starts to split it at");
+        if (ch[0].status) return fail(c, PNA_E_INVAL, "corrupt zlib stream (measuring its size)");
+    }
+    uint64_t out = 0;
+    for (const ISChunkH &h : ch) out += (uint64_t)h.nlit + h.mtot;
+    *size = out;
+    return PNA_OK;
+}
+
+int pna::open_size(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, OpenSize *m, hipStream_t st) {
+    *m = OpenSize();
+    if (algo == PNA_ALGO_STORE) { m->size = src_len; m->exact = 1; return PNA_OK; }
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "only zstd, deflate and stored streams are measured");
+    if (algo == PNA_ALGO_DEFLATE) {
+        const int rc = inflate_measure(c, d_src, src_off, src_len, &m->size, st); if (rc) return rc;
+        m->exact = 1;
+        return PNA_OK;
+    }
+    if (!launch_zsize) return fail(c, PNA_E_UNSUPPORTED, "this build has no k_zsize");
+    if (c->z_work.ensure(64)) return fail(c, PNA_E_NOMEM, "measurement workspace");
+    unsigned long long o[5] = {0, 0, 0, 0, 0};
+    launch_zsize((const uint8_t *)d_src, src_off, src_len, (unsigned long long *)c->z_work.p, st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(o, c->z_work.p, sizeof o, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (o[2]) return fail(c, PNA_E_INVAL, "corrupt stream (not a sequence of well-formed zstd frames)");
+    m->size = o[0]; m->exact = o[1] ? 1 : 0; m->frames = o[3]; m->last = o[4];
+    return PNA_OK;
+}
+
+extern "C" int pna_gpu_open_size_device(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, int *exact, void *hip_stream) {
+    if (!c || (!d_src && src_len) || !size || !exact) return fail(c, PNA_E_INVAL, "null argument");
+    *size = 0; *exact = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    OpenSize m;
+    const int rc = open_size(c, algo, d_src, src_off, src_len, &m, hip_stream ? (hipStream_t)hip_stream : c->stream); if (rc) return rc;
+    *size = m.size; *exact = m.exact;
+    return PNA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Read side: decompress_reader (lib/src/entry/read.rs:171-190); entries already in device memory.
 static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                              const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign = true);
+                              const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign = true,
+                              const OpenSize *plan = nullptr);
 
 extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off,
                                                const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
@@ -305,6 +393,11 @@ extern "C" int pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *c, const void *d
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     return zstd_decode_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &dst_cap, true, raw_len, st);
+}
+
+int pna::zstd_open_decode_planned(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, const OpenSize &m, uint64_t *got, hipStream_t st) {
+    const uint64_t dst_off = 0, cap = m.size;
+    return zstd_decode_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &cap, true, got, st, true, &m);
 }
 
 // A payload k_zscan could not place -- frames of other sizes than this library's grid, skippable frames between them: anything zstd::stream::read::Decoder
@@ -356,23 +449,29 @@ static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_o
 }
 
 static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                              const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign) {
+                              const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign,
+                              const OpenSize *plan) {
     std::vector<ZEntry> ents(n);
     uint64_t nfr = 0;
     for (size_t i = 0; i < n; i++) {
-        const uint64_t k = raw_len[i] ? (raw_len[i] + SEG_SIZE - 1) / SEG_SIZE : 1;
+        uint64_t k = raw_len[i] ? (raw_len[i] + SEG_SIZE - 1) / SEG_SIZE : 1;
+        // a measured stream of several frames (plan: n = 1): one slot per frame, 1 MiB each but the last, which gets its own measured room -- a stream
+        // that does not have this library's shape goes through zstd_decode_foreign with all of raw_len
+        if (plan && plan->frames > 1) k = plan->frames;
         if (nfr + k > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "too many frames");
-        ents[i] = ZEntry{src_off[i], src_len[i], dst_off[i], raw_len[i], (uint32_t)nfr, (uint32_t)k, open ? 1u : 0u, 0u};
+        const uint64_t room = plan && plan->frames > 1 ? std::min<uint64_t>(raw_len[i], (k - 1) * SEG_SIZE + plan->last) : raw_len[i];
+        ents[i] = ZEntry{src_off[i], src_len[i], dst_off[i], room, (uint32_t)nfr, (uint32_t)k, open ? 1u : 0u, 0u};
         nfr += k;
     }
     // per-frame bounds of the lane-parallel pipeline (frames that exceed them fall back to the one-workgroup-per-frame kernel)
     std::vector<ZFrameX> fxs(nfr);
     uint64_t nblk_cap = 0, nslot = 0, nseq_cap = 0, out_span = 0;
     for (size_t i = 0; i < n; i++) {
-        out_span = std::max<uint64_t>(out_span, dst_off[i] + raw_len[i]);
+        const uint64_t room = ents[i].raw_len;
+        out_span = std::max<uint64_t>(out_span, dst_off[i] + room);
         for (uint32_t f = 0; f < ents[i].n_frames; f++) {
             const uint64_t done = (uint64_t)f * SEG_SIZE;
-            const uint64_t dl = (f + 1 == ents[i].n_frames) ? (raw_len[i] > done ? raw_len[i] - done : 0) : SEG_SIZE;
+            const uint64_t dl = (f + 1 == ents[i].n_frames) ? (room > done ? room - done : 0) : SEG_SIZE;
             ZFrameX &x = fxs[ents[i].first_frame + f];
             x.blk_base = (uint32_t)nblk_cap; x.blk_cap = (uint32_t)std::min<uint64_t>((dl >> 12) + 4, 1u << 20);
             x.slot_base = (uint32_t)nslot; x.slot_cap = (uint32_t)std::min<uint64_t>((dl >> 17) + 2, 1u << 16);
@@ -402,7 +501,7 @@ static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const
         const uint64_t big_min = (uint64_t)c->tun.zexec_par_min_mib << 20;
         if (c->tun.zexec_par_min_mib > 0) {
             bool any = false;
-            for (size_t i = 0; i < n && !any; i++) any = raw_len[i] >= big_min;
+            for (size_t i = 0; i < n && !any; i++) any = ents[i].raw_len >= big_min;
             if (any) {
                 HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, nfr * sizeof(ZFrame), hipMemcpyDeviceToHost, st));
                 HIPCHK(c, hipStreamSynchronize(st));

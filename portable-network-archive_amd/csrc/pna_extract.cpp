@@ -405,18 +405,24 @@ static int decode_sized(pna_gpu_ctx *c, const std::vector<XEntry> &ents, int slo
     }
     return PNA_OK;
 }
-// A stream whose decoded size only the decoder finds -- an entry without fSIZ, a solid stream -- decoded into c->solid_plain and copied to `out`
-// (a stored one is copied from the packed buffer as it is)
+// A stream whose decoded size is recorded nowhere -- an entry without fSIZ, a solid stream -- measured on the device (pna_gpu_open_size_device: the exact
+// size, or a proven bound), decoded into c->solid_plain of that size and copied to `out` (a stored one is copied from the packed buffer as it is)
 static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::vector<uint8_t> &out, hipStream_t st) {
     uint64_t got = s.pay_len; const void *d = (const uint8_t *)c->x_pk.p + s.pk_off;
     if (s.compression != PNA_ALGO_STORE) {
-        uint32_t nfr = 1; int rc;
-        if (s.compression == PNA_ALGO_ZSTD) { rc = pna_gpu_zstd_stream_frames_device(c, c->x_pk.p, s.pk_off, s.pay_len, &nfr, st); if (rc) return rc; }
-        // this library's zstd solid streams: frames of 1 MiB; one frame / one zlib stream: a bounded guess of its size
-        const uint64_t cap = nfr > 1 ? (uint64_t)nfr * SEG_SIZE : std::min<uint64_t>(1ull << 30, std::max<uint64_t>(64ull << 20, 64 * s.pay_len));
-        if (c->solid_plain.ensure(cap + 8192)) return fail(c, PNA_E_NOMEM, what);
-        rc = s.compression == PNA_ALGO_ZSTD ? pna_gpu_zstd_decompress_open_device(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, 0, cap, &got, st)
+        OpenSize m;
+        int rc = open_size(c, s.compression, c->x_pk.p, s.pk_off, s.pay_len, &m, st); if (rc) return rc;
+        const uint64_t cap = m.size; const int exact = m.exact;
+        auto nomem = [&]() {
+            char msg[192];
+            snprintf(msg, sizeof msg, "%s: the stream decodes to %s%llu bytes, more than the device's free memory takes (with the decoder's workspace)", what,
+                     exact ? "" : "at most ", (unsigned long long)cap);
+            return fail(c, PNA_E_NOMEM, msg);
+        };
+        if (c->solid_plain.ensure(cap + 8192)) return nomem();
+        rc = s.compression == PNA_ALGO_ZSTD ? zstd_open_decode_planned(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, m, &got, st)
                                             : pna_gpu_inflate_open_device(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, 0, cap, &got, st);
+        if (rc == PNA_E_NOMEM) return nomem();
         if (rc) return rc;
         d = c->solid_plain.p;
     }
