@@ -308,8 +308,9 @@ int  pna_gpu_create_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n
  *   PNA_ALGO_DEFLATE: one RFC 1950 zlib stream (any block types, sync-flush markers, window <= 32 KiB); Adler-32 is verified.
  *     Streams of 4 GiB and more (compressed or decoded) are decoded by their sync-flush delimited pieces -- what this library
  *     writes --, or, a foreign encoder's stream without such markers (one flate2 / zlib stream per entry: what the reference writes), in chunks between
- *     block starts found by trial, as long as its COMPRESSED bytes stay below 4 GiB and it has dynamic blocks to find (up to ~5.9 GiB of content);
- *     what fits neither is PNA_E_UNSUPPORTED (the wave-per-stream walk counts in 32 bits).
+ *     block starts found by trial -- dynamic and stored blocks; compressed positions are 64-bit, so the compressed size is not limited --; what
+ *     fits neither (a stream of 4 GiB and more whose only block boundaries are fixed-Huffman blocks) is PNA_E_UNSUPPORTED (the wave-per-stream
+ *     walk counts in 32 bits).
  *   Single streams of any size are executed in parallel (zstd frames of 2 GiB and more since the second half of round 4: the executor's windows,
  *     option "zexec_win_mib"); a zstd frame whose compressed bytes exceed 4 GiB, or which does not fit its pooled resources, is left to one workgroup
  *     (~11 MiB/s) unless the option "zdec_fallback_max_mib" refuses it.
@@ -339,7 +340,8 @@ int  pna_gpu_inflate_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t s
  * *exact = 0: an upper bound -- a zstd frame without a content size (what the reference's solid writer emits) counts its raw and RLE blocks exactly and
  * each compressed block as Block_Maximum_Size (min(window, 128 KiB)).  The open decoders report the true size.  PNA_E_INVAL for bytes that are not a
  * well-formed stream (truncated, reserved block types, a content size its blocks contradict, a corrupt zlib block); no read leaves the stream's bytes (zlib:
- * its aligned 4-byte words).  PNA_E_UNSUPPORTED: zlib streams of 4 GiB of compressed bytes and more, or of more than 4 GiB of content without dynamic blocks to split them at. */
+ * its aligned 4-byte words).  PNA_E_UNSUPPORTED: zlib streams of 4 GiB of compressed bytes and more, or of more than 4 GiB of content, that have no dynamic or
+ * stored blocks to split them at (fixed-Huffman blocks only). */
 int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, int *exact, void *hip_stream);
 
 /* Read-side driver for archives in host memory (normal and solid entries): `pna extract` / `pna verify` (cli/src/command/extract.rs:594-640,

@@ -245,6 +245,8 @@ def load_library() -> ctypes.CDLL:
     L.pna_gpu_extract_archive_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ENTRY_FN, vp]
     L.pna_gpu_open_size_device.restype = ctypes.c_int
     L.pna_gpu_open_size_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.POINTER(ctypes.c_int), vp]
+    L.pna_gpu_inflate_open_device.restype = ctypes.c_int
+    L.pna_gpu_inflate_open_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, vp]
     L.pna_kdf_pbkdf2_sha256.restype = ctypes.c_int
     L.pna_kdf_pbkdf2_sha256.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, u32, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
     L.pna_split_archive.restype = ctypes.c_int
@@ -404,6 +406,14 @@ class Context:
         self._check(self._L.pna_gpu_open_size_device(self._h, algo, ctypes.c_void_p(d_src), src_off, src_len, ctypes.byref(size), ctypes.byref(exact),
                                                      ctypes.c_void_p(stream) if stream else None))
         return size.value, bool(exact.value)
+
+    def inflate_open_device(self, d_src: int, src_off: int, src_len: int, d_dst: int, dst_off: int, dst_cap: int, stream: int = 0) -> int:
+        """One zlib stream in device memory whose size is recorded nowhere, decoded into dst_cap bytes of room (pna_gpu_inflate_open_device).
+        Returns the decoded size."""
+        raw = ctypes.c_uint64()
+        self._check(self._L.pna_gpu_inflate_open_device(self._h, ctypes.c_void_p(d_src), src_off, src_len, ctypes.c_void_p(d_dst), dst_off, dst_cap,
+                                                        ctypes.byref(raw), ctypes.c_void_p(stream) if stream else None))
+        return raw.value
 
     def cipher_apply_device(self, cipher: Cipher, d_buf: int, off: Sequence[int], length: Sequence[int], decrypt: bool = False,
                             stream: int = 0) -> None:

@@ -58,7 +58,7 @@ void k_frame(const FrameDesc *__restrict__ fd, const uint8_t *__restrict__ blob,
     // an inner entry's data chunk reaches the device window by window)
     const uint32_t tlen = (d.pad & 8) ? 0u : 4u;
     const uint32_t n = tlen + d.payload_len;                         // "FDAT" || payload  (payload_len <= 2^32 - 5 checked by the host)
-    const uint32_t ntile = (n + FR_TILE - 1) / FR_TILE;
+    const uint32_t ntile = (uint32_t)(((uint64_t)n + FR_TILE - 1) / FR_TILE);   // (n reaches 2^32 - 1)
     const uint32_t pad = ntile * FR_TILE - n;                        // zero bytes put in front, < FR_TILE
     const int64_t base = (int64_t)pay - (int64_t)tlen - (int64_t)pad; // dst offset of message position 0 (may be negative)
     const uint32_t a = (uint32_t)(base & 15);                        // two's complement: correct for negative base too

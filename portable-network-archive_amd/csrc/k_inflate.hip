@@ -106,7 +106,9 @@ __device__ uint32_t if_build(const uint8_t *lens, uint32_t nsym, uint32_t root, 
 // CHUNK MODE (chunks != nullptr; round 4): one LARGE stream of a foreign encoder -- no sync-flush markers to cut it at, one wave's walk is a few MiB/s -- is walked by
 // one wave per CHUNK: [start_bit, end_bit) of the stream's bits, block starts that k_ispec found by testing every bit position for a well-formed dynamic block header
 // (complete code-length code, complete literal / length and distance codes, an end-of-block code: the chance of a false one is negligible, and a false one breaks the
-// chain -- a chunk must end exactly where the next begins -- which sends the stream to the serial walk).  The records need no window (matches are only recorded), so a
+// chain -- a chunk must end exactly where the next begins -- which sends the stream to the serial walk), or a stored block (k_ispec's second trial; a chunk may end
+// anywhere in the zero bits in front of such a start's LEN).  Stream positions are 64-bit, the reader's are 32-bit from the chunk's first word, so a stream of any
+// length splits as long as no chunk needs more than 4 GiB of it.  The records need no window (matches are only recorded), so a
 // chunk starts from nothing.  Two passes: COUNT (sizes of every chunk's literals, records and output), then -- prefix sums on the host -- EMIT into the stream's regions,
 // one ZBlock per chunk; k_zexec_par executes them.
 struct ISChunk {
@@ -135,32 +137,40 @@ void k_inflate(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint
     if (!chunks && mode && IF_U(mode[f]) != 1u) return;                    // lane-per-piece decode (or the chunk mode) took this stream (VM_SERIAL = 1)
     const uint64_t src_off = (uint64_t)IF_U((uint32_t)frames[f].src_off) | ((uint64_t)IF_U((uint32_t)(frames[f].src_off >> 32)) << 32);
     const uint64_t dst_off = (uint64_t)IF_U((uint32_t)frames[f].dst_off) | ((uint64_t)IF_U((uint32_t)(frames[f].dst_off >> 32)) << 32);
-    if (IF_U((uint32_t)(frames[f].src_len >> 32)) | (chunks ? 0u : IF_U((uint32_t)(frames[f].dst_len >> 32)))) {      // this walk counts in 32 bits: streams of 4 GiB and more are decoded by pieces, in chunks
-                                                                                                                           // (whose output positions are 64-bit: only the COMPRESSED bytes must fit 32 bits there) or not at all
+    if (!chunks && IF_U((uint32_t)(frames[f].src_len >> 32)) | IF_U((uint32_t)(frames[f].dst_len >> 32))) {   // the whole-stream walk counts in 32 bits: streams of 4 GiB and more are decoded
+                                                                                                               // by pieces or in chunks (64-bit output positions, reader rebased per chunk) or not at all
         if (l0) { frames[f].status = IF_UNSUPPORTED; fx[f].nblk = 0; }
         return;
     }
-    const uint32_t src_len = IF_U((uint32_t)frames[f].src_len);
+    const uint64_t src_len = (uint64_t)IF_U((uint32_t)frames[f].src_len) | ((uint64_t)IF_U((uint32_t)(frames[f].src_len >> 32)) << 32);
     const uint64_t dst_len = (uint64_t)IF_U((uint32_t)frames[f].dst_len) | ((uint64_t)IF_U((uint32_t)(frames[f].dst_len >> 32)) << 32);
     const bool open = (IF_U(frames[f].out_len) & ZF_OPEN) != 0;        // dst_len is a capacity: the stream's size is reported back
     const uint64_t seq_base = (uint64_t)IF_U((uint32_t)fx[f].seq_base) | ((uint64_t)IF_U((uint32_t)(fx[f].seq_base >> 32)) << 32);
     const uint32_t seq_cap = IF_U(fx[f].seq_cap), blk_base = IF_U(fx[f].blk_base), blk_cap = IF_U(fx[f].blk_cap);
     const uint64_t a0 = src_off & ~(uint64_t)3;
     const uint32_t mis = (uint32_t)(src_off & 3);
-    const uint64_t end_bytes = (uint64_t)mis + src_len;                    // stream end, relative to a0
-    const uint32_t nwords = (uint32_t)((end_bytes + 3) >> 2);
-    const uint32_t *gsrc = (const uint32_t *)(src + a0);
-    auto gload = [&](uint32_t w) -> uint32_t { return w < nwords ? gsrc[w] : 0u; };
     auto u64u = [&](const uint64_t &v) -> uint64_t { return (uint64_t)IF_U((uint32_t)v) | ((uint64_t)IF_U((uint32_t)(v >> 32)) << 32); };
     const uint64_t sbit = chunks ? u64u(chunks[ck].start_bit) : 0, ebit = chunks ? u64u(chunks[ck].end_bit) : ~0ull;
     const uint64_t lit_base = chunks ? u64u(chunks[ck].lit_base) : 0, rec_base = chunks ? u64u(chunks[ck].rec_base) : 0, out_base = chunks ? u64u(chunks[ck].out_base) : 0;
     uint8_t *lit_out = lit_scratch + dst_off + lit_base;
     uint64_t *rec_out = seqs + seq_base + rec_base;
 
-    // the reader starts at bit `sbit` of the stream (0 but for the chunks of a large stream)
-    const uint64_t abit = (uint64_t)mis * 8 + sbit;
-    const uint32_t wi0 = (uint32_t)(abit >> 5), boff = (uint32_t)abit & 31u;
-    uint32_t rbase = wi0 & ~(IF_HALF - 1);
+    // The reader starts at bit `sbit` of the stream (0 but for the chunks of a large stream).  Its word and byte positions are 32-bit and count from the
+    // aligned word that holds that bit (gsrc): a chunk of a stream of any length reads up to IF_REACH bytes from there (what the whole-stream walk reads of a
+    // stream of 2^32 - 1 bytes behind a misaligned start); a walk that needs more (a chunk of more than 4 GiB: no block start inside it was found) stops with
+    // IF_UNSUPPORTED.  org = the stream bit position of gsrc's first bit (mod 2^64).
+    constexpr uint64_t IF_REACH = (1ull << 32) + 2;
+    const uint64_t abit = (uint64_t)mis * 8 + sbit, wb = abit >> 5;
+    const uint64_t org = wb * 32 - (uint64_t)mis * 8;
+    const uint64_t end_full = (uint64_t)mis + src_len - wb * 4;            // stream end, relative to gsrc
+    const bool reach = end_full > IF_REACH;
+    const uint64_t end_bytes = reach ? IF_REACH : end_full;
+    const uint32_t nwords = (uint32_t)((end_bytes + 3) >> 2);
+    const uint32_t *gsrc = (const uint32_t *)(src + a0) + wb;
+    const uint32_t past_end = reach ? IF_UNSUPPORTED : IF_CORRUPT;        // the verdict on a walk that runs past end_bytes
+    auto gload = [&](uint32_t w) -> uint32_t { return w < nwords ? gsrc[w] : 0u; };
+    const uint32_t wi0 = 0, boff = (uint32_t)abit & 31u;
+    uint32_t rbase = 0;
     uint32_t pend[4];
 #pragma unroll
     for (int k = 0; k < 8; k++) { const uint32_t w = rbase + lane + 64 * (uint32_t)k; ring[w & (IF_RING - 1)] = gload(w); }
@@ -171,6 +181,7 @@ void k_inflate(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint
     uint32_t state = sbit ? IST_BLOCK : IST_ZHEAD, last = 0, ll = 0, status = IF_OK, adler = 0;
     uint32_t nseq_tot = 0, nlit_tot = 0;
     uint64_t mtot = 0;                                                      // bytes produced by matches
+    uint64_t end_at = ~0ull;                                                // chunk mode: the chunk ended at the next chunk's stored-block start (ebit)
     __builtin_amdgcn_wave_barrier();
 
     auto refill = [&]() { if (bitcnt <= 32) { bitbuf |= (uint64_t)IF_U(ring[wi & (IF_RING - 1)]) << bitcnt; bitcnt += 32; wi++; } };
@@ -190,7 +201,16 @@ void k_inflate(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint
         state = IF_U(state); last = IF_U(last); ll = IF_U(ll); status = IF_U(status); nseq_tot = IF_U(nseq_tot); nlit_tot = IF_U(nlit_tot); rbase = IF_U(rbase);
         mtot = (uint64_t)IF_U((uint32_t)mtot) | ((uint64_t)IF_U((uint32_t)(mtot >> 32)) << 32);
         if (chunks && state == IST_BLOCK) {                                 // a chunk ends at the block start that is the next chunk's first bit
-            const uint64_t bp = (uint64_t)wi * 32 - bitcnt - (uint64_t)mis * 8;
+            const uint64_t bp = org + (uint64_t)wi * 32 - bitcnt;
+            if (bp != ebit && ebit != ~0ull && ((bp + 10) >> 3) == ((ebit + 10) >> 3)) {
+                // The next chunk starts at a stored block (k_ispec: the lowest bit from which header and padding are zero up to its LEN at byte q): a header at
+                // bp reaches the same LEN when the bits from bp on are zero as well -- then this is that block's start, whichever of the two positions it is.
+                const uint64_t q = (ebit + 10) >> 3, lo = bp < ebit ? bp : ebit;
+                const uint8_t *sb = src + src_off;
+                const uint32_t two = ((uint32_t)sb[q - 1] << 8) | (q >= 2 ? (uint32_t)sb[q - 2] : 0u);   // bits 8q - 16 .. 8q - 1
+                const uint32_t k = (uint32_t)(lo - (8 * q - 16));                                         // 6 .. 13
+                if (IF_U((two >> k) == 0u)) { end_at = ebit; break; }
+            }
             if (bp > ebit) status = IF_CHAIN;
             if (bp >= ebit) break;
         }
@@ -326,13 +346,13 @@ void k_inflate(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint
             nseq_tot += nq; nlit_tot += nl;
         }
         // every consumed bit must lie inside the stream
-        if (status == IF_OK && (uint64_t)wi * 32 - bitcnt > end_bytes * 8) status = IF_CORRUPT;
+        if (status == IF_OK && (uint64_t)wi * 32 - bitcnt > end_bytes * 8) status = past_end;
         if (status != IF_OK) break;
         if (act == IACT_STORED) {
             const uint32_t len = p0;
-            if ((uint64_t)p1 + len > end_bytes) { status = IF_CORRUPT; break; }
+            if ((uint64_t)p1 + len > end_bytes) { status = past_end; break; }
             if (out_base + nlit_tot + len + mtot > dst_len) { status = IF_DSTSIZE; break; }
-            const uint8_t *sp = src + a0 + p1;
+            const uint8_t *sp = (const uint8_t *)gsrc + p1;
             uint8_t *dp = lit_out + nlit_tot;
             if (emit_on) for (uint32_t i = lane * 8; i < len; i += 512) {
                 if (i + 8 <= len) *(if_u64u *)(dp + i) = *(const if_u64u *)(sp + i);
@@ -372,10 +392,11 @@ void k_inflate(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint
     const uint64_t total = (uint64_t)nlit_tot + mtot;
     if (chunks) {
         if (status == IF_OK && state != IST_DONE && state != IST_BLOCK) status = IF_CORRUPT;
+        if (status == IF_OK && state == IST_DONE && ebit != ~0ull) status = IF_CHAIN;   // the stream ended in this chunk: the next chunk's start was not a block start
         if (status == IF_OK && total > 0xFFFFFFFFull) status = IF_UNSUPPORTED;
         if (l0) {
             ISChunk &cr = chunks[ck];
-            cr.end_found = (uint64_t)wi * 32 - bitcnt - (uint64_t)mis * 8; cr.mtot = mtot; cr.nlit = nlit_tot; cr.nrec = nseq_tot; cr.status = status; cr.adler = adler;
+            cr.end_found = end_at != ~0ull ? end_at : org + (uint64_t)wi * 32 - bitcnt; cr.mtot = mtot; cr.nlit = nlit_tot; cr.nrec = nseq_tot; cr.status = status; cr.adler = adler;
             if (emit && status == IF_OK && ck < blk_cap) {
                 ZBlock b;
                 b.body = 0; b.out_off = dst_off + out_base; b.seq_pos = seq_base + rec_base; b.size = 0; b.type = 2;
@@ -466,7 +487,8 @@ void launch_iadler(ZFrame *frames, const ZFrameX *fx, const ZBlock *blocks, uint
 // ------------------------------------------------------------------ k_ispec: block starts of a large foreign stream, by trial
 // One workgroup per chunk of `cbytes` compressed bytes: the first bit position in the chunk at which a DYNAMIC block with BFINAL = 0 can start -- BTYPE 2, HLIT / HDIST
 // in range, a complete code-length code, and the HLIT + HDIST lengths it codes forming complete literal / length and distance codes (or a single one-bit code, as
-// zlib's inflate_table accepts) with an end-of-block code.  256 bit positions per round, one per thread: the three-bit lengths' Kraft sum is the cheap filter (a few in
+// zlib's inflate_table accepts) with an end-of-block code -- or a STORED block with BFINAL = 0 (isp_stored_ok: what zlib and miniz_oxide write for incompressible
+// data, which has no dynamic headers to split at).  256 bit positions per round, one per thread: the three-bit lengths' Kraft sum is the cheap filter (a few in
 // a thousand positions pass), the lengths are then decoded canonically on the lane (puff's scheme: counts per length and the symbols in canonical order, held in
 // registers).  start[c] = the bit position relative to the stream, or ~0 (none: the chunk before simply runs on through this one).
 __device__ __forceinline__ uint64_t isp_bits(const uint8_t *s, uint64_t bit) { return *(const if_u64u *)(s + (bit >> 3)) >> (bit & 7); }     // >= 57 valid bits
@@ -529,6 +551,32 @@ __device__ bool isp_header_ok(const uint8_t *s, uint64_t p, uint64_t nbits) {
     if (kd != 32768u && !(kd < 32768u && maxd <= 1)) return false;
     return true;
 }
+// A STORED block with BFINAL = 0 whose header starts at bit p: its three header bits sit somewhere in the 8 bit positions in front of the byte-aligned LEN at byte
+// q = (p + 10) / 8 (8q - 10 <= p <= 8q - 3); with zero padding (what every encoder writes) the header's own position is ambiguous, so ONE start per stored block is
+// canonical: the lowest p from which all bits up to byte q are zero.  (k_inflate's chunk mode accepts a walk that ends anywhere in that run as ending there.)
+// LEN / NLEN must be complements and the stored bytes must be followed by a plausible block: another stored header (zero padding; a final one ends exactly in
+// front of the Adler-32 trailer), a dynamic header (isp_header_ok), or the stream's last 64 bytes, too short to tell -- but not the trailer alone (a FINAL stored
+// header, 0x01, looks like a non-final one a bit further on).  A false start is repaired like any other.
+__device__ bool isp_stored_ok(const uint8_t *s, uint64_t p, uint64_t src_len) {
+    const uint64_t q = (p + 10) >> 3;
+    if (q < 2 || q + 6 > src_len) return false;
+    const uint64_t w = *(const if_u64u *)(s + q - 2);                            // bits 8q - 16 .. 8q + 47
+    const uint32_t o = (uint32_t)(p - 8 * (q - 2));                               // 6 .. 13
+    if (((uint32_t)w & 0xFFFFu) >> o) return false;                               // header bits and padding: zero up to byte q
+    if (o > 6 && !((w >> (o - 1)) & 1u)) return false;                            // not the lowest such position
+    const uint32_t len = (uint32_t)(w >> 16) & 0xFFFFu, nlen = (uint32_t)(w >> 32) & 0xFFFFu;
+    if ((len ^ nlen) != 0xFFFFu) return false;
+    const uint64_t r = q + 4 + len;                                               // the next block's first byte
+    if (r + 4 >= src_len) return false;                                           // (only the trailer behind it: the final block, BFINAL read one bit too late)
+    if (r + 64 > src_len) return true;
+    const uint64_t f = isp_bits(s, 8 * r);
+    if ((f & 0xFEu) == 0) {                                                       // stored: BTYPE 00, zero padding
+        const uint32_t l2 = (uint32_t)(f >> 8) & 0xFFFFu, n2 = (uint32_t)(f >> 24) & 0xFFFFu;
+        if ((l2 ^ n2) != 0xFFFFu) return false;
+        return (f & 1u) ? r + 5 + l2 + 4 == src_len : r + 5 + l2 + 4 <= src_len;
+    }
+    return isp_header_ok(s, 8 * r, src_len * 8);
+}
 __global__ __launch_bounds__(256)
 void k_ispec(const uint8_t *__restrict__ src, uint64_t src_off, uint64_t src_len, uint32_t cbytes, uint32_t nchunks, uint64_t *__restrict__ start) {
     __shared__ unsigned long long best;
@@ -541,7 +589,7 @@ void k_ispec(const uint8_t *__restrict__ src, uint64_t src_off, uint64_t src_len
     const uint64_t nbits = src_len * 8, b0 = (uint64_t)c * cbytes * 8, b1 = (uint64_t)(c + 1) * cbytes * 8 < nbits ? (uint64_t)(c + 1) * cbytes * 8 : nbits;
     for (uint64_t base = b0; base < b1; base += 256) {
         const uint64_t p = base + tid;
-        if (p < b1 && isp_header_ok(s, p, nbits)) atomicMin(&best, (unsigned long long)p);
+        if (p < b1 && (isp_header_ok(s, p, nbits) || isp_stored_ok(s, p, src_len))) atomicMin(&best, (unsigned long long)p);
         __syncthreads();
         if (best != ~0ull) break;
         __syncthreads();

@@ -82,6 +82,16 @@ static int count_chunks(pna_gpu_ctx *c, uint32_t f, std::vector<ISChunkH> &ch, I
     *ok = true;
     return PNA_OK;
 }
+// Why a stream was not decoded in chunks; corrupt: a chunk's walk found damage (and no false start explains it).  A stream of 4 GiB and more has no other way:
+// it is refused with this (a stream of fixed-Huffman blocks only has no block start the trial can find: PNA_E_UNSUPPORTED).
+struct SpecWhy { std::string text = "too few block starts found"; bool corrupt = false; };
+static int big_unsplit(pna_gpu_ctx *c, uint64_t src_len, const SpecWhy &w) {
+    char msg[384];
+    if (w.corrupt) { snprintf(msg, sizeof msg, "corrupt zlib stream of %llu compressed bytes (decoding it in chunks: %s)", (unsigned long long)src_len, w.text.c_str()); return fail(c, PNA_E_INVAL, msg); }
+    snprintf(msg, sizeof msg, "zlib stream of %llu compressed bytes not decoded: a stream of 4 GiB and more is decoded in chunks between dynamic or stored block starts, and this one "
+             "does not split (%s) -- a stream of fixed-Huffman blocks only has no start to split at", (unsigned long long)src_len, w.text.c_str());
+    return fail(c, PNA_E_UNSUPPORTED, msg);
+}
 // block starts of a stream by trial (k_ispec): one chunk per start found, each running up to the next (nch chunks of SPEC_CHUNK bytes searched)
 static int find_chunks(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, uint32_t nch, uint64_t *d_start, std::vector<ISChunkH> &ch, hipStream_t st) {
     std::vector<uint64_t> start(nch);
@@ -97,9 +107,9 @@ static int find_chunks(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint
 // A LARGE stream the lane-per-piece decoder cannot take (a foreign encoder's: no sync flush behind every 128 KiB -- what the reference itself writes for a large
 // deflate entry): block starts found by trial (k_ispec), one wave per chunk between two of them (k_inflate's chunk mode: COUNT, prefix sums here, EMIT), one ZBlock per
 // chunk.  *ok = false: something did not fit (no chunk starts found, a chunk's walk did not end where the next begins, sizes that do not add up) -- the serial walk
-// takes the stream, nothing is lost but time.  The records are executed by k_zexec_par afterwards (the caller).
+// takes the stream, nothing is lost but time; a stream of 4 GiB and more is refused then (big_unsplit).  The records are executed by k_zexec_par afterwards (the caller).
 static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, const ZFrameX &x, const void *d_src, hipStream_t st, uint32_t *nblk_out, bool *ok,
-                               bool open, uint64_t *out_len) {
+                               bool open, uint64_t *out_len, SpecWhy *reason) {
     *ok = false;
     const uint32_t nch = (uint32_t)((fr.src_len + SPEC_CHUNK - 1) / SPEC_CHUNK);
     if (nch < 4 || nch > x.blk_cap) return PNA_OK;
@@ -109,11 +119,14 @@ static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, con
     std::vector<ISChunkH> ch;
     int rc = find_chunks(c, d_src, fr.src_off, fr.src_len, nch, d_start, ch, st); if (rc) return rc;
     uint32_t m = (uint32_t)ch.size();
-    auto why = [&](const char *what, uint64_t a, uint64_t b) { if (c->tun.trace) fprintf(stderr, "[pna inflate] stream %u of %llu B not decoded in chunks: %s (%llu, %llu)\n", f, (unsigned long long)fr.src_len, what, (unsigned long long)a, (unsigned long long)b); };
-    if (m < 4) { why("too few block starts found", m, nch); return PNA_OK; }                                      // (stored data, or blocks of more than a chunk each: not worth the two passes)
+    auto why = [&](const char *what, uint64_t a, uint64_t b) {
+        char t[192]; snprintf(t, sizeof t, "%s (%llu, %llu)", what, (unsigned long long)a, (unsigned long long)b); reason->text = t;
+        if (c->tun.trace) fprintf(stderr, "[pna inflate] stream %u of %llu B not decoded in chunks: %s\n", f, (unsigned long long)fr.src_len, t);
+    };
+    if (m < 4) { why("too few block starts found", m, nch); return PNA_OK; }                                      // (fixed-code blocks, or blocks of more than a chunk each: not worth the two passes)
     bool counted = false;
     rc = count_chunks(c, f, ch, d_chunks, d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p, st, why, &counted); if (rc) return rc;
-    if (!counted) return PNA_OK;
+    if (!counted) { for (const ISChunkH &h : ch) reason->corrupt |= h.status == 1u; return PNA_OK; }
     m = (uint32_t)ch.size();
     uint64_t lit = 0, out = 0, rec = 0;
     for (uint32_t k = 0; k < m; k++) { const ISChunkH &h = ch[k]; lit += h.nlit; out += (uint64_t)h.nlit + h.mtot; rec += h.nrec; }
@@ -124,7 +137,7 @@ static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, con
     lit = out = rec = 0;
     for (uint32_t k = 0; k < m; k++) { ISChunkH &h = ch[k]; h.lit_base = lit; h.out_base = out; h.rec_base = rec; lit += h.nlit; out += (uint64_t)h.nlit + h.mtot; rec += h.nrec; }
     rc = run_chunks(c, f, ch, std::vector<uint32_t>(), 1, d_chunks, d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p, st); if (rc) return rc;
-    for (uint32_t k = 0; k < m; k++) if (ch[k].status) { why("a chunk's second walk failed: chunk, status", k, ch[k].status); return PNA_OK; }
+    for (uint32_t k = 0; k < m; k++) if (ch[k].status) { why("a chunk's second walk failed: chunk, status", k, ch[k].status); reason->corrupt = ch[k].status == 1u; return PNA_OK; }
     *nblk_out = m; *ok = true;
     return PNA_OK;
 }
@@ -169,8 +182,10 @@ static int inflate_batch_device(pna_gpu_ctx *c, size_t n, const void *d_src, con
     // a handful of pieces is served better by the wave-per-stream walk (a lane needs ~110 ms for a 128 KiB piece, however few there are)
     if (tot_pieces < 1024) lanes = false;
     for (size_t i = 0; i < n; i++) {
-        // streams of 4 GiB and more: decoded by pieces (this library's layout: a sync flush behind every 128 KiB); the wave-per-stream walk counts in 32 bits
-        if ((raw_len[i] > 0xFFFFFFFFull || src_len[i] > 0xFFFFFFFFull) && !lanes) return fail(c, PNA_E_UNSUPPORTED, "zlib streams of 4 GiB and more are decoded by sync-flush delimited pieces only");
+        // (open: raw_len is the room, the size comes out of the count; the stream must be worth it by its compressed size then)
+        const bool is_cand = spec_min && (open ? src_len[i] >= spec_min / 4 : raw_len[i] >= spec_min) && src_len[i] >= 8ull * SPEC_CHUNK;   // (output of any size: the executor works in windows)
+        // streams of 4 GiB and more: decoded by pieces (this library's layout: a sync flush behind every 128 KiB) or in chunks; the wave-per-stream walk counts in 32 bits
+        if ((raw_len[i] > 0xFFFFFFFFull || src_len[i] > 0xFFFFFFFFull) && !lanes && !is_cand) return fail(c, PNA_E_UNSUPPORTED, "zlib streams of 4 GiB and more are decoded by sync-flush delimited pieces or in chunks only");
         frs[i] = ZFrame{src_off[i], dst_off[i], src_len[i], raw_len[i], 0, open ? ZF_OPEN : 0u};   // open: raw_len is a capacity
         ZFrameX &x = fxs[i];
         const uint64_t P = lanes ? npc[i] : 1;
@@ -185,8 +200,7 @@ static int inflate_batch_device(pna_gpu_ctx *c, size_t n, const void *d_src, con
         cbase[i] = (uint32_t)pieces;
         pieces += (raw_len[i] + 65535) >> 16;
         if (pieces > 0xFFFFFFF0ull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
-        // (open: raw_len is the room, the size comes out of the count; the stream must be worth it by its compressed size then)
-        if (spec_min && (open ? src_len[i] >= spec_min / 4 : raw_len[i] >= spec_min) && src_len[i] < (1ull << 32) && src_len[i] >= 8ull * SPEC_CHUNK) cand.push_back((uint32_t)i);   // (output of any size: the executor works in windows)
+        if (is_cand) cand.push_back((uint32_t)i);
     }
     cbase[n] = (uint32_t)pieces;
     for (uint32_t i : cand) { cand_base.push_back(nblk); nblk += (src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK; if (nblk > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call"); }
@@ -214,9 +228,10 @@ static int inflate_batch_device(pna_gpu_ctx *c, size_t n, const void *d_src, con
             ZFrameX xs = fxs[i];
             xs.blk_base = (uint32_t)cand_base[k]; xs.blk_cap = (uint32_t)((src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK); xs.nblk = 0; xs.pad = 0;
             HIPCHK(c, hipMemcpyAsync((ZFrameX *)c->z_fx.p + i, &xs, sizeof xs, hipMemcpyHostToDevice, st));
-            bool ok = false; uint32_t m = 0; uint64_t olen = 0;
-            const int rcs = inflate_spec_stream(c, i, frs[i], xs, d_src, st, &m, &ok, open, &olen);
+            bool ok = false; uint32_t m = 0; uint64_t olen = 0; SpecWhy reason;
+            const int rcs = inflate_spec_stream(c, i, frs[i], xs, d_src, st, &m, &ok, open, &olen, &reason);
             if (rcs) return rcs;
+            if (!ok && (src_len[i] > 0xFFFFFFFFull || raw_len[i] > 0xFFFFFFFFull)) return big_unsplit(c, src_len[i], reason);   // (the serial walk counts in 32 bits)
             static const uint32_t three = 3u;                           // (not 1: the serial walk leaves the stream alone)
             if (ok) {
                 xs.nblk = m; xs.pad = 1; HIPCHK(c, hipMemcpyAsync((uint32_t *)c->z_mode.p + i, &three, 4, hipMemcpyHostToDevice, st));
@@ -289,10 +304,10 @@ extern "C" int pna_gpu_inflate_open_device(pna_gpu_ctx *c, const void *d_src, ui
 // ---------------------------------------------------------------------------------------------------------
 // The decoded size of one stream whose size is recorded nowhere, measured before it is decoded: no output buffer, scratch by the compressed length.
 // zlib: k_inflate's chunk mode in its count pass (emit = 0: nothing but the chunk descriptors is written) between block starts found by trial (k_ispec --
-// this library's sync-flush pieces and a foreign encoder's dynamic blocks alike), one wave per chunk, false starts repaired; one wave over the whole stream
-// when there are fewer than four starts (small streams, stored or fixed-code blocks) or the chain does not hold.  The count is exact.
+// this library's sync-flush pieces, a foreign encoder's dynamic and stored blocks alike), one wave per chunk, false starts repaired; one wave over the whole
+// stream when there are fewer than four starts (small streams, fixed-code blocks) or the chain does not hold -- below 4 GiB of compressed bytes: a longer
+// stream that does not split is refused (big_unsplit).  The count is exact.
 static int inflate_measure(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, hipStream_t st) {
-    if (src_len > 0xFFFFFFFFull) return fail(c, PNA_E_UNSUPPORTED, "zlib streams of 4 GiB of compressed bytes and more are not measured");
     const uint32_t nch = src_len >= 8ull * SPEC_CHUNK ? (uint32_t)((src_len + SPEC_CHUNK - 1) / SPEC_CHUNK) : 1u;
     if (c->z_spec.ensure((size_t)nch * (8 + sizeof(ISChunkH)) + 64) || c->z_frames.ensure(sizeof(ZFrame)) || c->z_fx.ensure(sizeof(ZFrameX)))
         return fail(c, PNA_E_NOMEM, "measurement workspace");
@@ -307,9 +322,17 @@ static int inflate_measure(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, 
     std::vector<ISChunkH> ch;
     int rc = PNA_OK;
     if (nch >= 8) { rc = find_chunks(c, d_src, src_off, src_len, nch, d_start, ch, st); if (rc) return rc; }
-    auto why = [&](const char *what, uint64_t a, uint64_t b) { if (c->tun.trace) fprintf(stderr, "[pna inflate] stream of %llu B measured by one wave: %s (%llu, %llu)\n", (unsigned long long)src_len, what, (unsigned long long)a, (unsigned long long)b); };
+    SpecWhy w;
+    auto why = [&](const char *what, uint64_t a, uint64_t b) {
+        char t[192]; snprintf(t, sizeof t, "%s (%llu, %llu)", what, (unsigned long long)a, (unsigned long long)b); w.text = t;
+        if (c->tun.trace) fprintf(stderr, "[pna inflate] stream of %llu B measured by one wave: %s\n", (unsigned long long)src_len, t);
+    };
     bool ok = false;
     if (ch.size() >= 4) { rc = count_chunks(c, 0, ch, d_chunks, d_src, (ZBlock *)none, none, (uint64_t *)none, st, why, &ok); if (rc) return rc; }
+    if (!ok && src_len > 0xFFFFFFFFull) {                                 // (the one-wave walk reads 32 bits' worth of a stream)
+        for (const ISChunkH &h : ch) w.corrupt |= h.status == 1u;
+        return big_unsplit(c, src_len, w);
+    }
     if (!ok) {                                                            // one wave over the whole stream: its verdict stands
         ch.assign(1, ISChunkH{}); ch[0].end_bit = ~0ull;
         rc = run_chunks(c, 0, ch, std::vector<uint32_t>(), 0, d_chunks, d_src, (ZBlock *)none, none, (uint64_t *)none, st); if (rc) return rc;

@@ -142,7 +142,7 @@ static int walk_archive(pna_gpu_ctx *c, const uint8_t *a, size_t archive_len, st
         const int r = next_chunk(a, archive_len, pos, ch);          // (pos moves behind the chunk)
         if (r) return fail(c, PNA_E_INVAL, r == CHUNK_SHORT_HEADER ? "truncated chunk header" : "truncated chunk body");
         const bool is_fdat = memcmp(ch.type, "FDAT", 4) == 0, is_sdat = memcmp(ch.type, "SDAT", 4) == 0;
-        if (is_fdat || is_sdat) { if (ch.len >= 0xFFFFFFF0u) return fail(c, PNA_E_INVAL, "data chunk too long"); (is_fdat ? dchunks : schunks).push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
+        if (is_fdat || is_sdat) { if (ch.len > 0xFFFFFFFBu) return fail(c, PNA_E_INVAL, "data chunk too long"); (is_fdat ? dchunks : schunks).push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
         else if (!chunk_crc_ok(ch)) return fail(c, PNA_E_INVAL, "chunk CRC mismatch");
         if (!seen_ahed) {
             if (memcmp(ch.type, "AHED", 4) != 0 || ch.len != 8 || ch.data[0] != 0) return fail(c, PNA_E_INVAL, "first chunk must be AHED (major version 0)");
@@ -440,7 +440,7 @@ static int walk_solid(pna_gpu_ctx *c, const XSolid &so, std::vector<uint8_t> &pl
         const int r = next_chunk(plain.data(), plain.size(), q, ch);
         if (r) return fail(c, PNA_E_INVAL, r == CHUNK_SHORT_HEADER ? "solid stream: truncated chunk header" : "solid stream: truncated chunk body");
         const bool fd = memcmp(ch.type, "FDAT", 4) == 0;
-        if (fd) { if (ch.len >= 0xFFFFFFF0u) return fail(c, PNA_E_INVAL, "data chunk too long"); ichunks.push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
+        if (fd) { if (ch.len > 0xFFFFFFFBu) return fail(c, PNA_E_INVAL, "data chunk too long"); ichunks.push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
         else if (!chunk_crc_ok(ch)) return fail(c, PNA_E_INVAL, "solid stream: chunk CRC mismatch");
         if (memcmp(ch.type, "FHED", 4) == 0) {
             if (in_i || ch.len < 6 || ch.data[0] != 0 || ch.data[1] != 0) return fail(c, PNA_E_INVAL, "solid stream: bad entry header");
