@@ -344,7 +344,7 @@ int  pna_gpu_inflate_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t s
  * stored blocks to split them at (fixed-Huffman blocks only). */
 int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, int *exact, void *hip_stream);
 
-/* Read-side driver for archives in host memory (normal and solid entries): `pna extract` / `pna verify` (cli/src/command/extract.rs:594-640,
+/* Read-side driver for archives in host memory (normal and solid entries): `pna extract` (verify: pna_gpu_verify_archive_host below) (cli/src/command/extract.rs:594-640,
  * verify.rs:140-188; Archive::read_header + entries, lib/src/archive/read.rs:22-66; read_chunk's mandatory CRC check, lib/src/io.rs:117-149;
  * decrypt_reader / decompress_reader, lib/src/entry/read.rs:59-104,171-190).  The chunk walk and the small chunks' CRCs are host work;
  * the FDAT CRC-32s, the gather of every entry's data pieces, AES decryption -- CTR, CBC (PKCS#7 checked), GCM STREAM (key confirmation,
@@ -363,6 +363,45 @@ int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uin
 typedef int (*pna_entry_fn)(void *user, size_t index, const char *name, int kind, const void *data, size_t len);
 int  pna_gpu_extract_archive_host(pna_gpu_ctx *ctx, const void *archive, size_t archive_len, const void *password, size_t password_len,
                                   pna_entry_fn cb, void *user);
+
+/* `pna experimental verify` (cli/src/command/verify.rs verify_archive): every entry checked, one verdict per entry, the walk goes on after damage.
+ * The read-side driver above in verdict mode: the same chunk walk, windows, CRC-32, AES and decoding kernels, but a failure marks the entries it
+ * concerns instead of ending the call -- per-chunk CRC verdicts, per-segment GCM tag verdicts and CBC padding verdicts are folded on the device
+ * (k_verdict) into one status word per entry, and the decoders report a status per stream.  No decoded byte of a normal entry goes to the host (a
+ * solid stream is still decoded into host memory, as extract does, to walk its inner entries).
+ *   parts / part_len / n_parts: the archive, or the parts of a split archive in order (what pna_join_parts takes), read in place; an entry may span parts.
+ *   vflags: PNA_VERIFY_FAST = chunk structure and CRC-32 only (no key derivation, no decryption, no decoding; every intact entry is OK, encrypted ones too).
+ *   cb: one record per entry in archive order.  Solid blocks: one record per inner entry in deep mode; one record for the whole block (kind
+ *     PNA_VERIFY_KIND_SOLID) in fast mode, when it is encrypted and no password is given, or when it fails -- unlike the reference, which counts the
+ *     inner entries it read before the failure as ok.  `name` is the sanitised path extract hands out; NULL when the FHED is unreadable (a bad CRC, not
+ *     UTF-8).  A chunk that fails its CRC is consumed (its length field trusted, as io::read_chunk does) and the walk resumes behind it; a bad FHED makes
+ *     the chunks up to the next FEND / SEND one PNA_VERIFY_KIND_BROKEN record.  Each broken entry is its own record (the reference merges neighbouring
+ *     failures into one).  A wrong fSIZ is PNA_VERIFY_SIZE_HINT on an OK record: a stream that fails against its fSIZ is decoded once more without it.
+ *   Without a password, encrypted entries are PNA_VERIFY_SKIPPED; with one, every PHSF string is derived once per call.
+ * Returns PNA_OK when the walk reached AEND, even when entries failed (summary->failed says so); PNA_E_INVAL with summary->broken = 1 when it could
+ * not go on (a truncated chunk, no AEND, a part missing) -- every entry before the break has its record; HIP, allocation and callback errors
+ * (PNA_E_SINK) as usual.  A zlib stream of 4 GiB and more that cannot be split into chunks still fails the call, as in extract. */
+#define PNA_VERIFY_FAST            1u   /* chunk structure + CRC-32 only: no key derivation, no decryption, no decoding */
+/* status of one record */
+#define PNA_VERIFY_OK              0
+#define PNA_VERIFY_SKIPPED         1    /* encrypted, no password given */
+#define PNA_VERIFY_BAD_CRC         2    /* a chunk of the entry failed its CRC-32 */
+#define PNA_VERIFY_BAD_STRUCTURE   3    /* bad header chunk, unknown critical chunk, entry without FHED, ... */
+#define PNA_VERIFY_BAD_AUTH        4    /* GCM: key confirmation or a segment tag */
+#define PNA_VERIFY_BAD_DECRYPT     5    /* CBC length / PKCS#7 padding */
+#define PNA_VERIFY_BAD_STREAM      6    /* corrupt zstd / zlib stream, content checksum, Adler-32 */
+#define PNA_VERIFY_UNSUPPORTED     7    /* xz, Camellia, ...: what this build does not decode */
+/* flags of one record */
+#define PNA_VERIFY_SIZE_HINT       1u   /* fSIZ present and != the decoded size (a warning; status stays OK) */
+#define PNA_VERIFY_UNAUTHENTICATED 2u   /* AES CBC / CTR: a wrong password cannot be told from damage (verify.rs is_unauthenticated) */
+#define PNA_VERIFY_KIND_SOLID  (-1)     /* record of a whole solid block (fast mode, skipped, or failed) */
+#define PNA_VERIFY_KIND_BROKEN (-2)     /* chunks that belong to no readable entry header */
+typedef struct { uint64_t total, ok, failed, skipped, unsupported; uint32_t unauthenticated_failure, broken; } pna_verify_summary;
+typedef int (*pna_verify_fn)(void *user, size_t index, const char *name /* NULL if unknown */, int kind, int status,
+                             uint32_t flags, uint64_t size /* decoded bytes; 0 in fast mode */, const char *detail);
+int  pna_gpu_verify_archive_host(pna_gpu_ctx *ctx, const void *const *parts, const size_t *part_len, size_t n_parts,
+                                 const void *password, size_t password_len, uint32_t vflags,
+                                 pna_verify_fn cb, void *user, pna_verify_summary *summary);
 
 /* pna_gpu_create_archive_host for ONE PART of an archive (PNA_PART_HEAD: signature + AHED first, PNA_PART_TAIL: AEND last): what
  * `pna append` writes behind the existing entries (PNA_PART_TAIL only) and `pna update` for the entries it re-creates (neither flag). */

@@ -100,6 +100,20 @@ SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctype
 PART_SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t)
 RAW_ENTRY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64)
 ENTRY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t)
+VERIFY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                             ctypes.c_uint64, ctypes.c_char_p)
+
+# pna_gpu_verify_archive_host (include/pna_gpu.h): flags, record statuses, record flags, record kinds
+VERIFY_FAST = 1
+VERIFY_OK, VERIFY_SKIPPED, VERIFY_BAD_CRC, VERIFY_BAD_STRUCTURE, VERIFY_BAD_AUTH, VERIFY_BAD_DECRYPT, VERIFY_BAD_STREAM, VERIFY_UNSUPPORTED = range(8)
+VERIFY_SIZE_HINT, VERIFY_UNAUTHENTICATED = 1, 2
+VERIFY_KIND_SOLID, VERIFY_KIND_BROKEN = -1, -2
+
+
+class VerifySummary(ctypes.Structure):
+    """pna_verify_summary (include/pna_gpu.h)."""
+    _fields_ = [("total", ctypes.c_uint64), ("ok", ctypes.c_uint64), ("failed", ctypes.c_uint64), ("skipped", ctypes.c_uint64),
+                ("unsupported", ctypes.c_uint64), ("unauthenticated_failure", ctypes.c_uint32), ("broken", ctypes.c_uint32)]
 
 _lib = None
 
@@ -125,6 +139,8 @@ EXPORTS = [
     # streaming entries, parts, append (include/pna_gpu.h)
     "pna_gpu_create_archive_part_host", "pna_gpu_create_archive_multi_host", "pna_gpu_append_archive_host", "pna_gpu_stream_entry_begin", "pna_gpu_stream_entry_write",
     "pna_gpu_stream_entry_finish", "pna_gpu_stream_entry_abort",
+    # pna verify (include/pna_gpu.h)
+    "pna_gpu_verify_archive_host",
 ]
 
 
@@ -243,6 +259,9 @@ def load_library() -> ctypes.CDLL:
                                                    ctypes.POINTER(sz), ctypes.POINTER(CipherStruct), ctypes.POINTER(MetaStruct), SINK_FN, vp]
     L.pna_gpu_extract_archive_host.restype = ctypes.c_int
     L.pna_gpu_extract_archive_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ENTRY_FN, vp]
+    L.pna_gpu_verify_archive_host.restype = ctypes.c_int
+    L.pna_gpu_verify_archive_host.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz, ctypes.c_char_p, sz, ctypes.c_uint32,
+                                              VERIFY_FN, vp, ctypes.POINTER(VerifySummary)]
     L.pna_gpu_open_size_device.restype = ctypes.c_int
     L.pna_gpu_open_size_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.POINTER(ctypes.c_int), vp]
     L.pna_gpu_inflate_open_device.restype = ctypes.c_int
@@ -972,6 +991,33 @@ def extract_archive(ctx: Context, archive: bytes, password: Optional[bytes] = No
     rc = ctx._L.pna_gpu_extract_archive_host(ctx._h, buf, len(buf), password, len(password) if password else 0, cb, None)
     ctx._check(rc)
     return out
+
+
+def verify_archive(ctx: Context, archive_or_parts, password: Optional[bytes] = None, fast: bool = False):
+    """`pna experimental verify` (pna_gpu_verify_archive_host): every entry checked on the device, the walk going on after damage.
+    `archive_or_parts`: one archive image, or the parts of a split archive in order.  Returns (records, summary): records are
+    (name or None, kind, status, flags, size, detail) in archive order (VERIFY_* constants), summary a dict of pna_verify_summary's
+    fields plus "rc" -- E_INVAL with summary["broken"] == 1 when the archive's structure broke off (the records before the break are
+    kept); any other error raises PnaGpuError."""
+    parts = [archive_or_parts] if isinstance(archive_or_parts, (bytes, bytearray, memoryview)) else list(archive_or_parts)
+    keep = [p if isinstance(p, bytes) else bytes(p) for p in parts]
+    n = len(keep)
+    arr = (ctypes.c_char_p * max(n, 1))(*keep)
+    lens = (ctypes.c_size_t * max(n, 1))(*[len(p) for p in keep])
+    recs = []
+
+    def _cb(_u, idx, name, kind, status, flags, size, detail):
+        recs.append((name.decode("utf-8") if name is not None else None, kind, status, flags, size, detail.decode() if detail else ""))
+        return 0
+    cb = VERIFY_FN(_cb)
+    summ = VerifySummary()
+    rc = ctx._L.pna_gpu_verify_archive_host(ctx._h, arr, lens, n, password, len(password) if password else 0,
+                                            VERIFY_FAST if fast else 0, cb, None, ctypes.byref(summ))
+    if rc != PNA_OK and not (rc == E_INVAL and summ.broken):
+        ctx._check(rc)
+    out = {f: getattr(summ, f) for f, _ in VerifySummary._fields_}
+    out["rc"] = rc
+    return recs, out
 
 
 def kdf_argon2(kind: int, password: bytes, salt: bytes, t_cost: int, m_cost_kib: int, lanes: int, key_len: int = 32) -> bytes:

@@ -198,6 +198,8 @@ __device__ G128 g_mul_bitwise(const G128 &x, G128 v) {                 // x * v,
 }
 __device__ __forceinline__ uint32_t be32(uint32_t v) { return __builtin_bswap32(v); }
 
+// PER (read side only): one verdict word per segment (bad[segment] = 1 when its tag does not match, 0 otherwise) instead of the shared counter
+template <bool PER = false>
 __global__ __launch_bounds__(GH_THREADS)
 void k_gcm_tag(const GcmEntry *__restrict__ ents, uint8_t *__restrict__ buf, const uint8_t *__restrict__ expect, uint32_t *__restrict__ bad) {
     __shared__ G128 sM[16];                  // nibble multiples of H^256: sM[8] = H^256, sM[4] = H^256 x, sM[2], sM[1], the rest by addition
@@ -272,16 +274,22 @@ void k_gcm_tag(const GcmEntry *__restrict__ ents, uint8_t *__restrict__ buf, con
         U4u t; t.x = be32(s.a ^ e.ej0[0]); t.y = be32(s.b ^ e.ej0[1]); t.z = be32(s.c ^ e.ej0[2]); t.w = be32(s.d ^ e.ej0[3]);
         if (expect) {                                                  // read side: the tag is compared, nothing is written
             const U4u x = *(const U4u *)(expect + 16 * (size_t)blockIdx.x);
-            if (((t.x ^ x.x) | (t.y ^ x.y) | (t.z ^ x.z) | (t.w ^ x.w)) != 0) atomicAdd(bad, 1u);
+            const bool mism = ((t.x ^ x.x) | (t.y ^ x.y) | (t.z ^ x.z) | (t.w ^ x.w)) != 0;
+            if (PER) bad[blockIdx.x] = mism ? 1u : 0u;
+            else if (mism) atomicAdd(bad, 1u);
         } else *(U4u *)(buf + e.off + e.len) = t;
     }
 }
 
 void launch_gcm_tag(const GcmEntry *ents, uint32_t n, uint8_t *buf, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_gcm_tag, dim3(n), dim3(GH_THREADS), 0, st, ents, buf, (const uint8_t *)nullptr, (uint32_t *)nullptr);
+    if (n) hipLaunchKernelGGL(k_gcm_tag<false>, dim3(n), dim3(GH_THREADS), 0, st, ents, buf, (const uint8_t *)nullptr, (uint32_t *)nullptr);
 }
 void launch_gcm_verify(const GcmEntry *ents, uint32_t n, const uint8_t *buf, const uint8_t *expect, uint32_t *bad, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_gcm_tag, dim3(n), dim3(GH_THREADS), 0, st, ents, const_cast<uint8_t *>(buf), expect, bad);
+    if (n) hipLaunchKernelGGL(k_gcm_tag<false>, dim3(n), dim3(GH_THREADS), 0, st, ents, const_cast<uint8_t *>(buf), expect, bad);
+}
+// `pna verify`: every segment's tag checked, one verdict word per segment in verdict[0 .. n)
+void launch_gcm_verdict(const GcmEntry *ents, uint32_t n, const uint8_t *buf, const uint8_t *expect, uint32_t *verdict, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_gcm_tag<true>, dim3(n), dim3(GH_THREADS), 0, st, ents, const_cast<uint8_t *>(buf), expect, verdict);
 }
 
 

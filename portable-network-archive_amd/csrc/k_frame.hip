@@ -35,6 +35,8 @@ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
     return p;
 }
 
+// PER (verify mode only): one verdict word per descriptor (verify[ent] = 1 on a mismatch, 0 otherwise) instead of the shared counter
+template <bool PER = false>
 __global__ __launch_bounds__(FR_THREADS)
 void k_frame(const FrameDesc *__restrict__ fd, const uint8_t *__restrict__ blob, const CrcTabs *__restrict__ ct,
              uint8_t *__restrict__ dst, uint64_t cap16, uint32_t fend_crc, uint32_t ty_x, uint32_t with_fend, uint32_t *__restrict__ verify,
@@ -118,7 +120,8 @@ void k_frame(const FrameDesc *__restrict__ fd, const uint8_t *__restrict__ blob,
         if (tid == 0) {
             const uint8_t *q = dst + pay + d.payload_len;
             const uint32_t stored = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-            if (stored != ~part[0]) { atomicAdd(&verify[0], 1u); atomicMin(&verify[1], ent); }
+            if (PER) verify[ent] = stored != ~part[0] ? 1u : 0u;
+            else if (stored != ~part[0]) { atomicAdd(&verify[0], 1u); atomicMin(&verify[1], ent); }
         }
         continue;
     }
@@ -151,6 +154,7 @@ __device__ __forceinline__ uint32_t gf2_xpow_dev(uint64_t e) {
     while (e) { if (e & 1) r = gf2_mulmod(base, r); base = gf2_mulmod(base, base); e >>= 1; }
     return r;
 }
+template <bool PER = false>
 __global__ __launch_bounds__(256)
 void k_frame_wave(const FrameDesc *__restrict__ fd, const uint8_t *__restrict__ blob, const CrcTabs *__restrict__ ct, uint8_t *__restrict__ dst,
                   uint32_t fend_crc, uint32_t ty_x, uint32_t with_fend, uint32_t nent, uint32_t *__restrict__ verify) {
@@ -205,7 +209,8 @@ void k_frame_wave(const FrameDesc *__restrict__ fd, const uint8_t *__restrict__ 
         if (lane == 0) {
             const uint8_t *q = dst + pay + d.payload_len;
             const uint32_t stored = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-            if (stored != ~x) { atomicAdd(&verify[0], 1u); atomicMin(&verify[1], ent); }
+            if (PER) verify[ent] = stored != ~x ? 1u : 0u;
+            else if (stored != ~x) { atomicAdd(&verify[0], 1u); atomicMin(&verify[1], ent); }
         }
         return;
     }
@@ -256,28 +261,66 @@ void launch_frame(const FrameDesc *fd, uint32_t nentry, const uint8_t *blob, con
                   uint32_t fend_crc, const char ty[4], bool with_fend, hipStream_t st, uint32_t max_payload) {
     const uint32_t ty_le = (uint32_t)(uint8_t)ty[0] | ((uint32_t)(uint8_t)ty[1] << 8) | ((uint32_t)(uint8_t)ty[2] << 16) | ((uint32_t)(uint8_t)ty[3] << 24);
     if (nentry && max_payload && max_payload <= 16380u) {
-        hipLaunchKernelGGL(k_frame_wave, dim3((nentry + 3) / 4), dim3(256), 0, st, fd, blob, ct, dst, fend_crc, ~ty_le, with_fend ? 1u : 0u, nentry, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(k_frame_wave<false>, dim3((nentry + 3) / 4), dim3(256), 0, st, fd, blob, ct, dst, fend_crc, ~ty_le, with_fend ? 1u : 0u, nentry, (uint32_t *)nullptr);
         return;
     }
     const uint32_t epw = 1u;                                    // (4 entries per workgroup measured SLOWER for 10^6 small entries: 9.1 vs 8.0 ms -- more workgroups in flight hide the per-entry chain better)
-    if (nentry) hipLaunchKernelGGL(k_frame, dim3((nentry + epw - 1) / epw), dim3(FR_THREADS), 0, st, fd, blob, ct, dst, cap16, fend_crc, ~ty_le, with_fend ? 1u : 0u, (uint32_t *)nullptr, nentry, epw);
+    if (nentry) hipLaunchKernelGGL(k_frame<false>, dim3((nentry + epw - 1) / epw), dim3(FR_THREADS), 0, st, fd, blob, ct, dst, cap16, fend_crc, ~ty_le, with_fend ? 1u : 0u, (uint32_t *)nullptr, nentry, epw);
 }
 // Read side: CRC-32 of n data chunks of type `ty` where they stand in buf (FrameDesc: arc_off = chunk start, prefix_len = 8,
 // payload_len = chunk length); verify[0] counts mismatches, verify[1] keeps the lowest failing descriptor index.
 void launch_frame_verify(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, const uint8_t *buf, uint64_t cap16, const char ty[4], uint32_t *verify, hipStream_t st, uint32_t max_payload) {
     const uint32_t ty_le = (uint32_t)(uint8_t)ty[0] | ((uint32_t)(uint8_t)ty[1] << 8) | ((uint32_t)(uint8_t)ty[2] << 16) | ((uint32_t)(uint8_t)ty[3] << 24);
     if (n && max_payload && max_payload <= 16380u) {               // many small chunks: a wave per chunk
-        hipLaunchKernelGGL(k_frame_wave, dim3((n + 3) / 4), dim3(256), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), 0u, ~ty_le, 0u, n, verify);
+        hipLaunchKernelGGL(k_frame_wave<false>, dim3((n + 3) / 4), dim3(256), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), 0u, ~ty_le, 0u, n, verify);
         return;
     }
     const uint32_t epw = 1u;
-    if (n) hipLaunchKernelGGL(k_frame, dim3((n + epw - 1) / epw), dim3(FR_THREADS), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), cap16, 0u, ~ty_le, 0u, verify, n, epw);
+    if (n) hipLaunchKernelGGL(k_frame<false>, dim3((n + epw - 1) / epw), dim3(FR_THREADS), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), cap16, 0u, ~ty_le, 0u, verify, n, epw);
+}
+
+// The same with one verdict word per descriptor (`pna verify`: every damaged chunk is named, the walk goes on): verdict[i] = 1 when chunk i's CRC
+// does not match, 0 otherwise -- no shared counter, so the verdicts of neighbouring entries cannot mix.
+void launch_frame_verdict(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, const uint8_t *buf, uint64_t cap16, const char ty[4], uint32_t *verdict, hipStream_t st, uint32_t max_payload) {
+    const uint32_t ty_le = (uint32_t)(uint8_t)ty[0] | ((uint32_t)(uint8_t)ty[1] << 8) | ((uint32_t)(uint8_t)ty[2] << 16) | ((uint32_t)(uint8_t)ty[3] << 24);
+    if (n && max_payload && max_payload <= 16380u) {
+        hipLaunchKernelGGL(k_frame_wave<true>, dim3((n + 3) / 4), dim3(256), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), 0u, ~ty_le, 0u, n, verdict);
+        return;
+    }
+    if (n) hipLaunchKernelGGL(k_frame<true>, dim3(n), dim3(FR_THREADS), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), cap16, 0u, ~ty_le, 0u, verdict, n, 1u);
+}
+
+// k_verdict: one status word per record of a window, by the first stage that failed -- chunk CRC (2), the host walk's finding, a GCM segment tag (4),
+// the CBC padding (5).  A wave per 64 records: the wave walks its records one after the other, its lanes stride over the record's chunk and segment
+// verdicts and a ballot folds them; lane j keeps record j's word, one coalesced store per wave.  No LDS, no barriers.
+__global__ __launch_bounds__(256)
+void k_verdict(const VerdictEnt *__restrict__ ve, uint32_t n, const uint32_t *__restrict__ crc_v, const uint32_t *__restrict__ gcm_v,
+               const uint32_t *__restrict__ cbc_plen, uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63, base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+    if (base >= n) return;
+    const uint32_t cnt = min(64u, n - base);
+    uint32_t mine = 0;
+    for (uint32_t j = 0; j < cnt; j++) {
+        const VerdictEnt e = ve[base + j];                           // (the same address on every lane: one broadcast load)
+        uint32_t bc = 0, bg = 0;
+        for (uint32_t i = e.c0 + lane; i < e.c1; i += 64) bc |= crc_v[i];
+        for (uint32_t i = e.g0 + lane; i < e.g1; i += 64) bg |= gcm_v[i];
+        const bool any_c = __ballot(bc != 0) != 0, any_g = __ballot(bg != 0) != 0;
+        uint32_t s = any_c ? 2u : e.pre;
+        if (s == 0 && any_g) s = 4u;
+        if (s == 0 && e.cbc_unit != 0xFFFFFFFFu && cbc_plen[e.cbc_unit] == 0xFFFFFFFFu) s = 5u;
+        if (lane == j) mine = s;
+    }
+    if (lane < cnt) out[base + lane] = mine;
+}
+void launch_verdict(const VerdictEnt *ve, uint32_t n, const uint32_t *crc_v, const uint32_t *gcm_v, const uint32_t *cbc_plen, uint32_t *out, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_verdict, dim3((n + 255) / 256), dim3(256), 0, st, ve, n, crc_v, gcm_v, cbc_plen, out);
 }
 
 // Pieces of chunks (FrameDesc::pad bits 4 / 8, above): raw CRC registers into states[0 .. n)
 void launch_frame_pieces(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, const uint8_t *buf, uint64_t cap16, const char ty[4], uint32_t *states, hipStream_t st) {
     const uint32_t ty_le = (uint32_t)(uint8_t)ty[0] | ((uint32_t)(uint8_t)ty[1] << 8) | ((uint32_t)(uint8_t)ty[2] << 16) | ((uint32_t)(uint8_t)ty[3] << 24);
-    if (n) hipLaunchKernelGGL(k_frame, dim3(n), dim3(FR_THREADS), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), cap16, 0u, ~ty_le, 0u, states, n, 1u);
+    if (n) hipLaunchKernelGGL(k_frame<false>, dim3(n), dim3(FR_THREADS), 0, st, fd, (const uint8_t *)nullptr, ct, const_cast<uint8_t *>(buf), cap16, 0u, ~ty_le, 0u, states, n, 1u);
 }
 // Big-endian CRC fields written where the host says: patch i puts the bytes j of crc[i] with bit j of mask[i] set at dst[off[i] + j] (a field may straddle the
 // buffer's end: the host then hands the other bytes to the next window)

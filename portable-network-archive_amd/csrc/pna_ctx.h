@@ -64,6 +64,9 @@ void launch_frame_pieces(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, con
 struct CrcPatchH { int64_t off; uint32_t crc, mask; };   // = CrcPatch of k_frame.hip
 void launch_crc_patch(const void *patches, uint32_t n, uint8_t *dst, hipStream_t st);
 void launch_frame_verify(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, const uint8_t *buf, uint64_t cap16, const char ty[4], uint32_t *verify, hipStream_t st, uint32_t max_payload);
+// `pna verify`'s kernels (weak: the sanitizer build has no stand-ins for them, pna_gpu_verify_archive_host refuses to run there)
+__attribute__((weak)) void launch_frame_verdict(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, const uint8_t *buf, uint64_t cap16, const char ty[4], uint32_t *verdict, hipStream_t st, uint32_t max_payload);
+__attribute__((weak)) void launch_verdict(const VerdictEnt *ve, uint32_t n, const uint32_t *crc_v, const uint32_t *gcm_v, const uint32_t *cbc_plen, uint32_t *out, hipStream_t st);
 void launch_zdec(ZFrame *frames, uint32_t n, const uint8_t *src, uint8_t *dst, uint8_t *lit_scratch, uint32_t dbg, hipStream_t st);
 void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *dst, hipStream_t st);
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st);
@@ -84,6 +87,9 @@ void launch_zstreams(uint32_t n_huf, uint32_t n_seq, const uint32_t *huf_list, c
 struct OpenSize { uint64_t size = 0; int exact = 0; uint64_t frames = 0, last = 0; };
 int open_size(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, OpenSize *out, hipStream_t st);
 int zstd_open_decode_planned(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, const OpenSize &m, uint64_t *got, hipStream_t st);
+// the batch decode in verdict mode: one status per entry (ZFrame::status) instead of a call-level failure (pna_decode.cpp)
+int decode_batch_status(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
+                        const uint64_t *dst_off, const uint64_t *raw_len, uint32_t *ent_status, hipStream_t st);
 struct ISChunkH { uint64_t start_bit, end_bit, lit_base, out_base, rec_base, end_found, mtot; uint32_t nlit, nrec, status, adler; };   // = ISChunk of k_inflate.hip
 static_assert(sizeof(ISChunkH) == 72, "ISChunk layout");
 void launch_ispec(const uint8_t *src, uint64_t src_off, uint64_t src_len, uint32_t cbytes, uint32_t nchunks, uint64_t *start, hipStream_t st);
@@ -130,6 +136,7 @@ void sha256_bytes(const void *a, size_t an, const void *b, size_t bn, uint8_t ou
 void hkdf_sha256_32(const void *ikm, size_t ikm_len, const void *salt, size_t salt_len, const void *info, size_t info_len, uint8_t okm[32]);
 void launch_gcm_tag(const GcmEntry *ents, uint32_t n, uint8_t *buf, hipStream_t st);
 void launch_gcm_verify(const GcmEntry *ents, uint32_t n, const uint8_t *buf, const uint8_t *expect, uint32_t *bad, hipStream_t st);
+__attribute__((weak)) void launch_gcm_verdict(const GcmEntry *ents, uint32_t n, const uint8_t *buf, const uint8_t *expect, uint32_t *verdict, hipStream_t st);
 void launch_aes_cbc_dec(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesDecTabs *tabs, uint8_t *buf, const AesKey &dkey, uint32_t *plain_len, hipStream_t st);
 size_t frame_entry_prefix_enc_bound(const char *name, const char *phsf);
 void launch_aes_ctr(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *tabs, uint8_t *buf, const AesKey &key, const AesKey *keys, hipStream_t st);
@@ -248,6 +255,7 @@ struct pna_gpu_ctx {
     DevBuf fr_desc, fr_blob, fr_segdst, fr_entoff, crc_tabs;
     PinBuf h_entoff;
     DevBuf x_arc, x_pk, x_raw[2], x_desc, x_place, x_flag, x_tags, x_plen, aes_dtabs;
+    DevBuf v_crc, v_seg, v_ent, v_out;   // pna verify: chunk and segment verdicts, the records' VerdictEnt, their status words
     hipStream_t x_cp = nullptr; hipEvent_t x_ev[2] = {}, x_done = nullptr;   // extract driver: D2H of window k on x_cp next to window k+1's work
     bool aes_dec_ready = false;        // read side (pna_gpu_extract_archive_host): archive image, packed payloads, decoded entries
     DevBuf z_vp, z_pb, z_mode;                                 // lane-per-piece inflate: piece list, piece boundaries, per-stream mode

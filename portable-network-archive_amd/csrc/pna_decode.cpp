@@ -143,7 +143,8 @@ static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, con
 }
 
 static int inflate_batch_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                                const uint64_t *dst_off, const uint64_t *raw_len, hipStream_t st, bool open = false, uint64_t *raw_out = nullptr) {
+                                const uint64_t *dst_off, const uint64_t *raw_len, hipStream_t st, bool open = false, uint64_t *raw_out = nullptr,
+                                uint32_t *ent_status = nullptr) {
     if (n > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
     std::vector<ZFrame> frs(n);
     std::vector<ZFrameX> fxs(n);
@@ -280,7 +281,8 @@ static int inflate_batch_device(pna_gpu_ctx *c, size_t n, const void *d_src, con
     (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]); (void)hipEventElapsedTime(&ms_h, c->ev[0], c->ev[2]); (void)hipEventElapsedTime(&ms_x, c->ev[2], c->ev[3]);
     c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms; c->timing.ms_stats = ms_h; c->timing.ms_lit = ms_x;   // total, Huffman walk, execution
     c->timing.lz_match_launches = spec.size();                      // (decode calls: the large foreign streams that went through the chunk decoder)
-    for (size_t i = 0; i < n; i++)
+    if (ent_status) for (size_t i = 0; i < n; i++) ent_status[i] = frs[i].status;     // verdict mode: every stream's own status, no call-level failure
+    for (size_t i = 0; i < n && !ent_status; i++)
         if (frs[i].status) {
             char msg[160];
             snprintf(msg, sizeof msg, "entry %zu: %s (produced %u of %llu bytes)", i,
@@ -380,7 +382,7 @@ extern "C" int pna_gpu_open_size_device(pna_gpu_ctx *c, int algo, const void *d_
 // Read side: decompress_reader (lib/src/entry/read.rs:171-190); entries already in device memory.
 static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
                               const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign = true,
-                              const OpenSize *plan = nullptr);
+                              const OpenSize *plan = nullptr, uint32_t *ent_status = nullptr);
 
 extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off,
                                                const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
@@ -392,6 +394,15 @@ extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t 
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, st);
     return zstd_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, st);
+}
+
+// The same in verdict mode (`pna verify`): ent_status[i] = entry i's ZFrame status (0 good, 1 corrupt, 2 unsupported, 3 size mismatch) instead of a
+// failure of the call at the first bad entry; workspace, HIP and batch-shape errors still fail the call.
+int pna::decode_batch_status(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
+                             const uint64_t *dst_off, const uint64_t *raw_len, uint32_t *ent_status, hipStream_t st) {
+    if (!n) return PNA_OK;
+    if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, st, false, nullptr, ent_status);
+    return zstd_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, st, true, nullptr, ent_status);
 }
 
 // A zstd stream whose decoded size is not recorded anywhere (the SDAT stream of a solid entry: SHED carries no size): step 1 counts
@@ -428,7 +439,7 @@ int pna::zstd_open_decode_planned(pna_gpu_ctx *c, const void *d_src, uint64_t sr
 // single-frame entries (the pipeline above, side by side), a frame without one on its own with an open size (its content's length is only known once it is
 // decoded), one after the other.  `room` = the entry's raw length (open: its capacity); *found = the bytes produced.
 static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t room, bool open,
-                               uint64_t *found, hipStream_t st) {
+                               uint64_t *found, hipStream_t st, bool *size_mismatch = nullptr) {
     struct Item { uint64_t off, len, fcs; };
     constexpr uint32_t CAP = 4096;
     if (c->z_list.ensure(CAP * sizeof(Item) + 64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
@@ -449,16 +460,23 @@ static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_o
                 size_t b = a; uint64_t pos = produced;
                 std::vector<uint64_t> so, sl, dof, rl;
                 while (b < k && items[b].fcs != ~0ull) {
-                    if (items[b].fcs > room - pos) return fail(c, PNA_E_INVAL, "size mismatch: the frames hold more than the entry's size");
+                    if (items[b].fcs > room - pos) { if (size_mismatch) *size_mismatch = true; return fail(c, PNA_E_INVAL, "size mismatch: the frames hold more than the entry's size"); }
                     so.push_back(items[b].off); sl.push_back(items[b].len); dof.push_back(dst_off + pos); rl.push_back(items[b].fcs); pos += items[b].fcs; b++;
                 }
-                int rc = zstd_decode_device(c, so.size(), d_src, so.data(), sl.data(), d_dst, dof.data(), rl.data(), false, nullptr, st, false);
+                // (verdict mode, size_mismatch given: the frames' own statuses, so that a frame that overflows the entry's size is told from a corrupt one)
+                std::vector<uint32_t> fst(size_mismatch ? so.size() : 0);
+                int rc = zstd_decode_device(c, so.size(), d_src, so.data(), sl.data(), d_dst, dof.data(), rl.data(), false, nullptr, st, false, nullptr,
+                                            size_mismatch ? fst.data() : nullptr);
                 if (rc) return rc;
+                for (uint32_t v : fst) if (v) { *size_mismatch = v == 3; return fail(c, v == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, "corrupt or mis-sized frame"); }
                 produced = pos; a = b;
             } else {                                                      // no content size in the header: decoded with an open size
                 uint64_t cap = room - produced, got = 0, dof = dst_off + produced;
-                int rc = zstd_decode_device(c, 1, d_src, &items[a].off, &items[a].len, d_dst, &dof, &cap, true, &got, st, false);
+                uint32_t fst = 0;
+                int rc = zstd_decode_device(c, 1, d_src, &items[a].off, &items[a].len, d_dst, &dof, &cap, true, &got, st, false, nullptr,
+                                            size_mismatch ? &fst : nullptr);
                 if (rc) return rc;
+                if (fst) { *size_mismatch = fst == 3; return fail(c, fst == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, "corrupt or mis-sized frame"); }
                 produced += got; a++;
             }
         }
@@ -466,14 +484,14 @@ static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_o
         if (ip >= src_len) break;
         if (k == 0) return fail(c, PNA_E_INVAL, "corrupt stream");        // (no progress: cannot happen with hdr[2] == 0)
     }
-    if (!open && produced != room) return fail(c, PNA_E_INVAL, "size mismatch (the frames do not add up to the entry's size)");
+    if (!open && produced != room) { if (size_mismatch) *size_mismatch = true; return fail(c, PNA_E_INVAL, "size mismatch (the frames do not add up to the entry's size)"); }
     *found = produced;
     return PNA_OK;
 }
 
 static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
                               const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign,
-                              const OpenSize *plan) {
+                              const OpenSize *plan, uint32_t *ent_status) {
     std::vector<ZEntry> ents(n);
     uint64_t nfr = 0;
     for (size_t i = 0; i < n; i++) {
@@ -620,17 +638,23 @@ static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const
     float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
     c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms;            // decoder time reported in the first stage slot
     std::vector<uint64_t> foreign_len(n, ~0ull);                  // entries that went through zstd_decode_foreign: the bytes they produced
+    const pna_gpu_timing outer_timing = c->timing;                // (the foreign path runs decode calls of its own: this call's timing stays what it measured)
+    if (ent_status) for (size_t i = 0; i < n; i++) ent_status[i] = 0;
     for (size_t i = 0; i < n; i++)
         for (uint32_t f = 0; f < ents[i].n_frames; f++) {
             const ZFrame &fr = frs[ents[i].first_frame + f];
             if (allow_foreign && (fr.status == 1 || fr.status == 3)) {
                 // not one of the two shapes k_zscan places (or a frame of the grid walk did not hold its MiB): the payload's frames as they are
                 uint64_t got = 0;
-                const int rcf = zstd_decode_foreign(c, d_src, src_off[i], src_len[i], d_dst, dst_off[i], raw_len[i], open, &got, st);
+                bool mism = false;
+                const int rcf = zstd_decode_foreign(c, d_src, src_off[i], src_len[i], d_dst, dst_off[i], raw_len[i], open, &got, st, ent_status ? &mism : nullptr);
+                c->timing = outer_timing;
+                if (rcf && ent_status && (rcf == PNA_E_INVAL || rcf == PNA_E_UNSUPPORTED)) { ent_status[i] = rcf == PNA_E_UNSUPPORTED ? 2u : (mism ? 3u : 1u); break; }
                 if (rcf) return rcf;
                 foreign_len[i] = got;
                 break;
             }
+            if (fr.status && fr.status != 4 && ent_status) { ent_status[i] = fr.status; break; }     // verdict mode: this entry's status, the others go on
             if (fr.status && fr.status != 4) {                    // 4: void slot behind a single frame that holds the whole entry
                 char msg[160];
                 snprintf(msg, sizeof msg, "entry %zu frame %u: %s (produced %u of %llu bytes)", i, f,

@@ -170,6 +170,11 @@ struct GcmEntry {            // k_gcm_tag: one GCM segment (this library writes 
     uint32_t h[4];           // hash subkey H = E(K, 0^128), big-endian words (word 0 = bytes 0..3)
     uint32_t ej0[4];         // E(K, nonce || 00000001), same form
 };
+// k_verdict (`pna verify`): what one record of a window is folded from -- its data chunks' CRC verdicts [c0, c1), its GCM segments' tag verdicts
+// [g0, g1), the CBC unit whose plaintext length tells its padding's verdict (~0u: none), and what the host walk found (`pre`, a PNA_VERIFY_* status)
+struct VerdictEnt {
+    uint32_t c0, c1, g0, g1, cbc_unit, pre;
+};
 
 // zstd decoder (k_zdec): one descriptor per frame
 struct ZFrame {

@@ -41,10 +41,14 @@ struct XStream {
     uint32_t gcm_seg = 0;                                      // GCM STREAM: segment size of the stream header
     uint8_t iv[16] = {0};                                      // CTR / CBC: the IV in front of the ciphertext
     uint64_t lo = 0, hi = 0;                                   // archive bytes [lo, hi) that hold the entry
+    // verdict mode (`pna verify`): what the host found (a PNA_VERIFY_* status, 0 = nothing yet), the record's flags, its GCM segments [g0, g1) and
+    // CBC padding unit in the window's verdict arrays
+    int vst = 0; uint32_t vfl = 0, g0 = 0, g1 = 0, cbc_unit = 0xFFFFFFFFu;
 };
 struct XEntry : XStream {
     std::string name; int kind = 0;
     bool has_size = false; uint64_t raw_size = 0, raw_off = 0; // fSIZ; decoded bytes in the raw buffer
+    bool noname = false, odd_size = false;                     // verdict mode: FHED unreadable (the record has no name); fSIZ out of proportion (decoded as without one)
     size_t d0 = 0, d1 = 0;                                     // its FDAT chunks in the descriptor list
 };
 struct XSolid : XStream {                                      // SHED [PHSF] SDAT* SEND -- lib/src/entry.rs:465-484,567-583
@@ -56,6 +60,7 @@ struct Inner { std::string name; int kind; std::vector<XPiece> pieces; uint64_t 
 struct XCall {
     pna_gpu_ctx *c; const void *password; size_t password_len; pna_entry_fn cb; void *user;
     std::vector<std::pair<std::string, std::vector<uint8_t>>> keys; size_t index = 0;
+    bool verdict = false, fast = false;                        // `pna verify` (pna_gpu_verify_archive_host): failures become records; --fast: chunk structure and CRCs only
 };
 // a window's layout: packed payloads and decoded bytes, the gather of the data streams, the streams each cipher stage takes
 struct XPlan {
@@ -67,13 +72,23 @@ struct XOut {
     std::vector<XEntry> ents; std::vector<size_t> solid_order; std::vector<std::vector<Inner>> inner; std::vector<std::vector<uint8_t>> plain, nosize_data;
     size_t index0 = 0;
 };
+// The archive as the driver reads it: one image, or the parts of a split archive laid end to end (part k at virtual offset vb[k]) and read in place --
+// a chunk never crosses a part, so every chunk, data piece, IV and tag is contiguous in host memory; a window's span may take bytes from two parts.
+struct ArcParts {
+    const uint8_t *const *p; const size_t *len; size_t n; std::vector<uint64_t> vb;
+    const uint8_t *at(uint64_t v) const { const size_t k = (size_t)(std::upper_bound(vb.begin(), vb.end(), v) - vb.begin()) - 1; return p[k] + (v - vb[k]); }
+};
+struct WinSrc {                                                // a window's bytes: `a + o` is the byte at window offset o
+    const ArcParts *ap; uint64_t base;
+    const uint8_t *operator+(uint64_t o) const { return ap->at(base + o); }
+};
 uint32_t max_chunk_len(const std::vector<FrameDesc> &v) {      // the longest data chunk of a list (0: none below 16 380 bytes, the wave-per-chunk CRC kernel's limit)
     uint32_t m = 1;
     for (const FrameDesc &d : v) { if (d.payload_len > 16380u) return 0u; m = std::max(m, d.payload_len); }
     return m;
 }
 // bytes [lo, lo + n) of a data stream whose pieces lie in `a` (a prefix or a tag may span pieces: prepend_data_prefix makes the prefix a piece of its own)
-void stream_read(const uint8_t *a, const std::vector<XPiece> &pieces, uint64_t lo, uint64_t n, uint8_t *out) {
+void stream_read(const WinSrc &a, const std::vector<XPiece> &pieces, uint64_t lo, uint64_t n, uint8_t *out) {
     uint64_t at = 0;
     for (const XPiece &p : pieces) {
         if (!n) break;
@@ -131,47 +146,116 @@ static int phsf_key(XCall &x, const std::string &phsf, const uint8_t **out) {
     return PNA_OK;
 }
 
-// ---- 1. the chunk walk (host): structure, small-chunk CRCs, data-chunk descriptors
-static int walk_archive(pna_gpu_ctx *c, const uint8_t *a, size_t archive_len, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks,
-                        std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids) {
+// ---- 1. the chunk walk (host): structure, small-chunk CRCs, data-chunk descriptors.  Verdict mode (`pna verify`, x.verdict) goes on after damage:
+// a chunk that fails its CRC is consumed (its length field trusted, as io::read_chunk does) and marks the entry that holds it BAD_CRC -- a bad FHED, or
+// damage between entries, opens a KIND_BROKEN record that runs to the next FEND / SEND --; structural faults mark their entry; the parts of a split
+// archive are walked one after the other (ANXT: the next part, its signature and AHED).  Where the walk cannot go on (a truncated chunk, no AEND)
+// *broken is set and what was complete before the break is kept.
+static int walk_archive(pna_gpu_ctx *c, const ArcParts &ap, bool verdict, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks,
+                        std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids, bool *broken) {
     XSolid scur; bool in_solid = false;
-    XEntry cur; bool in_entry = false, seen_ahed = false, ended = false;
-    size_t pos = 8;
-    while (pos < archive_len) {
-        PnaChunk ch;
-        const int r = next_chunk(a, archive_len, pos, ch);          // (pos moves behind the chunk)
-        if (r) return fail(c, PNA_E_INVAL, r == CHUNK_SHORT_HEADER ? "truncated chunk header" : "truncated chunk body");
-        const bool is_fdat = memcmp(ch.type, "FDAT", 4) == 0, is_sdat = memcmp(ch.type, "SDAT", 4) == 0;
-        if (is_fdat || is_sdat) { if (ch.len > 0xFFFFFFFBu) return fail(c, PNA_E_INVAL, "data chunk too long"); (is_fdat ? dchunks : schunks).push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
-        else if (!chunk_crc_ok(ch)) return fail(c, PNA_E_INVAL, "chunk CRC mismatch");
-        if (!seen_ahed) {
-            if (memcmp(ch.type, "AHED", 4) != 0 || ch.len != 8 || ch.data[0] != 0) return fail(c, PNA_E_INVAL, "first chunk must be AHED (major version 0)");
-            seen_ahed = true;
-        } else if (memcmp(ch.type, "AEND", 4) == 0) { ended = true; break; }
-        else if (memcmp(ch.type, "ANXT", 4) == 0) return fail(c, PNA_E_UNSUPPORTED, "multipart archives are not read by this driver");
-        else if (memcmp(ch.type, "SHED", 4) == 0) {
-            if (in_entry || in_solid || ch.len != 5 || ch.data[0] != 0 || ch.data[1] != 0) return fail(c, PNA_E_INVAL, "bad solid header");
-            scur = XSolid(); in_solid = true; scur.order = ents.size(); scur.s0 = schunks.size(); scur.lo = ch.off;
-            scur.compression = ch.data[2]; scur.encryption = ch.data[3]; scur.cipher_mode = ch.data[4]; scur.htype = "SHED"; scur.hdr.assign(ch.data, ch.data + ch.len);
-        } else if (in_solid) {
-            if (is_sdat) { scur.pieces.push_back(XPiece{ch.off + 8, ch.len}); scur.stream_len += ch.len; }
-            else if (memcmp(ch.type, "PHSF", 4) == 0) scur.phsf.assign((const char *)ch.data, ch.len);
-            else if (memcmp(ch.type, "SEND", 4) == 0) { scur.s1 = schunks.size(); scur.hi = ch.off + 12; solids.push_back(std::move(scur)); in_solid = false; }
-            else if (!(ch.type[0] & 0x20)) return fail(c, PNA_E_INVAL, "unknown critical chunk in a solid entry");
+    XEntry cur; bool in_entry = false, ended = false;
+    auto mark = [](XStream &s, int st) { if (!s.vst) s.vst = st; };
+    auto close_entry = [&](uint64_t hi) { cur.d1 = dchunks.size(); cur.hi = hi; ents.push_back(std::move(cur)); in_entry = false; };
+    auto close_solid = [&](uint64_t hi) { scur.s1 = schunks.size(); scur.hi = hi; solids.push_back(std::move(scur)); in_solid = false; };
+    auto open_broken = [&](uint64_t off, int st) { cur = XEntry(); in_entry = true; cur.d0 = dchunks.size(); cur.lo = off; cur.kind = PNA_VERIFY_KIND_BROKEN; cur.noname = true; cur.vst = st; };
+    // verdict mode: a record still open where a new header (or AEND) stands ends there -- it, not what follows, is marked (it lost its FEND / SEND)
+    auto close_open = [&](uint64_t off) {
+        if (in_entry) { mark(cur, PNA_VERIFY_BAD_STRUCTURE); close_entry(off); }
+        if (in_solid) { mark(scur, PNA_VERIFY_BAD_STRUCTURE); close_solid(off); }
+    };
+    for (size_t part = 0; part < ap.n && !ended; part++) {
+        const uint8_t *a = ap.p[part]; const size_t archive_len = ap.len[part]; const uint64_t vb = ap.vb[part];
+        if (part > 0 && (archive_len < 8 || memcmp(a, PNA_SIGNATURE, 8) != 0)) { *broken = true; return PNA_OK; }
+        bool seen_ahed = false, next_part = false;
+        size_t pos = 8;
+        while (pos < archive_len) {
+            PnaChunk ch;
+            const int r = next_chunk(a, archive_len, pos, ch);          // (pos moves behind the chunk)
+            if (r && verdict) { *broken = true; return PNA_OK; }
+            if (r) return fail(c, PNA_E_INVAL, r == CHUNK_SHORT_HEADER ? "truncated chunk header" : "truncated chunk body");
+            const uint64_t off = vb + ch.off;                              // the chunk's position in the parts laid end to end
+            const bool is_fdat = memcmp(ch.type, "FDAT", 4) == 0, is_sdat = memcmp(ch.type, "SDAT", 4) == 0;
+            const bool is_fend = memcmp(ch.type, "FEND", 4) == 0, is_send = memcmp(ch.type, "SEND", 4) == 0;
+            const bool is_head = memcmp(ch.type, "FHED", 4) == 0 || memcmp(ch.type, "SHED", 4) == 0;
+            const bool ends_broken = in_entry && cur.kind == PNA_VERIFY_KIND_BROKEN && (is_fend || is_send);   // (verdict mode only: kind is a byte otherwise)
+            if (is_fdat || is_sdat) {
+                if (ch.len > 0xFFFFFFFBu) {
+                    if (!verdict) return fail(c, PNA_E_INVAL, "data chunk too long");
+                    if (in_solid) mark(scur, PNA_VERIFY_BAD_STRUCTURE); else if (in_entry) mark(cur, PNA_VERIFY_BAD_STRUCTURE);
+                    continue;
+                }
+                if (verdict && !in_entry && !in_solid && seen_ahed) open_broken(off, PNA_VERIFY_BAD_STRUCTURE);     // a data chunk of no entry
+                (is_fdat ? dchunks : schunks).push_back(FrameDesc{off, ch.len, 0, 8, 0});
+            }
+            else if (!chunk_crc_ok(ch)) {
+                if (!verdict) return fail(c, PNA_E_INVAL, "chunk CRC mismatch");
+                if (!seen_ahed || memcmp(ch.type, "AEND", 4) == 0 || memcmp(ch.type, "ANXT", 4) == 0) { *broken = true; return PNA_OK; }
+                if (is_head) { close_open(off); open_broken(off, PNA_VERIFY_BAD_CRC); }     // an unreadable header: its chunks up to the next FEND / SEND
+                else if (in_solid) { mark(scur, PNA_VERIFY_BAD_CRC); if (is_send) close_solid(off + 12 + ch.len); }
+                else if (in_entry) { mark(cur, PNA_VERIFY_BAD_CRC); if (is_fend || ends_broken) close_entry(off + 12 + ch.len); }
+                else if (!is_fend && !is_send) open_broken(off, PNA_VERIFY_BAD_CRC);      // a damaged chunk between entries
+                continue;
+            }
+            if (verdict && in_solid && memcmp(ch.type, "FHED", 4) == 0) close_open(off);     // a solid entry that lost its SEND ends at the next header
+            if (!seen_ahed) {
+                if (memcmp(ch.type, "AHED", 4) != 0 || ch.len != 8 || ch.data[0] != 0) {
+                    if (verdict) { *broken = true; return PNA_OK; }
+                    return fail(c, PNA_E_INVAL, "first chunk must be AHED (major version 0)");
+                }
+                seen_ahed = true;
+            } else if (memcmp(ch.type, "AEND", 4) == 0) { if (verdict) close_open(off); ended = true; break; }
+            else if (memcmp(ch.type, "ANXT", 4) == 0) {
+                if (!verdict) return fail(c, PNA_E_UNSUPPORTED, "multipart archives are not read by this driver");
+                if (part + 1 == ap.n) { *broken = true; return PNA_OK; }             // the archive goes on in a part that was not given
+                next_part = true; break;
+            }
+            else if (memcmp(ch.type, "SHED", 4) == 0) {
+                const bool bad = ch.len != 5 || ch.data[0] != 0 || ch.data[1] != 0;
+                if ((bad || in_entry || in_solid) && !verdict) return fail(c, PNA_E_INVAL, "bad solid header");
+                close_open(off);                                              // (verdict mode: a record without FEND / SEND ends here)
+                scur = XSolid(); in_solid = true; scur.order = ents.size(); scur.s0 = schunks.size(); scur.lo = off;
+                if (ch.len >= 5) { scur.compression = ch.data[2]; scur.encryption = ch.data[3]; scur.cipher_mode = ch.data[4]; }
+                scur.htype = "SHED"; scur.hdr.assign(ch.data, ch.data + ch.len);
+                if (bad) scur.vst = PNA_VERIFY_BAD_STRUCTURE;
+            } else if (in_solid) {
+                if (is_sdat) { scur.pieces.push_back(XPiece{off + 8, ch.len}); scur.stream_len += ch.len; }
+                else if (memcmp(ch.type, "PHSF", 4) == 0) scur.phsf.assign((const char *)ch.data, ch.len);
+                else if (is_send) close_solid(off + 12);
+                else if (!(ch.type[0] & 0x20)) { if (!verdict) return fail(c, PNA_E_INVAL, "unknown critical chunk in a solid entry"); mark(scur, PNA_VERIFY_BAD_STRUCTURE); }
+            }
+            else if (memcmp(ch.type, "FHED", 4) == 0) {
+                const bool bad = ch.len < 6 || ch.data[0] != 0 || ch.data[1] != 0;
+                if ((bad || in_entry) && !verdict) return fail(c, PNA_E_INVAL, "bad entry header");
+                close_open(off);
+                cur = XEntry(); in_entry = true; cur.d0 = dchunks.size(); cur.lo = off;
+                if (ch.len >= 6) {
+                    cur.kind = ch.data[2]; cur.compression = ch.data[3]; cur.encryption = ch.data[4]; cur.cipher_mode = ch.data[5];
+                    cur.name.assign((const char *)ch.data + 6, ch.len - 6);
+                } else cur.noname = true;
+                cur.hdr.assign(ch.data, ch.data + ch.len);
+                if (bad) cur.vst = PNA_VERIFY_BAD_STRUCTURE;
+            } else if (!in_entry) {
+                if (!(ch.type[0] & 0x20)) {
+                    if (!verdict) return fail(c, PNA_E_INVAL, "unknown critical chunk between entries");
+                    if (!is_fend && !is_send) open_broken(off, PNA_VERIFY_BAD_STRUCTURE);
+                }
+            }
+            else if (is_fdat) { cur.pieces.push_back(XPiece{off + 8, ch.len}); cur.stream_len += ch.len; }
+            else if (memcmp(ch.type, "fSIZ", 4) == 0) {
+                if (ch.len > 8) { if (!verdict) return fail(c, PNA_E_UNSUPPORTED, "entry beyond 2^64 bytes"); mark(cur, PNA_VERIFY_UNSUPPORTED); continue; }
+                cur.has_size = true; cur.raw_size = 0; for (uint32_t i = 0; i < ch.len; i++) cur.raw_size = (cur.raw_size << 8) | ch.data[i];
+            }
+            else if (memcmp(ch.type, "PHSF", 4) == 0) cur.phsf.assign((const char *)ch.data, ch.len);
+            else if (is_fend || ends_broken) close_entry(off + 12);
+            else if (!(ch.type[0] & 0x20)) { if (!verdict) return fail(c, PNA_E_INVAL, "unknown critical chunk"); mark(cur, PNA_VERIFY_BAD_STRUCTURE); }   // chunk/types.rs: bit 5 of byte 0 clear = critical
         }
-        else if (memcmp(ch.type, "FHED", 4) == 0) {
-            if (in_entry || ch.len < 6 || ch.data[0] != 0 || ch.data[1] != 0) return fail(c, PNA_E_INVAL, "bad entry header");
-            cur = XEntry(); in_entry = true; cur.d0 = dchunks.size(); cur.lo = ch.off;
-            cur.kind = ch.data[2]; cur.compression = ch.data[3]; cur.encryption = ch.data[4]; cur.cipher_mode = ch.data[5];
-            cur.name.assign((const char *)ch.data + 6, ch.len - 6); cur.hdr.assign(ch.data, ch.data + ch.len);
-        } else if (!in_entry) { if (!(ch.type[0] & 0x20)) return fail(c, PNA_E_INVAL, "unknown critical chunk between entries"); }
-        else if (is_fdat) { cur.pieces.push_back(XPiece{ch.off + 8, ch.len}); cur.stream_len += ch.len; }
-        else if (memcmp(ch.type, "fSIZ", 4) == 0) { if (ch.len > 8) return fail(c, PNA_E_UNSUPPORTED, "entry beyond 2^64 bytes"); cur.has_size = true; cur.raw_size = 0; for (uint32_t i = 0; i < ch.len; i++) cur.raw_size = (cur.raw_size << 8) | ch.data[i]; }
-        else if (memcmp(ch.type, "PHSF", 4) == 0) cur.phsf.assign((const char *)ch.data, ch.len);
-        else if (memcmp(ch.type, "FEND", 4) == 0) { cur.d1 = dchunks.size(); cur.hi = ch.off + 12; ents.push_back(std::move(cur)); in_entry = false; }
-        else if (!(ch.type[0] & 0x20)) return fail(c, PNA_E_INVAL, "unknown critical chunk");      // chunk/types.rs: bit 5 of byte 0 clear = critical
+        if (!next_part) break;
     }
-    if (!ended || in_entry || in_solid) return fail(c, PNA_E_INVAL, "archive not terminated by AEND");
+    if (!ended || in_entry || in_solid) {
+        if (verdict) { *broken = true; return PNA_OK; }
+        return fail(c, PNA_E_INVAL, "archive not terminated by AEND");
+    }
     return PNA_OK;
 }
 // the streams of a window and their data chunks, moved to offsets relative to the window's first byte `base`
@@ -188,9 +272,27 @@ struct XDeferred { std::function<int()> issue, deliver; bool issued = false; exp
 // A data stream (the concatenated FDAT / SDAT bodies) is laid into the packed buffer at pk_off with its cipher prefix stripped: CTR / CBC lose the
 // IV, a GCM STREAM its header and the segments' tags (only the ciphertext is gathered).  Sets pay_len (and gcm_seg) and registers the stream
 // with the cipher stage.
-static int plan_stream(XCall &x, const uint8_t *a, XStream &s, XPlan &P) {
+static int plan_stream(XCall &x, const WinSrc &a, XStream &s, XPlan &P) {
     pna_gpu_ctx *c = x.c;
     s.pk_off = P.pk_total;
+    // verdict mode: a stream this stage cannot take becomes its record's status (the pieces it placed so far are taken back) instead of the call's error
+    const size_t places0 = P.places.size();
+    auto fail = [&](pna_gpu_ctx *cc, int code, const char *what) {
+        if (!x.verdict) return ::fail(cc, code, what);
+        P.places.resize(places0);
+        s.vst = code == PNA_E_UNSUPPORTED ? PNA_VERIFY_UNSUPPORTED : (s.cipher_mode == PNA_MODE_GCM ? PNA_VERIFY_BAD_STRUCTURE : PNA_VERIFY_BAD_DECRYPT);
+        return PNA_OK;
+    };
+    if (x.verdict && s.encryption != PNA_ENC_NONE) {
+        if (s.encryption != PNA_ENC_AES) { s.vst = PNA_VERIFY_UNSUPPORTED; return PNA_OK; }
+        if (!x.password) { s.vst = PNA_VERIFY_SKIPPED; return PNA_OK; }
+        if (s.phsf.empty()) { s.vst = PNA_VERIFY_BAD_STRUCTURE; return PNA_OK; }
+        const uint8_t *k = nullptr;                                   // derived here, once per PHSF string: a PHSF the reader cannot use is this record's fault
+        const int rk = phsf_key(x, s.phsf, &k);
+        if (rk == PNA_E_UNSUPPORTED) { s.vst = PNA_VERIFY_UNSUPPORTED; return PNA_OK; }
+        if (rk == PNA_E_INVAL) { s.vst = PNA_VERIFY_BAD_STRUCTURE; return PNA_OK; }
+        if (rk) return rk;
+    }
     auto place = [&](uint64_t lo, uint64_t hi, uint64_t dst) {
         uint64_t at = 0;
         for (const XPiece &p : s.pieces) {
@@ -210,6 +312,7 @@ static int plan_stream(XCall &x, const uint8_t *a, XStream &s, XPlan &P) {
             s.pay_len = s.stream_len - 16;
             place(16, s.stream_len, s.pk_off);
             P.enc_list.push_back(&s);
+            s.vfl |= PNA_VERIFY_UNAUTHENTICATED;                       // (read only in verdict mode)
         } else if (s.cipher_mode == PNA_MODE_GCM) {
             // stream header, then segments of (segment size + 16-byte tag), the last one shorter: only the ciphertext is gathered
             if (s.stream_len < 75 + 16) return fail(c, PNA_E_INVAL, "datastream shorter than the stream header");
@@ -220,25 +323,33 @@ static int plan_stream(XCall &x, const uint8_t *a, XStream &s, XPlan &P) {
             while (rest) {
                 const uint64_t segl = std::min<uint64_t>(rest, (uint64_t)s.gcm_seg + 16);
                 if (segl < 16) return fail(c, PNA_E_INVAL, "GCM segment shorter than a tag");
+                if (x.verdict && segl != rest && segl != (uint64_t)s.gcm_seg + 16) return fail(c, PNA_E_INVAL, "GCM STREAM: short non-final segment");
                 place(at, at + segl - 16, outp);
                 outp += segl - 16; at += segl; rest -= segl;
             }
             s.pay_len = outp - s.pk_off;
             P.gcm_list.push_back(&s);
         } else return fail(c, PNA_E_UNSUPPORTED, "unknown cipher mode");
+        if (s.vst) return PNA_OK;
     }
     P.pk_total = (P.pk_total + s.pay_len + 15) & ~(uint64_t)15;
     return PNA_OK;
 }
 static bool decoded_here(int compression) { return compression == PNA_ALGO_STORE || compression == PNA_ALGO_ZSTD || compression == PNA_ALGO_DEFLATE; }
 // the window plan: packed payloads, decoded entries, the gather, the cipher stages' stream lists, the entries without fSIZ
-static int plan_window(XCall &x, const uint8_t *a, std::vector<XEntry> &ents, std::vector<XSolid> &solids, XPlan &P) {
+static int plan_window(XCall &x, const WinSrc &a, std::vector<XEntry> &ents, std::vector<XSolid> &solids, XPlan &P) {
     pna_gpu_ctx *c = x.c;
+    if (x.fast) return PNA_OK;                                        // verify --fast: chunk structure and CRCs, nothing gathered, decrypted or decoded
     for (size_t i = 0; i < ents.size(); i++) {
         XEntry &e = ents[i];
-        if (!decoded_here(e.compression)) return fail(c, PNA_E_UNSUPPORTED, "compression method not decoded on the device (xz)");
+        if (x.verdict && e.vst) continue;                              // (a structural fault found by the walk: nothing to decode)
+        if (!decoded_here(e.compression)) { if (x.verdict) { e.vst = PNA_VERIFY_UNSUPPORTED; continue; } return fail(c, PNA_E_UNSUPPORTED, "compression method not decoded on the device (xz)"); }
         const int r = plan_stream(x, a, e, P); if (r) return r;
+        if (e.vst) continue;
         if (e.compression == PNA_ALGO_STORE) continue;
+        // verdict mode: an fSIZ no payload of this length can decode to is a wrong size hint -- the entry is decoded as one without fSIZ
+        if (x.verdict && e.has_size && (e.raw_size > (1ull << 40) || e.raw_size / 65536 > e.pay_len + 1)) e.odd_size = true;
+        if (e.odd_size) { P.nosize_idx.push_back(i); continue; }
         // fSIZ is optional (older writers omit it): the payload is then decoded like a solid stream, its size found by the decoder
         if (!e.has_size) { P.nosize_idx.push_back(i); continue; }
         // fSIZ comes from the archive: a size no payload of this length can decode to (deflate tops out at 1032 : 1, zstd at a few
@@ -248,7 +359,8 @@ static int plan_window(XCall &x, const uint8_t *a, std::vector<XEntry> &ents, st
         if (P.raw_total > (1ull << 42)) return fail(c, PNA_E_NOMEM, "archive decodes to more than this driver takes in one call");
     }
     for (XSolid &so : solids) {
-        if (!decoded_here(so.compression)) return fail(c, PNA_E_UNSUPPORTED, "solid stream: compression method not decoded on the device (xz)");
+        if (x.verdict && so.vst) continue;
+        if (!decoded_here(so.compression)) { if (x.verdict) { so.vst = PNA_VERIFY_UNSUPPORTED; continue; } return fail(c, PNA_E_UNSUPPORTED, "solid stream: compression method not decoded on the device (xz)"); }
         const int r = plan_stream(x, a, so, P); if (r) return r;
     }
     return PNA_OK;
@@ -265,21 +377,32 @@ static int read_back(pna_gpu_ctx *c, void *dst, const void *src, size_t n, hipSt
     return PNA_OK;
 }
 // ---- 3. device: the window's bytes in, the data chunks' CRCs, the gather of the data streams into the packed buffer
-static int upload_window(pna_gpu_ctx *c, const uint8_t *a, size_t archive_len, const std::vector<FrameDesc> &dchunks, const std::vector<FrameDesc> &schunks,
-                         const XPlan &P, int slot, uint32_t flag[2], hipStream_t st) {
+// Verdict mode (`pna verify`): one CRC verdict word per data chunk into c->v_crc (a window holds FDAT or SDAT chunks, never both) instead of the shared
+// flag, and nothing is decoded into the raw buffer's host side.  The window's bytes come from one part, or from two where it spans a part's end.
+static int upload_window(pna_gpu_ctx *c, const WinSrc &a, size_t archive_len, const std::vector<FrameDesc> &dchunks, const std::vector<FrameDesc> &schunks,
+                         const XPlan &P, int slot, uint32_t flag[2], hipStream_t st, bool verdict = false) {
     int rc = ensure_crc(c); if (rc) return rc;
     if (c->x_arc.ensure(archive_len + 64) || c->x_pk.ensure(P.pk_total + 8192) || c->x_raw[slot].ensure(P.raw_total + 64) || c->x_flag.ensure(64) ||
-        c->x_desc.ensure(dchunks.size() * sizeof(FrameDesc) + 16) || c->x_place.ensure(P.places.size() * sizeof(PlaceDescH) + 16)) return fail(c, PNA_E_NOMEM, "extract workspace");
-    HIPCHK(c, hipMemcpyAsync(c->x_arc.p, a, archive_len, hipMemcpyHostToDevice, st));
+        c->x_desc.ensure(dchunks.size() * sizeof(FrameDesc) + 16) || c->x_place.ensure(P.places.size() * sizeof(PlaceDescH) + 16) ||
+        (verdict && c->v_crc.ensure((dchunks.size() + schunks.size()) * 4 + 16))) return fail(c, PNA_E_NOMEM, "extract workspace");
+    for (size_t k = 0; k < a.ap->n; k++) {                              // the parts that hold bytes of [base, base + archive_len)
+        const uint64_t p0 = a.ap->vb[k], p1 = p0 + a.ap->len[k], lo = std::max<uint64_t>(p0, a.base), hi = std::min<uint64_t>(p1, a.base + archive_len);
+        if (lo < hi) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->x_arc.p + (lo - a.base), a.ap->p[k] + (lo - p0), hi - lo, hipMemcpyHostToDevice, st));
+    }
     HIPCHK(c, hipMemcpyAsync(c->x_flag.p, flag0, 8, hipMemcpyHostToDevice, st));
+    auto check = [&](const DevBuf &desc, const std::vector<FrameDesc> &v, const char *ty) {
+        if (verdict) launch_frame_verdict((const FrameDesc *)desc.p, (uint32_t)v.size(), (const CrcTabs *)c->crc_tabs.p, (const uint8_t *)c->x_arc.p,
+                                          (uint64_t)c->x_arc.cap & ~(uint64_t)15, ty, (uint32_t *)c->v_crc.p, st, max_chunk_len(v));
+        else verify_chunks(c, desc, v, c->x_arc, ty, st);
+    };
     if (!dchunks.empty()) {
         HIPCHK(c, hipMemcpyAsync(c->x_desc.p, dchunks.data(), dchunks.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
-        verify_chunks(c, c->x_desc, dchunks, c->x_arc, "FDAT", st);
+        check(c->x_desc, dchunks, "FDAT");
     }
     if (!schunks.empty()) {
         if (c->solid_desc.ensure(schunks.size() * sizeof(FrameDesc) + 16)) return fail(c, PNA_E_NOMEM, "extract workspace");
         HIPCHK(c, hipMemcpyAsync(c->solid_desc.p, schunks.data(), schunks.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
-        verify_chunks(c, c->solid_desc, schunks, c->x_arc, "SDAT", st);
+        check(c->solid_desc, schunks, "SDAT");
     }
     if (!P.places.empty()) {
         HIPCHK(c, hipMemcpyAsync(c->x_place.p, P.places.data(), P.places.size() * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
@@ -290,9 +413,15 @@ static int upload_window(pna_gpu_ctx *c, const uint8_t *a, size_t archive_len, c
 // CBC of one key group (DecryptCbcAes256Reader, lib/src/entry/read.rs:77-82): a block's plaintext needs its own and the previous ciphertext block
 // only, so a long stream -- a solid one -- is cut into units of 16 MiB whose IV is the ciphertext block in front; the padding is read at the end of
 // the stream's last unit
-static int decrypt_cbc(pna_gpu_ctx *c, const uint8_t *key, const std::vector<XStream *> &grp, hipStream_t st) {
+// Verdict mode (`verdict`): a bad length marks its stream, the padding's verdict stays on the device for k_verdict (CBC units from unit0 on: the
+// window's CBC groups share x_plen), and no stream fails the call.
+static constexpr uint64_t CBC_UNIT = 16u << 20;
+static int decrypt_cbc(pna_gpu_ctx *c, const uint8_t *key, const std::vector<XStream *> &grp_in, hipStream_t st, bool verdict = false, uint32_t *unit0 = nullptr) {
     int rc = ensure_aes_dec(c); if (rc) return rc;
-    constexpr uint64_t CBC_UNIT = 16u << 20;
+    std::vector<XStream *> grp;
+    for (XStream *s : grp_in) { if (verdict && (s->pay_len == 0 || (s->pay_len & 15))) s->vst = PNA_VERIFY_BAD_DECRYPT; else grp.push_back(s); }
+    if (grp.empty()) return PNA_OK;
+    const uint32_t u0 = unit0 ? *unit0 : 0u;
     std::vector<CipherUnit> units; std::vector<size_t> last_unit(grp.size());
     for (size_t q = 0; q < grp.size(); q++) {
         const XStream &s = *grp[q];
@@ -302,7 +431,7 @@ static int decrypt_cbc(pna_gpu_ctx *c, const uint8_t *key, const std::vector<XSt
             last_unit[q] = units.size() - 1;
         }
     }
-    if (c->ci_units.ensure(units.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure(units.size() * 16 + 16) || c->x_plen.ensure(units.size() * 4 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+    if (c->ci_units.ensure(units.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure(units.size() * 16 + 16) || c->x_plen.ensure((u0 + units.size()) * 4 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
     // the units' IVs: the stream's own for its first unit, else the 16 ciphertext bytes in front of the unit (copied on the device BEFORE the
     // kernel overwrites them: the decryption is in place)
     { size_t u = 0;
@@ -315,10 +444,12 @@ static int decrypt_cbc(pna_gpu_ctx *c, const uint8_t *key, const std::vector<XSt
     std::vector<uint32_t> plen(units.size());
     HIPCHK(c, hipMemcpyAsync(c->ci_units.p, units.data(), units.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
     launch_aes_cbc_dec((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesDecTabs *)c->aes_dtabs.p,
-                       (uint8_t *)c->x_pk.p, dk, (uint32_t *)c->x_plen.p, st);
-    rc = read_back(c, plen.data(), c->x_plen.p, units.size() * 4, st); if (rc) return rc;
+                       (uint8_t *)c->x_pk.p, dk, (uint32_t *)c->x_plen.p + u0, st);
+    rc = read_back(c, plen.data(), (uint32_t *)c->x_plen.p + u0, units.size() * 4, st); if (rc) return rc;
+    if (unit0) *unit0 += (uint32_t)units.size();
     for (size_t q = 0; q < grp.size(); q++) {
         const uint32_t pl = plen[last_unit[q]];
+        if (verdict) { grp[q]->cbc_unit = u0 + (uint32_t)last_unit[q]; if (pl == 0xFFFFFFFFu) continue; }     // (k_verdict reads the padding's verdict)
         if (pl == 0xFFFFFFFFu) return fail(c, PNA_E_INVAL, "CBC: bad length or padding (wrong password or damaged data)");
         grp[q]->pay_len = (grp[q]->pay_len - 1) / CBC_UNIT * CBC_UNIT + pl;
     }
@@ -328,6 +459,12 @@ static int decrypt_cbc(pna_gpu_ctx *c, const uint8_t *key, const std::vector<XSt
 static int decrypt_ctr_cbc(XCall &x, const std::vector<XStream *> &enc_list, hipStream_t st) {
     pna_gpu_ctx *c = x.c;
     std::vector<bool> done(enc_list.size(), false);
+    uint32_t cbc_units = 0;                                           // verdict mode: the window's CBC units, one x_plen word each
+    if (x.verdict) {                                                  // ... sized once for the window: the groups' verdicts stay side by side until k_verdict reads them
+        uint64_t all = 0;
+        for (const XStream *s : enc_list) if (s->cipher_mode == PNA_MODE_CBC) all += (s->pay_len + CBC_UNIT - 1) / CBC_UNIT;
+        if (c->x_plen.ensure(all * 4 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+    }
     for (size_t j = 0; j < enc_list.size(); j++) {
         if (done[j]) continue;
         const XStream &s0 = *enc_list[j];
@@ -341,25 +478,29 @@ static int decrypt_ctr_cbc(XCall &x, const std::vector<XStream *> &enc_list, hip
             for (const XStream *e : grp) { off.push_back(e->pk_off); len.push_back(e->pay_len); ivs.insert(ivs.end(), e->iv, e->iv + 16); }
             pna_gpu_cipher ci{}; ci.encryption = PNA_ENC_AES; ci.cipher_mode = PNA_MODE_CTR; memcpy(ci.key, key, 32); ci.phsf = ""; ci.ivs = ivs.data();
             rc = pna_gpu_cipher_apply_device(c, &ci, 1, off.size(), c->x_pk.p, off.data(), len.data(), st);
-        } else rc = decrypt_cbc(c, key, grp, st);
+        } else rc = decrypt_cbc(c, key, grp, st, x.verdict, x.verdict ? &cbc_units : nullptr);
         if (rc) return rc;
     }
     return PNA_OK;
 }
 // GCM STREAM (decrypt_reader, (_, CipherMode::GCM): lib/src/entry/read.rs:105-140): key confirmation first -- a wrong password is told apart from
 // tampering --, then every segment's tag (k_gcm_tag in verify mode), then the CTR keystream with the stream keys
-static int decrypt_gcm(XCall &x, const uint8_t *a, const std::vector<XStream *> &gcm_list, uint32_t flag[2], hipStream_t st) {
+// Verdict mode: a failed key confirmation marks its stream BAD_AUTH, every segment's tag verdict goes to c->v_seg (the stream's segments [g0, g1))
+// for k_verdict, and the keystream is applied to every segment all the same (a record that failed is not decoded).
+static int decrypt_gcm(XCall &x, const WinSrc &a, const std::vector<XStream *> &gcm_list, uint32_t flag[2], hipStream_t st) {
     pna_gpu_ctx *c = x.c;
     int rc = ensure_aes(c); if (rc) return rc;
     std::vector<GcmEntry> gents; std::vector<uint8_t> tags, giv; std::vector<AesKey> gkeys; std::vector<CipherUnit> units;
-    for (const XStream *e : gcm_list) {
-        const XStream &s = *e;
+    for (XStream *e : gcm_list) {
+        XStream &s = *e;
         const uint8_t *km = nullptr;
         rc = phsf_key(x, s.phsf, &km); if (rc) return rc;
         GcmMaterial m; stream_read(a, s.pieces, 0, 75, m.header);
         const GcmCallKeys ck = gcm_call_keys(km, s.phsf.data(), s.phsf.size());
         { uint8_t diff = 0; for (int b = 0; b < 32; b++) diff |= (uint8_t)(ck.kc[b] ^ m.header[43 + b]);      // constant time, like the reference's ct_eq
+          if (diff && x.verdict) { s.vst = PNA_VERIFY_BAD_AUTH; continue; }
           if (diff) return fail(c, PNA_E_INVAL, "GCM STREAM: key confirmation failed (wrong password)"); }
+        s.g0 = (uint32_t)gents.size();
         gcm_stream_key(km, m.header, s.htype, s.hdr, ck.phsf_hash, m.rk, m.h);
         uint64_t rest = s.stream_len - 75, at = 75, outp = s.pk_off; uint32_t counter = 0;
         while (rest) {
@@ -376,7 +517,9 @@ static int decrypt_gcm(XCall &x, const uint8_t *a, const std::vector<XStream *> 
             outp += ctl; at += segl; rest -= segl; counter++;
             if (!fin && segl != (uint64_t)s.gcm_seg + 16) return fail(c, PNA_E_INVAL, "GCM STREAM: short non-final segment");
         }
+        s.g1 = (uint32_t)gents.size();
     }
+    if (gents.empty()) return PNA_OK;                                  // (verdict mode: every stream failed its key confirmation)
     if (c->ci_gcm.ensure(gents.size() * sizeof(GcmEntry) + 16) || c->x_tags.ensure(tags.size() + 16) || c->ci_keys.ensure(gkeys.size() * sizeof(AesKey) + 16) ||
         c->ci_ivs.ensure(giv.size() + 16) || c->ci_units.ensure(units.size() * sizeof(CipherUnit) + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
     HIPCHK(c, hipMemcpyAsync(c->x_flag.p, flag0, 8, hipMemcpyHostToDevice, st));
@@ -385,9 +528,14 @@ static int decrypt_gcm(XCall &x, const uint8_t *a, const std::vector<XStream *> 
     HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, gkeys.data(), gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, giv.data(), giv.size(), hipMemcpyHostToDevice, st));
     if (!units.empty()) HIPCHK(c, hipMemcpyAsync(c->ci_units.p, units.data(), units.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
-    launch_gcm_verify((const GcmEntry *)c->ci_gcm.p, (uint32_t)gents.size(), (const uint8_t *)c->x_pk.p, (const uint8_t *)c->x_tags.p, (uint32_t *)c->x_flag.p, st);
-    rc = read_back(c, flag, c->x_flag.p, 8, st); if (rc) return rc;
-    if (flag[0]) return fail(c, PNA_E_INVAL, "GCM STREAM: authentication failure (a segment tag does not match)");
+    if (x.verdict) {
+        if (c->v_seg.ensure(gents.size() * 4 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+        launch_gcm_verdict((const GcmEntry *)c->ci_gcm.p, (uint32_t)gents.size(), (const uint8_t *)c->x_pk.p, (const uint8_t *)c->x_tags.p, (uint32_t *)c->v_seg.p, st);
+    } else {
+        launch_gcm_verify((const GcmEntry *)c->ci_gcm.p, (uint32_t)gents.size(), (const uint8_t *)c->x_pk.p, (const uint8_t *)c->x_tags.p, (uint32_t *)c->x_flag.p, st);
+        rc = read_back(c, flag, c->x_flag.p, 8, st); if (rc) return rc;
+        if (flag[0]) return fail(c, PNA_E_INVAL, "GCM STREAM: authentication failure (a segment tag does not match)");
+    }
     AesKey k0{};
     launch_aes_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)c->x_pk.p, k0, (const AesKey *)c->ci_keys.p, st);
     HIPCHK(c, hipGetLastError());
@@ -407,7 +555,8 @@ static int decode_sized(pna_gpu_ctx *c, const std::vector<XEntry> &ents, int slo
 }
 // A stream whose decoded size is recorded nowhere -- an entry without fSIZ, a solid stream -- measured on the device (pna_gpu_open_size_device: the exact
 // size, or a proven bound), decoded into c->solid_plain of that size and copied to `out` (a stored one is copied from the packed buffer as it is)
-static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::vector<uint8_t> &out, hipStream_t st) {
+// (out == NULL: `pna verify` -- decoded on the device and dropped; *size_out receives the size found)
+static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::vector<uint8_t> *out, hipStream_t st, uint64_t *size_out = nullptr) {
     uint64_t got = s.pay_len; const void *d = (const uint8_t *)c->x_pk.p + s.pk_off;
     if (s.compression != PNA_ALGO_STORE) {
         OpenSize m;
@@ -426,32 +575,38 @@ static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::
         if (rc) return rc;
         d = c->solid_plain.p;
     }
-    out.resize((size_t)got);
-    if (got) HIPCHK(c, hipMemcpy(out.data(), d, got, hipMemcpyDeviceToHost));
+    if (size_out) *size_out = got;
+    if (!out) return PNA_OK;
+    out->resize((size_t)got);
+    if (got) HIPCHK(c, hipMemcpy(out->data(), d, got, hipMemcpyDeviceToHost));
     return PNA_OK;
 }
 // A solid entry: its stream decoded, then read_next_normal_entry_from_stream over it (lib/src/entry.rs:401-424): small chunks checked here, the
 // inner FDAT CRCs on the device over the decoded stream where it stands
-static int walk_solid(pna_gpu_ctx *c, const XSolid &so, std::vector<uint8_t> &plain, std::vector<Inner> &inner, uint32_t flag[2], hipStream_t st) {
-    int rc = decode_open(c, so, "solid stream buffer", plain, st); if (rc) return rc;
+// Verdict mode (vst != NULL): what fails marks the whole block (*vst, a PNA_VERIFY_* status) instead of failing the call.
+static int walk_solid(pna_gpu_ctx *c, const XSolid &so, std::vector<uint8_t> &plain, std::vector<Inner> &inner, uint32_t flag[2], hipStream_t st, int *vst = nullptr) {
+    auto vfail = [&](int code, int status, const char *what) { if (!vst) return fail(c, code, what); *vst = status; inner.clear(); return (int)PNA_OK; };
+    int rc = decode_open(c, so, "solid stream buffer", &plain, st);
+    if (rc && vst && (rc == PNA_E_INVAL || rc == PNA_E_UNSUPPORTED)) return vfail(rc, rc == PNA_E_INVAL ? PNA_VERIFY_BAD_STREAM : PNA_VERIFY_UNSUPPORTED, "");
+    if (rc) return rc;
     std::vector<FrameDesc> ichunks; Inner ic; bool in_i = false;
     for (size_t q = 0; q < plain.size();) {
         PnaChunk ch;
         const int r = next_chunk(plain.data(), plain.size(), q, ch);
-        if (r) return fail(c, PNA_E_INVAL, r == CHUNK_SHORT_HEADER ? "solid stream: truncated chunk header" : "solid stream: truncated chunk body");
+        if (r) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, r == CHUNK_SHORT_HEADER ? "solid stream: truncated chunk header" : "solid stream: truncated chunk body");
         const bool fd = memcmp(ch.type, "FDAT", 4) == 0;
-        if (fd) { if (ch.len > 0xFFFFFFFBu) return fail(c, PNA_E_INVAL, "data chunk too long"); ichunks.push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
-        else if (!chunk_crc_ok(ch)) return fail(c, PNA_E_INVAL, "solid stream: chunk CRC mismatch");
+        if (fd) { if (ch.len > 0xFFFFFFFBu) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "data chunk too long"); ichunks.push_back(FrameDesc{ch.off, ch.len, 0, 8, 0}); }
+        else if (!chunk_crc_ok(ch)) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_CRC, "solid stream: chunk CRC mismatch");
         if (memcmp(ch.type, "FHED", 4) == 0) {
-            if (in_i || ch.len < 6 || ch.data[0] != 0 || ch.data[1] != 0) return fail(c, PNA_E_INVAL, "solid stream: bad entry header");
-            if (ch.data[3] != PNA_ALGO_STORE || ch.data[4] != PNA_ENC_NONE) return fail(c, PNA_E_UNSUPPORTED, "solid stream: inner entry that is not stored");
+            if (in_i || ch.len < 6 || ch.data[0] != 0 || ch.data[1] != 0) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: bad entry header");
+            if (ch.data[3] != PNA_ALGO_STORE || ch.data[4] != PNA_ENC_NONE) return vfail(PNA_E_UNSUPPORTED, PNA_VERIFY_UNSUPPORTED, "solid stream: inner entry that is not stored");
             ic = Inner(); in_i = true; ic.kind = ch.data[2]; ic.len = 0; ic.name.assign((const char *)ch.data + 6, ch.len - 6);
-        } else if (!in_i) { if (!(ch.type[0] & 0x20)) return fail(c, PNA_E_INVAL, "solid stream: unknown critical chunk"); }
+        } else if (!in_i) { if (!(ch.type[0] & 0x20)) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: unknown critical chunk"); }
         else if (fd) { ic.pieces.push_back(XPiece{ch.off + 8, ch.len}); ic.len += ch.len; }
         else if (memcmp(ch.type, "FEND", 4) == 0) { inner.push_back(std::move(ic)); in_i = false; }
-        else if (memcmp(ch.type, "fSIZ", 4) != 0 && !(ch.type[0] & 0x20)) return fail(c, PNA_E_INVAL, "solid stream: unknown critical chunk");
+        else if (memcmp(ch.type, "fSIZ", 4) != 0 && !(ch.type[0] & 0x20)) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: unknown critical chunk");
     }
-    if (in_i) return fail(c, PNA_E_INVAL, "solid stream: dangling chunks");
+    if (in_i) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: dangling chunks");
     if (ichunks.empty()) return PNA_OK;
     if (c->solid_desc.ensure(ichunks.size() * sizeof(FrameDesc) + 16)) return fail(c, PNA_E_NOMEM, "extract workspace");
     HIPCHK(c, hipMemcpyAsync(c->x_flag.p, flag0, 8, hipMemcpyHostToDevice, st));
@@ -460,7 +615,7 @@ static int walk_solid(pna_gpu_ctx *c, const XSolid &so, std::vector<uint8_t> &pl
     HIPCHK(c, hipMemcpyAsync(c->solid_desc.p, ichunks.data(), ichunks.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
     verify_chunks(c, c->solid_desc, ichunks, stored ? c->x_pk : c->solid_plain, "FDAT", st);
     rc = read_back(c, flag, c->x_flag.p, 8, st); if (rc) return rc;
-    if (flag[0]) return fail(c, PNA_E_INVAL, "solid stream: inner FDAT CRC mismatch");
+    if (flag[0]) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_CRC, "solid stream: inner FDAT CRC mismatch");
     return PNA_OK;
 }
 // ---- 4. the hand-out: entries in archive order, solid entries' inner entries in front of the normal entry that followed them
@@ -527,7 +682,7 @@ static int hand_out(XCall &x, std::shared_ptr<XOut> D, const XPlan &P, bool any_
 }
 
 // One window of the driver above: `a` / archive_len are the window's bytes, every offset in ents / dchunks / schunks / solids is relative to it.
-static int extract_window(XCall &x, const uint8_t *a, size_t archive_len, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks, std::vector<FrameDesc> &schunks,
+static int extract_window(XCall &x, const WinSrc &a, size_t archive_len, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks, std::vector<FrameDesc> &schunks,
                           std::vector<XSolid> &solids, int slot, XDeferred *later, XDeferred *prev) {
     pna_gpu_ctx *c = x.c;
     XPlan P;
@@ -552,7 +707,7 @@ static int extract_window(XCall &x, const uint8_t *a, size_t archive_len, std::v
     for (size_t i : P.nosize_idx) {                                   // compatibility path, one decode call per entry
         XEntry &e = ents[i];
         D->nosize_data.emplace_back();
-        rc = decode_open(c, e, "entry buffer", D->nosize_data.back(), st); if (rc) return rc;
+        rc = decode_open(c, e, "entry buffer", &D->nosize_data.back(), st); if (rc) return rc;
         e.raw_size = D->nosize_data.back().size(); e.raw_off = D->nosize_data.size() - 1;      // index into nosize_data
     }
     D->inner.resize(solids.size()); D->plain.resize(solids.size());
@@ -567,20 +722,47 @@ static int extract_window(XCall &x, const uint8_t *a, size_t archive_len, std::v
     return hand_out(x, D, P, any_store, defer, slot, later, st);
 }
 
+// ---- 2. windows: a run of entries whose archive bytes, packed payloads and decoded bytes stay within a few GiB each goes through the device at a time
+// (an archive of any size in host memory against a bounded footprint in HBM); a solid entry is a window of its own.  Moves the next window's entries,
+// chunks and solid entry out of the walk's lists, offsets relative to its first byte `base`.
+struct XWindow { std::vector<XEntry> we; std::vector<FrameDesc> wd, ws; std::vector<XSolid> wso; uint64_t base = 0, span = 0; };
+static void next_window(pna_gpu_ctx *c, std::vector<XEntry> &ents, const std::vector<FrameDesc> &dchunks, const std::vector<FrameDesc> &schunks,
+                        std::vector<XSolid> &solids, size_t &w0, size_t &si, XWindow &W) {
+    const size_t n_all = ents.size();
+    const uint64_t WIN = (uint64_t)c->tun.extract_win_mib << 20;  // 1 GiB of archive (and at most 3 GiB decoded) per window by default: small enough to pipeline, large enough for the kernels
+    if (si < solids.size() && solids[si].order <= w0) {
+        W.wso.push_back(std::move(solids[si++])); W.wso[0].order = 0;
+        W.base = W.wso[0].lo; W.span = W.wso[0].hi - W.base;
+        rebase(W.wso, schunks, W.wso[0].s0, W.wso[0].s1, W.ws, W.base);
+    } else {
+        size_t w1 = w0; uint64_t raw = 0, pk = 0;
+        const size_t stop = si < solids.size() ? std::min(n_all, solids[si].order) : n_all;
+        while (w1 < stop) {
+            const XEntry &e = ents[w1];
+            const uint64_t r = e.has_size ? e.raw_size : 0;
+            if (w1 > w0 && (e.hi - ents[w0].lo > WIN || raw + r > 3 * WIN || pk + e.stream_len > WIN)) break;
+            raw += r; pk += e.stream_len; w1++;
+        }
+        W.we.assign(std::make_move_iterator(ents.begin() + w0), std::make_move_iterator(ents.begin() + w1));
+        W.base = W.we.front().lo; W.span = W.we.back().hi - W.base;
+        rebase(W.we, dchunks, W.we.front().d0, W.we.back().d1, W.wd, W.base);
+        w0 = w1;
+    }
+}
+
 extern "C" int pna_gpu_extract_archive_host(pna_gpu_ctx *c, const void *archive, size_t archive_len, const void *password, size_t password_len,
                                             pna_entry_fn cb, void *user) {
     if (!c || !archive || !cb || (!password && password_len)) return fail(c, PNA_E_INVAL, "null argument");
     const uint8_t *a = (const uint8_t *)archive;
     if (archive_len < 8 + 20 + 12 || memcmp(a, PNA_SIGNATURE, 8) != 0) return fail(c, PNA_E_INVAL, "not a PNA archive");
+    const ArcParts ap{&a, &archive_len, 1, {0}};
     std::vector<XEntry> ents; std::vector<FrameDesc> dchunks, schunks; std::vector<XSolid> solids;
-    int rc = walk_archive(c, a, archive_len, ents, dchunks, schunks, solids);
+    bool broken = false;
+    int rc = walk_archive(c, ap, false, ents, dchunks, schunks, solids, &broken);
     if (rc) return rc;
-    // ---- 2. windows: a run of entries whose archive bytes, packed payloads and decoded bytes stay within a few GiB each goes through the
-    // device at a time (an archive of any size in host memory against a bounded footprint in HBM); a solid entry is a window of its own
     XCall x{c, password, password_len, cb, user, {}, 0};
     size_t si = 0, w0 = 0;
     const size_t n_all = ents.size();
-    const uint64_t WIN = (uint64_t)c->tun.extract_win_mib << 20;  // 1 GiB of archive (and at most 3 GiB decoded) per window by default: small enough to pipeline, large enough for the kernels
     // Windows are pipelined against each other: the decoded entries of window k travel to the host (their own stream, their own pair of
     // buffers) while window k + 1 is copied in and decoded; window k's entries are handed out once k + 1 has been launched, before k + 1's.
     XDeferred pending; int slot = 0;
@@ -591,32 +773,158 @@ extern "C" int pna_gpu_extract_archive_host(pna_gpu_ctx *c, const void *archive,
         return f.deliver();
     };
     while (w0 < n_all || si < solids.size()) {
-        std::vector<XEntry> we; std::vector<FrameDesc> wd, ws; std::vector<XSolid> wso;
-        uint64_t base, span;
-        if (si < solids.size() && solids[si].order <= w0) {
-            wso.push_back(std::move(solids[si++])); wso[0].order = 0;
-            base = wso[0].lo; span = wso[0].hi - base;
-            rebase(wso, schunks, wso[0].s0, wso[0].s1, ws, base);
-        } else {
-            size_t w1 = w0; uint64_t raw = 0, pk = 0;
-            const size_t stop = si < solids.size() ? std::min(n_all, solids[si].order) : n_all;
-            while (w1 < stop) {
-                const XEntry &e = ents[w1];
-                const uint64_t r = e.has_size ? e.raw_size : 0;
-                if (w1 > w0 && (e.hi - ents[w0].lo > WIN || raw + r > 3 * WIN || pk + e.stream_len > WIN)) break;
-                raw += r; pk += e.stream_len; w1++;
-            }
-            we.assign(std::make_move_iterator(ents.begin() + w0), std::make_move_iterator(ents.begin() + w1));
-            base = we.front().lo; span = we.back().hi - base;
-            rebase(we, dchunks, we.front().d0, we.back().d1, wd, base);
-            w0 = w1;
-        }
+        XWindow W;
+        next_window(c, ents, dchunks, schunks, solids, w0, si, W);
         XDeferred cur;
-        rc = extract_window(x, a + base, (size_t)span, we, wd, ws, wso, slot, &cur, pending ? &pending : nullptr);
+        rc = extract_window(x, WinSrc{&ap, W.base}, (size_t)W.span, W.we, W.wd, W.ws, W.wso, slot, &cur, pending ? &pending : nullptr);
         const int rc2 = finish_pending();
         if (rc == PNA_OK) rc = rc2;
         if (rc != PNA_OK) { (void)hipDeviceSynchronize(); return rc; }
         pending = std::move(cur); slot ^= 1;
     }
     return finish_pending();
+}
+
+// ---- `pna verify` (pna_gpu_verify_archive_host): the same stages in verdict mode.  One window: its bytes and the data chunks' CRC verdicts (one word per
+// chunk), CTR / CBC / GCM with their verdicts kept on the device (CBC plaintext lengths, one word per GCM segment), k_verdict folding them with the walk's
+// findings into one status word per record -- the only read-back besides the decoders' own --, then the records that passed are decoded into the device's
+// raw buffer and dropped: nothing decoded goes to the host (solid streams excepted: their inner entries are walked on the host, as extract does).
+struct VCall {
+    pna_verify_fn cb; void *user; pna_verify_summary sum{};
+};
+static int emit(XCall &x, VCall &v, const char *name, int kind, int status, uint32_t flags, uint64_t size) {
+    static const char *const what[] = {"", "encrypted, no password given", "chunk CRC mismatch", "broken chunk structure", "authentication failed (wrong password or tampering)",
+                                       "bad CBC length or padding (wrong password or damaged data)", "corrupt stream", "not decoded by this build"};
+    const char *detail = status >= 0 && status <= PNA_VERIFY_UNSUPPORTED ? what[status] : "";
+    v.sum.total++;
+    if (status == PNA_VERIFY_OK) v.sum.ok++;
+    else if (status == PNA_VERIFY_SKIPPED) v.sum.skipped++;
+    else if (status == PNA_VERIFY_UNSUPPORTED) v.sum.unsupported++;
+    else { v.sum.failed++; if (flags & PNA_VERIFY_UNAUTHENTICATED) v.sum.unauthenticated_failure = 1; }
+    if (v.cb(v.user, x.index++, name, kind, status, flags, size, detail) != 0) return fail(x.c, PNA_E_SINK, "verify callback failed");
+    return PNA_OK;
+}
+static uint32_t fail_flags(const XStream &s, int status) {     // CTR / CBC: a failure after the CRC check may be a wrong password (verify.rs is_unauthenticated)
+    return (status == PNA_VERIFY_BAD_DECRYPT || status == PNA_VERIFY_BAD_STREAM || status == PNA_VERIFY_BAD_AUTH) ? (s.vfl & PNA_VERIFY_UNAUTHENTICATED) : 0u;
+}
+static int verify_window(XCall &x, VCall &v, const WinSrc &a, size_t span, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks,
+                         std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids) {
+    pna_gpu_ctx *c = x.c;
+    XPlan P;
+    int rc = plan_window(x, a, ents, solids, P); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    uint32_t flag[2] = {0, 0};
+    rc = upload_window(c, a, span, dchunks, schunks, P, 0, flag, st, true); if (rc) return rc;
+    if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
+    if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
+    // the fold: one VerdictEnt per record (the window's entries, or its solid entry), one status word back per record
+    std::vector<VerdictEnt> ve;
+    const size_t d_base = ents.empty() ? 0 : ents.front().d0;
+    for (const XEntry &e : ents) ve.push_back(VerdictEnt{(uint32_t)(e.d0 - d_base), (uint32_t)(e.d1 - d_base), e.g0, e.g1, e.cbc_unit, (uint32_t)e.vst});
+    for (const XSolid &so : solids) ve.push_back(VerdictEnt{0u, (uint32_t)schunks.size(), so.g0, so.g1, so.cbc_unit, (uint32_t)so.vst});
+    std::vector<uint32_t> vs(ve.size());
+    if (!ve.empty()) {
+        if (c->v_ent.ensure(ve.size() * sizeof(VerdictEnt) + 16) || c->v_out.ensure(ve.size() * 4 + 16)) return fail(c, PNA_E_NOMEM, "verify workspace");
+        HIPCHK(c, hipMemcpyAsync(c->v_ent.p, ve.data(), ve.size() * sizeof(VerdictEnt), hipMemcpyHostToDevice, st));
+        launch_verdict((const VerdictEnt *)c->v_ent.p, (uint32_t)ve.size(), (const uint32_t *)c->v_crc.p, (const uint32_t *)c->v_seg.p, (const uint32_t *)c->x_plen.p,
+                       (uint32_t *)c->v_out.p, st);
+        rc = read_back(c, vs.data(), c->v_out.p, vs.size() * 4, st); if (rc) return rc;
+    }
+    if (!solids.empty()) {                                             // a solid entry: one record for the block, or one per inner entry
+        const XSolid &so = solids[0];
+        int status = (int)vs[0];
+        if (!x.fast && status == PNA_VERIFY_OK) {
+            std::vector<uint8_t> plain; std::vector<Inner> inner; int vst = 0;
+            rc = walk_solid(c, so, plain, inner, flag, st, &vst); if (rc) return rc;
+            if (!vst) {
+                for (const Inner &ie : inner) {
+                    std::string path;
+                    const bool named = entry_path(c, ie.name, path) == PNA_OK;
+                    rc = emit(x, v, named ? path.c_str() : nullptr, ie.kind, named ? PNA_VERIFY_OK : PNA_VERIFY_BAD_STRUCTURE, 0u, ie.len); if (rc) return rc;
+                }
+                return PNA_OK;
+            }
+            status = vst;
+        }
+        return emit(x, v, nullptr, PNA_VERIFY_KIND_SOLID, status, fail_flags(so, status), 0);
+    }
+    std::vector<uint64_t> size(ents.size(), 0); std::vector<uint32_t> flags(ents.size(), 0);
+    for (size_t i = 0; i < ents.size(); i++) {
+        XEntry &e = ents[i];
+        if (x.fast || vs[i]) continue;
+        if (e.compression == PNA_ALGO_STORE) { size[i] = e.pay_len; if (e.has_size && e.raw_size != e.pay_len) flags[i] |= PNA_VERIFY_SIZE_HINT; }
+    }
+    // the entries with fSIZ that passed so far: one decode call per codec into the raw buffer, a status per entry; a stream whose size disagrees with its
+    // fSIZ (status 3) is decoded once more without it (the reference reads an entry to its end and only warns about a wrong fSIZ), a corrupt one is not
+    std::vector<size_t> retry;
+    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE}) {
+        if (x.fast) break;
+        std::vector<uint64_t> so, sl, dof, rl; std::vector<size_t> idx;
+        for (size_t i = 0; i < ents.size(); i++) {
+            const XEntry &e = ents[i];
+            if (!vs[i] && e.compression == algo && e.has_size && !e.odd_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); idx.push_back(i); }
+        }
+        if (so.empty()) continue;
+        std::vector<uint32_t> es(so.size(), 0);
+        rc = decode_batch_status(c, algo, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[0].p, dof.data(), rl.data(), es.data(), st); if (rc) return rc;
+        for (size_t k = 0; k < idx.size(); k++) {
+            const size_t i = idx[k];
+            if (es[k] == 0) size[i] = ents[i].raw_size;
+            else if (es[k] == 2) vs[i] = PNA_VERIFY_UNSUPPORTED;
+            else if (es[k] == 3) retry.push_back(i);                     // the stream does not hold fSIZ bytes: measured and decoded without it
+            else vs[i] = PNA_VERIFY_BAD_STREAM;
+        }
+    }
+    for (size_t i : P.nosize_idx) if (!vs[i]) retry.push_back(i);   // (entries without fSIZ, or with one out of proportion to their data)
+    for (size_t i : retry) {
+        XEntry &e = ents[i];
+        uint64_t got = 0;
+        rc = decode_open(c, e, "entry buffer", nullptr, st, &got);
+        if (rc == PNA_E_INVAL || rc == PNA_E_UNSUPPORTED) { vs[i] = rc == PNA_E_INVAL ? PNA_VERIFY_BAD_STREAM : PNA_VERIFY_UNSUPPORTED; continue; }
+        if (rc) return rc;
+        size[i] = got;
+        if (e.has_size && got != e.raw_size) flags[i] |= PNA_VERIFY_SIZE_HINT;
+    }
+    for (size_t i = 0; i < ents.size(); i++) {
+        const XEntry &e = ents[i];
+        int status = (int)vs[i];
+        std::string path; const char *name = nullptr;
+        if (!e.noname) {
+            if (entry_path(c, e.name, path) == PNA_OK) name = path.c_str();
+            else if (status == PNA_VERIFY_OK) status = PNA_VERIFY_BAD_STRUCTURE;      // a name that is not UTF-8 (InvalidData in the reference)
+        }
+        if (status != PNA_VERIFY_OK) size[i] = 0;
+        rc = emit(x, v, name, e.kind, status, status == PNA_VERIFY_OK ? flags[i] : fail_flags(e, status), size[i]); if (rc) return rc;
+    }
+    return PNA_OK;
+}
+
+extern "C" int pna_gpu_verify_archive_host(pna_gpu_ctx *c, const void *const *parts, const size_t *part_len, size_t n_parts, const void *password,
+                                           size_t password_len, uint32_t vflags, pna_verify_fn cb, void *user, pna_verify_summary *summary) {
+    if (!c || !parts || !part_len || !n_parts || !cb || (!password && password_len)) return fail(c, PNA_E_INVAL, "null argument");
+    if (vflags & ~(uint32_t)PNA_VERIFY_FAST) return fail(c, PNA_E_INVAL, "unknown verify flag");
+    for (size_t k = 0; k < n_parts; k++) if (!parts[k]) return fail(c, PNA_E_INVAL, "null argument");
+    if (part_len[0] < 8 || memcmp(parts[0], PNA_SIGNATURE, 8) != 0) return fail(c, PNA_E_INVAL, "not a PNA archive");
+    if (!launch_frame_verdict || !launch_verdict || !launch_gcm_verdict) return fail(c, PNA_E_UNSUPPORTED, "this build has no verdict kernels");
+    ArcParts ap{(const uint8_t *const *)parts, part_len, n_parts, {}};
+    uint64_t at = 0;
+    for (size_t k = 0; k < n_parts; k++) { ap.vb.push_back(at); at += part_len[k]; }
+    const bool fast = (vflags & PNA_VERIFY_FAST) != 0;
+    XCall x{c, fast ? nullptr : password, fast ? 0 : password_len, nullptr, nullptr, {}, 0};
+    x.verdict = true; x.fast = fast;
+    VCall v{cb, user};
+    std::vector<XEntry> ents; std::vector<FrameDesc> dchunks, schunks; std::vector<XSolid> solids;
+    bool broken = false;
+    int rc = walk_archive(c, ap, true, ents, dchunks, schunks, solids, &broken);
+    size_t si = 0, w0 = 0;
+    while (rc == PNA_OK && (w0 < ents.size() || si < solids.size())) {
+        XWindow W;
+        next_window(c, ents, dchunks, schunks, solids, w0, si, W);
+        rc = verify_window(x, v, WinSrc{&ap, W.base}, (size_t)W.span, W.we, W.wd, W.ws, W.wso);
+    }
+    if (rc) (void)hipDeviceSynchronize();
+    if (rc == PNA_OK && broken) { v.sum.broken = 1; rc = fail(c, PNA_E_INVAL, "archive structure is broken; verification aborted"); }
+    if (summary) *summary = v.sum;
+    return rc;
 }
