@@ -107,6 +107,7 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
  *   "strong_gtab" [PNA_STRONG_GTAB]       zstd levels 10..22 with the hash table in global memory (1, default) or in LDS (0)
  *   "lit_beside_seq" [PNA_LIT_BESIDE_SEQ] large zstd batches: the literal coder on a second stream next to the sequence coder (1, default)
  *   "max_chunk_size" [PNA_MAX_CHUNK_SIZE] (FDAT chunk size of the entry points without such a parameter), "sub_mib" [PNA_SUB_MIB], "stage_threads" [PNA_STAGE_THREADS],
+ *   "diff_slot_mib" [PNA_DIFF_SLOT_MIB]   pna_gpu_diff_archive_host: MiB of each of the two page-locked (and two device) slots the files' bytes travel through (256)
  *   "extract_win_mib" [PNA_EXTRACT_WIN_MIB], "batch_piece_mib" [PNA_BATCH_PIECE_MIB], "inflate_serial" [PNA_INFLATE_SERIAL],
  *   "zdec_serial" [PNA_ZDEC_SERIAL], "zdec_dbg" [PNA_ZDEC_DBG] (diagnostics of the one-workgroup zstd decoder: bit 8 = small re-base distances, for its test), "stream_pool_mib" [PNA_STREAM_POOL_MIB], "stream_linger_us" [PNA_STREAM_LINGER_US] (-1 = adaptive): DESIGN.md. */
 int  pna_gpu_set_option(pna_gpu_ctx *ctx, const char *name, long value);
@@ -402,6 +403,60 @@ typedef int (*pna_verify_fn)(void *user, size_t index, const char *name /* NULL 
 int  pna_gpu_verify_archive_host(pna_gpu_ctx *ctx, const void *const *parts, const size_t *part_len, size_t n_parts,
                                  const void *password, size_t password_len, uint32_t vflags,
                                  pna_verify_fn cb, void *user, pna_verify_summary *summary);
+
+/* `pna experimental diff` (cli/src/command/diff.rs diff_archive -> compare_entry -> streams_equal(fs_file, entry.reader())): is the archive still
+ * equal to the files, and if not, which entries differ and from which byte.  The verify driver above with a second input: for every entry the host
+ * is asked for the filesystem side (`source`), the files' bytes are copied to the device next to the decoded entries -- through two page-locked
+ * slots of option "diff_slot_mib" [PNA_DIFF_SLOT_MIB] (default 256) MiB each and two device slots of that size, on a stream of their own, a file
+ * larger than a slot in pieces -- and k_diff finds the first differing byte of every entry.  No decoded byte of a normal entry goes to the host; a solid
+ * stream is copied to the host once to walk its inner headers (as verify does) and its inner entries are compared on the device where the stream lies.
+ *   source: called once per entry that has a readable name, in archive order, before the entry is decrypted or decoded; it fills *out: fs_kind, and
+ *     for PNA_DIFF_FS_FILE the file's bytes, for PNA_DIFF_FS_SYMLINK the link's target bytes.  `data` must stay valid until that entry's record
+ *     callback has been called, and not longer (a host may mmap per entry and munmap in the record callback).  Bytes that lie in a buffer of
+ *     pna_gpu_host_alloc are copied from there without staging.  stored_size is the entry's fSIZ, UINT64_MAX if it has none.  PNA_DIFF_FS_IGNORE is
+ *     the host's filter: the entry is not compared.  A non-zero return ends the call with PNA_E_SINK.
+ *   cb: one record per entry in archive order; index / name / kind as in verify (PNA_VERIFY_KIND_SOLID for a solid block that is skipped or fails,
+ *     PNA_VERIFY_KIND_BROKEN for chunks of no readable header; name NULL where verify's is).  status, following compare_entry (diff.rs:336-421):
+ *       SAME; MISSING; TYPE_MISMATCH (entry kind against fs_kind); SIZE_DIFFERS -- fSIZ present and != len, decided before anything of the entry is
+ *       decrypted or decoded (diff.rs:361-365); CONTENTS_DIFFER -- every other difference of a file's content, a stream without fSIZ (or whose fSIZ
+ *       equals len) that decodes to another length included; SYMLINK_DIFFERS; NOT_COMPARED (PNA_DIFF_FS_IGNORE, directories, hard links, other
+ *       kinds); SKIPPED (encrypted, no password); DAMAGED -- a compared entry that fails a check: verify_status is the PNA_VERIFY_* status verify
+ *       gives that entry and flags carries PNA_VERIFY_UNAUTHENTICATED where verify sets it.  MISSING, TYPE_MISMATCH, SIZE_DIFFERS and NOT_COMPARED
+ *       entries are not gathered, decrypted or decoded; their chunks' CRCs are still checked and the finding is their verify_status (0 = none).
+ *     first_diff: CONTENTS_DIFFER / SYMLINK_DIFFERS -- the offset of the first byte that differs; where one side is a strict prefix of the other, the
+ *       shorter length.  UINT64_MAX otherwise.  (The reference does not report it.)  size: the entry's decoded bytes where it was decoded, else 0.
+ *     link_target: hard-link entries whose path is a file on the host (PNA_DIFF_FS_FILE) are NOT_COMPARED and their decoded target (at most 64 KiB)
+ *       is handed out here, NUL-terminated -- whether two paths are the same file is the host's question (is_same_file).  NULL otherwise.
+ *   Mode, mtime, uid / gid and the other metadata chunks stay with the host (compare_file_metadata: metadata interpretation is not this library's).
+ * The walk goes on after damage; return codes, summary->broken and the callback-error rule (PNA_E_SINK) as in verify.  PNA_E_UNSUPPORTED in a build
+ * without k_diff.  Page-locked memory: the two slots (pna_gpu_debug_pinned_bytes shows them), whatever the archive's size. */
+#define PNA_DIFF_FS_MISSING   0
+#define PNA_DIFF_FS_FILE      1
+#define PNA_DIFF_FS_DIR       2
+#define PNA_DIFF_FS_SYMLINK   3    /* data = the link's target bytes */
+#define PNA_DIFF_FS_OTHER     4
+#define PNA_DIFF_FS_IGNORE    5    /* the host's filter: entry not compared */
+#define PNA_DIFF_SAME             0
+#define PNA_DIFF_MISSING          1
+#define PNA_DIFF_TYPE_MISMATCH    2
+#define PNA_DIFF_SIZE_DIFFERS     3
+#define PNA_DIFF_CONTENTS_DIFFER  4
+#define PNA_DIFF_SYMLINK_DIFFERS  5
+#define PNA_DIFF_NOT_COMPARED     6
+#define PNA_DIFF_SKIPPED          7
+#define PNA_DIFF_DAMAGED          8
+typedef struct { int fs_kind; const void *data; uint64_t len; } pna_diff_file;
+typedef struct { uint64_t total, same, differ /* missing + type + size + contents + symlink */, not_compared, skipped, damaged; uint32_t broken, pad; } pna_diff_summary;
+typedef int (*pna_diff_source_fn)(void *user, size_t index, const char *name, int kind, uint64_t stored_size /* fSIZ, UINT64_MAX if none */,
+                                  pna_diff_file *out);
+typedef int (*pna_diff_fn)(void *user, size_t index, const char *name /* NULL if unknown */, int kind, int status, int verify_status, uint32_t flags,
+                           uint64_t size, uint64_t first_diff, const char *link_target);
+int  pna_gpu_diff_archive_host(pna_gpu_ctx *ctx, const void *const *parts, const size_t *part_len, size_t n_parts,
+                               const void *password, size_t password_len, pna_diff_source_fn source, pna_diff_fn cb, void *user,
+                               pna_diff_summary *summary);
+/* The latest pna_gpu_diff_archive_host call of the context: streams handed to the decoders, bytes k_diff compared, its HIP-event time (any pointer may
+ * be NULL).  Tests pin "SIZE_DIFFERS costs no decode" with it; not on any product path. */
+int  pna_gpu_debug_diff_stats(pna_gpu_ctx *ctx, uint64_t *decoded_streams, uint64_t *compared_bytes, double *ms_k_diff);
 
 /* pna_gpu_create_archive_host for ONE PART of an archive (PNA_PART_HEAD: signature + AHED first, PNA_PART_TAIL: AEND last): what
  * `pna append` writes behind the existing entries (PNA_PART_TAIL only) and `pna update` for the entries it re-creates (neither flag). */

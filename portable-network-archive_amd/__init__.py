@@ -10,6 +10,7 @@ There is no CPU fallback: if the HIP extension is missing or no GPU is usable, c
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 from typing import Iterable, List, Optional, Sequence
@@ -115,6 +116,30 @@ class VerifySummary(ctypes.Structure):
     _fields_ = [("total", ctypes.c_uint64), ("ok", ctypes.c_uint64), ("failed", ctypes.c_uint64), ("skipped", ctypes.c_uint64),
                 ("unsupported", ctypes.c_uint64), ("unauthenticated_failure", ctypes.c_uint32), ("broken", ctypes.c_uint32)]
 
+# pna_gpu_diff_archive_host (include/pna_gpu.h): what the host's side of an entry is, record statuses
+DIFF_FS_MISSING, DIFF_FS_FILE, DIFF_FS_DIR, DIFF_FS_SYMLINK, DIFF_FS_OTHER, DIFF_FS_IGNORE = range(6)
+(DIFF_SAME, DIFF_MISSING, DIFF_TYPE_MISMATCH, DIFF_SIZE_DIFFERS, DIFF_CONTENTS_DIFFER, DIFF_SYMLINK_DIFFERS, DIFF_NOT_COMPARED, DIFF_SKIPPED,
+ DIFF_DAMAGED) = range(9)
+DIFF_NO_OFFSET = (1 << 64) - 1                                  # first_diff of a record that has none
+DIFF_TILE = 16384                                               # bytes one wave of k_diff compares (pna_dev.h DIFF_TILE)
+
+
+class DiffFile(ctypes.Structure):
+    """pna_diff_file (include/pna_gpu.h)."""
+    _fields_ = [("fs_kind", ctypes.c_int), ("data", ctypes.c_void_p), ("len", ctypes.c_uint64)]
+
+
+class DiffSummary(ctypes.Structure):
+    """pna_diff_summary (include/pna_gpu.h)."""
+    _fields_ = [("total", ctypes.c_uint64), ("same", ctypes.c_uint64), ("differ", ctypes.c_uint64), ("not_compared", ctypes.c_uint64),
+                ("skipped", ctypes.c_uint64), ("damaged", ctypes.c_uint64), ("broken", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+DIFF_SOURCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(DiffFile))
+DIFF_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p)
+DiffRecord = collections.namedtuple("DiffRecord", "name kind status verify_status flags size first_diff link_target")
+
 _lib = None
 
 EXPORTS = [
@@ -141,6 +166,8 @@ EXPORTS = [
     "pna_gpu_stream_entry_finish", "pna_gpu_stream_entry_abort",
     # pna verify (include/pna_gpu.h)
     "pna_gpu_verify_archive_host",
+    # pna diff (include/pna_gpu.h)
+    "pna_gpu_diff_archive_host", "pna_gpu_debug_diff_stats",
 ]
 
 
@@ -262,6 +289,11 @@ def load_library() -> ctypes.CDLL:
     L.pna_gpu_verify_archive_host.restype = ctypes.c_int
     L.pna_gpu_verify_archive_host.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz, ctypes.c_char_p, sz, ctypes.c_uint32,
                                               VERIFY_FN, vp, ctypes.POINTER(VerifySummary)]
+    L.pna_gpu_diff_archive_host.restype = ctypes.c_int
+    L.pna_gpu_diff_archive_host.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz, ctypes.c_char_p, sz, DIFF_SOURCE_FN, DIFF_FN, vp,
+                                            ctypes.POINTER(DiffSummary)]
+    L.pna_gpu_debug_diff_stats.restype = ctypes.c_int
+    L.pna_gpu_debug_diff_stats.argtypes = [vp, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
     L.pna_gpu_open_size_device.restype = ctypes.c_int
     L.pna_gpu_open_size_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.POINTER(ctypes.c_int), vp]
     L.pna_gpu_inflate_open_device.restype = ctypes.c_int
@@ -1018,6 +1050,69 @@ def verify_archive(ctx: Context, archive_or_parts, password: Optional[bytes] = N
     out = {f: getattr(summ, f) for f, _ in VerifySummary._fields_}
     out["rc"] = rc
     return recs, out
+
+
+def diff_archive(ctx: Context, archive_or_parts, source, password: Optional[bytes] = None):
+    """`pna experimental diff` (pna_gpu_diff_archive_host): the archive's entries against the host's files, compared on the device.
+    `source`: a mapping path -> bytes (a path that is absent is a missing file), or a callable (index, path, kind, stored_size) -> (fs_kind, data)
+    (DIFF_FS_* constants; data: bytes-like, or None; a (address, length) pair names memory the caller keeps alive until the entry's record, e.g. inside a
+    Context.host_alloc buffer, which is copied without staging).  Returns (records, summary): records are DiffRecord tuples in archive order (DIFF_*
+    statuses; first_diff is None where the record has none), summary a dict of pna_diff_summary's fields plus "rc" as in verify_archive."""
+    parts = [archive_or_parts] if isinstance(archive_or_parts, (bytes, bytearray, memoryview)) else list(archive_or_parts)
+    keep = [p if isinstance(p, bytes) else bytes(p) for p in parts]
+    n = len(keep)
+    arr = (ctypes.c_char_p * max(n, 1))(*keep)
+    lens = (ctypes.c_size_t * max(n, 1))(*[len(p) for p in keep])
+    recs, held, err = [], {}, []
+
+    def _src(_u, idx, name, kind, stored, out):
+        try:
+            path = name.decode("utf-8")
+            if callable(source):
+                fs_kind, data = source(idx, path, kind, None if stored == DIFF_NO_OFFSET else stored)
+            else:
+                data = source.get(path)
+                fs_kind = DIFF_FS_MISSING if data is None else DIFF_FS_FILE
+            out[0].fs_kind, out[0].data, out[0].len = fs_kind, None, 0
+            if data is not None and fs_kind in (DIFF_FS_FILE, DIFF_FS_SYMLINK):
+                if isinstance(data, tuple):
+                    out[0].data, out[0].len = data
+                elif len(data):
+                    if not isinstance(data, bytes):
+                        try:
+                            data = (ctypes.c_char * len(data)).from_buffer(data)        # (a writable buffer: bytearray, numpy array, mmap -- no copy)
+                        except TypeError:
+                            data = bytes(data)
+                    held[idx] = data                            # alive until the entry's record
+                    out[0].data = ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value if isinstance(data, bytes) else ctypes.addressof(data)
+                    out[0].len = len(data)
+            return 0
+        except Exception as e:  # noqa: BLE001 - reported through the call's return code
+            err.append(e)
+            return 1
+
+    def _cb(_u, idx, name, kind, status, vstatus, flags, size, first, link):
+        held.pop(idx, None)
+        recs.append(DiffRecord(name.decode("utf-8") if name is not None else None, kind, status, vstatus, flags, size,
+                               None if first == DIFF_NO_OFFSET else first, link))
+        return 0
+    src_cb, cb = DIFF_SOURCE_FN(_src), DIFF_FN(_cb)
+    summ = DiffSummary()
+    rc = ctx._L.pna_gpu_diff_archive_host(ctx._h, arr, lens, n, password, len(password) if password else 0, src_cb, cb, None, ctypes.byref(summ))
+    if err:
+        raise err[0]
+    if rc != PNA_OK and not (rc == E_INVAL and summ.broken):
+        ctx._check(rc)
+    out = {f: getattr(summ, f) for f, _ in DiffSummary._fields_ if f != "pad"}
+    out["rc"] = rc
+    return recs, out
+
+
+def diff_stats(ctx: Context):
+    """(streams handed to the decoders, bytes compared by k_diff, k_diff's HIP-event milliseconds) of the context's latest diff_archive call."""
+    a, b, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
+    ctx._check(ctx._L.pna_gpu_debug_diff_stats(ctx._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(ms)))
+    return a.value, b.value, ms.value
 
 
 def kdf_argon2(kind: int, password: bytes, salt: bytes, t_cost: int, m_cost_kib: int, lanes: int, key_len: int = 32) -> bytes:

@@ -67,6 +67,8 @@ void launch_frame_verify(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, con
 // `pna verify`'s kernels (weak: the sanitizer build has no stand-ins for them, pna_gpu_verify_archive_host refuses to run there)
 __attribute__((weak)) void launch_frame_verdict(const FrameDesc *fd, uint32_t n, const CrcTabs *ct, const uint8_t *buf, uint64_t cap16, const char ty[4], uint32_t *verdict, hipStream_t st, uint32_t max_payload);
 __attribute__((weak)) void launch_verdict(const VerdictEnt *ve, uint32_t n, const uint32_t *crc_v, const uint32_t *gcm_v, const uint32_t *cbc_plen, uint32_t *out, hipStream_t st);
+// `pna diff`'s kernel (k_diff.hip; weak like the verdict kernels: pna_gpu_diff_archive_host refuses to run without it)
+__attribute__((weak)) void launch_diff(const DiffPiece *pieces, uint32_t npieces, uint32_t ntiles, const uint8_t *a, const uint8_t *b, unsigned long long *first, hipStream_t st);
 void launch_zdec(ZFrame *frames, uint32_t n, const uint8_t *src, uint8_t *dst, uint8_t *lit_scratch, uint32_t dbg, hipStream_t st);
 void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *dst, hipStream_t st);
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st);
@@ -169,6 +171,12 @@ struct PinBuf {                                  // page-locked host staging: as
         if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return -1; }
         cap = want; return 0;
     }
+    int ensure_exact(size_t n) {                 // no headroom: a buffer whose size is a documented bound
+        if (n <= cap) return 0;
+        release();
+        if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) { p = nullptr; return -1; }
+        cap = n; return 0;
+    }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
@@ -184,6 +192,7 @@ struct Tuning {
     long sub_mib = 256;              // PNA_SUB_MIB: largest sub-batch (input bytes) of the bounded host pipeline
     long stage_threads = 0;          // PNA_STAGE_THREADS: host threads that stage entries into page-locked memory (0: min(8, cores / 2))
     long extract_win_mib = 1024;     // PNA_EXTRACT_WIN_MIB: archive bytes per window of the extract driver
+    long diff_slot_mib = 256;        // PNA_DIFF_SLOT_MIB: pna_gpu_diff_archive_host carries the files' bytes to the device through two page-locked slots of this many MiB (and two device slots)
     long solid_win_mib = 256;        // PNA_SOLID_WIN_MIB: pna_gpu_create_solid_archive_host takes the serialised inner entries through in windows of this many MiB (page-locked memory: ~4 windows)
     long batch_piece_mib = 256;      // PNA_BATCH_PIECE_MIB: pna_gpu_compress_batch takes a large batch through in pieces of this size (0: one piece)
     long inflate_serial = 0;         // PNA_INFLATE_SERIAL: deflate decoding on the wave-per-stream walk only
@@ -256,6 +265,11 @@ struct pna_gpu_ctx {
     PinBuf h_entoff;
     DevBuf x_arc, x_pk, x_raw[2], x_desc, x_place, x_flag, x_tags, x_plen, aes_dtabs;
     DevBuf v_crc, v_seg, v_ent, v_out;   // pna verify: chunk and segment verdicts, the records' VerdictEnt, their status words
+    // pna diff: the files' bytes travel through two page-locked slots (df_pin) into two device slots (df_dev) on a stream of their own; df_ev_cp[s]: slot s is on the
+    // device, df_ev_k[s]: the k_diff launches that read it are done; the piece lists, first[] of the window's records; event pairs around the k_diff launches
+    PinBuf df_pin[2]; DevBuf df_dev[2], df_pieces, df_first;
+    hipStream_t df_cp = nullptr; hipEvent_t df_ev_cp[2] = {}, df_ev_k[2] = {}; std::vector<hipEvent_t> df_tev; size_t df_tused = 0;
+    uint64_t df_streams = 0, df_bytes = 0; double df_ms = 0;   // the latest diff call: streams handed to the decoders, bytes compared by k_diff, its HIP-event time
     hipStream_t x_cp = nullptr; hipEvent_t x_ev[2] = {}, x_done = nullptr;   // extract driver: D2H of window k on x_cp next to window k+1's work
     bool aes_dec_ready = false;        // read side (pna_gpu_extract_archive_host): archive image, packed payloads, decoded entries
     DevBuf z_vp, z_pb, z_mode;                                 // lane-per-piece inflate: piece list, piece boundaries, per-stream mode

@@ -175,6 +175,14 @@ struct GcmEntry {            // k_gcm_tag: one GCM segment (this library writes 
 struct VerdictEnt {
     uint32_t c0, c1, g0, g1, cbc_unit, pre;
 };
+// k_diff (`pna diff`): bytes [base, base + len) of record `entry` -- the decoded side at a_off of the launch's a buffer, the file's side at b_off of its
+// b buffer (a_off and b_off congruent mod 16: the driver places the file bytes).  A piece is DIFF_TILE-byte tiles tile0, tile0 + 1, ... of the launch.
+constexpr uint32_t DIFF_TILE = 16384;
+struct DiffPiece {
+    uint64_t a_off, b_off, len, base;
+    uint32_t entry, tile0;
+};
+static_assert(sizeof(DiffPiece) == 40, "DiffPiece layout");
 
 // zstd decoder (k_zdec): one descriptor per frame
 struct ZFrame {

@@ -50,12 +50,13 @@ struct XEntry : XStream {
     bool has_size = false; uint64_t raw_size = 0, raw_off = 0; // fSIZ; decoded bytes in the raw buffer
     bool noname = false, odd_size = false;                     // verdict mode: FHED unreadable (the record has no name); fSIZ out of proportion (decoded as without one)
     size_t d0 = 0, d1 = 0;                                     // its FDAT chunks in the descriptor list
+    bool nodecode = false;                                     // `pna diff`: settled without its bytes (missing, type, size, not compared) -- its chunks' CRCs are checked, nothing is gathered or decoded
 };
 struct XSolid : XStream {                                      // SHED [PHSF] SDAT* SEND -- lib/src/entry.rs:465-484,567-583
     size_t order = 0;                                          // number of normal entries in front of it
     size_t s0 = 0, s1 = 0;                                     // its SDAT chunks in the descriptor list
 };
-struct Inner { std::string name; int kind; std::vector<XPiece> pieces; uint64_t len; };     // an entry of a decoded solid stream
+struct Inner { std::string name; int kind; std::vector<XPiece> pieces; uint64_t len; bool has_size = false; uint64_t raw_size = 0; };     // an entry of a decoded solid stream (its fSIZ: `pna diff`)
 // one call of the driver: the caller's arguments, the keys derived so far (one derivation per distinct PHSF string), the next entry's index
 struct XCall {
     pna_gpu_ctx *c; const void *password; size_t password_len; pna_entry_fn cb; void *user;
@@ -342,7 +343,7 @@ static int plan_window(XCall &x, const WinSrc &a, std::vector<XEntry> &ents, std
     if (x.fast) return PNA_OK;                                        // verify --fast: chunk structure and CRCs, nothing gathered, decrypted or decoded
     for (size_t i = 0; i < ents.size(); i++) {
         XEntry &e = ents[i];
-        if (x.verdict && e.vst) continue;                              // (a structural fault found by the walk: nothing to decode)
+        if (x.verdict && (e.vst || e.nodecode)) continue;              // (a structural fault found by the walk, or `pna diff` needs no byte of it: nothing to decode)
         if (!decoded_here(e.compression)) { if (x.verdict) { e.vst = PNA_VERIFY_UNSUPPORTED; continue; } return fail(c, PNA_E_UNSUPPORTED, "compression method not decoded on the device (xz)"); }
         const int r = plan_stream(x, a, e, P); if (r) return r;
         if (e.vst) continue;
@@ -604,6 +605,7 @@ static int walk_solid(pna_gpu_ctx *c, const XSolid &so, std::vector<uint8_t> &pl
         } else if (!in_i) { if (!(ch.type[0] & 0x20)) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: unknown critical chunk"); }
         else if (fd) { ic.pieces.push_back(XPiece{ch.off + 8, ch.len}); ic.len += ch.len; }
         else if (memcmp(ch.type, "FEND", 4) == 0) { inner.push_back(std::move(ic)); in_i = false; }
+        else if (memcmp(ch.type, "fSIZ", 4) == 0 && ch.len <= 8) { ic.has_size = true; ic.raw_size = 0; for (uint32_t i = 0; i < ch.len; i++) ic.raw_size = (ic.raw_size << 8) | ch.data[i]; }
         else if (memcmp(ch.type, "fSIZ", 4) != 0 && !(ch.type[0] & 0x20)) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: unknown critical chunk");
     }
     if (in_i) return vfail(PNA_E_INVAL, PNA_VERIFY_BAD_STRUCTURE, "solid stream: dangling chunks");
@@ -807,14 +809,11 @@ static int emit(XCall &x, VCall &v, const char *name, int kind, int status, uint
 static uint32_t fail_flags(const XStream &s, int status) {     // CTR / CBC: a failure after the CRC check may be a wrong password (verify.rs is_unauthenticated)
     return (status == PNA_VERIFY_BAD_DECRYPT || status == PNA_VERIFY_BAD_STREAM || status == PNA_VERIFY_BAD_AUTH) ? (s.vfl & PNA_VERIFY_UNAUTHENTICATED) : 0u;
 }
-static int verify_window(XCall &x, VCall &v, const WinSrc &a, size_t span, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks,
-                         std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids) {
+// plan, upload, decryption and the fold of a window in verdict mode: vs receives one status word per record (the window's entries, or its solid entry)
+static int window_verdicts(XCall &x, const WinSrc &a, size_t span, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks, std::vector<FrameDesc> &schunks,
+                           std::vector<XSolid> &solids, XPlan &P, std::vector<uint32_t> &vs, uint32_t flag[2], hipStream_t st) {
     pna_gpu_ctx *c = x.c;
-    XPlan P;
     int rc = plan_window(x, a, ents, solids, P); if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    uint32_t flag[2] = {0, 0};
     rc = upload_window(c, a, span, dchunks, schunks, P, 0, flag, st, true); if (rc) return rc;
     if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
     if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
@@ -823,7 +822,7 @@ static int verify_window(XCall &x, VCall &v, const WinSrc &a, size_t span, std::
     const size_t d_base = ents.empty() ? 0 : ents.front().d0;
     for (const XEntry &e : ents) ve.push_back(VerdictEnt{(uint32_t)(e.d0 - d_base), (uint32_t)(e.d1 - d_base), e.g0, e.g1, e.cbc_unit, (uint32_t)e.vst});
     for (const XSolid &so : solids) ve.push_back(VerdictEnt{0u, (uint32_t)schunks.size(), so.g0, so.g1, so.cbc_unit, (uint32_t)so.vst});
-    std::vector<uint32_t> vs(ve.size());
+    vs.assign(ve.size(), 0);
     if (!ve.empty()) {
         if (c->v_ent.ensure(ve.size() * sizeof(VerdictEnt) + 16) || c->v_out.ensure(ve.size() * 4 + 16)) return fail(c, PNA_E_NOMEM, "verify workspace");
         HIPCHK(c, hipMemcpyAsync(c->v_ent.p, ve.data(), ve.size() * sizeof(VerdictEnt), hipMemcpyHostToDevice, st));
@@ -831,6 +830,42 @@ static int verify_window(XCall &x, VCall &v, const WinSrc &a, size_t span, std::
                        (uint32_t *)c->v_out.p, st);
         rc = read_back(c, vs.data(), c->v_out.p, vs.size() * 4, st); if (rc) return rc;
     }
+    return PNA_OK;
+}
+// the entries with fSIZ that passed so far: one decode call per codec into the raw buffer, a status per entry; a stream whose size disagrees with its
+// fSIZ (status 3) goes to `retry` (decoded once more without it: the reference reads an entry to its end and only warns about a wrong fSIZ), a corrupt
+// one does not.  Returns the number of streams handed to the decoders in *streams.
+static int decode_sized_status(pna_gpu_ctx *c, const std::vector<XEntry> &ents, std::vector<uint32_t> &vs, std::vector<uint64_t> &size, std::vector<size_t> &retry,
+                               hipStream_t st, uint64_t *streams = nullptr) {
+    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE}) {
+        std::vector<uint64_t> so, sl, dof, rl; std::vector<size_t> idx;
+        for (size_t i = 0; i < ents.size(); i++) {
+            const XEntry &e = ents[i];
+            if (!vs[i] && !e.nodecode && e.compression == algo && e.has_size && !e.odd_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); idx.push_back(i); }
+        }
+        if (so.empty()) continue;
+        if (streams) *streams += so.size();
+        std::vector<uint32_t> es(so.size(), 0);
+        const int rc = decode_batch_status(c, algo, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[0].p, dof.data(), rl.data(), es.data(), st); if (rc) return rc;
+        for (size_t k = 0; k < idx.size(); k++) {
+            const size_t i = idx[k];
+            if (es[k] == 0) size[i] = ents[i].raw_size;
+            else if (es[k] == 2) vs[i] = PNA_VERIFY_UNSUPPORTED;
+            else if (es[k] == 3) retry.push_back(i);                     // the stream does not hold fSIZ bytes: measured and decoded without it
+            else vs[i] = PNA_VERIFY_BAD_STREAM;
+        }
+    }
+    return PNA_OK;
+}
+static int verify_window(XCall &x, VCall &v, const WinSrc &a, size_t span, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks,
+                         std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids) {
+    pna_gpu_ctx *c = x.c;
+    XPlan P;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    uint32_t flag[2] = {0, 0};
+    std::vector<uint32_t> vs;
+    int rc = window_verdicts(x, a, span, ents, dchunks, schunks, solids, P, vs, flag, st); if (rc) return rc;
     if (!solids.empty()) {                                             // a solid entry: one record for the block, or one per inner entry
         const XSolid &so = solids[0];
         int status = (int)vs[0];
@@ -855,27 +890,8 @@ static int verify_window(XCall &x, VCall &v, const WinSrc &a, size_t span, std::
         if (x.fast || vs[i]) continue;
         if (e.compression == PNA_ALGO_STORE) { size[i] = e.pay_len; if (e.has_size && e.raw_size != e.pay_len) flags[i] |= PNA_VERIFY_SIZE_HINT; }
     }
-    // the entries with fSIZ that passed so far: one decode call per codec into the raw buffer, a status per entry; a stream whose size disagrees with its
-    // fSIZ (status 3) is decoded once more without it (the reference reads an entry to its end and only warns about a wrong fSIZ), a corrupt one is not
     std::vector<size_t> retry;
-    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE}) {
-        if (x.fast) break;
-        std::vector<uint64_t> so, sl, dof, rl; std::vector<size_t> idx;
-        for (size_t i = 0; i < ents.size(); i++) {
-            const XEntry &e = ents[i];
-            if (!vs[i] && e.compression == algo && e.has_size && !e.odd_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); idx.push_back(i); }
-        }
-        if (so.empty()) continue;
-        std::vector<uint32_t> es(so.size(), 0);
-        rc = decode_batch_status(c, algo, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[0].p, dof.data(), rl.data(), es.data(), st); if (rc) return rc;
-        for (size_t k = 0; k < idx.size(); k++) {
-            const size_t i = idx[k];
-            if (es[k] == 0) size[i] = ents[i].raw_size;
-            else if (es[k] == 2) vs[i] = PNA_VERIFY_UNSUPPORTED;
-            else if (es[k] == 3) retry.push_back(i);                     // the stream does not hold fSIZ bytes: measured and decoded without it
-            else vs[i] = PNA_VERIFY_BAD_STREAM;
-        }
-    }
+    if (!x.fast) { rc = decode_sized_status(c, ents, vs, size, retry, st); if (rc) return rc; }
     for (size_t i : P.nosize_idx) if (!vs[i]) retry.push_back(i);   // (entries without fSIZ, or with one out of proportion to their data)
     for (size_t i : retry) {
         XEntry &e = ents[i];
@@ -927,4 +943,334 @@ extern "C" int pna_gpu_verify_archive_host(pna_gpu_ctx *c, const void *const *pa
     if (rc == PNA_OK && broken) { v.sum.broken = 1; rc = fail(c, PNA_E_INVAL, "archive structure is broken; verification aborted"); }
     if (summary) *summary = v.sum;
     return rc;
+}
+
+// ---- `pna experimental diff` (pna_gpu_diff_archive_host; cli/src/command/diff.rs diff_archive -> compare_entry): the verify driver with a second input.
+// Per window: the host is asked for every record's filesystem side and settles what needs no byte (missing, type, size, not compared: left out of the
+// decode lists); the rest is uploaded, decrypted, folded and decoded exactly as verify does; the files' bytes travel through two page-locked slots into
+// two device slots on a stream of their own (DiffFeed) and k_diff compares them with the decoded bytes where the decoders left them -- the raw buffer,
+// the packed buffer (stored entries) or the open-decode buffer (entries without fSIZ, solid streams) --; one read-back of first[] per window.
+namespace {
+struct DCall { pna_diff_source_fn src; pna_diff_fn cb; void *user; pna_diff_summary sum{}; };
+// one record of a window: what the host said, what was settled without bytes (status, -1: the bytes are compared), where its decoded bytes lie
+struct DRec {
+    pna_diff_file f{PNA_DIFF_FS_MISSING, nullptr, 0};
+    std::string path; bool named = false, want_link = false; int status = -1;
+    int a_buf = 0; uint64_t a_off = 0, a_len = 0; bool a_ready = false;      // a_buf: 0 raw buffer, 1 packed buffer, 2 open-decode buffer; a_off is a multiple of 16
+    std::string link;
+};
+// a run of a file's bytes in a slot: bytes [base, base + len) of record `rec`, their decoded side at the record's a_off + a_rel, the file's at `src`;
+// slot number q of the window (device slot q & 1) at b_off, which is congruent to a_rel mod 16
+struct FPiece { uint32_t rec; uint64_t a_rel, base, len; const uint8_t *src; uint64_t q, b_off; };
+// compare_entry's match (diff.rs:353-419) as far as it is decided without the entry's bytes; -1: they are compared
+int settle(int kind, const pna_diff_file &f, bool has_size, uint64_t raw_size, bool *want_link) {
+    if (f.fs_kind == PNA_DIFF_FS_IGNORE) return PNA_DIFF_NOT_COMPARED;
+    if (f.fs_kind == PNA_DIFF_FS_MISSING) return PNA_DIFF_MISSING;
+    switch (kind) {
+        case 0: if (f.fs_kind != PNA_DIFF_FS_FILE) return PNA_DIFF_TYPE_MISMATCH; return has_size && raw_size != f.len ? PNA_DIFF_SIZE_DIFFERS : -1;
+        case 1: return f.fs_kind == PNA_DIFF_FS_DIR ? PNA_DIFF_NOT_COMPARED : PNA_DIFF_TYPE_MISMATCH;
+        case 2: return f.fs_kind == PNA_DIFF_FS_SYMLINK ? -1 : PNA_DIFF_TYPE_MISMATCH;
+        case 3: if (f.fs_kind != PNA_DIFF_FS_FILE) return PNA_DIFF_TYPE_MISMATCH; *want_link = true; return PNA_DIFF_NOT_COMPARED;
+        default: return PNA_DIFF_NOT_COMPARED;
+    }
+}
+constexpr uint64_t LINK_MAX = 65536;                            // a hard link's target handed to the host: at most this many bytes
+// The files' side of a window.  add() plans where every byte goes (in record order, slot after slot, each run placed congruent to its decoded side
+// mod 16); stage(q) fills slot q -- page-locked copy, then one H2D on the copy stream; bytes in a pna_gpu_host_alloc buffer go straight from there --;
+// run(r) launches k_diff for the runs of the records up to r, slot by slot, staging slot q + 1 as soon as slot q - 1's launches are queued, so that
+// its copy runs beside the kernels of slot q.  A slot is reused when the launches that read it are done (df_ev_k) and its copy has left (df_ev_cp).
+struct DiffFeed {
+    pna_gpu_ctx *c; hipStream_t st; std::vector<DRec> &recs; uint64_t cap;
+    std::vector<FPiece> fp; size_t next = 0, stage_i = 0;
+    uint64_t fill_q = 0, fill_pos = 0; int64_t staged = -1, cur_q = -1;
+    std::vector<DiffPiece> pend[3]; uint32_t ptiles[3] = {0, 0, 0};
+    DiffFeed(pna_gpu_ctx *ctx, hipStream_t s, std::vector<DRec> &r) : c(ctx), st(s), recs(r), cap((uint64_t)ctx->tun.diff_slot_mib << 20) {}
+    int init(size_t nrec) {
+        if (!c->df_cp) {
+            HIPCHK(c, hipStreamCreateWithFlags(&c->df_cp, hipStreamNonBlocking));
+            for (auto &e : c->df_ev_cp) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (auto &e : c->df_ev_k) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        if (c->df_first.ensure(nrec * 8 + 16)) return fail(c, PNA_E_NOMEM, "diff workspace");
+        HIPCHK(c, hipMemsetAsync(c->df_first.p, 0xFF, nrec * 8 + 16, st));
+        return PNA_OK;
+    }
+    void add(uint32_t rec, uint64_t a_rel, uint64_t base, uint64_t len, const uint8_t *src) {
+        while (len) {
+            const uint64_t b = fill_pos + ((a_rel - fill_pos) & 15);
+            if (b >= cap) { fill_q++; fill_pos = 0; continue; }
+            const uint64_t n = std::min(len, cap - b);
+            fp.push_back(FPiece{rec, a_rel, base, n, src, fill_q, b});
+            fill_pos = b + n; a_rel += n; base += n; src += n; len -= n;
+        }
+    }
+    bool lent(const uint8_t *p, uint64_t n, size_t &hint) const {       // (under lent_mu)
+        for (size_t k = 0; k < c->lent.size(); k++) {
+            const auto &bf = c->lent[(hint + k) % c->lent.size()];
+            if (p >= bf.first && p + n <= bf.first + bf.second) { hint = (hint + k) % c->lent.size(); return true; }
+        }
+        return false;
+    }
+    int stage(uint64_t q) {
+        const int s = (int)(q & 1);
+        size_t i1 = stage_i; uint64_t extent = 0;
+        while (i1 < fp.size() && fp[i1].q == q) { extent = std::max(extent, fp[i1].b_off + fp[i1].len); i1++; }
+        if (c->df_pin[s].ensure_exact(cap) || c->df_dev[s].ensure(cap + 64)) return fail(c, PNA_E_NOMEM, "diff slots");
+        if (q >= 2) {
+            HIPCHK(c, hipEventSynchronize(c->df_ev_cp[s]));                          // the slot's previous bytes have left the page-locked buffer
+            HIPCHK(c, hipStreamWaitEvent(c->df_cp, c->df_ev_k[s], 0));               // ... and the launches that read them on the device are done
+        }
+        struct Job { uint8_t *dst; const uint8_t *src; uint64_t n; };
+        std::vector<Job> jobs; std::vector<size_t> direct; uint64_t bytes = 0;
+        {
+            std::lock_guard<std::mutex> lk(c->lent_mu);
+            size_t hint = 0;
+            for (size_t i = stage_i; i < i1; i++) {
+                const FPiece &p = fp[i];
+                if (!c->lent.empty() && lent(p.src, p.len, hint)) { direct.push_back(i); continue; }
+                for (uint64_t o = 0; o < p.len; o += 1u << 20) jobs.push_back(Job{(uint8_t *)c->df_pin[s].p + p.b_off + o, p.src + o, std::min<uint64_t>(1u << 20, p.len - o)});
+                bytes += p.len;
+            }
+        }
+        if (!jobs.empty()) {
+            const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+            const unsigned T = c->tun.stage_threads > 0 ? (unsigned)c->tun.stage_threads : std::min(8u, std::max(1u, hw / 2));
+            const unsigned nt = (unsigned)std::min<uint64_t>(T, std::max<uint64_t>(1, bytes >> 22));
+            par_ranges(jobs.size(), nt, [&](unsigned, size_t a0, size_t a1) { for (size_t j = a0; j < a1; j++) memcpy(jobs[j].dst, jobs[j].src, jobs[j].n); });
+            HIPCHK(c, hipMemcpyAsync(c->df_dev[s].p, c->df_pin[s].p, extent, hipMemcpyHostToDevice, c->df_cp));
+        }
+        for (size_t i : direct) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->df_dev[s].p + fp[i].b_off, fp[i].src, fp[i].len, hipMemcpyHostToDevice, c->df_cp));
+        HIPCHK(c, hipEventRecord(c->df_ev_cp[s], c->df_cp));
+        stage_i = i1; staged = (int64_t)q;
+        return PNA_OK;
+    }
+    int prefill() {                                                   // the first two slots, before the window's own bytes are decoded: their copies run beside that
+        for (uint64_t q = 0; q < 2 && !fp.empty() && q <= fp.back().q; q++) { const int rc = stage(q); if (rc) return rc; }
+        return PNA_OK;
+    }
+    int flush() {                                                     // the pending runs to k_diff, one launch per buffer of decoded bytes
+        const uint8_t *abuf[3] = {(const uint8_t *)c->x_raw[0].p, (const uint8_t *)c->x_pk.p, (const uint8_t *)c->solid_plain.p};
+        for (int k = 0; k < 3; k++) {
+            if (pend[k].empty()) continue;
+            if (c->df_pieces.ensure(pend[k].size() * sizeof(DiffPiece) + 16)) return fail(c, PNA_E_NOMEM, "diff workspace");
+            while (c->df_tev.size() < c->df_tused + 2) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->df_tev.push_back(e); }
+            HIPCHK(c, hipMemcpyAsync(c->df_pieces.p, pend[k].data(), pend[k].size() * sizeof(DiffPiece), hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipEventRecord(c->df_tev[c->df_tused], st));
+            launch_diff((const DiffPiece *)c->df_pieces.p, (uint32_t)pend[k].size(), ptiles[k], abuf[k], (const uint8_t *)c->df_dev[cur_q & 1].p, (unsigned long long *)c->df_first.p, st);
+            HIPCHK(c, hipEventRecord(c->df_tev[c->df_tused + 1], st));
+            HIPCHK(c, hipGetLastError());
+            c->df_tused += 2;
+            pend[k].clear(); ptiles[k] = 0;
+        }
+        return PNA_OK;
+    }
+    int finish_slot() {
+        if (cur_q < 0) return PNA_OK;
+        const int rc = flush(); if (rc) return rc;
+        HIPCHK(c, hipEventRecord(c->df_ev_k[cur_q & 1], st));
+        return PNA_OK;
+    }
+    int run(uint32_t upto) {                                          // the runs of the records up to `upto` (whose decoded bytes are where the records say)
+        while (next < fp.size() && fp[next].rec <= upto) {
+            const FPiece &p = fp[next];
+            if ((int64_t)p.q != cur_q) {
+                int rc = finish_slot(); if (rc) return rc;
+                cur_q = (int64_t)p.q;
+                if (staged < cur_q) { rc = stage((uint64_t)cur_q); if (rc) return rc; }
+                HIPCHK(c, hipStreamWaitEvent(st, c->df_ev_cp[cur_q & 1], 0));
+                if (staged < cur_q + 1 && (uint64_t)cur_q + 1 <= fp.back().q) { rc = stage((uint64_t)cur_q + 1); if (rc) return rc; }
+            }
+            const DRec &r = recs[p.rec];
+            if (r.a_ready && p.base < r.a_len) {                     // (the decoded side may be shorter than the file: the rest is a length difference)
+                const uint64_t n = std::min(p.len, r.a_len - p.base);
+                const uint64_t tiles = (n + DIFF_TILE - 1) / DIFF_TILE;
+                if ((uint64_t)ptiles[r.a_buf] + tiles > 0x7FFFFFFFu) { const int rc = flush(); if (rc) return rc; }
+                pend[r.a_buf].push_back(DiffPiece{r.a_off + p.a_rel, p.b_off, n, p.base, p.rec, ptiles[r.a_buf]});
+                ptiles[r.a_buf] += (uint32_t)tiles;
+                c->df_bytes += n;
+            }
+            next++;
+        }
+        return PNA_OK;
+    }
+    int finish(std::vector<uint64_t> &first) {                        // everything launched: first[] back (the stream drained), k_diff's time
+        int rc = run(0xFFFFFFFFu); if (rc) return rc;
+        rc = finish_slot(); if (rc) return rc;
+        rc = read_back(c, first.data(), c->df_first.p, first.size() * 8, st); if (rc) return rc;
+        for (size_t k = 0; k + 1 < c->df_tused; k += 2) { float ms = 0; if (hipEventElapsedTime(&ms, c->df_tev[k], c->df_tev[k + 1]) == hipSuccess) c->df_ms += ms; }
+        c->df_tused = 0;
+        return PNA_OK;
+    }
+};
+int emit_diff(XCall &x, DCall &d, const char *name, int kind, int status, int vstatus, uint32_t flags, uint64_t size, uint64_t first, const char *link) {
+    d.sum.total++;
+    if (status == PNA_DIFF_SAME) d.sum.same++;
+    else if (status == PNA_DIFF_NOT_COMPARED) d.sum.not_compared++;
+    else if (status == PNA_DIFF_SKIPPED) d.sum.skipped++;
+    else if (status == PNA_DIFF_DAMAGED) d.sum.damaged++;
+    else d.sum.differ++;
+    if (d.cb(d.user, x.index++, name, kind, status, vstatus, flags, size, first, link) != 0) return fail(x.c, PNA_E_SINK, "diff callback failed");
+    return PNA_OK;
+}
+// a record whose bytes were compared: SAME, or where the sides part
+void compared(const DRec &r, int kind, uint64_t first, int *status, uint64_t *at) {
+    const int differ = kind == 2 ? PNA_DIFF_SYMLINK_DIFFERS : PNA_DIFF_CONTENTS_DIFFER;
+    *status = PNA_DIFF_SAME; *at = UINT64_MAX;
+    if (first != UINT64_MAX) { *status = differ; *at = first; }
+    else if (r.a_len != r.f.len) { *status = differ; *at = std::min<uint64_t>(r.a_len, r.f.len); }     // one side is a strict prefix of the other
+}
+int ask(XCall &x, DCall &d, size_t index, const std::string &raw_name, int kind, bool has_size, uint64_t raw_size, DRec &r) {
+    r.named = entry_path(x.c, raw_name, r.path) == PNA_OK;
+    if (!r.named) return PNA_OK;
+    if (d.src(d.user, index, r.path.c_str(), kind, has_size ? raw_size : UINT64_MAX, &r.f) != 0) return fail(x.c, PNA_E_SINK, "diff source callback failed");
+    if (r.f.fs_kind < PNA_DIFF_FS_MISSING || r.f.fs_kind > PNA_DIFF_FS_IGNORE) return fail(x.c, PNA_E_INVAL, "diff source callback: unknown fs_kind");
+    if (r.f.len && !r.f.data && (r.f.fs_kind == PNA_DIFF_FS_FILE || r.f.fs_kind == PNA_DIFF_FS_SYMLINK)) return fail(x.c, PNA_E_INVAL, "diff source callback: bytes announced, none given");
+    r.status = settle(kind, r.f, has_size, raw_size, &r.want_link);
+    return PNA_OK;
+}
+// a solid block: one record for a block that is skipped or fails, else its inner entries against the decoded stream where it lies
+int diff_solid(XCall &x, DCall &d, const XSolid &so, int status, uint32_t flag[2], hipStream_t st) {
+    pna_gpu_ctx *c = x.c;
+    std::vector<uint8_t> plain; std::vector<Inner> inner;
+    if (status == PNA_VERIFY_OK) {
+        int vst = 0;
+        c->df_streams++;
+        const int rc = walk_solid(c, so, plain, inner, flag, st, &vst); if (rc) return rc;
+        status = vst;
+    }
+    if (status) return emit_diff(x, d, nullptr, PNA_VERIFY_KIND_SOLID, status == PNA_VERIFY_SKIPPED ? PNA_DIFF_SKIPPED : PNA_DIFF_DAMAGED, status, fail_flags(so, status), 0, UINT64_MAX, nullptr);
+    std::vector<DRec> recs(inner.size());
+    DiffFeed feed(c, st, recs);
+    const bool stored = so.compression == PNA_ALGO_STORE;            // (a stored stream lies in the packed buffer)
+    for (size_t k = 0; k < inner.size(); k++) {
+        const Inner &ie = inner[k]; DRec &r = recs[k];
+        int rc = ask(x, d, x.index + k, ie.name, ie.kind, ie.has_size, ie.raw_size, r); if (rc) return rc;
+        if (!r.named) continue;
+        if (r.want_link) for (const XPiece &p : ie.pieces) { if (r.link.size() < LINK_MAX) r.link.append((const char *)plain.data() + p.off, (size_t)std::min<uint64_t>(p.len, LINK_MAX - r.link.size())); }
+        if (r.status != -1) continue;
+        r.a_buf = stored ? 1 : 2; r.a_off = stored ? so.pk_off : 0; r.a_len = ie.len; r.a_ready = true;
+        uint64_t base = 0;
+        for (const XPiece &p : ie.pieces) {
+            if (base < r.f.len) feed.add((uint32_t)k, p.off, base, std::min<uint64_t>(p.len, r.f.len - base), (const uint8_t *)r.f.data + base);
+            base += p.len;
+        }
+    }
+    std::vector<uint64_t> first(recs.size(), UINT64_MAX);
+    if (!recs.empty()) {
+        int rc = feed.init(recs.size()); if (rc) return rc;
+        rc = feed.finish(first); if (rc) return rc;
+    }
+    for (size_t k = 0; k < inner.size(); k++) {
+        const DRec &r = recs[k];
+        int rc;
+        if (!r.named) rc = emit_diff(x, d, nullptr, inner[k].kind, PNA_DIFF_DAMAGED, PNA_VERIFY_BAD_STRUCTURE, 0, 0, UINT64_MAX, nullptr);
+        else if (r.status != -1) rc = emit_diff(x, d, r.path.c_str(), inner[k].kind, r.status, 0, 0, 0, UINT64_MAX, r.want_link ? r.link.c_str() : nullptr);
+        else { int stt; uint64_t at; compared(r, inner[k].kind, first[k], &stt, &at); rc = emit_diff(x, d, r.path.c_str(), inner[k].kind, stt, 0, 0, inner[k].len, at, nullptr); }
+        if (rc) return rc;
+    }
+    return PNA_OK;
+}
+int diff_window(XCall &x, DCall &d, const WinSrc &a, size_t span, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks, std::vector<FrameDesc> &schunks,
+                std::vector<XSolid> &solids) {
+    pna_gpu_ctx *c = x.c;
+    XPlan P;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    uint32_t flag[2] = {0, 0};
+    std::vector<uint32_t> vs;
+    // 1. the filesystem side of every record, and what is settled without the entry's bytes
+    std::vector<DRec> recs(ents.size());
+    DiffFeed feed(c, st, recs);
+    for (size_t i = 0; i < ents.size(); i++) {
+        XEntry &e = ents[i]; DRec &r = recs[i];
+        if (e.noname || e.kind == PNA_VERIFY_KIND_BROKEN) continue;
+        int rc = ask(x, d, x.index + i, e.name, e.kind, e.has_size, e.raw_size, r); if (rc) return rc;
+        if (!r.named) continue;
+        e.nodecode = r.status != -1 && !r.want_link;
+        if (r.status == -1 && r.f.len) feed.add((uint32_t)i, 0, 0, r.f.len, (const uint8_t *)r.f.data);     // (every normal entry's decoded bytes start at a multiple of 16)
+    }
+    int rc = PNA_OK;
+    if (!ents.empty()) { rc = feed.init(ents.size()); if (rc) return rc; rc = feed.prefill(); if (rc) return rc; }
+    // 2. upload, decryption, the fold, the sized decode: as verify
+    rc = window_verdicts(x, a, span, ents, dchunks, schunks, solids, P, vs, flag, st); if (rc) return rc;
+    if (!solids.empty()) return diff_solid(x, d, solids[0], (int)vs[0], flag, st);
+    std::vector<uint64_t> size(ents.size(), 0); std::vector<size_t> open;
+    rc = decode_sized_status(c, ents, vs, size, open, st, &c->df_streams); if (rc) return rc;
+    for (size_t i : P.nosize_idx) if (!vs[i]) open.push_back(i);     // (entries without fSIZ, or with one out of proportion to their data)
+    std::sort(open.begin(), open.end());
+    // 3. the compare, in record order: an entry without a usable fSIZ is decoded into the open-decode buffer when its turn comes and compared before the next one overwrites it
+    size_t oi = 0;
+    for (size_t i = 0; i < ents.size(); i++) {
+        XEntry &e = ents[i]; DRec &r = recs[i];
+        if (vs[i] || e.nodecode || !r.named) continue;
+        if (oi < open.size() && open[oi] == i) {
+            oi++;
+            rc = feed.flush(); if (rc) return rc;
+            uint64_t got = 0;
+            c->df_streams++;
+            rc = decode_open(c, e, "entry buffer", nullptr, st, &got);
+            if (rc == PNA_E_INVAL || rc == PNA_E_UNSUPPORTED) { vs[i] = rc == PNA_E_INVAL ? PNA_VERIFY_BAD_STREAM : PNA_VERIFY_UNSUPPORTED; continue; }
+            if (rc) return rc;
+            size[i] = got; r.a_buf = 2; r.a_off = 0;
+        } else if (e.compression == PNA_ALGO_STORE) { size[i] = e.pay_len; r.a_buf = 1; r.a_off = e.pk_off; }
+        else { r.a_buf = 0; r.a_off = e.raw_off; }                  // (decoded by decode_sized_status: size[i] = fSIZ)
+        r.a_len = size[i]; r.a_ready = true;
+        if (r.want_link && r.a_len) {
+            r.link.resize((size_t)std::min<uint64_t>(r.a_len, LINK_MAX));
+            const uint8_t *src = (const uint8_t *)(r.a_buf == 0 ? c->x_raw[0].p : r.a_buf == 1 ? c->x_pk.p : c->solid_plain.p) + r.a_off;
+            rc = read_back(c, &r.link[0], src, r.link.size(), st); if (rc) return rc;
+        }
+        rc = feed.run((uint32_t)i); if (rc) return rc;
+    }
+    std::vector<uint64_t> first(ents.size(), UINT64_MAX);
+    if (!ents.empty()) { rc = feed.finish(first); if (rc) return rc; }
+    // 4. the records
+    for (size_t i = 0; i < ents.size(); i++) {
+        const XEntry &e = ents[i]; const DRec &r = recs[i];
+        const int v = (int)vs[i];
+        const char *name = r.named ? r.path.c_str() : nullptr;
+        if (!r.named) rc = emit_diff(x, d, nullptr, e.kind, v == PNA_VERIFY_SKIPPED ? PNA_DIFF_SKIPPED : PNA_DIFF_DAMAGED, v ? v : PNA_VERIFY_BAD_STRUCTURE, v ? fail_flags(e, v) : 0u, 0, UINT64_MAX, nullptr);
+        else if (e.nodecode) rc = emit_diff(x, d, name, e.kind, r.status, v, 0, 0, UINT64_MAX, nullptr);                 // (v: what the chunk CRCs and the walk found)
+        else if (v) rc = emit_diff(x, d, name, e.kind, v == PNA_VERIFY_SKIPPED ? PNA_DIFF_SKIPPED : PNA_DIFF_DAMAGED, v, fail_flags(e, v), 0, UINT64_MAX, nullptr);
+        else if (r.want_link) rc = emit_diff(x, d, name, e.kind, PNA_DIFF_NOT_COMPARED, 0, 0, size[i], UINT64_MAX, r.link.c_str());
+        else { int stt; uint64_t at; compared(r, e.kind, first[i], &stt, &at); rc = emit_diff(x, d, name, e.kind, stt, 0, 0, size[i], at, nullptr); }
+        if (rc) return rc;
+    }
+    return PNA_OK;
+}
+}
+
+extern "C" int pna_gpu_diff_archive_host(pna_gpu_ctx *c, const void *const *parts, const size_t *part_len, size_t n_parts, const void *password,
+                                         size_t password_len, pna_diff_source_fn source, pna_diff_fn cb, void *user, pna_diff_summary *summary) {
+    if (!c || !parts || !part_len || !n_parts || !source || !cb || (!password && password_len)) return fail(c, PNA_E_INVAL, "null argument");
+    for (size_t k = 0; k < n_parts; k++) if (!parts[k]) return fail(c, PNA_E_INVAL, "null argument");
+    if (part_len[0] < 8 || memcmp(parts[0], PNA_SIGNATURE, 8) != 0) return fail(c, PNA_E_INVAL, "not a PNA archive");
+    if (!launch_frame_verdict || !launch_verdict || !launch_gcm_verdict || !launch_diff) return fail(c, PNA_E_UNSUPPORTED, "this build has no verdict / diff kernels");
+    ArcParts ap{(const uint8_t *const *)parts, part_len, n_parts, {}};
+    uint64_t at = 0;
+    for (size_t k = 0; k < n_parts; k++) { ap.vb.push_back(at); at += part_len[k]; }
+    XCall x{c, password, password_len, nullptr, nullptr, {}, 0};
+    x.verdict = true;
+    DCall d{source, cb, user};
+    c->df_streams = 0; c->df_bytes = 0; c->df_ms = 0; c->df_tused = 0;
+    std::vector<XEntry> ents; std::vector<FrameDesc> dchunks, schunks; std::vector<XSolid> solids;
+    bool broken = false;
+    int rc = walk_archive(c, ap, true, ents, dchunks, schunks, solids, &broken);
+    size_t si = 0, w0 = 0;
+    while (rc == PNA_OK && (w0 < ents.size() || si < solids.size())) {
+        XWindow W;
+        next_window(c, ents, dchunks, schunks, solids, w0, si, W);
+        rc = diff_window(x, d, WinSrc{&ap, W.base}, (size_t)W.span, W.we, W.wd, W.ws, W.wso);
+    }
+    if (rc) (void)hipDeviceSynchronize();                               // (nothing of a window that failed is left in flight: the host's buffers are its own again)
+    if (rc == PNA_OK && broken) { d.sum.broken = 1; rc = fail(c, PNA_E_INVAL, "archive structure is broken; diff aborted"); }
+    if (summary) *summary = d.sum;
+    return rc;
+}
+extern "C" int pna_gpu_debug_diff_stats(pna_gpu_ctx *c, uint64_t *decoded_streams, uint64_t *compared_bytes, double *ms_k_diff) {
+    if (!c) return PNA_E_INVAL;
+    if (decoded_streams) *decoded_streams = c->df_streams;
+    if (compared_bytes) *compared_bytes = c->df_bytes;
+    if (ms_k_diff) *ms_k_diff = c->df_ms;
+    return PNA_OK;
 }

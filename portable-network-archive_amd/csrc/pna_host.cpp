@@ -7,7 +7,7 @@ static const TuningName TUNING_NAMES[] = {
     {"lz_split_min", "PNA_LZ_SPLIT_MIN", &Tuning::lz_split_min, 0, 1 << 30}, {"lz_pbuf_fail", "PNA_LZ_PBUF_FAIL", &Tuning::lz_pbuf_fail, 0, 1},
     {"max_chunk_size", "PNA_MAX_CHUNK_SIZE", &Tuning::max_chunk_size, 0, 0xFFFFFFFFl},
     {"sub_mib", "PNA_SUB_MIB", &Tuning::sub_mib, 16, 16384}, {"stage_threads", "PNA_STAGE_THREADS", &Tuning::stage_threads, 0, 64},
-    {"extract_win_mib", "PNA_EXTRACT_WIN_MIB", &Tuning::extract_win_mib, 1, 1 << 20}, {"batch_piece_mib", "PNA_BATCH_PIECE_MIB", &Tuning::batch_piece_mib, 0, 1 << 20}, {"solid_win_mib", "PNA_SOLID_WIN_MIB", &Tuning::solid_win_mib, 1, 1 << 16},
+    {"extract_win_mib", "PNA_EXTRACT_WIN_MIB", &Tuning::extract_win_mib, 1, 1 << 20}, {"batch_piece_mib", "PNA_BATCH_PIECE_MIB", &Tuning::batch_piece_mib, 0, 1 << 20}, {"solid_win_mib", "PNA_SOLID_WIN_MIB", &Tuning::solid_win_mib, 1, 1 << 16}, {"diff_slot_mib", "PNA_DIFF_SLOT_MIB", &Tuning::diff_slot_mib, 1, 1 << 14},
     {"inflate_serial", "PNA_INFLATE_SERIAL", &Tuning::inflate_serial, 0, 1}, {"zdec_serial", "PNA_ZDEC_SERIAL", &Tuning::zdec_serial, 0, 1}, {"zdec_dbg", "PNA_ZDEC_DBG", &Tuning::zdec_dbg, 0, 15},
     {"blk_log", "PNA_BLK_LOG", &Tuning::blk_log, 0, PNA_BLK_LOG}, {"unit_log", "PNA_LZ_UNIT_LOG", &Tuning::unit_log, 0, 20},
     {"latency_max_mib", "PNA_LATENCY_MAX_MIB", &Tuning::latency_max_mib, 0, 1 << 20}, {"hist_by_block", "PNA_HIST_BY_BLOCK", &Tuning::hist_by_block, -1, 1},
@@ -100,6 +100,12 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->cp_in) (void)hipStreamDestroy(c->cp_in);
     if (c->cp_out) (void)hipStreamDestroy(c->cp_out);
+    for (DevBuf *b : {&c->v_crc, &c->v_seg, &c->v_ent, &c->v_out, &c->df_dev[0], &c->df_dev[1], &c->df_pieces, &c->df_first}) b->release();
+    for (auto &b : c->df_pin) b.release();
+    if (c->df_cp) (void)hipStreamDestroy(c->df_cp);
+    for (auto &e : c->df_ev_cp) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->df_ev_k) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->df_tev) if (e) (void)hipEventDestroy(e);
     if (c->x_cp) (void)hipStreamDestroy(c->x_cp);
     for (auto &e : c->x_ev) if (e) (void)hipEventDestroy(e);
     if (c->x_done) (void)hipEventDestroy(c->x_done);

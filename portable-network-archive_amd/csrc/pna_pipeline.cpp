@@ -184,6 +184,7 @@ extern "C" uint64_t pna_gpu_debug_pinned_bytes(pna_gpu_ctx *c) {
     uint64_t t = 0;
     for (auto &b : c->hp_in) t += b.cap;
     for (auto &b : c->hp_out) t += b.cap;
+    for (auto &b : c->df_pin) t += b.cap;                       // pna diff's two slots
     return t;
 }
 
