@@ -458,6 +458,67 @@ int  pna_gpu_diff_archive_host(pna_gpu_ctx *ctx, const void *const *parts, const
  * be NULL).  Tests pin "SIZE_DIFFERS costs no decode" with it; not on any product path. */
 int  pna_gpu_debug_diff_stats(pna_gpu_ctx *ctx, uint64_t *decoded_streams, uint64_t *compared_bytes, double *ms_k_diff);
 
+/* `pna extract archive.pna path...` (cli/src/command/extract.rs:1038-1121 filter_entry: a reader is built for the kept entries only): extract for the
+ * entries the host chooses, each to host memory or to device memory of the caller's.  The extract driver's stages and failure semantics over windows
+ * that hold the selected entries only; parts / part_len / n_parts as in pna_gpu_verify_archive_host (a split archive is read in place).
+ *   select: called once per entry, in archive order, before anything of that entry is uploaded; index, name (the sanitised path; a name that is not
+ *     UTF-8 or holds a NUL fails the call with PNA_E_INVAL) and kind are what pna_entry_fn gets, stored_size is the entry's fSIZ (UINT64_MAX if it
+ *     has none).  It fills *out: PNA_EXTRACT_SKIP (the preset), PNA_EXTRACT_HOST, or PNA_EXTRACT_DEVICE with d_dst / cap.  A non-zero return ends the
+ *     call with PNA_E_SINK; `where` outside 0..2, or PNA_EXTRACT_DEVICE with d_dst NULL and cap > 0, with PNA_E_INVAL.
+ *   cb: one record per SELECTED entry, in archive order (entries without data -- directories ... -- with len 0).  HOST: `data` are the decoded bytes in
+ *     host memory, valid during the call.  DEVICE: the decoded bytes have been written to d_dst[0 .. len) -- byte-exactly, nothing of the entry went to
+ *     the host -- and `data` is d_dst; a window's records follow its kernels, so the callback may use d_dst.  cap < the decoded size:
+ *     PNA_EXTRACT_TOO_SMALL, nothing written, data NULL, len = the size needed (for an entry without fSIZ the size the decoder found).
+ *   Structural damage, a bad CRC, a corrupt stream, a wrong password or an authentication failure on a selected entry: PNA_E_INVAL, as in extract.  The
+ *   small chunks the host walks (FHED, fSIZ, PHSF, FEND ...) are CRC-checked for every entry.  The data chunks (FDAT) of entries that are NOT selected are
+ *   neither uploaded nor checked -- a deliberate departure from the reference, whose io::read_chunk checks every chunk it passes: taking one file out of
+ *   a large archive must not cost the whole archive over the host link.  PNA_EXTRACT_CHECK_ALL restores the reference's behaviour: those chunks are
+ *   uploaded and CRC-checked, but not gathered or decoded (as pna_gpu_diff_archive_host treats NOT_COMPARED entries).
+ *   Upload: a window's H2D copies are the records (FHED .. FEND) of its selected entries; records at most PNA_EXTRACT_GAP_MAX bytes apart travel as one
+ *   copy (pna_extract_plan_runs).  Windows are cut by the bytes uploaded ("extract_win_mib"), not by the archive span they reach over.
+ *   Keys: a PHSF string is derived only when a selected stream needs it, once per call.
+ *   Solid blocks: a block is one stream -- uploaded, decrypted (an encrypted block without a password fails the call, as in extract) and decoded whole,
+ *   even when nothing turns out to be wanted from it: the inner entries' names lie in the decoded stream.  It is copied to the host once for its header
+ *   walk, as extract / verify / diff do; `select` is then asked for every inner entry, HOST records point into that copy, DEVICE records are copied on the
+ *   device from the decoded stream where it lies.
+ * PNA_E_UNSUPPORTED in a build without k_pick (and for what extract does not decode). */
+#define PNA_EXTRACT_SKIP    0   /* not wanted: no record, nothing of the entry gathered, decrypted or decoded */
+#define PNA_EXTRACT_HOST    1   /* decoded bytes handed out in host memory during the record callback (what extract does today) */
+#define PNA_EXTRACT_DEVICE  2   /* decoded bytes written to d_dst[0 .. len), cap bytes available there */
+typedef struct { int where; void *d_dst; uint64_t cap; } pna_extract_dest;
+typedef int (*pna_extract_select_fn)(void *user, size_t index, const char *name, int kind,
+                                     uint64_t stored_size /* fSIZ, UINT64_MAX if none */, pna_extract_dest *out);
+#define PNA_EXTRACT_OK         0
+#define PNA_EXTRACT_TOO_SMALL  1   /* DEVICE: cap < decoded size; nothing written, len = the size needed */
+typedef int (*pna_extract_record_fn)(void *user, size_t index, const char *name, int kind, int status,
+                                     const void *data /* HOST: host bytes, valid during the call; DEVICE: d_dst; NULL when TOO_SMALL */,
+                                     uint64_t len);
+/* total: entries `select` was asked about; selected = to_host + to_device + too_small */
+typedef struct { uint64_t total, selected, to_host, to_device, too_small; } pna_extract_summary;
+#define PNA_EXTRACT_CHECK_ALL  1u  /* xflags: also upload and CRC-check the FDAT / SDAT chunks of entries that are not selected */
+int  pna_gpu_extract_select_host(pna_gpu_ctx *ctx, const void *const *parts, const size_t *part_len, size_t n_parts,
+                                 const void *password, size_t password_len, uint32_t xflags,
+                                 pna_extract_select_fn select, pna_extract_record_fn cb, void *user,
+                                 pna_extract_summary *summary);
+/* The upload plan of a window (host code, no device): records [rec_off[i], rec_off[i] + rec_len[i]) in archive order, none inside another; the wanted
+ * ones (wanted[i] != 0, rec_len[i] > 0) become runs, two wanted records whose gap is at most gap_max bytes sharing one -- the gap's bytes travel with
+ * them.  run_off / run_len (room for n each; either may be NULL) and *n_runs receive the runs.  PNA_E_INVAL for null arguments or records out of order.
+ * PNA_EXTRACT_GAP_MAX is the driver's gap_max: a host-to-device copy costs some 10 us before its first byte moves, the time in which the link carries
+ * several hundred KiB, so a gap of 64 KiB is always cheaper to send than to cut at, and what it wastes stays small against the records around it. */
+#define PNA_EXTRACT_GAP_MAX  65536u
+int  pna_extract_plan_runs(const uint64_t *rec_off, const uint64_t *rec_len, const uint8_t *wanted, size_t n,
+                           uint64_t gap_max, uint64_t *run_off, uint64_t *run_len, size_t *n_runs);
+/* The latest pna_gpu_extract_select_host call of the context (any pointer may be NULL): bytes of its H2D archive copies; streams taken through the decode
+ * stage (every selected entry that has data -- a stored one's decode is the identity -- and every solid stream); key derivations; bytes k_pick moved and
+ * its HIP-event time.  Not on any product path. */
+int  pna_gpu_debug_extract_stats(pna_gpu_ctx *ctx, uint64_t *uploaded_bytes, uint64_t *decoded_streams,
+                                 uint64_t *kdf_runs, uint64_t *picked_bytes, double *ms_k_pick);
+/* k_pick alone, for its test: n ranges d_src[src_off[i] .. +len[i]) -> d_dst[i][0 .. len[i]) (src_off, d_dst, len: host arrays).  The 16-byte groups
+ * of d_src that hold a range's first and last byte must be readable.  Drains hip_stream (NULL: the context's); picked_bytes and ms_k_pick of
+ * pna_gpu_debug_extract_stats then hold this call's. */
+int  pna_gpu_debug_pick_device(pna_gpu_ctx *ctx, size_t n, const void *d_src, const uint64_t *src_off,
+                               void *const *d_dst, const uint64_t *len, void *hip_stream);
+
 /* pna_gpu_create_archive_host for ONE PART of an archive (PNA_PART_HEAD: signature + AHED first, PNA_PART_TAIL: AEND last): what
  * `pna append` writes behind the existing entries (PNA_PART_TAIL only) and `pna update` for the entries it re-creates (neither flag). */
 int  pna_gpu_create_archive_part_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,

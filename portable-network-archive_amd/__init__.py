@@ -140,6 +140,29 @@ DIFF_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctype
                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p)
 DiffRecord = collections.namedtuple("DiffRecord", "name kind status verify_status flags size first_diff link_target")
 
+# pna_gpu_extract_select_host (include/pna_gpu.h): destinations, record statuses, flags
+EXTRACT_SKIP, EXTRACT_HOST, EXTRACT_DEVICE = range(3)
+EXTRACT_OK, EXTRACT_TOO_SMALL = 0, 1
+EXTRACT_CHECK_ALL = 1
+EXTRACT_GAP_MAX = 65536                                         # records at most this far apart travel in one copy (PNA_EXTRACT_GAP_MAX)
+EXTRACT_NO_SIZE = (1 << 64) - 1                                 # stored_size of an entry without fSIZ
+PICK_TILE = 16384                                               # bytes one wave of k_pick copies (pna_dev.h PICK_TILE)
+
+
+class ExtractDest(ctypes.Structure):
+    """pna_extract_dest (include/pna_gpu.h)."""
+    _fields_ = [("where", ctypes.c_int), ("d_dst", ctypes.c_void_p), ("cap", ctypes.c_uint64)]
+
+
+class ExtractSummary(ctypes.Structure):
+    """pna_extract_summary (include/pna_gpu.h)."""
+    _fields_ = [("total", ctypes.c_uint64), ("selected", ctypes.c_uint64), ("to_host", ctypes.c_uint64), ("to_device", ctypes.c_uint64),
+                ("too_small", ctypes.c_uint64)]
+
+
+EXTRACT_SELECT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ExtractDest))
+EXTRACT_RECORD_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64)
+
 _lib = None
 
 EXPORTS = [
@@ -168,6 +191,8 @@ EXPORTS = [
     "pna_gpu_verify_archive_host",
     # pna diff (include/pna_gpu.h)
     "pna_gpu_diff_archive_host", "pna_gpu_debug_diff_stats",
+    # extract of chosen entries, to host or device (include/pna_gpu.h)
+    "pna_gpu_extract_select_host", "pna_extract_plan_runs", "pna_gpu_debug_extract_stats", "pna_gpu_debug_pick_device",
 ]
 
 
@@ -294,6 +319,15 @@ def load_library() -> ctypes.CDLL:
                                             ctypes.POINTER(DiffSummary)]
     L.pna_gpu_debug_diff_stats.restype = ctypes.c_int
     L.pna_gpu_debug_diff_stats.argtypes = [vp, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
+    L.pna_gpu_extract_select_host.restype = ctypes.c_int
+    L.pna_gpu_extract_select_host.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), sz, ctypes.c_char_p, sz, ctypes.c_uint32,
+                                              EXTRACT_SELECT_FN, EXTRACT_RECORD_FN, vp, ctypes.POINTER(ExtractSummary)]
+    L.pna_extract_plan_runs.restype = ctypes.c_int
+    L.pna_extract_plan_runs.argtypes = [u64p, u64p, ctypes.POINTER(ctypes.c_uint8), sz, ctypes.c_uint64, u64p, u64p, ctypes.POINTER(sz)]
+    L.pna_gpu_debug_extract_stats.restype = ctypes.c_int
+    L.pna_gpu_debug_extract_stats.argtypes = [vp, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
+    L.pna_gpu_debug_pick_device.restype = ctypes.c_int
+    L.pna_gpu_debug_pick_device.argtypes = [vp, sz, vp, u64p, ctypes.POINTER(vp), u64p, vp]
     L.pna_gpu_open_size_device.restype = ctypes.c_int
     L.pna_gpu_open_size_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.POINTER(ctypes.c_int), vp]
     L.pna_gpu_inflate_open_device.restype = ctypes.c_int
@@ -1113,6 +1147,123 @@ def diff_stats(ctx: Context):
     a, b, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
     ctx._check(ctx._L.pna_gpu_debug_diff_stats(ctx._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(ms)))
     return a.value, b.value, ms.value
+
+
+def extract_plan_runs(rec_off: Sequence[int], rec_len: Sequence[int], wanted: Sequence[int], gap_max: int = EXTRACT_GAP_MAX):
+    """pna_extract_plan_runs: the H2D copies [(offset, length)] that carry the wanted records (host code, no device)."""
+    n = len(rec_off)
+    ro, rl = (ctypes.c_uint64 * max(n, 1))(*rec_off), (ctypes.c_uint64 * max(n, 1))(*rec_len)
+    w = (ctypes.c_uint8 * max(n, 1))(*[1 if x else 0 for x in wanted])
+    uo, ul, k = (ctypes.c_uint64 * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))(), ctypes.c_size_t()
+    rc = load_library().pna_extract_plan_runs(ro, rl, w, n, gap_max, uo, ul, ctypes.byref(k))
+    if rc:
+        raise PnaGpuError(rc, load_library().pna_gpu_strerror(rc).decode())
+    return [(uo[i], ul[i]) for i in range(k.value)]
+
+
+def extract_select(ctx: Context, archive_or_parts, select, password: Optional[bytes] = None, check_all: bool = False):
+    """`pna extract archive.pna path...` (pna_gpu_extract_select_host): the entries `select` chooses, to host memory or to device memory of the caller's.
+    `archive_or_parts`: one archive image, or the parts of a split archive in order.  select(index, name, kind, stored_size) -- stored_size None for an
+    entry without fSIZ -- returns None (skip), "host", or a contiguous torch.uint8 CUDA tensor (device; cap = numel).  Returns (records, summary): a
+    record is (index, name, kind, status, data, length) for a selected entry, in archive order; data is bytes for host records, the caller's tensor
+    for device records (None when status is EXTRACT_TOO_SMALL: length then is the size needed); summary a dict of pna_extract_summary's fields."""
+    parts = [archive_or_parts] if isinstance(archive_or_parts, (bytes, bytearray, memoryview)) else list(archive_or_parts)
+    keep = [p if isinstance(p, bytes) else bytes(p) for p in parts]
+    n = len(keep)
+    arr = (ctypes.c_char_p * max(n, 1))(*keep)
+    lens = (ctypes.c_size_t * max(n, 1))(*[len(p) for p in keep])
+    recs, held, err = [], {}, []
+
+    def _sel(_u, idx, name, kind, stored, out):
+        try:
+            d = select(idx, name.decode("utf-8"), kind, None if stored == EXTRACT_NO_SIZE else stored)
+            if d is None:
+                out[0].where = EXTRACT_SKIP
+            elif isinstance(d, str):
+                if d != "host":
+                    raise ValueError("select returns None, \"host\" or a torch.uint8 CUDA tensor")
+                out[0].where = EXTRACT_HOST
+            else:
+                import torch
+                if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.uint8 and d.is_contiguous()):
+                    raise ValueError("select returns None, \"host\" or a contiguous torch.uint8 CUDA tensor")
+                held[idx] = d
+                out[0].where, out[0].d_dst, out[0].cap = EXTRACT_DEVICE, (d.data_ptr() if d.numel() else None), d.numel()
+            return 0
+        except Exception as e:  # noqa: BLE001 - reported through the call's return code
+            err.append(e)
+            return 1
+
+    def _cb(_u, idx, name, kind, status, data, length):
+        t = held.pop(idx, None)
+        if t is not None:
+            recs.append((idx, name.decode("utf-8"), kind, status, None if status == EXTRACT_TOO_SMALL else t, length))
+        else:
+            recs.append((idx, name.decode("utf-8"), kind, status, ctypes.string_at(data, length) if length else b"", length))
+        return 0
+    sel_cb, cb = EXTRACT_SELECT_FN(_sel), EXTRACT_RECORD_FN(_cb)
+    summ = ExtractSummary()
+    try:
+        import torch
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()                            # (the destinations' earlier work on torch's streams is done before the library's stream writes them)
+    except ImportError:  # pragma: no cover - torch is optional unless tensors are handed in
+        pass
+    rc = ctx._L.pna_gpu_extract_select_host(ctx._h, arr, lens, n, password, len(password) if password else 0, EXTRACT_CHECK_ALL if check_all else 0,
+                                            sel_cb, cb, None, ctypes.byref(summ))
+    if rc != PNA_OK:                                            # (a `select` that raised: E_SINK, its exception as the cause)
+        raise PnaGpuError(rc, ctx._L.pna_gpu_last_error(ctx._h).decode() or ctx._L.pna_gpu_strerror(rc).decode()) from (err[0] if err else None)
+    return recs, {f: getattr(summ, f) for f, _ in ExtractSummary._fields_}
+
+
+def extract_to_device(ctx: Context, archive_or_parts, names=None, password: Optional[bytes] = None):
+    """The named file entries (all of them when `names` is None) decoded into device memory: {name: torch.uint8 tensor}.  A first call selects nothing
+    and collects the fSIZ values; one tensor is allocated from them, entries at 256-byte strides, and extract_select fills it.  Entries without
+    fSIZ are offered an empty destination there and report their size (EXTRACT_TOO_SMALL): they, and any entry whose fSIZ was too small, go through a
+    second call with the sizes reported."""
+    import torch
+    want = None if names is None else set(names)
+    sizes = {}                                                  # index -> bytes offered
+
+    def _list(idx, name, kind, stored):
+        if kind == 0 and (want is None or name in want):
+            sizes[idx] = stored or 0
+        return None
+    extract_select(ctx, archive_or_parts, _list, password)
+    out = {}
+    for _ in range(2):
+        offs, at = {}, 0
+        for idx, n in sizes.items():
+            offs[idx] = at
+            at += (n + 255) & ~255
+        buf = torch.empty(max(at, 1), dtype=torch.uint8, device="cuda")
+        recs, _s = extract_select(ctx, archive_or_parts,
+                                  lambda idx, name, kind, stored: buf[offs[idx]:offs[idx] + sizes[idx]] if idx in offs else None, password)
+        sizes = {}
+        for idx, name, kind, status, data, length in recs:
+            if status == EXTRACT_TOO_SMALL:
+                sizes[idx] = length
+            else:
+                out[name] = data
+        if not sizes:
+            return out
+    raise PnaGpuError(E_INVAL, "extract_to_device: an entry decoded to another size than the call before reported")
+
+
+def extract_stats(ctx: Context):
+    """(bytes of H2D archive copies, streams taken through the decode stage, key derivations, bytes k_pick moved, k_pick's HIP-event milliseconds) of the
+    context's latest extract_select call."""
+    a, b, k, p, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
+    ctx._check(ctx._L.pna_gpu_debug_extract_stats(ctx._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(k), ctypes.byref(p), ctypes.byref(ms)))
+    return a.value, b.value, k.value, p.value, ms.value
+
+
+def pick_device(ctx: Context, src, src_off: Sequence[int], dsts: Sequence[int], lens: Sequence[int], stream: int = 0) -> None:
+    """k_pick alone (pna_gpu_debug_pick_device): bytes [src_off[i], src_off[i] + lens[i]) of the CUDA tensor `src` to device address dsts[i]."""
+    n = len(src_off)
+    so, ln = (ctypes.c_uint64 * max(n, 1))(*src_off), (ctypes.c_uint64 * max(n, 1))(*lens)
+    dd = (ctypes.c_void_p * max(n, 1))(*dsts)
+    ctx._check(ctx._L.pna_gpu_debug_pick_device(ctx._h, n, src.data_ptr(), so, dd, ln, stream or None))
 
 
 def kdf_argon2(kind: int, password: bytes, salt: bytes, t_cost: int, m_cost_kib: int, lanes: int, key_len: int = 32) -> bytes:

@@ -69,6 +69,8 @@ __attribute__((weak)) void launch_frame_verdict(const FrameDesc *fd, uint32_t n,
 __attribute__((weak)) void launch_verdict(const VerdictEnt *ve, uint32_t n, const uint32_t *crc_v, const uint32_t *gcm_v, const uint32_t *cbc_plen, uint32_t *out, hipStream_t st);
 // `pna diff`'s kernel (k_diff.hip; weak like the verdict kernels: pna_gpu_diff_archive_host refuses to run without it)
 __attribute__((weak)) void launch_diff(const DiffPiece *pieces, uint32_t npieces, uint32_t ntiles, const uint8_t *a, const uint8_t *b, unsigned long long *first, hipStream_t st);
+// pna_gpu_extract_select_host's kernel (k_pick.hip; weak like launch_diff: the entry point refuses to run without it)
+__attribute__((weak)) void launch_pick(const PickPiece *pieces, uint32_t npieces, uint32_t ntiles, const uint8_t *src, hipStream_t st);
 void launch_zdec(ZFrame *frames, uint32_t n, const uint8_t *src, uint8_t *dst, uint8_t *lit_scratch, uint32_t dbg, hipStream_t st);
 void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *dst, hipStream_t st);
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st);
@@ -270,6 +272,10 @@ struct pna_gpu_ctx {
     PinBuf df_pin[2]; DevBuf df_dev[2], df_pieces, df_first;
     hipStream_t df_cp = nullptr; hipEvent_t df_ev_cp[2] = {}, df_ev_k[2] = {}; std::vector<hipEvent_t> df_tev; size_t df_tused = 0;
     uint64_t df_streams = 0, df_bytes = 0; double df_ms = 0;   // the latest diff call: streams handed to the decoders, bytes compared by k_diff, its HIP-event time
+    // pna_gpu_extract_select_host: k_pick's piece list, event pairs around its launches, and the latest call's counters -- bytes of H2D archive copies, streams
+    // taken through the decode stage, key derivations, bytes k_pick moved, its HIP-event time
+    DevBuf xs_pieces; std::vector<hipEvent_t> xs_tev; size_t xs_tused = 0;
+    uint64_t xs_uploaded = 0, xs_streams = 0, xs_kdf = 0, xs_picked = 0; double xs_ms = 0;
     hipStream_t x_cp = nullptr; hipEvent_t x_ev[2] = {}, x_done = nullptr;   // extract driver: D2H of window k on x_cp next to window k+1's work
     bool aes_dec_ready = false;        // read side (pna_gpu_extract_archive_host): archive image, packed payloads, decoded entries
     DevBuf z_vp, z_pb, z_mode;                                 // lane-per-piece inflate: piece list, piece boundaries, per-stream mode

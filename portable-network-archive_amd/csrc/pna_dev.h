@@ -183,6 +183,16 @@ struct DiffPiece {
     uint32_t entry, tile0;
 };
 static_assert(sizeof(DiffPiece) == 40, "DiffPiece layout");
+// k_pick (pna_gpu_extract_select_host's device destinations): bytes [src_off, src_off + len) of the launch's source buffer go to dst[0 .. len), any
+// alignment on either side.  A piece is PICK_TILE-byte tiles tile0, tile0 + 1, ... of the launch.
+constexpr uint32_t PICK_TILE = 16384;
+struct PickPiece {
+    uint64_t src_off;
+    uint8_t *dst;
+    uint64_t len;
+    uint32_t tile0, pad;
+};
+static_assert(sizeof(PickPiece) == 32, "PickPiece layout");
 
 // zstd decoder (k_zdec): one descriptor per frame
 struct ZFrame {

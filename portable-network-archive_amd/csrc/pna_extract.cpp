@@ -62,6 +62,7 @@ struct XCall {
     pna_gpu_ctx *c; const void *password; size_t password_len; pna_entry_fn cb; void *user;
     std::vector<std::pair<std::string, std::vector<uint8_t>>> keys; size_t index = 0;
     bool verdict = false, fast = false;                        // `pna verify` (pna_gpu_verify_archive_host): failures become records; --fast: chunk structure and CRCs only
+    uint64_t kdf_runs = 0;                                     // key derivations of the call (one per distinct PHSF string that a stream needed)
 };
 // a window's layout: packed payloads and decoded bytes, the gather of the data streams, the streams each cipher stage takes
 struct XPlan {
@@ -79,9 +80,14 @@ struct ArcParts {
     const uint8_t *const *p; const size_t *len; size_t n; std::vector<uint64_t> vb;
     const uint8_t *at(uint64_t v) const { const size_t k = (size_t)(std::upper_bound(vb.begin(), vb.end(), v) - vb.begin()) - 1; return p[k] + (v - vb[k]); }
 };
+struct XRun { uint64_t dev, arc, len; };                       // a run of a sparse window (pna_gpu_extract_select_host): archive bytes [arc, arc + len) lie at window offset dev
 struct WinSrc {                                                // a window's bytes: `a + o` is the byte at window offset o
-    const ArcParts *ap; uint64_t base;
-    const uint8_t *operator+(uint64_t o) const { return ap->at(base + o); }
+    const ArcParts *ap; uint64_t base; const std::vector<XRun> *runs = nullptr;      // runs: the window holds these runs of the archive only, packed (base unused)
+    const uint8_t *operator+(uint64_t o) const {
+        if (!runs) return ap->at(base + o);
+        const XRun &r = *(std::upper_bound(runs->begin(), runs->end(), o, [](uint64_t v, const XRun &q) { return v < q.dev; }) - 1);
+        return ap->at(r.arc + (o - r.dev));
+    }
 };
 uint32_t max_chunk_len(const std::vector<FrameDesc> &v) {      // the longest data chunk of a list (0: none below 16 380 bytes, the wave-per-chunk CRC kernel's limit)
     uint32_t m = 1;
@@ -143,7 +149,7 @@ static int phsf_key(XCall &x, const std::string &phsf, const uint8_t **out) {
     const int rc = kind >= 0 ? pna_kdf_argon2(kind, x.password, x.password_len, salt.data(), salt.size(), t, m, lanes, key.data(), 32)
                              : pna_kdf_pbkdf2_sha256(x.password, x.password_len, salt.data(), salt.size(), rounds, key.data(), 32, nullptr, 0);
     if (rc) return fail(c, rc, kind >= 0 ? "key derivation failed (argon2 parameters)" : "key derivation failed");
-    x.keys.emplace_back(phsf, std::move(key)); *out = x.keys.back().second.data();
+    x.keys.emplace_back(phsf, std::move(key)); *out = x.keys.back().second.data(); x.kdf_runs++;
     return PNA_OK;
 }
 
@@ -151,9 +157,10 @@ static int phsf_key(XCall &x, const std::string &phsf, const uint8_t **out) {
 // a chunk that fails its CRC is consumed (its length field trusted, as io::read_chunk does) and marks the entry that holds it BAD_CRC -- a bad FHED, or
 // damage between entries, opens a KIND_BROKEN record that runs to the next FEND / SEND --; structural faults mark their entry; the parts of a split
 // archive are walked one after the other (ANXT: the next part, its signature and AHED).  Where the walk cannot go on (a truncated chunk, no AEND)
-// *broken is set and what was complete before the break is kept.
+// *broken is set and what was complete before the break is kept.  `multipart` (pna_gpu_extract_select_host): the strict walk over the parts of a split
+// archive -- a missing part or a part without its signature fails the call.
 static int walk_archive(pna_gpu_ctx *c, const ArcParts &ap, bool verdict, std::vector<XEntry> &ents, std::vector<FrameDesc> &dchunks,
-                        std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids, bool *broken) {
+                        std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids, bool *broken, bool multipart = false) {
     XSolid scur; bool in_solid = false;
     XEntry cur; bool in_entry = false, ended = false;
     auto mark = [](XStream &s, int st) { if (!s.vst) s.vst = st; };
@@ -167,7 +174,7 @@ static int walk_archive(pna_gpu_ctx *c, const ArcParts &ap, bool verdict, std::v
     };
     for (size_t part = 0; part < ap.n && !ended; part++) {
         const uint8_t *a = ap.p[part]; const size_t archive_len = ap.len[part]; const uint64_t vb = ap.vb[part];
-        if (part > 0 && (archive_len < 8 || memcmp(a, PNA_SIGNATURE, 8) != 0)) { *broken = true; return PNA_OK; }
+        if (part > 0 && (archive_len < 8 || memcmp(a, PNA_SIGNATURE, 8) != 0)) { if (!verdict) return fail(c, PNA_E_INVAL, "a part is not a PNA archive"); *broken = true; return PNA_OK; }
         bool seen_ahed = false, next_part = false;
         size_t pos = 8;
         while (pos < archive_len) {
@@ -207,8 +214,8 @@ static int walk_archive(pna_gpu_ctx *c, const ArcParts &ap, bool verdict, std::v
                 seen_ahed = true;
             } else if (memcmp(ch.type, "AEND", 4) == 0) { if (verdict) close_open(off); ended = true; break; }
             else if (memcmp(ch.type, "ANXT", 4) == 0) {
-                if (!verdict) return fail(c, PNA_E_UNSUPPORTED, "multipart archives are not read by this driver");
-                if (part + 1 == ap.n) { *broken = true; return PNA_OK; }             // the archive goes on in a part that was not given
+                if (!verdict && !multipart) return fail(c, PNA_E_UNSUPPORTED, "multipart archives are not read by this driver");
+                if (part + 1 == ap.n) { if (!verdict) return fail(c, PNA_E_INVAL, "the archive goes on in a part that was not given"); *broken = true; return PNA_OK; }
                 next_part = true; break;
             }
             else if (memcmp(ch.type, "SHED", 4) == 0) {
@@ -386,10 +393,16 @@ static int upload_window(pna_gpu_ctx *c, const WinSrc &a, size_t archive_len, co
     if (c->x_arc.ensure(archive_len + 64) || c->x_pk.ensure(P.pk_total + 8192) || c->x_raw[slot].ensure(P.raw_total + 64) || c->x_flag.ensure(64) ||
         c->x_desc.ensure(dchunks.size() * sizeof(FrameDesc) + 16) || c->x_place.ensure(P.places.size() * sizeof(PlaceDescH) + 16) ||
         (verdict && c->v_crc.ensure((dchunks.size() + schunks.size()) * 4 + 16))) return fail(c, PNA_E_NOMEM, "extract workspace");
-    for (size_t k = 0; k < a.ap->n; k++) {                              // the parts that hold bytes of [base, base + archive_len)
-        const uint64_t p0 = a.ap->vb[k], p1 = p0 + a.ap->len[k], lo = std::max<uint64_t>(p0, a.base), hi = std::min<uint64_t>(p1, a.base + archive_len);
-        if (lo < hi) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->x_arc.p + (lo - a.base), a.ap->p[k] + (lo - p0), hi - lo, hipMemcpyHostToDevice, st));
-    }
+    auto copy_in = [&](uint64_t arc, uint64_t n, uint64_t dev) -> int {      // archive bytes [arc, arc + n) to window offset dev, from the parts that hold them
+        for (size_t k = 0; k < a.ap->n; k++) {
+            const uint64_t p0 = a.ap->vb[k], p1 = p0 + a.ap->len[k], lo = std::max<uint64_t>(p0, arc), hi = std::min<uint64_t>(p1, arc + n);
+            if (lo < hi) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->x_arc.p + dev + (lo - arc), a.ap->p[k] + (lo - p0), hi - lo, hipMemcpyHostToDevice, st));
+        }
+        c->xs_uploaded += n;
+        return PNA_OK;
+    };
+    if (a.runs) { for (const XRun &r : *a.runs) { rc = copy_in(r.arc, r.len, r.dev); if (rc) return rc; } }      // a sparse window: its runs, one copy each
+    else { rc = copy_in(a.base, archive_len, 0); if (rc) return rc; }
     HIPCHK(c, hipMemcpyAsync(c->x_flag.p, flag0, 8, hipMemcpyHostToDevice, st));
     auto check = [&](const DevBuf &desc, const std::vector<FrameDesc> &v, const char *ty) {
         if (verdict) launch_frame_verdict((const FrameDesc *)desc.p, (uint32_t)v.size(), (const CrcTabs *)c->crc_tabs.p, (const uint8_t *)c->x_arc.p,
@@ -1273,4 +1286,305 @@ extern "C" int pna_gpu_debug_diff_stats(pna_gpu_ctx *c, uint64_t *decoded_stream
     if (compared_bytes) *compared_bytes = c->df_bytes;
     if (ms_k_diff) *ms_k_diff = c->df_ms;
     return PNA_OK;
+}
+
+// ---- pna_gpu_extract_select_host: extract for the entries the host chooses, to host memory or to device memory of the caller's.  The stages above in
+// extract's (strict) mode over windows of its own making: `select` is asked for every entry in archive order, and a window holds the selected entries
+// only -- its H2D copies are the runs pna_extract_plan_runs makes of their records (all records that have data chunks under PNA_EXTRACT_CHECK_ALL), laid
+// one behind the other in the window buffer, and it is cut by the bytes it uploads, packs and decodes, not by the archive span it reaches over.  The
+// decoders write into the window buffers as ever; k_pick carries DEVICE entries from there to their destinations (one launch per window and source
+// buffer: the raw buffer, the packed buffer for stored entries; an entry without fSIZ is decoded into the open-decode buffer and picked from there
+// before the next one overwrites it), HOST entries travel through page-locked memory, and the window's records follow once the stream has drained.
+// A solid block is a window of its own, uploaded and decoded whole BEFORE anything is known to be wanted from it -- its inner entries' names lie in
+// the decoded stream -- and copied to the host once for its header walk (walk_solid); HOST records point into that copy, DEVICE records are picked
+// from the decoded stream where it lies.  Windows are not pipelined against each other here (extract's deferred hand-out): a callback may use d_dst,
+// so a window's records wait for its kernels anyway.
+constexpr uint64_t EXTRACT_GAP_MAX = PNA_EXTRACT_GAP_MAX;      // see include/pna_gpu.h
+extern "C" int pna_extract_plan_runs(const uint64_t *rec_off, const uint64_t *rec_len, const uint8_t *wanted, size_t n, uint64_t gap_max,
+                                     uint64_t *run_off, uint64_t *run_len, size_t *n_runs) {
+    if (!n_runs || (n && (!rec_off || !rec_len || !wanted))) return PNA_E_INVAL;
+    size_t k = 0; uint64_t start = 0, end = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (rec_off[i] + rec_len[i] < rec_off[i] || (i && rec_off[i] < rec_off[i - 1] + rec_len[i - 1])) return PNA_E_INVAL;      // records in archive order, none inside another
+        if (!wanted[i] || !rec_len[i]) continue;
+        if (k && rec_off[i] - end <= gap_max) end = rec_off[i] + rec_len[i];                 // the gap travels with its neighbours
+        else { start = rec_off[i]; end = start + rec_len[i]; k++; if (run_off) run_off[k - 1] = start; }
+        if (run_len) run_len[k - 1] = end - start;
+    }
+    *n_runs = k;
+    return PNA_OK;
+}
+namespace {
+struct SCall { pna_extract_select_fn sel; pna_extract_record_fn cb; void *user; bool check_all; pna_extract_summary sum{}; };
+// a record of a window: what `select` said, where the entry's bytes are handed out
+struct SRec {
+    size_t index = 0; std::string path; int kind = 0; pna_extract_dest d{PNA_EXTRACT_SKIP, nullptr, 0};
+    int ei = -1;                                                 // its entry in the window's list (-1: a data-less record, or an inner entry of a solid stream)
+    int status = PNA_EXTRACT_OK; uint64_t len = 0;
+    const uint8_t *host = nullptr; bool staged = false; uint64_t hoff = 0; std::vector<uint8_t> own;      // HOST: bytes in the caller's view / in the page-locked slot at hoff / of its own
+};
+int ask_select(XCall &x, SCall &s, const std::string &raw_name, int kind, bool has_size, uint64_t raw_size, SRec &r) {
+    int rc = entry_path(x.c, raw_name, r.path); if (rc) return rc;
+    r.index = x.index++; r.kind = kind; r.d = pna_extract_dest{PNA_EXTRACT_SKIP, nullptr, 0};
+    if (s.sel(s.user, r.index, r.path.c_str(), kind, has_size ? raw_size : UINT64_MAX, &r.d) != 0) return fail(x.c, PNA_E_SINK, "select callback failed");
+    if (r.d.where < PNA_EXTRACT_SKIP || r.d.where > PNA_EXTRACT_DEVICE) return fail(x.c, PNA_E_INVAL, "select callback: unknown destination");
+    if (r.d.where == PNA_EXTRACT_DEVICE && !r.d.d_dst && r.d.cap) return fail(x.c, PNA_E_INVAL, "select callback: device destination announced, none given");
+    s.sum.total++;
+    if (r.d.where != PNA_EXTRACT_SKIP) s.sum.selected++;
+    return PNA_OK;
+}
+// k_pick's launches: pieces of one source buffer are collected and go out together
+struct PickList {
+    pna_gpu_ctx *c; hipStream_t st; const uint8_t *src = nullptr; std::vector<PickPiece> pend; uint32_t tiles = 0;
+    int flush() {
+        if (pend.empty()) return PNA_OK;
+        if (c->xs_pieces.ensure(pend.size() * sizeof(PickPiece) + 16)) return fail(c, PNA_E_NOMEM, "extract workspace");
+        while (c->xs_tev.size() < c->xs_tused + 2) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->xs_tev.push_back(e); }
+        HIPCHK(c, hipMemcpyAsync(c->xs_pieces.p, pend.data(), pend.size() * sizeof(PickPiece), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipEventRecord(c->xs_tev[c->xs_tused], st));
+        // every load of k_pick stays inside the source range rounded out to 16 bytes: the window buffers (x_raw, x_pk, solid_plain) start at a multiple of
+        // 16 and are allocated with at least 64 bytes behind the last entry
+        launch_pick((const PickPiece *)c->xs_pieces.p, (uint32_t)pend.size(), tiles, src, st);
+        HIPCHK(c, hipEventRecord(c->xs_tev[c->xs_tused + 1], st));
+        HIPCHK(c, hipGetLastError());
+        c->xs_tused += 2;
+        pend.clear(); tiles = 0;
+        return PNA_OK;
+    }
+    int add(const void *buf, uint64_t off, void *dst, uint64_t len) {
+        if (!len) return PNA_OK;
+        const uint64_t t = (len + PICK_TILE - 1) / PICK_TILE;
+        if (t > 0x7FFFFFFFu) return fail(c, PNA_E_UNSUPPORTED, "entry too large for one k_pick launch");
+        if ((buf != src && !pend.empty()) || (uint64_t)tiles + t > 0x7FFFFFFFu) { const int rc = flush(); if (rc) return rc; }
+        src = (const uint8_t *)buf;
+        pend.push_back(PickPiece{off, (uint8_t *)dst, len, tiles, 0});
+        tiles += (uint32_t)t; c->xs_picked += len;
+        return PNA_OK;
+    }
+    int finish() {                                                  // the last launch, the stream drained, k_pick's time
+        const int rc = flush(); if (rc) return rc;
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (size_t k = 0; k + 1 < c->xs_tused; k += 2) { float ms = 0; if (hipEventElapsedTime(&ms, c->xs_tev[k], c->xs_tev[k + 1]) == hipSuccess) c->xs_ms += ms; }
+        c->xs_tused = 0;
+        return PNA_OK;
+    }
+};
+// HOST entries on their way back: ranges of the device buffers into one page-locked slot, neighbours in one copy
+struct HostCopies {
+    struct Job { const uint8_t *buf; uint64_t off, len, hoff; };
+    std::vector<Job> jobs; uint64_t total = 0;
+    uint64_t add(const void *buf, uint64_t off, uint64_t len) {
+        if (!jobs.empty()) {
+            Job &j = jobs.back();
+            if (j.buf == buf && off >= j.off + j.len && off <= ((j.off + j.len + 15) & ~(uint64_t)15)) { j.len = off + len - j.off; total = j.hoff + j.len; return j.hoff + (off - j.off); }
+        }
+        const uint64_t h = (total + 15) & ~(uint64_t)15;
+        jobs.push_back(Job{(const uint8_t *)buf, off, len, h}); total = h + len;
+        return h;
+    }
+    int issue(pna_gpu_ctx *c, hipStream_t st) {
+        if (c->hp_out[0].ensure(total + 64)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
+        for (const Job &j : jobs) if (j.len) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->hp_out[0].p + j.hoff, j.buf + j.off, j.len, hipMemcpyDeviceToHost, st));
+        return PNA_OK;
+    }
+};
+// where a selected entry's `size` decoded bytes at buf + off go: a pick, a copy to the host, or nowhere (TOO_SMALL)
+int route(pna_gpu_ctx *c, SRec &r, const void *buf, uint64_t off, uint64_t size, PickList &picks, HostCopies &hc) {
+    r.len = size;
+    if (r.d.where == PNA_EXTRACT_DEVICE) {
+        if (r.d.cap < size) { r.status = PNA_EXTRACT_TOO_SMALL; return PNA_OK; }
+        return picks.add(buf, off, r.d.d_dst, size);
+    }
+    if (size) { r.hoff = hc.add(buf, off, size); r.staged = true; }
+    return PNA_OK;
+}
+int emit_records(XCall &x, SCall &s, std::vector<SRec> &recs) {
+    pna_gpu_ctx *c = x.c;
+    for (SRec &r : recs) {
+        const void *data = nullptr;
+        if (r.d.where == PNA_EXTRACT_DEVICE) {
+            if (r.status == PNA_EXTRACT_TOO_SMALL) s.sum.too_small++; else { s.sum.to_device++; data = r.d.d_dst; }
+        } else {
+            s.sum.to_host++;
+            if (r.len) data = r.staged ? (const uint8_t *)c->hp_out[0].p + r.hoff : r.host;
+        }
+        if (s.cb(s.user, r.index, r.path.c_str(), r.kind, r.status, data, r.len) != 0) return fail(c, PNA_E_SINK, "record callback failed");
+    }
+    return PNA_OK;
+}
+// a window of selected normal entries: `ents` are the entries recs[].ei name, `chunks` the data chunks to check, offsets relative to the packed window
+int select_window(XCall &x, SCall &s, const WinSrc &a, uint64_t win_len, std::vector<XEntry> &ents, std::vector<FrameDesc> &chunks, std::vector<SRec> &recs) {
+    pna_gpu_ctx *c = x.c;
+    XPlan P; std::vector<XSolid> no_solid; std::vector<FrameDesc> no_sdat;
+    int rc = plan_window(x, a, ents, no_solid, P); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    uint32_t flag[2] = {0, 0};
+    rc = upload_window(c, a, (size_t)win_len, chunks, no_sdat, P, 0, flag, st); if (rc) return rc;
+    if (flag[0]) { c->err = "data chunk CRC mismatch (" + std::to_string(flag[0]) + " FDAT chunks)"; return PNA_E_INVAL; }
+    if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
+    if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
+    rc = decode_sized(c, ents, 0, st); if (rc) return rc;
+    c->xs_streams += ents.size();                                     // (a stored entry's decode is the identity)
+    PickList picks{c, st}; HostCopies hc;
+    std::vector<bool> open(ents.size(), false);
+    for (size_t i : P.nosize_idx) open[i] = true;
+    for (int pass = 0; pass < 2; pass++)                              // the raw buffer's entries, then the packed buffer's: one k_pick launch each
+        for (SRec &r : recs) {
+            if (r.ei < 0 || open[(size_t)r.ei]) continue;
+            const XEntry &e = ents[(size_t)r.ei];
+            const bool stored = e.compression == PNA_ALGO_STORE;
+            if (stored != (pass == 1)) continue;
+            if (stored && e.has_size && e.raw_size != e.pay_len) return fail(c, PNA_E_INVAL, "stored entry: fSIZ differs from the data length");
+            rc = stored ? route(c, r, c->x_pk.p, e.pk_off, e.pay_len, picks, hc) : route(c, r, c->x_raw[0].p, e.raw_off, e.raw_size, picks, hc);
+            if (rc) return rc;
+        }
+    for (SRec &r : recs) {                                            // entries without fSIZ: measured and decoded one by one, as extract does
+        if (r.ei < 0 || !open[(size_t)r.ei]) continue;
+        const XEntry &e = ents[(size_t)r.ei];
+        if (r.d.where == PNA_EXTRACT_HOST) { rc = decode_open(c, e, "entry buffer", &r.own, st); if (rc) return rc; r.len = r.own.size(); r.host = r.own.data(); continue; }
+        uint64_t got = 0;
+        rc = decode_open(c, e, "entry buffer", nullptr, st, &got); if (rc) return rc;
+        rc = route(c, r, c->solid_plain.p, 0, got, picks, hc); if (rc) return rc;
+        rc = picks.flush(); if (rc) return rc;                       // (before the next entry is decoded into the same buffer)
+    }
+    rc = hc.issue(c, st); if (rc) return rc;
+    rc = picks.finish(); if (rc) return rc;
+    return emit_records(x, s, recs);
+}
+// a solid block: uploaded, decrypted, decoded and walked as extract does; then the question for every inner entry
+int select_solid(XCall &x, SCall &s, const WinSrc &a, size_t span, std::vector<FrameDesc> &schunks, std::vector<XSolid> &solids) {
+    pna_gpu_ctx *c = x.c;
+    XPlan P; std::vector<XEntry> no_ents; std::vector<FrameDesc> no_fdat;
+    int rc = plan_window(x, a, no_ents, solids, P); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    uint32_t flag[2] = {0, 0};
+    rc = upload_window(c, a, span, no_fdat, schunks, P, 0, flag, st); if (rc) return rc;
+    if (flag[0]) { c->err = "data chunk CRC mismatch (" + std::to_string(flag[0]) + " SDAT chunks)"; return PNA_E_INVAL; }
+    if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
+    if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
+    const XSolid &so = solids[0];
+    std::vector<uint8_t> plain; std::vector<Inner> inner;
+    c->xs_streams++;
+    rc = walk_solid(c, so, plain, inner, flag, st); if (rc) return rc;
+    const bool stored = so.compression == PNA_ALGO_STORE;            // (a stored stream lies in the packed buffer)
+    const void *buf = stored ? c->x_pk.p : c->solid_plain.p; const uint64_t base = stored ? so.pk_off : 0;
+    PickList picks{c, st};
+    std::vector<SRec> recs;
+    for (const Inner &ie : inner) {
+        SRec r;
+        rc = ask_select(x, s, ie.name, ie.kind, ie.has_size, ie.raw_size, r); if (rc) return rc;
+        if (r.d.where == PNA_EXTRACT_SKIP) continue;
+        r.len = ie.len;
+        if (r.d.where == PNA_EXTRACT_HOST) {
+            if (ie.pieces.size() == 1) r.host = plain.data() + ie.pieces[0].off;
+            else { for (const XPiece &p : ie.pieces) r.own.insert(r.own.end(), plain.data() + p.off, plain.data() + p.off + p.len); r.host = r.own.data(); }
+        } else if (r.d.cap < ie.len) r.status = PNA_EXTRACT_TOO_SMALL;
+        else {
+            uint64_t at = 0;
+            for (const XPiece &p : ie.pieces) { rc = picks.add(buf, base + p.off, (uint8_t *)r.d.d_dst + at, p.len); if (rc) return rc; at += p.len; }
+        }
+        recs.push_back(std::move(r));
+    }
+    rc = picks.finish(); if (rc) return rc;
+    return emit_records(x, s, recs);
+}
+}
+
+extern "C" int pna_gpu_extract_select_host(pna_gpu_ctx *c, const void *const *parts, const size_t *part_len, size_t n_parts, const void *password,
+                                           size_t password_len, uint32_t xflags, pna_extract_select_fn select, pna_extract_record_fn cb, void *user,
+                                           pna_extract_summary *summary) {
+    if (!c || !parts || !part_len || !n_parts || !select || !cb || (!password && password_len)) return fail(c, PNA_E_INVAL, "null argument");
+    if (xflags & ~(uint32_t)PNA_EXTRACT_CHECK_ALL) return fail(c, PNA_E_INVAL, "unknown extract flag");
+    for (size_t k = 0; k < n_parts; k++) if (!parts[k]) return fail(c, PNA_E_INVAL, "null argument");
+    if (part_len[0] < 8 || memcmp(parts[0], PNA_SIGNATURE, 8) != 0) return fail(c, PNA_E_INVAL, "not a PNA archive");
+    if (!launch_pick) return fail(c, PNA_E_UNSUPPORTED, "this build has no pick kernel");
+    ArcParts ap{(const uint8_t *const *)parts, part_len, n_parts, {}};
+    uint64_t at = 0;
+    for (size_t k = 0; k < n_parts; k++) { ap.vb.push_back(at); at += part_len[k]; }
+    XCall x{c, password, password_len, nullptr, nullptr, {}, 0};
+    SCall s{select, cb, user, (xflags & PNA_EXTRACT_CHECK_ALL) != 0};
+    c->xs_uploaded = 0; c->xs_streams = 0; c->xs_kdf = 0; c->xs_picked = 0; c->xs_ms = 0; c->xs_tused = 0;
+    std::vector<XEntry> ents; std::vector<FrameDesc> dchunks, schunks; std::vector<XSolid> solids;
+    bool broken = false;
+    int rc = walk_archive(c, ap, false, ents, dchunks, schunks, solids, &broken, true);
+    const uint64_t WIN = (uint64_t)c->tun.extract_win_mib << 20;
+    size_t si = 0, w0 = 0;
+    SRec carry; bool carried = false;                                 // the entry that did not fit the previous window: asked already
+    while (rc == PNA_OK && (w0 < ents.size() || si < solids.size())) {
+        if (si < solids.size() && solids[si].order <= w0) {
+            XWindow W;
+            next_window(c, ents, dchunks, schunks, solids, w0, si, W);
+            rc = select_solid(x, s, WinSrc{&ap, W.base}, (size_t)W.span, W.ws, W.wso);
+            continue;
+        }
+        // the next window: entries are asked about in archive order until what is wanted of them fills it
+        const size_t stop = si < solids.size() ? std::min(ents.size(), solids[si].order) : ents.size();
+        std::vector<XEntry> we; std::vector<FrameDesc> wd; std::vector<SRec> recs;
+        struct Need { uint64_t lo, len; size_t c0, c1; int ei; };      // a record that travels: its bytes, its chunks in wd, its entry in we (-1: checked only)
+        std::vector<Need> need;
+        uint64_t up = 0, raw = 0, pk = 0;
+        while (rc == PNA_OK && w0 < stop) {
+            XEntry &e = ents[w0];
+            SRec r;
+            if (carried) { r = std::move(carry); carried = false; }
+            else { rc = ask_select(x, s, e.name, e.kind, e.has_size, e.raw_size, r); if (rc) break; }
+            const bool sel = r.d.where != PNA_EXTRACT_SKIP, dataless = e.kind != 0 && e.pieces.empty();
+            if ((sel && !dataless) || (s.check_all && e.d1 > e.d0)) {
+                const bool dec = sel && !dataless;
+                const uint64_t b = e.hi - e.lo, rr = dec && e.has_size ? e.raw_size : 0, pp = dec ? e.stream_len : 0;
+                if (!need.empty() && (up + b > WIN || raw + rr > 3 * WIN || pk + pp > WIN)) { carry = std::move(r); carried = true; break; }
+                up += b; raw += rr; pk += pp;
+                need.push_back(Need{e.lo, b, wd.size(), wd.size() + (e.d1 - e.d0), dec ? (int)we.size() : -1});
+                wd.insert(wd.end(), dchunks.begin() + e.d0, dchunks.begin() + e.d1);
+                if (dec) { r.ei = (int)we.size(); we.push_back(std::move(e)); }
+            }
+            if (sel) recs.push_back(std::move(r));
+            w0++;
+        }
+        if (rc) break;
+        // the runs that travel, laid one behind the other (each at a multiple of 16), and everything of the window moved to where its run lies
+        std::vector<uint64_t> ro, rl, run_off(need.size()), run_len(need.size()); size_t nr = 0;
+        for (const Need &q : need) { ro.push_back(q.lo); rl.push_back(q.len); }
+        const std::vector<uint8_t> all(need.size(), 1);
+        rc = pna_extract_plan_runs(ro.data(), rl.data(), all.data(), need.size(), EXTRACT_GAP_MAX, run_off.data(), run_len.data(), &nr);
+        if (rc) { rc = fail(c, PNA_E_INVAL, "entries out of order"); break; }
+        std::vector<XRun> runs; uint64_t win_len = 0;
+        for (size_t k = 0; k < nr; k++) { runs.push_back(XRun{win_len, run_off[k], run_len[k]}); win_len = (win_len + run_len[k] + 15) & ~(uint64_t)15; }
+        size_t k = 0;
+        for (const Need &q : need) {
+            while (k + 1 < nr && q.lo >= runs[k + 1].arc) k++;
+            const uint64_t delta = runs[k].arc - runs[k].dev;
+            for (size_t j = q.c0; j < q.c1; j++) wd[j].arc_off -= delta;
+            if (q.ei >= 0) for (XPiece &p : we[(size_t)q.ei].pieces) p.off -= delta;
+        }
+        if (need.empty() && recs.empty()) continue;
+        rc = select_window(x, s, WinSrc{&ap, 0, &runs}, win_len, we, wd, recs);
+    }
+    c->xs_kdf = x.kdf_runs;
+    if (rc) (void)hipDeviceSynchronize();                               // (nothing of a window that failed is left in flight)
+    if (summary) *summary = s.sum;
+    return rc;
+}
+extern "C" int pna_gpu_debug_extract_stats(pna_gpu_ctx *c, uint64_t *uploaded_bytes, uint64_t *decoded_streams, uint64_t *kdf_runs, uint64_t *picked_bytes,
+                                           double *ms_k_pick) {
+    if (!c) return PNA_E_INVAL;
+    if (uploaded_bytes) *uploaded_bytes = c->xs_uploaded;
+    if (decoded_streams) *decoded_streams = c->xs_streams;
+    if (kdf_runs) *kdf_runs = c->xs_kdf;
+    if (picked_bytes) *picked_bytes = c->xs_picked;
+    if (ms_k_pick) *ms_k_pick = c->xs_ms;
+    return PNA_OK;
+}
+extern "C" int pna_gpu_debug_pick_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, void *const *d_dst, const uint64_t *len,
+                                         void *hip_stream) {
+    if (!c || (n && (!d_src || !src_off || !d_dst || !len))) return fail(c, PNA_E_INVAL, "null argument");
+    for (size_t i = 0; i < n; i++) if (len[i] && !d_dst[i]) return fail(c, PNA_E_INVAL, "null argument");
+    if (!launch_pick) return fail(c, PNA_E_UNSUPPORTED, "this build has no pick kernel");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->xs_picked = 0; c->xs_ms = 0; c->xs_tused = 0;
+    PickList picks{c, hip_stream ? (hipStream_t)hip_stream : c->stream};
+    for (size_t i = 0; i < n; i++) { const int rc = picks.add(d_src, src_off[i], d_dst[i], len[i]); if (rc) return rc; }
+    return picks.finish();                                              // (drains the stream: the counters above hold this call's bytes and time)
 }

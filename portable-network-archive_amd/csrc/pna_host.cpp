@@ -106,6 +106,8 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     for (auto &e : c->df_ev_cp) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->df_ev_k) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->df_tev) if (e) (void)hipEventDestroy(e);
+    c->xs_pieces.release();
+    for (auto &e : c->xs_tev) if (e) (void)hipEventDestroy(e);
     if (c->x_cp) (void)hipStreamDestroy(c->x_cp);
     for (auto &e : c->x_ev) if (e) (void)hipEventDestroy(e);
     if (c->x_done) (void)hipEventDestroy(c->x_done);
