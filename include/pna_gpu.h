@@ -91,6 +91,16 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
  *   "small_geometry" [PNA_SMALL_GEOMETRY] 1 (default): segments of at most 16 KiB -- small entries, the tail of longer ones -- are matched by one wave each with look-ups and inserts
  *                                         alternating per 256 positions (k_lzms) instead of by a workgroup per 4 096: such a segment's first tile finds nothing in the large
  *                                         geometry (4 KiB text entries: ratio 1.77 -> 2.04, libzstd -3: 2.05).  0: the large geometry for every segment.  Other bytes, same format
+ *   "mtile" [PNA_MTILE]                   0 (default): the match kernel of the large geometry (k_lzm, segments above 16 KiB) looks up all 4 096 positions of a tile before it inserts
+ *                                         any of them, so a position sees nothing less than a tile back.  256, 512, 1024 or 2048: look-ups and inserts alternate per sub-tile of that
+ *                                         many positions inside the tile, and a position finds the matches a few hundred bytes back that real text, sources and binaries are made of
+ *                                         (oracle: mtile; README has the measured cost and gain).  Any other value is PNA_E_INVAL.  Covers every set whose table lies in LDS -- zstd
+ *                                         1 .. 9 and deflate 1 .. 9 --, on every path that compresses through the context.  With it such segments always take the split form of the LZ
+ *                                         stage (lz_split, lz_split_min and PNA_F_LZ_FUSED no longer choose the one-kernel form, which has no sub-tiles; lz_split = 2 remains), the
+ *                                         latency mode keeps its small blocks but runs whole segments (pna_gpu_timing.lz_units == 0; an explicit unit_log is overridden, and there are
+ *                                         no tail units), and a words workspace that cannot be had is PNA_E_NOMEM instead of a fall-back.  NOT covered: zstd 10 .. 22 (table in global
+ *                                         memory) ignore the option; segments of at most 16 KiB run the small geometry as before (its sub-tiles are 256 positions anyway; with
+ *                                         small_geometry = 0 they run the large geometry with these sub-tiles).  Other bytes, same format
  *   "single_frame" [PNA_SINGLE_FRAME]     zstd: 1 = an entry's payload is ONE frame (one frame header, the 1 MiB segments' blocks behind each other, matches never
  *                                         cross a segment start) as the reference's encoder writes (lib/src/compress/zstandard.rs: one Encoder per entry);
  *                                         0 (default) = a frame per 1 MiB segment, which this library's decoder takes in parallel.  3 + 0..2 bytes per segment apart

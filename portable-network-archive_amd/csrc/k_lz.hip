@@ -633,6 +633,8 @@ static void launch_lz_g(const uint8_t *src, const SegDesc *segs, uint32_t nseg, 
     (void)attr_set;
     if (pbuf) {
         if (flags & FLAG_SPLIT_WAVEPARSE) {
+            if ((flags >> FLAG_MT_SHIFT) & 7u) launch_lz_split(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, nullptr, nullptr, nullptr);   // (option mtile: only k_lzm has sub-tiles -- here with words of four bytes, for the parse kernel below)
+            else
             hipLaunchKernelGGL((k_lz<false, G, CT, STRONG, 1, WLOG, TAB3>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, seqs, lits, blk, ctab, flags, max_off, max_len, pbuf, blk0);
             if (flags & FLAG_HAS_SMALL) launch_lz_small(src, segs, nseg, seqs, lits, blk, ctab, flags, max_len, st, pbuf, blk0, nullptr, false);   // (match kernel only; this form's words take four bytes)
             if (ev_match) (void)hipEventRecord(ev_match, st);

@@ -116,7 +116,27 @@ __device__ __forceinline__ uint32_t far_match(const uint32_t *win32, uint32_t q,
     return STRONG ? (l >= MIN_MATCH ? pk_make(l, so, bk3) : 0u) : pk_make(l >= MIN_MATCH ? l : 0u, so, bk3);
 }
 
-template <bool DEFL, int STRONG, uint32_t GLOG, uint32_t WLOG, bool FARP, bool TAB3>   // STRONG: 0 = two adoption rounds / 3 back bytes, 1 = + the round over four positions / 7 back bytes, 2 = + the round over eight / 15
+// the inserts of a lane's four positions (k_lzm): behind the tile's look-ups, with sub-tiles behind the sub-tile's
+// (A macro on purpose, expanded at both places: as a lambda or a function it changed the register allocation and the address arithmetic of the instances without
+// sub-tiles -- 2 - 4 VGPRs, a few dozen instructions moved --, whose code must stay what it was; LAB_LOG.md 6.1.  Do not tidy it into a function without comparing their assembly.)
+#define LZM_INSERT() \
+            if constexpr (TAB3) { \
+                /* one 64-bit maximum per even position: the word as the look-up saw it with this position's field replaced (position 0 is never stored: \
+                   its entry could be the empty one) */ \
+                if (FULL || (hv[0] && q0 != 0)) t3_max(&table64[hsh[0]], t3_put(w3a, sh3[0], t3_field(w3a, sh3[0]), t3_entry(q0, tag[0]))); \
+                if (FULL || hv[2]) t3_max(&table64[hsh[2]], t3_put(w3b, sh3[2], t3_field(w3b, sh3[2]), t3_entry(q0 + 2, tag[2]))); \
+            } else if (FULL) {                                                      /* (all but a block's last tile -- every position valid, no exec masks) */ \
+                _Pragma("unroll") \
+                for (int j = 0; j < 4; j++) if (ins_all || !(j & 1)) atomicMax(&table[hsh[j]], ((q0 + j + 1) << TAG_BITS) | tag[j]); \
+            } else { \
+                _Pragma("unroll") \
+                for (int j = 0; j < 4; j++) if (hv[j] && (ins_all || !(j & 1))) atomicMax(&table[hsh[j]], ((q0 + j + 1) << TAG_BITS) | tag[j]); \
+            }
+// SUBTILE (option mtile; the oracle's `mtile`): look-ups and inserts alternate per SUB-TILE of 256 << k positions inside the tile (FLAG_MT_SHIFT: k + 1) -- the waves that
+// own sub-tile p look up (hash, table entries: kept in registers), barrier, insert, barrier, so that the next sub-tile's look-ups see those inserts and a position finds
+// candidates inside its own tile (near ones: the window holds the tile).  Everything behind the look-ups -- candidates, far round, match, adoption, words -- is the tile's,
+// as without sub-tiles.  Only with the table in LDS; the instances without it are untouched.
+template <bool DEFL, int STRONG, uint32_t GLOG, uint32_t WLOG, bool FARP, bool TAB3, bool SUBTILE = false>   // STRONG: 0 = two adoption rounds / 3 back bytes, 1 = + the round over four positions / 7 back bytes, 2 = + the round over eight / 15
 __global__ __launch_bounds__(LZ_THREADS)
 void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, uint32_t flags, uint32_t max_off, uint32_t *__restrict__ pbuf, uint32_t blk0,
            uint32_t *__restrict__ gtab) {
@@ -133,6 +153,7 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
     static_assert(NEAR == GEO::NEARM, "lz_common.h: the one-kernel form numbers this kernel's far candidates (FLAG_FAR1)");
     static_assert(WIN_BYTES >= TILE_G + LA + NEAR + 8 + 200 && (!DEFL || NEAR >= 32768), "window: look-back (+ 8 back bytes) + this tile + look-ahead");
     static_assert(!TAB3 || (GLOG == 0 && !DEFL && FAR), "the packed table: zstd sets with the table in LDS and far candidates");
+    static_assert(!SUBTILE || GLOG == 0, "sub-tiles: the table in LDS (a workgroup barrier orders its inserts and look-ups)");
     static_assert(LZ_G_ZSTD == 4 && LZ_G_DEFLATE == 4 && WIN_MIRROR >= 40, "k_lzm: four positions per lane, 36 bytes read behind a lane's first position");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint32_t *win32 = (uint32_t *)(lds + L_WIN);
@@ -150,6 +171,8 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
     // for 6 .. 36: adopted lengths beyond 36 are clamped, FLAG_LEN36 tells the one-kernel form to do the same) and 19 for the offset (MAX_OFF_W3) --:
     // the parse kernel's time is the time to stream them (42 GB per step at 4 bytes).  With the table in global memory: 4 bytes, 6 + 20 bits.
     constexpr bool W3 = GLOG == 0;
+    const bool w4 = SUBTILE && (flags & FLAG_SPLIT_WAVEPARSE);        // (uniform) sub-tiles in front of the wave-per-region parse kernel, which reads words of four bytes
+    const uint32_t mt_ws = SUBTILE ? ((flags >> FLAG_MT_SHIFT) & 7u) - 1u : 0u;   // a sub-tile is 1 << mt_ws waves' positions
     uint32_t *pb = pbuf + ((size_t)(sd.blk_base - blk0) << blk_log);
     uint8_t *pb8 = (uint8_t *)pbuf + 3 * ((size_t)(sd.blk_base - blk0) << blk_log);
     const bool adopt = (flags & F_ADOPT) != 0, ins_all = !(flags & F_INS2);
@@ -200,6 +223,13 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
             uint32_t hsh[4], tag[4], ent[4];
             uint32_t sh3[4] = {0, 0, 0, 0}; uint64_t w3a = 0, w3b = 0;                  // TAB3: the fields' bit positions; the words of positions 0 and 2 as the look-ups saw them
             bool hv[4];
+            if constexpr (SUBTILE) for (int j = 0; j < 4; j++) { hsh[j] = tag[j] = ent[j] = 0; hv[j] = false; }   // (a wave behind a partial tile's last sub-tile looks nothing up)
+            // SUBTILE: the sub-tiles in order -- the owners of sub-tile ph look up, then insert; every wave takes every barrier.  (One wave per sub-tile: its own LDS
+            // operations are in order, the barrier between its look-ups and its inserts is not needed.)  With the packed table the contest "one contender per word"
+            // is therefore the sub-tile's: every contender of a sub-tile saw the same word.  Without sub-tiles: one turn, the tile's look-ups.
+            const uint32_t nph = SUBTILE ? (t1 - t0 + (RW << mt_ws) - 1) / (RW << mt_ws) : 1u, myph = SUBTILE ? wave >> mt_ws : 0u;
+            for (uint32_t ph = 0; ph < nph; ph++) {
+            if (!SUBTILE || ph == myph) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const uint32_t q = q0 + j;
@@ -219,6 +249,13 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
                 if (GLOG) ent[j] = hv[j] ? __hip_atomic_load(&table[hsh[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
                 else { const uint32_t e = table[hsh[j]]; ent[j] = hv[j] ? e : 0u; }     // (the LDS read goes out for every lane -- any slot is readable --, a select instead of an exec-masked region)
                 }
+            }
+            }
+            if constexpr (SUBTILE) {
+                if (mt_ws) __syncthreads();
+                if (ph == myph) { LZM_INSERT(); }
+                __syncthreads();
+            }
             }
             // ---- candidates (rules as in k_lz)
             uint32_t off[4];
@@ -377,19 +414,8 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
                 *(uint4 *)(lds + L_WIN + wo) = pf;
                 if (wo < WIN_MIRROR) *(uint4 *)(lds + L_WIN + WIN_BYTES + wo) = pf;
             }
-            if constexpr (TAB3) {
-                // one 64-bit maximum per even position: the word as the look-up saw it with this position's field replaced (position 0 is never stored:
-                // its entry could be the empty one)
-                if (FULL || (hv[0] && q0 != 0)) t3_max(&table64[hsh[0]], t3_put(w3a, sh3[0], t3_field(w3a, sh3[0]), t3_entry(q0, tag[0])));
-                if (FULL || hv[2]) t3_max(&table64[hsh[2]], t3_put(w3b, sh3[2], t3_field(w3b, sh3[2]), t3_entry(q0 + 2, tag[2])));
-            } else if (FULL) {                                                      // (all but a block's last tile -- every position valid, no exec masks)
-#pragma unroll
-                for (int j = 0; j < 4; j++) if (ins_all || !(j & 1)) atomicMax(&table[hsh[j]], ((q0 + j + 1) << TAG_BITS) | tag[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; j++) if (hv[j] && (ins_all || !(j & 1))) atomicMax(&table[hsh[j]], ((q0 + j + 1) << TAG_BITS) | tag[j]);
-            }
-            if (W3) {
+            if constexpr (!SUBTILE) { LZM_INSERT(); }
+            if (W3 && !w4) {
                 if (FULL || q0 < t1) {
                     uint32_t ww[4];
 #pragma unroll
@@ -403,6 +429,10 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
                     __builtin_nontemporal_store(__builtin_amdgcn_perm(ww[3], ww[2], 0x06050402u), &o->z);   // byte 2 of word 2, bytes 0 1 2 of word 3
                 }
             } else if (FULL || q0 < t1) {
+                if (w4 && (flags & FLAG_LEN36)) {                                   // (uniform) what the three-byte words keep
+#pragma unroll
+                    for (int j = 0; j < 4; j++) if ((P[j] >> PK_LEN) > 36u) P[j] = (P[j] & PK_LOW) | (36u << PK_LEN);
+                }
                 v4u wv;
                 wv.x = (P[0] >> PK_LEN) | (P[0] & (0xFFFFFu << PK_OFF)); wv.y = (P[1] >> PK_LEN) | (P[1] & (0xFFFFFu << PK_OFF));
                 wv.z = (P[2] >> PK_LEN) | (P[2] & (0xFFFFFu << PK_OFF)); wv.w = (P[3] >> PK_LEN) | (P[3] & (0xFFFFFu << PK_OFF));
@@ -418,6 +448,7 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
         }
     }
 }
+#undef LZM_INSERT
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // k_lzms -- the match half for SHORT segments (pna_dev.h: at most SMALL_SEG = 4 096 bytes).  k_lzm's tile is 4 096 positions whose look-ups all come before
@@ -1028,14 +1059,15 @@ void k_lzp(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, co
     }
 }
 
-template <bool CT, int STRONG, uint32_t GLOG, uint32_t WLOG, bool FARP = !CT, bool TAB3 = false>
+template <bool CT, int STRONG, uint32_t GLOG, uint32_t WLOG, bool FARP = !CT, bool TAB3 = false, bool SUBTILE = false>
 static void launch_split_g(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
                            uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg) {
     constexpr uint32_t LT = GLOG ? LzGeo<WLOG>::L_TABLE : LzGeo<WLOG, TAB3>::L_TOTAL;
-    static const hipError_t attr_set = hipFuncSetAttribute((const void *)k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LzGeo<WLOG, TAB3>::L_TOTAL);   // once per process, thread-safe
+    static const hipError_t attr_set = hipFuncSetAttribute((const void *)k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3, SUBTILE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LzGeo<WLOG, TAB3>::L_TOTAL);   // once per process, thread-safe
     (void)attr_set;
     constexpr bool W3 = GLOG == 0;
-    if (!(flags & FLAG_ALL_SMALL)) hipLaunchKernelGGL((k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, flags, max_off, pbuf, blk0, gtab);
+    if (!(flags & FLAG_ALL_SMALL)) hipLaunchKernelGGL((k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3, SUBTILE>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, flags, max_off, pbuf, blk0, gtab);
+    if (SUBTILE && (flags & FLAG_SPLIT_WAVEPARSE)) return;     // (sub-tiles in front of the wave-per-region parse: the caller launches the short segments' kernel -- words of four bytes -- and the parse)
     if (flags & FLAG_TIER1) hipLaunchKernelGGL((k_lzms<STRONG, W3>), dim3(nseg), dim3(64), lzms_lds(SMALL_SEG), st, src, segs, flags, pbuf, blk0, 0u, SMALL_SEG);     // the short segments, which k_lzm skipped
     if (flags & FLAG_TIER2) { const uint32_t mx = 8192u + 4096u * ((flags >> FLAG_T2_SHIFT) & 3u);
                               hipLaunchKernelGGL((k_lzms<STRONG, W3>), dim3(nseg), dim3(64), lzms_lds(mx), st, src, segs, flags, pbuf, blk0, SMALL_SEG, mx); }
@@ -1051,26 +1083,31 @@ static void launch_split_g(const uint8_t *src, const SegDesc *segs, uint32_t nse
 void launch_lz_split(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
                      uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg) {
     const bool strong = (flags & F_STRONG) && (flags & F_ADOPT), strong2 = strong && (flags & FLAG_STRONG2);     // (FLAG_STRONG2: only with the global table or the packed 16 KiB geometry)
-    if (ctab) { if (strong) launch_split_g<true, true, 0, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-                else launch_split_g<true, false, 0, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); }
+    const bool mt = !gtab && ((flags >> FLAG_MT_SHIFT) & 7u) != 0;           // option mtile: the instances with sub-tiles (every set with the table in LDS)
+#define LSG(CT_, ST_, WLOG_, FARP_, TAB3_) do { \
+        if (mt) launch_split_g<CT_, ST_, 0, WLOG_, FARP_, TAB3_, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); \
+        else launch_split_g<CT_, ST_, 0, WLOG_, FARP_, TAB3_>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); } while (0)
+    if (ctab) { if (strong) LSG(true, true, 16, false, false);
+                else LSG(true, false, 16, false, false); }
     else if (strong && gtab) { if (strong2) launch_split_g<false, 2, GTAB_LOG, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
                                else launch_split_g<false, true, GTAB_LOG, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
     else if ((flags & FLAG_TAB3) && (flags & FLAG_W16)) {
-           if (strong2) launch_split_g<false, 2, 0, 14, true, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else if (strong) launch_split_g<false, true, 0, 14, true, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else launch_split_g<false, false, 0, 14, true, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); }
+           if (strong2) LSG(false, 2, 14, true, true);
+           else if (strong) LSG(false, true, 14, true, true);
+           else LSG(false, false, 14, true, true); }
     else if ((flags & FLAG_TAB3) && (flags & FLAG_W32)) {
-           if (strong) launch_split_g<false, true, 0, 15, true, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else launch_split_g<false, false, 0, 15, true, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); }
+           if (strong) LSG(false, true, 15, true, true);
+           else LSG(false, false, 15, true, true); }
     else if (flags & FLAG_W16) {
-           if (strong) launch_split_g<false, true, 0, 14>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else launch_split_g<false, false, 0, 14>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); }
+           if (strong) LSG(false, true, 14, true, false);
+           else LSG(false, false, 14, true, false); }
     else if (flags & FLAG_W32) {
-           if (strong) launch_split_g<false, true, 0, 15>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else launch_split_g<false, false, 0, 15>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); }
-    else { if (strong) launch_split_g<false, true, 0, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else if (max_off <= NEAR_OFF) launch_split_g<false, false, 0, 16, false>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg);
-           else launch_split_g<false, false, 0, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); }
+           if (strong) LSG(false, true, 15, true, false);
+           else LSG(false, false, 15, true, false); }
+    else { if (strong) LSG(false, true, 16, true, false);
+           else if (max_off <= NEAR_OFF) LSG(false, false, 16, false, false);
+           else LSG(false, false, 16, true, false); }
+#undef LSG
 }
 // The short segments of a launch that took the one-kernel form (which skips them: FLAG_HAS_SMALL): k_lzms + the parse kernel over their blocks only.  w3: words of
 // three bytes (the caller's choice: every launch but the zstd levels with the table in global memory takes them, as in the split form).

@@ -214,6 +214,7 @@ struct Tuning {
     long zdec_fallback_max_mib = 0;  // PNA_ZDEC_FALLBACK_MAX_MIB: zstd frames of more content than this that the parallel paths cannot take are REFUSED (PNA_E_UNSUPPORTED) instead of decoded by one workgroup at ~11 MiB/s (0: no limit) -- a host may prefer its CPU decoder
     long zexec_win_mib = 1024;       // PNA_ZEXEC_WIN_MIB: output bytes of one window of the parallel executor (its words count 31 bits from the window's start: at most 1 024; tests take a few MiB)
     long small_geometry = 1;         // PNA_SMALL_GEOMETRY: 1 (default): segments of at most 4 096 bytes run the small geometry of the match finder (pna_dev.h SMALL_SEG: one wave per segment, sub-tiles of 256 positions); 0: the large one like every segment (they then find no match: one tile)
+    long mtile = 0;                  // PNA_MTILE: 0 (default): the match kernel k_lzm looks up all 4 096 positions of a tile before it inserts any; 256 / 512 / 1024 / 2048: look-ups and inserts alternate per sub-tile of that many positions, so that a position sees the tile's earlier sub-tiles (oracle: mtile).  Segments above 16 KiB of every set with the table in LDS -- zstd 1 .. 9, deflate --, always in the split form and in whole segments (no LZ units); zstd 10 .. 22 ignore it
     long tab3 = 1;                   // PNA_TAB3: 1 (default): the zstd sets on the 32 / 16 KiB geometries keep their table PACKED (three 21-bit entries per 64-bit LDS word: 49 062 / 55 206 slots, lz_common.h); 0: 32-bit entries (32 704 / 36 800)
     long strong2 = 1;                // PNA_STRONG2: 1 (default): zstd levels 4 .. 22 on their standard geometries adopt over eight positions as well and count up to 15 back bytes (levels 6 - 9: 2.864 -> 2.880); 0: the default set's three rounds
     long seq_hist = 1;               // PNA_SEQ_HIST: 1 (default): large zstd batches behind the split LZ stage -- the parse kernel counts every block's sequence codes, k_stats walks the literals only (2.6 -> 1.1 ms per 10 000 segments, + 0.5 in the parse kernel); 0: k_stats reads the sequences once more

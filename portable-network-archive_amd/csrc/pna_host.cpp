@@ -11,7 +11,7 @@ static const TuningName TUNING_NAMES[] = {
     {"inflate_serial", "PNA_INFLATE_SERIAL", &Tuning::inflate_serial, 0, 1}, {"zdec_serial", "PNA_ZDEC_SERIAL", &Tuning::zdec_serial, 0, 1}, {"zdec_dbg", "PNA_ZDEC_DBG", &Tuning::zdec_dbg, 0, 15},
     {"blk_log", "PNA_BLK_LOG", &Tuning::blk_log, 0, PNA_BLK_LOG}, {"unit_log", "PNA_LZ_UNIT_LOG", &Tuning::unit_log, 0, 20},
     {"latency_max_mib", "PNA_LATENCY_MAX_MIB", &Tuning::latency_max_mib, 0, 1 << 20}, {"hist_by_block", "PNA_HIST_BY_BLOCK", &Tuning::hist_by_block, -1, 1},
-    {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
+    {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"mtile", "PNA_MTILE", &Tuning::mtile, 0, 2048}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
 };
 
 extern "C" const char *pna_gpu_strerror(int code) {
@@ -29,6 +29,13 @@ extern "C" const char *pna_gpu_strerror(int code) {
 }
 extern "C" const char *pna_gpu_last_error(const pna_gpu_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
+static bool mtile_ok(long v) { return v == 0 || v == 256 || v == 512 || v == 1024 || v == 2048; }
+// option mtile as the launch flag of k_lzm (FLAG_MT_SHIFT): only where the match finder's table lies in LDS
+static uint32_t mtile_flag(const pna_gpu_ctx *c, bool gt) {
+    uint32_t k = 0;
+    for (long v = c->tun.mtile; v >= 256; v >>= 1) k++;
+    return gt ? 0u : k << FLAG_MT_SHIFT;
+}
 extern "C" int pna_gpu_init(pna_gpu_ctx **out, int device_id, uint32_t flags) {
     if (!out) return PNA_E_INVAL;
     *out = nullptr;
@@ -42,7 +49,7 @@ extern "C" int pna_gpu_init(pna_gpu_ctx **out, int device_id, uint32_t flags) {
     c->flags = (flags & PNA_F_DEFAULT) ? (F_HUF | F_FSE | F_LAZY | F_FAR | F_ADOPT | F_INS2) : (flags & 0xFF);
     c->flags &= ~F_REP;                    // repeat-offset codes are not produced by this build
     for (const TuningName &t : TUNING_NAMES)
-        if (const char *e = getenv(t.env)) { const long v = atol(e); if (v >= t.lo && v <= t.hi) c->tun.*(t.field) = v; }
+        if (const char *e = getenv(t.env)) { const long v = atol(e); if (v >= t.lo && v <= t.hi && (t.field != &Tuning::mtile || mtile_ok(v))) c->tun.*(t.field) = v; }
     if (const char *pm = getenv("PNA_STREAM_POOL_MIB")) c->pool_cap = (size_t)std::min<unsigned long>(strtoul(pm, nullptr, 10), 1ul << 20) << 20;
     if (const char *lg = getenv("PNA_STREAM_LINGER_US")) c->comb_linger_us = (uint32_t)std::min<unsigned long>(strtoul(lg, nullptr, 10), 100000ul);
     if (!(flags & PNA_F_DEFAULT)) c->flags |= flags & 0x3F00u;  // diagnostics: 0x100 phase stamps, 0x200 force the serial fallback in k_lz, 0x1000 / 0x2000 force the one-kernel / two-phase sequence coder
@@ -69,6 +76,7 @@ extern "C" int pna_gpu_set_option(pna_gpu_ctx *c, const char *name, long value) 
     if (!strcmp(name, "stream_linger_us")) { c->comb_linger_us = value < 0 ? 0xFFFFFFFFu : (uint32_t)std::min<long>(value, 100000); return PNA_OK; }
     for (const TuningName &t : TUNING_NAMES)
         if (!strcmp(name, t.name)) {
+            if (t.field == &Tuning::mtile && !mtile_ok(value)) return fail(c, PNA_E_INVAL, "mtile: 0, 256, 512, 1024 or 2048");
             if (value < t.lo || value > t.hi) return fail(c, PNA_E_INVAL, "option value out of range");
             if (t.field == &Tuning::blk_log && value != 0 && value < (long)BLK_LOG_MIN) return fail(c, PNA_E_INVAL, "blk_log: 0 or 13..17");
             c->tun.*(t.field) = value; return PNA_OK;
@@ -489,7 +497,11 @@ static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, u
     // zstd levels 10 .. 22 (the strong set): the match kernel's hash tables lie in global memory (2^19 slots per segment instead of the 24 512 LDS
     // holds; k_lz_split.hip) -- only k_lzm has that form, so those levels always take the split form, whatever the run's length
     const bool gt = !ctab && c->call_gtab;
-    const bool fused = !gt && ((c->call_flags & PNA_F_LZ_FUSED) || env_split == 0 || (flags & 0x100u));   // (0x100: the phase stamps live in the fused kernel)
+    // option mtile: only k_lzm has sub-tiles, so every run with a segment of the large geometry takes the split form -- whatever lz_split, lz_split_min or PNA_F_LZ_FUSED say --,
+    // in whole segments (no tail units: their pre-warm replays tiles), and a words workspace that cannot be had is an error: the one-kernel form would write other bytes
+    const uint32_t mt = (flags & FLAG_ALL_SMALL) ? 0u : mtile_flag(c, gt);
+    flags |= mt;
+    const bool fused = !gt && !mt && ((c->call_flags & PNA_F_LZ_FUSED) || env_split == 0 || (flags & 0x100u));   // (0x100: the phase stamps live in the fused kernel)
     const bool waveparse = !gt && ((c->call_flags & PNA_F_LZ_WAVEPARSE) || env_split == 2);
     uint32_t split_blocks = env_blocks;
     if (s1 > s0) {
@@ -507,7 +519,7 @@ static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, u
     // longer waits for one wave's walk over a whole segment (N x 1 MiB, one-kernel / split: 32: 2.3 / 1.6 ms, 256: 2.4 / 1.8, 1 024: 9.3 / 6.3,
     // 2 048: 18.6 / 12.3; scripts/lz_forms.py).  The one-kernel form remains for PNA_F_LZ_FUSED, for a workspace that cannot be allocated and for the
     // units of the latency mode; lz_split_min restores a threshold.
-    const uint32_t min_segs = gt ? 0u : (uint32_t)c->tun.lz_split_min;
+    const uint32_t min_segs = (gt || mt) ? 0u : (uint32_t)c->tun.lz_split_min;
     for (uint32_t a = s0; a < s1 && !fused;) {
         const uint32_t b0 = segs[a].blk_base;
         const uint32_t b = run_end(segs, nseg_all, nblk, a, s1, bps, split_blocks);
@@ -518,6 +530,7 @@ static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, u
             (void)hipGetLastError();                                   // (the failed allocation's sticky code)
             if (split_blocks > 1024 && b - a > 1) { split_blocks /= 2; continue; }                    // (for this call only: the next one tries the full run again)
             if (gt) return fail(c, PNA_E_NOMEM, "no room for the strong level set's hash tables");    // (the one-kernel form has LDS tables: other bytes)
+            if (mt) return fail(c, PNA_E_NOMEM, "mtile: no room for the words workspace (the one-kernel form has no sub-tiles)");
             s0 = a; break;                                             // no room for the words: the rest goes through the fused kernel
         }
         hipEvent_t e1 = nullptr;
@@ -531,7 +544,7 @@ static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, u
         // The match kernel runs one workgroup per segment and CU, all of equal length: a run of 3 334 segments is 13 full rounds of the 256 CUs and a 14th for
         // 6 of them.  The segments behind the last full round are therefore cut into UNITS of one block each (table pre-warmed: the same words, SS4a), a launch
         // of their own behind the full rounds: R x 8 short workgroups instead of R long ones next to 256 - R idle CUs.
-        uint32_t R = (!gt && !waveparse && c->tun.tail_units && b - a >= 2 * c->n_cus) ? (b - a) % c->n_cus : 0;     // (n_cus: the device's compute units, 256 on an MI355X)
+        uint32_t R = (!gt && !mt && !waveparse && c->tun.tail_units && b - a >= 2 * c->n_cus) ? (b - a) % c->n_cus : 0;     // (n_cus: the device's compute units, 256 on an MI355X)
         if (R > 3 * c->n_cus / 8 || (flags & FLAG_ALL_SMALL)) R = 0;
         if (R) {
             const uint32_t bl = segs[a].blk_log, bs = 1u << bl;
@@ -645,6 +658,8 @@ static void plan_geometry(const pna_gpu_ctx *c, int algo, uint64_t in_total, uin
         }
     }
     if (c->tun.unit_log) unit_log = (uint32_t)std::max<long>(c->tun.unit_log, blk_log);
+    // option mtile: whole segments -- a unit's pre-warm (lz_prewarm / lz_prewarm3) replays a tile's inserts as ONE contest, which is not what sub-tiles leave in the table
+    if (c->tun.mtile && !(algo == PNA_ALGO_ZSTD && c->call_gtab)) unit_log = 20;
     if (unit_log < blk_log) unit_log = blk_log;
     p.latency = latency; p.blk_log = blk_log; p.unit_log = unit_log;
 }
