@@ -323,8 +323,9 @@ int  pna_gpu_create_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n
  *     fits neither (a stream of 4 GiB and more whose only block boundaries are fixed-Huffman blocks) is PNA_E_UNSUPPORTED (the wave-per-stream
  *     walk counts in 32 bits).
  *   Single streams of any size are executed in parallel (zstd frames of 2 GiB and more since the second half of round 4: the executor's windows,
- *     option "zexec_win_mib"); a zstd frame whose compressed bytes exceed 4 GiB, or which does not fit its pooled resources, is left to one workgroup
- *     (~11 MiB/s) unless the option "zdec_fallback_max_mib" refuses it.
+ *     option "zexec_win_mib"), whatever their compressed size and however many literals they carry (the header walk and the literal scratch count in
+ *     64 bits); a zstd frame that does not fit its pooled resources -- more than 2^31 - 1 sequences, more blocks or table sets than its content's
+ *     size plans for -- is left to one workgroup (~11 MiB/s) unless the option "zdec_fallback_max_mib" refuses it.
  * Errors: PNA_E_INVAL for corrupt / mismatching streams (pna_gpu_last_error names the entry), PNA_E_UNSUPPORTED for
  * dictionaries and other algorithms. */
 int  pna_gpu_decompress_batch(pna_gpu_ctx *ctx, int algo, size_t n, const void *const *src, const size_t *src_len,

@@ -607,12 +607,19 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
     ZFrame fr = frames[f];
     ZFrameX x = fx[f];
     if (!ONE && x.pad) return;                                          // a large frame: k_zparse_a + k_zparse<true> take it
-    const uint8_t *in = src + fr.src_off;
-    const uint32_t in_len = (uint32_t)fr.src_len;
-    const uint64_t cap = fr.dst_len < 0xFFFFFFFFull ? fr.dst_len : 0xFFFFFFFFull;   // (literal positions count in 32 bits: a frame with 4 GiB of literals and more in compressed blocks is left to the one-workgroup kernel)
+    // Positions inside the compressed bytes (ip) count in 32 bits from `in`, which lies at in_abs of the compressed buffer: the frame's start for a frame this wave
+    // walks alone (such a frame has less than 4 GiB of compressed bytes: a longer one goes to the one-workgroup kernel if it ever gets here), the block's own
+    // header for ONE -- a frame of any compressed size, 64-bit positions from k_zparse_a's walk; in_len is what the frame has left from there, saturated (a block
+    // takes at most 128 KiB + 3 of it).
+    const uint64_t in_abs = ONE ? pre.body - 3 : fr.src_off;
+    const uint8_t *in = src + in_abs;
+    const uint64_t in_left = fr.src_len - (in_abs - fr.src_off);
+    const uint32_t in_len = (uint32_t)(in_left < 0xFFFFFFFFull ? in_left : 0xFFFFFFFFull);
+    const uint64_t cap = fr.dst_len;                                    // (a frame's literals are part of its content: no more of them than that)
     const uint64_t fcs_want = fr.dst_len;
     const bool open = (fr.out_len & ZF_OPEN) != 0;
     uint32_t status = fr.status, ip = 0;
+    if (!ONE && status == ZD_OK && fr.src_len > 0xFFFFFFFFull) status = ZD_UNSUPPORTED;
     // ---- frame header
     if (!ONE && status == ZD_OK) {
         if (in_len < 6) status = ZD_CORRUPT;
@@ -637,10 +644,10 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
         }
     }
     uint32_t nblk = 0, next_slot = 0, huf_slot = 0xFFFFFFFFu, slot3[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    uint32_t lit_pos = 0; uint64_t seq_pos = 0;
+    uint64_t lit_pos = 0, seq_pos = 0;                                  // (per block, on lane 0: the literal scratch of a frame is as long as its content)
     if (ONE) {                                                          // the walk's state in front of this block
         nblk = one_list[blockIdx.x] - x.blk_base; next_slot = pre.pad[3]; huf_slot = pre.huf_slot; slot3[0] = pre.slot[0]; slot3[1] = pre.slot[1]; slot3[2] = pre.slot[2];
-        lit_pos = pre.lit_pos; seq_pos = pre.seq_pos - x.seq_base; ip = (uint32_t)(pre.body - 3 - fr.src_off);
+        lit_pos = (uint64_t)pre.lit_pos | ((uint64_t)pre.pad[2] << 32); seq_pos = pre.seq_pos - x.seq_base;
         if (status != ZD_OK) return;
     }
     bool last = status != ZD_OK;
@@ -650,8 +657,9 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
         uint32_t bstat = ZD_OK;
         if (lane == 0) {
             b.body = 0; b.out_off = 0; b.seq_pos = x.seq_base + seq_pos; b.size = 0; b.type = 0; b.ltype = 0; b.regen = 0; b.streams = 1; b.lit_off = 0; b.lit_csize = 0;
-            b.lit_pos = lit_pos; b.nseq = 0; b.seq_off = 0; b.seq_len = 0; b.frame = f; b.out_len = 0; b.status = 0; b.uses_rep = 0;
+            b.lit_pos = (uint32_t)lit_pos; b.nseq = 0; b.seq_off = 0; b.seq_len = 0; b.frame = f; b.out_len = 0; b.status = 0; b.uses_rep = 0;
             for (int i = 0; i < 7; i++) b.pad[i] = 0;
+            b.pad[2] = (uint32_t)(lit_pos >> 32);
         }
         // ---- phase 1 (lane 0): headers + literals section + Huffman weights
         uint32_t p1_tree = 0;
@@ -661,7 +669,7 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
                 if (ip + 3 > in_len) { bstat = ZD_CORRUPT; break; }
                 const uint32_t bh = in[ip] | (in[ip + 1] << 8) | ((uint32_t)in[ip + 2] << 16);
                 b.type = (bh >> 1) & 3; b.size = bh >> 3; b.pad[0] = bh & 1;
-                b.body = fr.src_off + ip + 3;
+                b.body = in_abs + ip + 3;
                 if (b.type == 3 || b.size > (128u << 10)) { bstat = ZD_CORRUPT; break; }
                 if (b.type == 1) { if (ip + 4 > in_len) bstat = ZD_CORRUPT; b.out_len = b.size; break; }
                 if (ip + 3 + b.size > in_len) { bstat = ZD_CORRUPT; break; }
@@ -682,7 +690,7 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
                     else if (sf == 2) { streams = 4; hdr = 4; regen = (v >> 4) & 0x3FFF; comp = (v >> 18) & 0x3FFF; }
                     else { streams = 4; hdr = 5; regen = (v >> 4) & 0x3FFFF; comp = (v >> 22) & 0x3FFFF; }
                 }
-                if (regen > (128u << 10) || (uint64_t)lit_pos + regen > cap) { bstat = regen > (128u << 10) ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
+                if (regen > (128u << 10) || lit_pos + regen > cap) { bstat = regen > (128u << 10) ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
                 b.ltype = ltype; b.regen = regen; b.streams = streams;
                 uint32_t pos = hdr;
                 if (ltype == 0) { if (pos + regen > len) { bstat = ZD_CORRUPT; break; } b.lit_off = pos; pos += regen; }
@@ -867,11 +875,13 @@ __global__ void k_zparse_a(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx
     ZFrame fr = frames[f];
     const ZFrameX x = fx[f];
     const uint8_t *in = src + fr.src_off;
-    const uint32_t in_len = (uint32_t)fr.src_len;
-    const uint64_t cap = fr.dst_len < 0xFFFFFFFFull ? fr.dst_len : 0xFFFFFFFFull;   // (literal positions count in 32 bits: a frame with 4 GiB of literals and more in compressed blocks is left to the one-workgroup kernel)
+    // (the walk's positions -- in the compressed bytes and in the literal scratch -- count in 64 bits: one lane, a few dependent loads per block, nothing per byte;
+    // what is block-relative stays 32 bits)
+    const uint64_t in_len = fr.src_len;
+    const uint64_t cap = fr.dst_len;                                    // (a frame's literals are part of its content: no more of them than that)
     const uint64_t fcs_want = fr.dst_len;
     const bool open = (fr.out_len & ZF_OPEN) != 0;
-    uint32_t status = fr.status, ip = 0;
+    uint32_t status = fr.status; uint64_t ip = 0;
     if (status == ZD_OK) {
         if (in_len < 6) status = ZD_CORRUPT;
         else {
@@ -895,7 +905,7 @@ __global__ void k_zparse_a(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx
         }
     }
     uint32_t nblk = 0, next_slot = 0, huf_slot = 0xFFFFFFFFu, slot3[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    uint32_t lit_pos = 0; uint64_t seq_pos = 0;
+    uint64_t lit_pos = 0, seq_pos = 0;
     bool last = status != ZD_OK;
     while (!last) {
         if (nblk >= x.blk_cap) { status = ZD_UNSUPPORTED; break; }
@@ -906,10 +916,10 @@ __global__ void k_zparse_a(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx
         if (type == 1 ? ip + 4 > in_len : ip + 3 + size > in_len) { status = ZD_CORRUPT; break; }
         ZBlock b;
         b.body = fr.src_off + ip + 3; b.out_off = 0; b.seq_pos = x.seq_base + seq_pos; b.size = size; b.type = type; b.ltype = 0; b.regen = 0; b.streams = 1; b.lit_off = 0; b.lit_csize = 0;
-        b.lit_pos = lit_pos; b.huf_slot = huf_slot; b.slot[0] = slot3[0]; b.slot[1] = slot3[1]; b.slot[2] = slot3[2];
+        b.lit_pos = (uint32_t)lit_pos; b.huf_slot = huf_slot; b.slot[0] = slot3[0]; b.slot[1] = slot3[1]; b.slot[2] = slot3[2];
         b.nseq = 0; b.seq_off = 0; b.seq_len = 0; b.frame = f; b.out_len = type < 2 ? size : 0; b.status = 0; b.uses_rep = 0;
         for (int i = 0; i < 7; i++) b.pad[i] = 0;
-        b.pad[0] = bh & 1; b.pad[3] = next_slot;
+        b.pad[0] = bh & 1; b.pad[2] = (uint32_t)(lit_pos >> 32); b.pad[3] = next_slot;
         uint32_t regen = 0, nseq = 0;
         if (type == 2) {
             const uint8_t *p = in + ip + 3; const uint32_t len = size;
@@ -928,7 +938,7 @@ __global__ void k_zparse_a(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx
                 else if (sf == 2) { hdr = 4; regen = (v >> 4) & 0x3FFF; comp = (v >> 18) & 0x3FFF; }
                 else { hdr = 5; regen = (v >> 4) & 0x3FFFF; comp = (v >> 22) & 0x3FFFF; }
             }
-            if (regen > (128u << 10) || (uint64_t)lit_pos + regen > cap) { status = regen > (128u << 10) ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
+            if (regen > (128u << 10) || lit_pos + regen > cap) { status = regen > (128u << 10) ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
             uint32_t pos = hdr + (ltype == 0 ? regen : (ltype == 1 ? 1u : comp));
             if (pos >= len) { status = ZD_CORRUPT; break; }                 // (the sequences section holds at least its count)
             const uint32_t b0 = p[pos++];
@@ -969,7 +979,7 @@ void k_zhuf(const uint32_t *__restrict__ huf_list, const ZWork *__restrict__ wor
     const uint32_t lane = threadIdx.x, i = blockIdx.x * 64 + lane;
     const bool valid = i < work->n_huf;
     const uint32_t item = valid ? huf_list[i] : 0u, bi = item >> 2, sidx = item & 3;
-    ZBlock b; if (valid) b = blocks[bi]; else { b.huf_slot = 0xFFFFFFFFu; b.streams = 1; b.regen = 0; b.lit_csize = 0; b.body = 0; b.lit_off = 0; b.frame = 0; b.lit_pos = 0; }
+    ZBlock b; if (valid) b = blocks[bi]; else { b.huf_slot = 0xFFFFFFFFu; b.streams = 1; b.regen = 0; b.lit_csize = 0; b.body = 0; b.lit_off = 0; b.frame = 0; b.lit_pos = 0; b.pad[2] = 0; }
     // ---- table cache
     uint32_t mine = ZH_CACHE;
     {
@@ -1008,7 +1018,7 @@ void k_zhuf(const uint32_t *__restrict__ huf_list, const ZWork *__restrict__ wor
         const ZTables *T = tabs + b.huf_slot;
         const uint32_t mb = T->hufbits;
         const uint8_t *gs = cs + s_off;
-        uint8_t *lit = lit_scratch + frames[b.frame].dst_off + b.lit_pos + o_off;
+        uint8_t *lit = lit_scratch + frames[b.frame].dst_off + ((uint64_t)b.lit_pos | ((uint64_t)b.pad[2] << 32)) + o_off;
         auto fetch = [&](int64_t j) -> uint64_t { return *(const zd_u64u *)(gs + 8 * j); };
         auto cellof = [&](uint32_t idx) -> uint32_t { return mine < ZH_CACHE ? (uint32_t)ctab[mine][idx] : (uint32_t)T->huf[idx]; };
         ZdWin bw;
@@ -1425,14 +1435,14 @@ __global__ void k_zscan(const ZEntry *__restrict__ ents, uint32_t n, const uint8
     const uint64_t len = en.src_len;
     const uint32_t nfr = en.n_frames;
     // ONE frame that holds the whole entry, however large (what the reference writes: libzstd streaming, one frame per entry): it gets all of
-    // raw_len and -- its compressed bytes below 4 GiB -- all the block descriptors, table slots and sequence records planned for the entry's frames (their regions are
+    // raw_len and all the block descriptors, table slots and sequence records planned for the entry's frames (their regions are
     // contiguous), so that its blocks are decoded side by side like those of many small frames (k_zparse .. k_zexec: a 64 MiB frame 10.7 MiB/s on
-    // the one-workgroup kernel).  A frame of 4 GiB of COMPRESSED bytes and more, or one that still does not fit (k_zparse finds out), goes to that kernel.  The other
+    // the one-workgroup kernel).  One that still does not fit (k_zparse finds out) goes to that kernel.  The other
     // frame slots planned for the entry are void.
     if (nfr > 1 && zscan_frame_end(p, 0, len) == len) {
         ZFrame fr; fr.src_off = en.src_off; fr.dst_off = en.dst_off; fr.src_len = len; fr.out_len = en.open ? ZF_OPEN : 0u;
         fr.dst_len = en.raw_len; fr.status = 2u;
-        if (len <= 0xFFFFFFFFull && fx) {                            // (content of any size: the parse counts output in 64 bits, the executor works in windows; a compressed size beyond 32 bits stays with the one-workgroup kernel)
+        if (fx) {                                                    // (content and compressed bytes of any size: the header walk and the literal scratch count in 64 bits, the executor works in windows)
             ZFrameX x = fx[en.first_frame];
             uint64_t nb = 0, ns = 0, nq = 0;
             for (uint32_t g = 0; g < nfr; g++) { const ZFrameX y = fx[en.first_frame + g]; nb += y.blk_cap; ns += y.slot_cap; nq += y.seq_cap; }
@@ -1454,7 +1464,7 @@ __global__ void k_zscan(const ZEntry *__restrict__ ents, uint32_t n, const uint8
         if (en.raw_len - done > 0xFFFFFFFFull && f + 1 == nfr) fr.status = 2;
         const uint64_t q = zscan_frame_end(p, ip, len);
         if (!q) { fr.status = 1; fr.src_len = 0; frames[en.first_frame + f] = fr; for (uint32_t g = f + 1; g < nfr; g++) { fr.src_off = 0; frames[en.first_frame + g] = fr; } return; }
-        fr.src_len = (uint32_t)(q - ip);
+        fr.src_len = q - ip;                                          // (4 GiB and more, with at most 1 MiB of content: k_zparse leaves it to the one-workgroup kernel)
         if (en.open && f + 1 == nfr) fr.out_len = ZF_OPEN;             // the last frame of a stream of unknown size
         frames[en.first_frame + f] = fr;
         ip = q;

@@ -504,7 +504,13 @@ static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const
         ents[i] = ZEntry{src_off[i], src_len[i], dst_off[i], room, (uint32_t)nfr, (uint32_t)k, open ? 1u : 0u, 0u};
         nfr += k;
     }
-    // per-frame bounds of the lane-parallel pipeline (frames that exceed them fall back to the one-workgroup-per-frame kernel)
+    // per-frame bounds of the lane-parallel pipeline (frames that exceed them fall back to the one-workgroup-per-frame kernel).  They are planned per MiB of
+    // content -- 260 block descriptors, 10 table sets, 262 160 sequence records -- and ONE frame that holds an entry gets the sum (k_zscan, each sum saturated
+    // at 2^31 - 1).  One frame of 8 GiB: 2.1 M descriptors for its 65 536 blocks of 128 KiB, 81 920 table sets (it needs a set per block at most), and
+    // 2^31 - 1 records: the records' sum saturates from 8 GiB of content on, so a frame with more sequences than that -- one per four bytes of 8 GiB -- goes
+    // to the fallback (k_zparse_a finds out).  The batch limit below, 2^30 - 1 descriptors, is 4 TiB of content.  The min() of a single slot only binds where a
+    // measured stream's last frame gets room of its own (plan): 2^20 descriptors = 128 GiB of 128 KiB blocks, 2^16 table sets.  Compressed bytes and literals
+    // are not bounded here: the header walk and the literal scratch (z_lit: as long as the output span) count in 64 bits.
     std::vector<ZFrameX> fxs(nfr);
     uint64_t nblk_cap = 0, nslot = 0, nseq_cap = 0, out_span = 0;
     for (size_t i = 0; i < n; i++) {
@@ -534,7 +540,7 @@ static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const
     std::vector<ZFrame> frs(nfr);
     if (!serial_only) {
         // Large frames (the reference writes ONE frame per entry whatever its size): k_zscan has found them -- a frame whose content takes zexec_par_min_mib
-        // and more (below 2 GiB: the parallel executor's words hold 31-bit positions).  Their blocks are PARSED side by side (k_zparse_a: the header walk,
+        // and more, of any content, compressed and literal size (the executor works in windows, the header walk counts in 64 bits).  Their blocks are PARSED side by side (k_zparse_a: the header walk,
         // k_zparse<true>: a wave per block for the tables) and their sequences EXECUTED in parallel by pointer jumping (k_zexec_par.hip) instead of by one
         // wave each; the per-frame kernels skip them (ZFrameX::pad).
         std::vector<uint32_t> big;

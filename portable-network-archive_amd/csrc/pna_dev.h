@@ -199,8 +199,8 @@ static_assert(sizeof(PickPiece) == 32, "PickPiece layout");
 struct ZFrame {
     uint64_t src_off;        // frame start in the compressed buffer
     uint64_t dst_off;        // where its content goes
-    uint64_t src_len;        // bytes of the frame          } 64 bits for zlib streams that are decoded by pieces (k_vinflate); zstd frames and the
-    uint64_t dst_len;        // bytes of content it must produce } wave-per-stream inflate walk take what fits 32 bits (status 2 otherwise)
+    uint64_t src_len;        // bytes of the frame          } 64 bits: zlib streams decoded by pieces (k_vinflate) and single zstd frames (header walk k_zparse_a, a wave per
+    uint64_t dst_len;        // bytes of content it must produce } block) of any size; the wave-per-frame zstd parse and the wave-per-stream inflate walk take what fits 32 bits (status 2 otherwise)
     uint32_t status;         // out: 0 ok, 1 corrupt, 2 unsupported, 3 size mismatch
     uint32_t out_len;        // in: flags (ZF_OPEN); out: bytes produced, saturated at 2^32 - 1 (diagnostics)
 };
