@@ -35,6 +35,7 @@ extern "C" {
 #define PNA_ALGO_STORE    0
 #define PNA_ALGO_DEFLATE  1
 #define PNA_ALGO_ZSTD     2
+#define PNA_ALGO_XZ       4     /* == Compression::XZ.to_byte(); DECODE ONLY (every compress entry point answers PNA_E_UNSUPPORTED) */
 
 /* encoder feature bits (pna_gpu_init flags, low byte); default = all of them */
 #define PNA_F_HUF   1u
@@ -326,6 +327,20 @@ int  pna_gpu_create_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n
  *     option "zexec_win_mib"), whatever their compressed size and however many literals they carry (the header walk and the literal scratch count in
  *     64 bits); a zstd frame that does not fit its pooled resources -- more than 2^31 - 1 sequences, more blocks or table sets than its content's
  *     size plans for -- is left to one workgroup (~11 MiB/s) unless the option "zdec_fallback_max_mib" refuses it.
+ *   PNA_ALGO_XZ: ONE .xz stream (xz file format 1.0.4: stream header, blocks, Index, stream footer), as liblzma's XzEncoder::new(writer, level) writes it.
+ *     Container: magic, stream flags (equal in header and footer), backward size, the Index and every block header are validated with their CRC32s; the
+ *       Index is found from the end, so bytes behind the footer -- stream padding, a second stream -- are PNA_E_INVAL (a departure from the reference's
+ *       reader, which stops at the first stream's end).
+ *     Filters: exactly one, LZMA2 (id 0x21), dictionary-size byte 0 .. 40; Delta, BCJ and every other chain: PNA_E_UNSUPPORTED.
+ *     Checks: None, CRC32 and CRC64 (liblzma's default) are verified on the device per block; SHA-256 and the unassigned types: PNA_E_UNSUPPORTED.
+ *     Blocks are located from the Index (unpadded size and uncompressed size per record), so each decodes on its own, one wave per block, whether or
+ *       not its header carries the optional size fields -- where it does they must agree with the Index.  A block of 4 GiB or more of decoded bytes is
+ *       PNA_E_UNSUPPORTED; a stream of many blocks may be of any size.  raw_len[i] must be the sum of the Index records.
+ *     LZMA2: every chunk kind -- 0x00 end, 0x01 / 0x02 uncompressed, 0x80 .. 0xFF LZMA with the four reset levels --, every lc / lp / pb with
+ *       lc + lp <= 4.  Corrupt (PNA_E_INVAL): control bytes 0x03 .. 0x7F, a first chunk that does not reset the dictionary, a first LZMA chunk without
+ *       properties, a match distance beyond min(dictionary size, bytes produced since the dictionary reset), an end-of-payload marker, a chunk or
+ *       block that ends early or late or leaves compressed bytes unused, a range coder that does not start with a zero byte or end at zero.
+ *     A single block is a serial chain on one wave (measured: 1.8 - 2.8 MiB/s per block, profiles/xz_rate.txt); the gain is entries and blocks side by side.  There is no xz encoder.
  * Errors: PNA_E_INVAL for corrupt / mismatching streams (pna_gpu_last_error names the entry), PNA_E_UNSUPPORTED for
  * dictionaries and other algorithms. */
 int  pna_gpu_decompress_batch(pna_gpu_ctx *ctx, int algo, size_t n, const void *const *src, const size_t *src_len,
@@ -345,9 +360,14 @@ int  pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *ctx, const void *d_src, ui
 int  pna_gpu_inflate_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
                                  uint64_t dst_cap, uint64_t *raw_len, void *hip_stream);
 
-/* The decoded size of one such stream (algo: PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE or PNA_ALGO_STORE), measured on the device before it is decoded, so that
+/* The same for one .xz stream (xz entries without fSIZ, xz solid streams): its size is the sum of its Index records. */
+int  pna_gpu_xz_decompress_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
+                                       uint64_t dst_cap, uint64_t *raw_len, void *hip_stream);
+
+/* The decoded size of one such stream (algo: PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE, PNA_ALGO_XZ or PNA_ALGO_STORE), measured on the device before it is decoded, so that
  * the open decoders above can be given exactly the room it needs.  No output buffer is used; the scratch grows with src_len, not with the size.
- * GUARANTEE: *size is never below what the stream decodes to.  *exact = 1: *size IS that size -- always for zlib streams (their blocks are walked and
+ * GUARANTEE: *size is never below what the stream decodes to.  *exact = 1: *size IS that size -- always for xz streams (the sum of the Index records,
+ * after the whole container walk; nothing is decoded), always for zlib streams (their blocks are walked and
  * counted: k_inflate's count pass, one wave per chunk between block starts) and for zstd frames that carry Frame_Content_Size (this library's);
  * *exact = 0: an upper bound -- a zstd frame without a content size (what the reference's solid writer emits) counts its raw and RLE blocks exactly and
  * each compressed block as Block_Maximum_Size (min(window, 128 KiB)).  The open decoders report the true size.  PNA_E_INVAL for bytes that are not a
@@ -361,10 +381,10 @@ int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uin
  * decrypt_reader / decompress_reader, lib/src/entry/read.rs:59-104,171-190).  The chunk walk and the small chunks' CRCs are host work;
  * the FDAT CRC-32s, the gather of every entry's data pieces, AES decryption -- CTR, CBC (PKCS#7 checked), GCM STREAM (key confirmation,
  * every segment tag verified) -- with the key derived from the PHSF string ("$argon2{d,i,id}$..." or "$pbkdf2-sha256$...") and `password`,
- * and zstd / deflate / store decoding run on the device; entries without fSIZ are sized by the decoder.  cb is called once per entry in archive order (kind =
+ * and zstd / deflate / xz / store decoding run on the device; entries without fSIZ are sized by the decoder.  cb is called once per entry in archive order (kind =
  * DataKind::to_byte(): 0 file, 1 directory, ...); `data` is valid during the call.  PNA_E_INVAL: structural damage, CRC mismatch, corrupt
- * stream, wrong password (GCM key confirmation, CBC padding), authentication failure; PNA_E_UNSUPPORTED: multipart archives, xz,
- * Camellia, solid streams with inner entries that are not stored.  Solid entries (SHED [PHSF] SDAT* SEND; plain or AES CTR / CBC / GCM):
+ * stream, wrong password (GCM key confirmation, CBC padding), authentication failure; PNA_E_UNSUPPORTED: multipart archives,
+ * Camellia, xz streams outside the scope stated at pna_gpu_decompress_batch, solid streams with inner entries that are not stored.  Solid entries (SHED [PHSF] SDAT* SEND; plain or AES CTR / CBC / GCM):
  * SDAT CRCs and the inner FDAT CRCs on the device.  A solid stream or an entry without fSIZ has no recorded size: it is measured first
  * (pna_gpu_open_size_device), decoded into device memory of that size and copied once to host memory (an N-GiB solid stream: N GiB of host memory,
  * besides the archive); PNA_E_NOMEM, naming the size, when the device cannot hold it. */
@@ -402,7 +422,7 @@ int  pna_gpu_extract_archive_host(pna_gpu_ctx *ctx, const void *archive, size_t 
 #define PNA_VERIFY_BAD_AUTH        4    /* GCM: key confirmation or a segment tag */
 #define PNA_VERIFY_BAD_DECRYPT     5    /* CBC length / PKCS#7 padding */
 #define PNA_VERIFY_BAD_STREAM      6    /* corrupt zstd / zlib stream, content checksum, Adler-32 */
-#define PNA_VERIFY_UNSUPPORTED     7    /* xz, Camellia, ...: what this build does not decode */
+#define PNA_VERIFY_UNSUPPORTED     7    /* Camellia, an xz stream with a SHA-256 check or a filter chain, ...: what this build does not decode */
 /* flags of one record */
 #define PNA_VERIFY_SIZE_HINT       1u   /* fSIZ present and != the decoded size (a warning; status stays OK) */
 #define PNA_VERIFY_UNAUTHENTICATED 2u   /* AES CBC / CTR: a wrong password cannot be told from damage (verify.rs is_unauthenticated) */

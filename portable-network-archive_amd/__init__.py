@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("PNA_GPU_LIB") or os.path.join(_HERE, "libpna_gpu.so")
 
 PNA_OK = 0
 ALGO_STORE, ALGO_DEFLATE, ALGO_ZSTD = 0, 1, 2
+ALGO_XZ = 4                                                      # Compression::XZ: decode only (decompress_batch, open_size_device, xz_open_device, the read-side drivers)
 LEVEL_DEFAULT = -1000
 # error codes of include/pna_gpu.h
 E_NODEVICE, E_INVAL, E_NOMEM, E_DSTSIZE, E_HIP, E_SINK, E_UNSUPPORTED = -1, -2, -3, -4, -5, -6, -7
@@ -39,6 +40,7 @@ class Compression:
     No = ALGO_STORE
     Deflate = ALGO_DEFLATE
     ZStandard = ALGO_ZSTD
+    XZ = ALGO_XZ
 
 
 class PnaGpuError(RuntimeError):
@@ -177,7 +179,7 @@ EXPORTS = [
     "pna_gpu_create_archive_part_device", "pna_gpu_decompress_batch", "pna_gpu_decompress_batch_device",
     "pna_gpu_archive_enc_bound", "pna_gpu_create_archive_enc_device", "pna_gpu_cipher_apply_device", "pna_gpu_create_archive_enc_host",
     "pna_gpu_create_solid_archive_enc_device", "pna_gpu_create_solid_archive_enc_host", "pna_gpu_extract_archive_host", "pna_gpu_zstd_stream_frames_device",
-    "pna_gpu_zstd_decompress_open_device", "pna_gpu_inflate_open_device", "pna_gpu_open_size_device", "pna_gpu_create_archive_meta_device",
+    "pna_gpu_zstd_decompress_open_device", "pna_gpu_inflate_open_device", "pna_gpu_xz_decompress_open_device", "pna_gpu_open_size_device", "pna_gpu_create_archive_meta_device",
     "pna_gpu_create_archive_meta_host", "pna_gpu_stream_stats", "pna_bench_stream_threads",
     # include/pna_archive.h
     "pna_crc32", "pna_archive_new", "pna_archive_add_file", "pna_archive_add_dir", "pna_archive_add_solid",
@@ -332,6 +334,8 @@ def load_library() -> ctypes.CDLL:
     L.pna_gpu_open_size_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, ctypes.POINTER(ctypes.c_int), vp]
     L.pna_gpu_inflate_open_device.restype = ctypes.c_int
     L.pna_gpu_inflate_open_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, vp]
+    L.pna_gpu_xz_decompress_open_device.restype = ctypes.c_int
+    L.pna_gpu_xz_decompress_open_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, vp]
     L.pna_kdf_pbkdf2_sha256.restype = ctypes.c_int
     L.pna_kdf_pbkdf2_sha256.argtypes = [ctypes.c_char_p, sz, ctypes.c_char_p, sz, u32, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
     L.pna_split_archive.restype = ctypes.c_int
@@ -485,8 +489,8 @@ class Context:
         return total.value, (list(a_out) if want_offsets else None)      # the list conversion costs milliseconds for 10^5 entries
 
     def open_size_device(self, d_src: int, src_off: int, src_len: int, algo: int = ALGO_ZSTD, stream: int = 0):
-        """The decoded size of one zstd / zlib / stored stream in device memory whose size is recorded nowhere (pna_gpu_open_size_device):
-        (size, exact) -- exact False: a proven upper bound (zstd frames without a content size)."""
+        """The decoded size of one zstd / zlib / xz / stored stream in device memory whose size is recorded nowhere (pna_gpu_open_size_device):
+        (size, exact) -- exact False: a proven upper bound (zstd frames without a content size); an xz stream's size is the sum of its Index records, always exact."""
         size, exact = ctypes.c_uint64(), ctypes.c_int()
         self._check(self._L.pna_gpu_open_size_device(self._h, algo, ctypes.c_void_p(d_src), src_off, src_len, ctypes.byref(size), ctypes.byref(exact),
                                                      ctypes.c_void_p(stream) if stream else None))
@@ -498,6 +502,14 @@ class Context:
         raw = ctypes.c_uint64()
         self._check(self._L.pna_gpu_inflate_open_device(self._h, ctypes.c_void_p(d_src), src_off, src_len, ctypes.c_void_p(d_dst), dst_off, dst_cap,
                                                         ctypes.byref(raw), ctypes.c_void_p(stream) if stream else None))
+        return raw.value
+
+    def xz_open_device(self, d_src: int, src_off: int, src_len: int, d_dst: int, dst_off: int, dst_cap: int, stream: int = 0) -> int:
+        """One .xz stream in device memory whose size is recorded nowhere, decoded into dst_cap bytes of room (pna_gpu_xz_decompress_open_device).
+        Returns the decoded size."""
+        raw = ctypes.c_uint64()
+        self._check(self._L.pna_gpu_xz_decompress_open_device(self._h, ctypes.c_void_p(d_src), src_off, src_len, ctypes.c_void_p(d_dst), dst_off, dst_cap,
+                                                              ctypes.byref(raw), ctypes.c_void_p(stream) if stream else None))
         return raw.value
 
     def cipher_apply_device(self, cipher: Cipher, d_buf: int, off: Sequence[int], length: Sequence[int], decrypt: bool = False,
@@ -559,7 +571,7 @@ class Context:
         return bytes(out)
 
     def decompress_batch(self, payloads: Sequence[bytes], raw_sizes: Sequence[int], algo: int = ALGO_ZSTD) -> List[bytes]:
-        """decompress_reader for a batch of entries: payload i (concatenated FDAT bodies) -> raw_sizes[i] bytes."""
+        """decompress_reader for a batch of entries: payload i (concatenated FDAT bodies) -> raw_sizes[i] bytes (algo: ALGO_ZSTD, ALGO_DEFLATE, ALGO_XZ)."""
         n = len(payloads)
         keep = [p if isinstance(p, bytes) else bytes(p) for p in payloads]
         outs = [ctypes.create_string_buffer(max(r, 1)) for r in raw_sizes]

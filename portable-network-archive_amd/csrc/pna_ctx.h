@@ -24,6 +24,7 @@
 #include "../../include/pna_gpu.h"
 #include "../../include/pna_archive.h"
 
+struct XzScan; struct XzBlock;     // xz_core.h
 namespace pna {
 void launch_lz_small(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
                      uint32_t flags, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, const LzParseGrid *pg, bool w3);
@@ -71,6 +72,19 @@ __attribute__((weak)) void launch_verdict(const VerdictEnt *ve, uint32_t n, cons
 __attribute__((weak)) void launch_diff(const DiffPiece *pieces, uint32_t npieces, uint32_t ntiles, const uint8_t *a, const uint8_t *b, unsigned long long *first, hipStream_t st);
 // pna_gpu_extract_select_host's kernel (k_pick.hip; weak like launch_diff: the entry point refuses to run without it)
 __attribute__((weak)) void launch_pick(const PickPiece *pieces, uint32_t npieces, uint32_t ntiles, const uint8_t *src, hipStream_t st);
+// Compression::XZ, decode only (k_xz.hip; weak like launch_diff: without them xz stays "not decoded on the device").  streams: XzStreamInH x n (pna_decode.cpp);
+// launch_xzscan with blocks == null counts, otherwise writes the block descriptors and the check kernel's piece list
+__attribute__((weak)) void launch_xzscan(const void *streams, uint32_t n, const uint8_t *src, XzScan *out, XzBlock *blocks, void *pieces, hipStream_t st);
+__attribute__((weak)) void launch_lzma2(XzBlock *blocks, uint32_t nblk, const uint8_t *src, uint8_t *dst, uint32_t lclp, hipStream_t st);
+__attribute__((weak)) void launch_xzcheck(const void *pieces, uint32_t npieces, const XzBlock *blocks, uint32_t nblk, const uint8_t *src, const uint8_t *dst, uint64_t *acc,
+                                          uint32_t *stream_status, hipStream_t st);
+inline bool xz_kernels_present() { return launch_xzscan && launch_lzma2 && launch_xzcheck; }
+// pna_decode.cpp: which stream of an xz decode call failed and why (the call's error text is "entry <index>: <reason>"), for a caller that knows its streams by name
+struct XzFail { size_t index = ~(size_t)0; std::string reason; };
+// one open xz stream (size from its Index) into d_dst[0 ..], and the batch of sized streams; the batch form in verdict mode goes through decode_batch_status
+int xz_open_decode(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t cap, uint64_t *got, hipStream_t st, XzFail *why = nullptr);
+int xz_decode_sized(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
+                    hipStream_t st, XzFail *why);
 void launch_zdec(ZFrame *frames, uint32_t n, const uint8_t *src, uint8_t *dst, uint8_t *lit_scratch, uint32_t dbg, hipStream_t st);
 void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *dst, hipStream_t st);
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st);
@@ -279,6 +293,7 @@ struct pna_gpu_ctx {
     uint64_t xs_uploaded = 0, xs_streams = 0, xs_kdf = 0, xs_picked = 0; double xs_ms = 0;
     hipStream_t x_cp = nullptr; hipEvent_t x_ev[2] = {}, x_done = nullptr;   // extract driver: D2H of window k on x_cp next to window k+1's work
     bool aes_dec_ready = false;        // read side (pna_gpu_extract_archive_host): archive image, packed payloads, decoded entries
+    DevBuf xz_in, xz_scan, xz_blocks, xz_pieces, xz_acc;       // xz decode: stream descriptors, scan results, block descriptors, check pieces, accumulators + stream statuses
     DevBuf z_vp, z_pb, z_mode;                                 // lane-per-piece inflate: piece list, piece boundaries, per-stream mode
     DevBuf ci_spread, ci_spread_desc;                          // GCM entries of several segments: their compact payloads, the pieces to move
     DevBuf aes_tabs, ci_units, ci_ivs, ci_keys, ci_gcm;        // cipher stage: round tables, unit descriptors, IVs; GCM: per-entry round keys, segment descriptors

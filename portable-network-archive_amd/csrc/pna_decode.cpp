@@ -1,5 +1,6 @@
 // pna_decode.cpp -- the decoders' host side: pna_gpu_decompress_batch[_device], open-size decode, the routing of large frames.
 #include "pna_ctx.h"
+#include "xz_core.h"
 
 // The parallel executor (k_zexec_par.hip) runs a frame / stream in WINDOWS of whole blocks, at most zexec_win_mib (1 024) MiB of output each (its words count 31 bits from the
 // window's start): the cuts, from the blocks' output offsets (k_zoff / the chunk decoder's count pass have set them).  One window for everything up to 1 GiB.
@@ -347,9 +348,131 @@ static int inflate_measure(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, 
     return PNA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Read side, Compression::XZ: one .xz stream per entry (liblzma::bufread::XzDecoder, lib/src/entry/read.rs:171-190; include/pna_gpu.h says what is read).
+// k_xzscan walks every stream's container (pass 1: status, blocks, decoded size, largest lc + lp -- read back once), the host makes room, pass 2 writes a
+// descriptor per block; k_lzma2 decodes one block per wave, k_xzcheck / k_xzfin verify the blocks' checks and fold the statuses per stream.
+struct XzStreamInH { uint64_t src_off, src_len, dst_off; uint32_t blk_base, blk_cap, piece_base, piece_cap; };   // = XzStreamIn of k_xz.hip
+static_assert(sizeof(XzStreamInH) == 40 && sizeof(XzScan) == 32 && sizeof(XzBlock) == 56, "xz descriptor layouts");
+static constexpr uint64_t XZ_PIECE_BYTES = 256u << 10;               // = XZ_PIECE of k_xz.hip
+static const char *xz_unsup_text(uint32_t why) {
+    switch (why) {
+        case XZ_UNSUP_SHA256:    return "xz stream with a SHA-256 check (None, CRC32 and CRC64 are verified on the device)";
+        case XZ_UNSUP_CHECK:     return "xz stream with a check of an unassigned type";
+        case XZ_UNSUP_FILTER:    return "xz stream with a filter chain other than LZMA2 alone (Delta, BCJ)";
+        case XZ_UNSUP_BIG_BLOCK: return "xz stream with a block of 4 GiB or more of decoded bytes";
+        default:                 return "xz stream with header fields of a later format version";
+    }
+}
+// pass 1 over n streams: their scan results
+static int xz_scan_counts(pna_gpu_ctx *c, size_t n, const void *d_src, std::vector<XzStreamInH> &ins, std::vector<XzScan> &sc, hipStream_t st) {
+    if (c->xz_in.ensure(n * sizeof(XzStreamInH)) || c->xz_scan.ensure(n * sizeof(XzScan))) return fail(c, PNA_E_NOMEM, "decoder workspace");
+    HIPCHK(c, hipMemcpyAsync(c->xz_in.p, ins.data(), n * sizeof(XzStreamInH), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->ev[0], st));
+    launch_xzscan(c->xz_in.p, (uint32_t)n, (const uint8_t *)d_src, (XzScan *)c->xz_scan.p, nullptr, nullptr, st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev[2], st));
+    sc.resize(n);
+    HIPCHK(c, hipMemcpyAsync(sc.data(), c->xz_scan.p, n * sizeof(XzScan), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return PNA_OK;
+}
+// raw_len[i]: the decoded size (it must be the Index's total), or with `open` the room; raw_out: the sizes found; ent_status: verdict mode (decode_batch_status)
+static int xz_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off,
+                            const uint64_t *raw_len, bool open, uint64_t *raw_out, uint32_t *ent_status, hipStream_t st, XzFail *why = nullptr) {
+    if (!xz_kernels_present()) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
+    if (n > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+    std::vector<XzStreamInH> ins(n);
+    for (size_t i = 0; i < n; i++) ins[i] = XzStreamInH{src_off[i], src_len[i], dst_off[i], 0, 0, 0, 0};
+    std::vector<XzScan> sc;
+    int rc = xz_scan_counts(c, n, d_src, ins, sc, st); if (rc) return rc;
+    std::vector<uint32_t> status(n);
+    uint64_t nblk = 0, npieces = 0;
+    uint32_t lclp = 0;
+    for (size_t i = 0; i < n; i++) {
+        status[i] = sc[i].status;
+        if (!status[i] && (open ? sc[i].total > raw_len[i] : sc[i].total != raw_len[i])) status[i] = XZ_SIZE;
+        if (status[i]) continue;
+        ins[i].blk_base = (uint32_t)nblk; ins[i].blk_cap = sc[i].nblk; nblk += sc[i].nblk;
+        if (sc[i].check != XZ_CHECK_NONE) {
+            const uint64_t cap = sc[i].total / XZ_PIECE_BYTES + sc[i].nblk;
+            if (cap > 0x7FFFFFFFull - npieces) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+            ins[i].piece_base = (uint32_t)npieces; ins[i].piece_cap = (uint32_t)cap; npieces += cap;
+        }
+        lclp = std::max(lclp, sc[i].lclp);
+        if (nblk > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+    }
+    float ms_scan = 0, ms_dec = 0;
+    (void)hipEventElapsedTime(&ms_scan, c->ev[0], c->ev[2]);
+    if (nblk) {
+        const size_t acc_bytes = (size_t)nblk * 8, stat_bytes = n * 4;
+        if (c->xz_blocks.ensure((size_t)nblk * sizeof(XzBlock)) || c->xz_pieces.ensure((size_t)npieces * 8 + 8) || c->xz_acc.ensure(acc_bytes + stat_bytes))
+            return fail(c, PNA_E_NOMEM, "decoder workspace");
+        uint32_t *d_status = (uint32_t *)((uint8_t *)c->xz_acc.p + acc_bytes);
+        HIPCHK(c, hipMemcpyAsync(c->xz_in.p, ins.data(), n * sizeof(XzStreamInH), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(c->xz_acc.p, 0, acc_bytes + stat_bytes, st));
+        HIPCHK(c, hipEventRecord(c->ev[3], st));
+        launch_xzscan(c->xz_in.p, (uint32_t)n, (const uint8_t *)d_src, (XzScan *)c->xz_scan.p, (XzBlock *)c->xz_blocks.p, c->xz_pieces.p, st);
+        launch_lzma2((XzBlock *)c->xz_blocks.p, (uint32_t)nblk, (const uint8_t *)d_src, (uint8_t *)d_dst, lclp, st);
+        launch_xzcheck(c->xz_pieces.p, (uint32_t)npieces, (const XzBlock *)c->xz_blocks.p, (uint32_t)nblk, (const uint8_t *)d_src, (const uint8_t *)d_dst,
+                       (uint64_t *)c->xz_acc.p, d_status, st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev[1], st));
+        std::vector<uint32_t> dev(n);
+        HIPCHK(c, hipMemcpyAsync(dev.data(), d_status, stat_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        (void)hipEventElapsedTime(&ms_dec, c->ev[3], c->ev[1]);
+        for (size_t i = 0; i < n; i++) if (!status[i]) status[i] = dev[i];
+    }
+    c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms_scan + ms_dec; c->timing.ms_stats = ms_scan; c->timing.ms_lit = ms_dec;   // the xz kernels, the first scan, the rest
+    if (ent_status) for (size_t i = 0; i < n; i++) ent_status[i] = status[i];
+    for (size_t i = 0; i < n && !ent_status; i++)
+        if (status[i]) {
+            char reason[192];
+            if (status[i] == XZ_UNSUPPORTED) snprintf(reason, sizeof reason, "%s", xz_unsup_text(sc[i].why));
+            else if (status[i] == XZ_SIZE) snprintf(reason, sizeof reason, "size mismatch (the xz stream's Index adds up to %llu bytes, %s %llu)", (unsigned long long)sc[i].total,
+                                                    open ? "the room is" : "expected", (unsigned long long)raw_len[i]);
+            else snprintf(reason, sizeof reason, "corrupt xz stream");
+            if (why) { why->index = i; why->reason = reason; }
+            return fail(c, status[i] == XZ_UNSUPPORTED ? PNA_E_UNSUPPORTED : PNA_E_INVAL, ("entry " + std::to_string(i) + ": " + reason).c_str());
+        }
+    if (open && raw_out) for (size_t i = 0; i < n; i++) raw_out[i] = sc[i].total;
+    return PNA_OK;
+}
+int pna::xz_open_decode(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t cap, uint64_t *got, hipStream_t st, XzFail *why) {
+    return xz_decode_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &cap, true, got, nullptr, st, why);
+}
+int pna::xz_decode_sized(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
+                         hipStream_t st, XzFail *why) {
+    return xz_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, nullptr, st, why);
+}
+// An xz stream whose decoded size is recorded nowhere (xz entries without fSIZ, xz solid streams): decoded into dst_cap bytes of room, the size -- the sum
+// of its Index records -- is reported (PNA_E_INVAL when it does not fit).
+extern "C" int pna_gpu_xz_decompress_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
+                                                 uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
+    if (!c || !d_src || !d_dst || !raw_len) return fail(c, PNA_E_INVAL, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    return xz_open_decode(c, d_src, src_off, src_len, d_dst, dst_off, dst_cap, raw_len, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+// the decoded size of one xz stream: the sum of its Index records, after the whole container walk -- exact, nothing is decoded
+static int xz_measure(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, hipStream_t st) {
+    std::vector<XzStreamInH> ins(1, XzStreamInH{src_off, src_len, 0, 0, 0, 0, 0});
+    std::vector<XzScan> sc;
+    const int rc = xz_scan_counts(c, 1, d_src, ins, sc, st); if (rc) return rc;
+    if (sc[0].status == XZ_UNSUPPORTED) return fail(c, PNA_E_UNSUPPORTED, xz_unsup_text(sc[0].why));
+    if (sc[0].status) return fail(c, PNA_E_INVAL, "corrupt xz stream (measuring its size)");
+    *size = sc[0].total;
+    return PNA_OK;
+}
+
 int pna::open_size(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, OpenSize *m, hipStream_t st) {
     *m = OpenSize();
     if (algo == PNA_ALGO_STORE) { m->size = src_len; m->exact = 1; return PNA_OK; }
+    if (algo == PNA_ALGO_XZ && xz_kernels_present()) {
+        const int rc = xz_measure(c, d_src, src_off, src_len, &m->size, st); if (rc) return rc;
+        m->exact = 1;
+        return PNA_OK;
+    }
     if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "only zstd, deflate and stored streams are measured");
     if (algo == PNA_ALGO_DEFLATE) {
         const int rc = inflate_measure(c, d_src, src_off, src_len, &m->size, st); if (rc) return rc;
@@ -388,10 +511,12 @@ extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t 
                                                const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
                                                void *hip_stream) {
     if (!c || (n && (!d_src || !src_off || !src_len || !d_dst || !dst_off || !raw_len))) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
+    const bool xz = algo == PNA_ALGO_XZ && xz_kernels_present();
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !xz) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
     if (!n) return PNA_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (xz) return xz_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, nullptr, st);
     if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, st);
     return zstd_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, st);
 }
@@ -401,6 +526,7 @@ extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t 
 int pna::decode_batch_status(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
                              const uint64_t *dst_off, const uint64_t *raw_len, uint32_t *ent_status, hipStream_t st) {
     if (!n) return PNA_OK;
+    if (algo == PNA_ALGO_XZ) return xz_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, ent_status, st);
     if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, st, false, nullptr, ent_status);
     return zstd_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, st, true, nullptr, ent_status);
 }
@@ -682,7 +808,7 @@ static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const
 extern "C" int pna_gpu_decompress_batch(pna_gpu_ctx *c, int algo, size_t n, const void *const *src, const size_t *src_len,
                                         void *const *dst, const size_t *raw_len) {
     if (!c || (n && (!src || !src_len || !dst || !raw_len))) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !(algo == PNA_ALGO_XZ && xz_kernels_present())) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<uint64_t> so(n), sl(n), dof(n), rl(n);
     uint64_t sp = 0, dp = 0;

@@ -343,7 +343,9 @@ static int plan_stream(XCall &x, const WinSrc &a, XStream &s, XPlan &P) {
     P.pk_total = (P.pk_total + s.pay_len + 15) & ~(uint64_t)15;
     return PNA_OK;
 }
-static bool decoded_here(int compression) { return compression == PNA_ALGO_STORE || compression == PNA_ALGO_ZSTD || compression == PNA_ALGO_DEFLATE; }
+static bool decoded_here(int compression) {
+    return compression == PNA_ALGO_STORE || compression == PNA_ALGO_ZSTD || compression == PNA_ALGO_DEFLATE || (compression == PNA_ALGO_XZ && xz_kernels_present());
+}
 // the window plan: packed payloads, decoded entries, the gather, the cipher stages' stream lists, the entries without fSIZ
 static int plan_window(XCall &x, const WinSrc &a, std::vector<XEntry> &ents, std::vector<XSolid> &solids, XPlan &P) {
     pna_gpu_ctx *c = x.c;
@@ -557,11 +559,24 @@ static int decrypt_gcm(XCall &x, const WinSrc &a, const std::vector<XStream *> &
     return PNA_OK;
 }
 // the entries with fSIZ: one decode call per codec into the raw buffer
+// who a stream is, in an error's text
+static std::string stream_label(const XStream &s) { return s.htype[0] == 'S' ? std::string("solid stream") : "entry '" + static_cast<const XEntry &>(s).name + "'"; }
+// an xz stream of this driver's choosing failed for `reason`: the decoder numbers the streams of its call, the archive's reader knows them by name
+static int xz_named_error(pna_gpu_ctx *c, int rc, const XStream &s, const std::string &reason) {
+    if (rc == PNA_E_INVAL || rc == PNA_E_UNSUPPORTED) c->err = stream_label(s) + ": " + reason;
+    return rc;
+}
 static int decode_sized(pna_gpu_ctx *c, const std::vector<XEntry> &ents, int slot, hipStream_t st) {
-    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE}) {
-        std::vector<uint64_t> so, sl, dof, rl;
-        for (const XEntry &e : ents) if (e.compression == algo && e.has_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); }
+    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE, PNA_ALGO_XZ}) {
+        std::vector<uint64_t> so, sl, dof, rl; std::vector<const XEntry *> who;
+        for (const XEntry &e : ents) if (e.compression == algo && e.has_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); who.push_back(&e); }
         if (so.empty()) continue;
+        if (algo == PNA_ALGO_XZ) {
+            XzFail why;
+            const int rc = xz_decode_sized(c, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[slot].p, dof.data(), rl.data(), st, &why);
+            if (rc) return why.index < who.size() ? xz_named_error(c, rc, *who[why.index], why.reason) : rc;
+            continue;
+        }
         const int rc = pna_gpu_decompress_batch_device(c, algo, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[slot].p, dof.data(), rl.data(), st);
         if (rc) return rc;
     }
@@ -574,7 +589,9 @@ static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::
     uint64_t got = s.pay_len; const void *d = (const uint8_t *)c->x_pk.p + s.pk_off;
     if (s.compression != PNA_ALGO_STORE) {
         OpenSize m;
-        int rc = open_size(c, s.compression, c->x_pk.p, s.pk_off, s.pay_len, &m, st); if (rc) return rc;
+        int rc = open_size(c, s.compression, c->x_pk.p, s.pk_off, s.pay_len, &m, st);
+        if (rc) return s.compression == PNA_ALGO_XZ ? xz_named_error(c, rc, s, std::string(c->err)) : rc;      // (the measurement's text carries no stream number)
+        XzFail why;
         const uint64_t cap = m.size; const int exact = m.exact;
         auto nomem = [&]() {
             char msg[192];
@@ -584,9 +601,10 @@ static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::
         };
         if (c->solid_plain.ensure(cap + 8192)) return nomem();
         rc = s.compression == PNA_ALGO_ZSTD ? zstd_open_decode_planned(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, m, &got, st)
+           : s.compression == PNA_ALGO_XZ   ? xz_open_decode(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, 0, cap, &got, st, &why)
                                             : pna_gpu_inflate_open_device(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, 0, cap, &got, st);
         if (rc == PNA_E_NOMEM) return nomem();
-        if (rc) return rc;
+        if (rc) return why.index == 0 ? xz_named_error(c, rc, s, why.reason) : rc;
         d = c->solid_plain.p;
     }
     if (size_out) *size_out = got;
@@ -850,7 +868,7 @@ static int window_verdicts(XCall &x, const WinSrc &a, size_t span, std::vector<X
 // one does not.  Returns the number of streams handed to the decoders in *streams.
 static int decode_sized_status(pna_gpu_ctx *c, const std::vector<XEntry> &ents, std::vector<uint32_t> &vs, std::vector<uint64_t> &size, std::vector<size_t> &retry,
                                hipStream_t st, uint64_t *streams = nullptr) {
-    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE}) {
+    for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE, PNA_ALGO_XZ}) {
         std::vector<uint64_t> so, sl, dof, rl; std::vector<size_t> idx;
         for (size_t i = 0; i < ents.size(); i++) {
             const XEntry &e = ents[i];

@@ -115,6 +115,7 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     for (auto &e : c->df_ev_k) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->df_tev) if (e) (void)hipEventDestroy(e);
     c->xs_pieces.release();
+    for (DevBuf *b : {&c->xz_in, &c->xz_scan, &c->xz_blocks, &c->xz_pieces, &c->xz_acc}) b->release();
     for (auto &e : c->xs_tev) if (e) (void)hipEventDestroy(e);
     if (c->x_cp) (void)hipStreamDestroy(c->x_cp);
     for (auto &e : c->x_ev) if (e) (void)hipEventDestroy(e);
