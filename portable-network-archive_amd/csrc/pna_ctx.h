@@ -81,10 +81,6 @@ __attribute__((weak)) void launch_xzcheck(const void *pieces, uint32_t npieces, 
 inline bool xz_kernels_present() { return launch_xzscan && launch_lzma2 && launch_xzcheck; }
 // pna_decode.cpp: which stream of an xz decode call failed and why (the call's error text is "entry <index>: <reason>"), for a caller that knows its streams by name
 struct XzFail { size_t index = ~(size_t)0; std::string reason; };
-// one open xz stream (size from its Index) into d_dst[0 ..], and the batch of sized streams; the batch form in verdict mode goes through decode_batch_status
-int xz_open_decode(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t cap, uint64_t *got, hipStream_t st, XzFail *why = nullptr);
-int xz_decode_sized(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
-                    hipStream_t st, XzFail *why);
 void launch_zdec(ZFrame *frames, uint32_t n, const uint8_t *src, uint8_t *dst, uint8_t *lit_scratch, uint32_t dbg, hipStream_t st);
 void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *dst, hipStream_t st);
 void launch_zscan(const ZEntry *ents, uint32_t n, const uint8_t *src, ZFrame *frames, ZFrameX *fx, hipStream_t st);
@@ -100,14 +96,18 @@ void launch_zparse_big_b(ZFrame *frames, ZFrameX *fx, uint32_t nblocks, const ui
                          void *work, const uint32_t *one_list, hipStream_t st);
 void launch_zstreams(uint32_t n_huf, uint32_t n_seq, const uint32_t *huf_list, const uint32_t *seq_list, const void *work, ZBlock *blocks,
                      const ZFrame *frames, const ZTables *tabs, const uint8_t *src, uint8_t *lit_scratch, uint64_t *seqs, hipStream_t st);
-// pna_decode.cpp: the measurement behind pna_gpu_open_size_device (zstd: also its frames and the last frame's share of the size), and the open zstd
-// decode planned from it -- frames of 1 MiB but the last, which gets `last` bytes of room (the rest of `cap` only if the stream is not of that shape)
+// pna_decode.cpp: the measurement behind pna_gpu_open_size_device (zstd: also its frames and the last frame's share of the size)
 struct OpenSize { uint64_t size = 0; int exact = 0; uint64_t frames = 0, last = 0; };
 int open_size(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, OpenSize *out, hipStream_t st);
-int zstd_open_decode_planned(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, const OpenSize &m, uint64_t *got, hipStream_t st);
-// the batch decode in verdict mode: one status per entry (ZFrame::status) instead of a call-level failure (pna_decode.cpp)
-int decode_batch_status(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                        const uint64_t *dst_off, const uint64_t *raw_len, uint32_t *ent_status, hipStream_t st);
+// pna_decode.cpp: what one decode call decodes -- n streams of one codec, all in d_src, decoded into d_dst -- and the one way to the codecs' decoders.  decode_batch is internal: it
+// checks no pointer, the caller has set the device (hipSetDevice) and names the stream (the exports do all three before they call it).
+struct DecodeBatch {
+    size_t n; const void *d_src; const uint64_t *src_off, *src_len; void *d_dst; const uint64_t *dst_off, *raw_len;   // raw_len: the size, or with `open` the room
+    bool open = false; uint64_t *raw_out = nullptr;   // open: the sizes are recorded nowhere; raw_out: the sizes found
+    uint32_t *ent_status = nullptr; hipStream_t st;   // ent_status, verdict mode: one status per stream (ZFrame::status) instead of a failing call
+    const OpenSize *plan = nullptr;                   // zstd, n = 1, open: the stream's measurement -- frames of 1 MiB but the last, which gets plan->last bytes (the rest of the room only if the stream is not of that shape)
+};
+int decode_batch(pna_gpu_ctx *c, int algo, const DecodeBatch &b, XzFail *why = nullptr);
 struct ISChunkH { uint64_t start_bit, end_bit, lit_base, out_base, rec_base, end_found, mtot; uint32_t nlit, nrec, status, adler; };   // = ISChunk of k_inflate.hip
 static_assert(sizeof(ISChunkH) == 72, "ISChunk layout");
 void launch_ispec(const uint8_t *src, uint64_t src_off, uint64_t src_len, uint32_t cbytes, uint32_t nchunks, uint64_t *start, hipStream_t st);

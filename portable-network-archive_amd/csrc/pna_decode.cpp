@@ -1,4 +1,4 @@
-// pna_decode.cpp -- the decoders' host side: pna_gpu_decompress_batch[_device], open-size decode, the routing of large frames.
+// pna_decode.cpp -- the decoders' host side: DecodeBatch (pna_ctx.h) to its codec's decoder (decode_batch), the zstd and zlib decoders as stages, open-size measurement, the exports.
 #include "pna_ctx.h"
 #include "xz_core.h"
 
@@ -23,6 +23,33 @@ static int zx_windows(pna_gpu_ctx *c, const ZxFrame &h, hipStream_t st, std::vec
     win_blk.push_back(h.nblk); win_off.push_back(h.dst_len);
     *max_win = mx;
     return PNA_OK;
+}
+
+// the zstd and zlib decoders' workspace, typed
+static ZFrame *zframes(pna_gpu_ctx *c) { return (ZFrame *)c->z_frames.p; }
+static ZFrameX *zfx(pna_gpu_ctx *c) { return (ZFrameX *)c->z_fx.p; }
+static ZBlock *zblocks(pna_gpu_ctx *c) { return (ZBlock *)c->z_blocks.p; }
+static uint8_t *zlit(pna_gpu_ctx *c) { return (uint8_t *)c->z_lit.p; }
+static uint64_t *zseqs(pna_gpu_ctx *c) { return (uint64_t *)c->z_seqs.p; }
+// One frame / stream through the parallel executor: its windows, the workspace, the descriptor, the launch.  *zst: the executor's status (0: executed), the caller reacts to it
+static int exec_par_frame(pna_gpu_ctx *c, ZxFrame h, const void *d_src, void *d_dst, hipStream_t st, uint32_t *zst, const char *failed) {
+    std::vector<uint32_t> wblk; std::vector<uint64_t> woff; uint64_t wmax = 0;
+    { const int rw = zx_windows(c, h, st, wblk, woff, &wmax); if (rw) return rw; }
+    if (c->z_words.ensure(wmax * 4 + 4096) || c->z_rep.ensure((size_t)h.nblk * 24 + 64) || c->z_zxf.ensure(64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
+    HIPCHK(c, hipMemcpyAsync(c->z_zxf.p, &h, sizeof h, hipMemcpyHostToDevice, st));
+    if (launch_zexec_par((ZxFrame *)c->z_zxf.p, h, zblocks(c), (const uint8_t *)d_src, zlit(c), zseqs(c), (uint32_t *)c->z_rep.p, (uint32_t *)c->z_words.p, (uint8_t *)d_dst, zst, &c->zexec_par_rounds, st,
+                         (uint32_t)wblk.size() - 1, wblk.data(), woff.data()) != 0)
+        return fail(c, PNA_E_HIP, failed);
+    return PNA_OK;
+}
+// v (0 .. 3) into one 32-bit word of device memory, on the stream: the copy is asynchronous, its source is this table, which outlives every copy
+static const uint32_t WORD_VALUE[4] = {0u, 1u, 2u, 3u};
+static hipError_t poke32(void *d_word, uint32_t v, hipStream_t st) { return hipMemcpyAsync(d_word, &WORD_VALUE[v], 4, hipMemcpyHostToDevice, st); }
+// The first bad stream of a call as the call's failure: "<who>: <what> (produced x of y bytes)" -- who: "entry i" or "entry i frame f", size3: what status 3 is called
+static int fail_status(pna_gpu_ctx *c, const std::string &who, const ZFrame &fr, const char *size3) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s (produced %u of %llu bytes)", who.c_str(), fr.status == 2 ? "unsupported stream" : (fr.status == 3 ? size3 : "corrupt stream"), fr.out_len, (unsigned long long)fr.dst_len);
+    return fail(c, fr.status == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, msg);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -143,165 +170,162 @@ static int inflate_spec_stream(pna_gpu_ctx *c, uint32_t f, const ZFrame &fr, con
     return PNA_OK;
 }
 
-static int inflate_batch_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                                const uint64_t *dst_off, const uint64_t *raw_len, hipStream_t st, bool open = false, uint64_t *raw_out = nullptr,
-                                uint32_t *ent_status = nullptr) {
-    if (n > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
-    std::vector<ZFrame> frs(n);
-    std::vector<ZFrameX> fxs(n);
-    std::vector<uint32_t> cbase(n + 1);
-    uint64_t nseq_cap = 0, out_span = 0, pieces = 0, nblk = 0;
+struct InflateRun {
+    pna_gpu_ctx *c; const DecodeBatch &b; const uint8_t *src; uint8_t *dst;
+    std::vector<ZFrame> frs; std::vector<ZFrameX> fxs; struct VPieceH { uint32_t frame, j; }; std::vector<VPieceH> vp; std::vector<uint32_t> cbase, modes; bool lanes = false; uint32_t scan_g = 1; uint64_t nseq_cap = 0, out_span = 0, pieces = 0, nblk = 0;
+    std::vector<uint32_t> cand; std::vector<uint64_t> cand_base;   // large streams that may be a foreign encoder's, and where their chunks' blocks start
+    std::vector<std::pair<uint32_t, ZFrameX>> spec; std::vector<uint64_t> spec_len;   // ... those of them the chunk decoder took, and their decoded sizes
     // Streams of known size go lane-per-piece (k_vinflate): a stream of at most BLK_SIZE decoded bytes is one piece, a larger one is taken
     // to consist of ceil(raw_len / BLK_SIZE) sync-flush delimited pieces of BLK_SIZE bytes each (what this library's encoder writes) --
     // k_imark / k_vinflate / k_vfin check that and leave every stream that does not fit to the wave-per-stream kernel.  Streams of
     // unknown size (`open`) take the wave-per-stream kernel directly.
-    struct VPieceH { uint32_t frame, j; };
-    std::vector<VPieceH> vp;
     // pieces per stream: from the size when it is known; for streams of unknown size (solid streams, entries without fSIZ) from a count of
     // the sync-flush markers (one pass + one small read-back): markers + 1 pieces, all but the last holding BLK_SIZE bytes
-    std::vector<uint64_t> npc(n);
-    uint64_t tot_pieces = 0;
-    bool lanes = !c->tun.inflate_serial;
-    // workgroups per stream for the marker scans: one per 256 KiB of the batch's longest stream (n x G bounded)
-    uint64_t max_src = 0;
-    for (size_t i = 0; i < n; i++) max_src = std::max<uint64_t>(max_src, src_len[i]);
-    const uint32_t scan_g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(max_src >> 18, 1024), (1ull << 24) / std::max<size_t>(n, 1)));
-    // large streams that may turn out to be a foreign encoder's (inflate_spec_stream): candidates by size; their chunks' blocks live behind the batch's own
-    const uint64_t spec_min = (uint64_t)c->tun.zexec_par_min_mib << 20;
-    std::vector<uint32_t> cand; std::vector<uint64_t> cand_base;
-    if (lanes && open) {
-        std::vector<uint32_t> cnt(n);
-        if (c->z_pb.ensure(n * 4 + 8) || c->z_vp.ensure(n * 16 + 16)) return fail(c, PNA_E_NOMEM, "decoder workspace");
-        HIPCHK(c, hipMemcpyAsync(c->z_vp.p, src_off, n * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((uint8_t *)c->z_vp.p + n * 8, src_len, n * 8, hipMemcpyHostToDevice, st));
-        launch_icount((const uint8_t *)d_src, (const uint64_t *)c->z_vp.p, (const uint64_t *)((uint8_t *)c->z_vp.p + n * 8), (uint32_t)n, (uint32_t *)c->z_pb.p, scan_g, st);
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), c->z_pb.p, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        for (size_t i = 0; i < n; i++) { npc[i] = (uint64_t)cnt[i] + 1; if ((npc[i] - 1) * BLK_SIZE > raw_len[i]) npc[i] = 1; }   // more pieces than the room allows: not this library's layout
-    } else
-        for (size_t i = 0; i < n; i++) npc[i] = std::max<uint64_t>(1, (raw_len[i] + BLK_SIZE - 1) / BLK_SIZE);
-    for (size_t i = 0; i < n; i++) tot_pieces += npc[i];
-    // a handful of pieces is served better by the wave-per-stream walk (a lane needs ~110 ms for a 128 KiB piece, however few there are)
-    if (tot_pieces < 1024) lanes = false;
-    for (size_t i = 0; i < n; i++) {
-        // (open: raw_len is the room, the size comes out of the count; the stream must be worth it by its compressed size then)
-        const bool is_cand = spec_min && (open ? src_len[i] >= spec_min / 4 : raw_len[i] >= spec_min) && src_len[i] >= 8ull * SPEC_CHUNK;   // (output of any size: the executor works in windows)
-        // streams of 4 GiB and more: decoded by pieces (this library's layout: a sync flush behind every 128 KiB) or in chunks; the wave-per-stream walk counts in 32 bits
-        if ((raw_len[i] > 0xFFFFFFFFull || src_len[i] > 0xFFFFFFFFull) && !lanes && !is_cand) return fail(c, PNA_E_UNSUPPORTED, "zlib streams of 4 GiB and more are decoded by sync-flush delimited pieces or in chunks only");
-        frs[i] = ZFrame{src_off[i], dst_off[i], src_len[i], raw_len[i], 0, open ? ZF_OPEN : 0u};   // open: raw_len is a capacity
-        ZFrameX &x = fxs[i];
-        const uint64_t P = lanes ? npc[i] : 1;
-        const uint64_t pcap = std::min<uint64_t>(raw_len[i], lanes ? BLK_SIZE : raw_len[i]) / 3 + (raw_len[i] >> 16) / P + 16;   // matches are >= 3 bytes; + literal-run splits (serial walk)
-        if (nblk + P > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
-        x.blk_base = (uint32_t)nblk; x.blk_cap = (uint32_t)P; x.slot_base = 0; x.slot_cap = 0; x.nblk = 0;
-        x.seq_base = nseq_cap; x.seq_cap = (uint32_t)std::min<uint64_t>(P * pcap, 0x7FFFFFFFu); x.pcap = (uint32_t)std::min<uint64_t>(pcap, 0x7FFFFFFFu); x.pad = 0;
-        nseq_cap += P * pcap;
-        if (lanes) for (uint64_t j = 0; j < P; j++) vp.push_back(VPieceH{(uint32_t)i, (uint32_t)j});
-        nblk += P;
-        out_span = std::max<uint64_t>(out_span, dst_off[i] + raw_len[i]);
-        cbase[i] = (uint32_t)pieces;
-        pieces += (raw_len[i] + 65535) >> 16;
-        if (pieces > 0xFFFFFFF0ull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
-        if (is_cand) cand.push_back((uint32_t)i);
+    int count_pieces_and_plan() {
+        const size_t n = b.n;
+        if (n > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+        std::vector<uint64_t> npc(n);                                  // pieces per stream
+        lanes = !c->tun.inflate_serial;
+        // workgroups per stream for the marker scans: one per 256 KiB of the batch's longest stream (n x G bounded)
+        uint64_t max_src = 0, tot_pieces = 0;
+        for (size_t i = 0; i < n; i++) max_src = std::max<uint64_t>(max_src, b.src_len[i]);
+        scan_g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(max_src >> 18, 1024), (1ull << 24) / std::max<size_t>(n, 1)));
+        if (lanes && b.open) {
+            std::vector<uint32_t> cnt(n);
+            if (c->z_pb.ensure(n * 4 + 8) || c->z_vp.ensure(n * 16 + 16)) return fail(c, PNA_E_NOMEM, "decoder workspace");
+            HIPCHK(c, hipMemcpyAsync(c->z_vp.p, b.src_off, n * 8, hipMemcpyHostToDevice, b.st));
+            HIPCHK(c, hipMemcpyAsync((uint8_t *)c->z_vp.p + n * 8, b.src_len, n * 8, hipMemcpyHostToDevice, b.st));
+            launch_icount(src, (const uint64_t *)c->z_vp.p, (const uint64_t *)((uint8_t *)c->z_vp.p + n * 8), (uint32_t)n, (uint32_t *)c->z_pb.p, scan_g, b.st);
+            HIPCHK(c, hipMemcpyAsync(cnt.data(), c->z_pb.p, n * 4, hipMemcpyDeviceToHost, b.st));
+            HIPCHK(c, hipStreamSynchronize(b.st));
+            for (size_t i = 0; i < n; i++) { npc[i] = (uint64_t)cnt[i] + 1; if ((npc[i] - 1) * BLK_SIZE > b.raw_len[i]) npc[i] = 1; }   // more pieces than the room allows: not this library's layout
+        } else
+            for (size_t i = 0; i < n; i++) npc[i] = std::max<uint64_t>(1, (b.raw_len[i] + BLK_SIZE - 1) / BLK_SIZE);
+        for (size_t i = 0; i < n; i++) tot_pieces += npc[i];
+        // a handful of pieces is served better by the wave-per-stream walk (a lane needs ~110 ms for a 128 KiB piece, however few there are)
+        if (tot_pieces < 1024) lanes = false;
+        // host arithmetic: every stream's ZFrame and its share of the blocks, records and Adler pieces; the candidates for the chunk decoder
+        frs.resize(n); fxs.resize(n); cbase.resize(n + 1);
+        // large streams that may turn out to be a foreign encoder's (inflate_spec_stream): candidates by size; their chunks' blocks live behind the batch's own
+        const uint64_t spec_min = (uint64_t)c->tun.zexec_par_min_mib << 20;
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t src_len = b.src_len[i], raw_len = b.raw_len[i];
+            // (open: raw_len is the room, the size comes out of the count; the stream must be worth it by its compressed size then)
+            const bool is_cand = spec_min && (b.open ? src_len >= spec_min / 4 : raw_len >= spec_min) && src_len >= 8ull * SPEC_CHUNK;   // (output of any size: the executor works in windows)
+            // streams of 4 GiB and more: decoded by pieces (this library's layout: a sync flush behind every 128 KiB) or in chunks; the wave-per-stream walk counts in 32 bits
+            if ((raw_len > 0xFFFFFFFFull || src_len > 0xFFFFFFFFull) && !lanes && !is_cand) return fail(c, PNA_E_UNSUPPORTED, "zlib streams of 4 GiB and more are decoded by sync-flush delimited pieces or in chunks only");
+            frs[i] = ZFrame{b.src_off[i], b.dst_off[i], src_len, raw_len, 0, b.open ? ZF_OPEN : 0u};   // open: raw_len is a capacity
+            ZFrameX &x = fxs[i];
+            const uint64_t P = lanes ? npc[i] : 1;
+            const uint64_t pcap = std::min<uint64_t>(raw_len, lanes ? BLK_SIZE : raw_len) / 3 + (raw_len >> 16) / P + 16;   // matches are >= 3 bytes; + literal-run splits (serial walk)
+            if (nblk + P > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+            x.blk_base = (uint32_t)nblk; x.blk_cap = (uint32_t)P; x.slot_base = 0; x.slot_cap = 0; x.nblk = 0;
+            x.seq_base = nseq_cap; x.seq_cap = (uint32_t)std::min<uint64_t>(P * pcap, 0x7FFFFFFFu); x.pcap = (uint32_t)std::min<uint64_t>(pcap, 0x7FFFFFFFu); x.pad = 0;
+            nseq_cap += P * pcap;
+            if (lanes) for (uint64_t j = 0; j < P; j++) vp.push_back(VPieceH{(uint32_t)i, (uint32_t)j});
+            nblk += P;
+            out_span = std::max<uint64_t>(out_span, b.dst_off[i] + raw_len);
+            cbase[i] = (uint32_t)pieces;
+            pieces += (raw_len + 65535) >> 16;
+            if (pieces > 0xFFFFFFF0ull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+            if (is_cand) cand.push_back((uint32_t)i);
+        }
+        cbase[n] = (uint32_t)pieces;
+        for (uint32_t i : cand) { cand_base.push_back(nblk); nblk += (b.src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK; if (nblk > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call"); }
+        return PNA_OK;
     }
-    cbase[n] = (uint32_t)pieces;
-    for (uint32_t i : cand) { cand_base.push_back(nblk); nblk += (src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK; if (nblk > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call"); }
-    if (c->z_frames.ensure(n * sizeof(ZFrame)) || c->z_fx.ensure(n * sizeof(ZFrameX)) || c->z_blocks.ensure(nblk * sizeof(ZBlock)) ||
-        c->z_lit.ensure(out_span + 64) || c->z_seqs.ensure(nseq_cap * 8 + 64) || c->z_cbase.ensure((n + 1) * 4) || c->z_apart.ensure(pieces * 8 + 8) ||
-        c->z_mode.ensure(n * 4 + 8 + (lanes ? (size_t)n * scan_g * 4 : 0)) ||
-        (lanes && (c->z_vp.ensure(vp.size() * 8 + 8) || c->z_pb.ensure((nblk + n) * 8 + 8))))
-        return fail(c, PNA_E_NOMEM, "decoder workspace");
-    std::vector<uint32_t> modes(n, 1u);                            // 1 = the wave-per-stream walk's (VM_SERIAL); the lane-per-piece decoder decides for itself when it runs
-    if (!lanes) HIPCHK(c, hipMemcpyAsync(c->z_mode.p, modes.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->z_frames.p, frs.data(), n * sizeof(ZFrame), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->z_fx.p, fxs.data(), n * sizeof(ZFrameX), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->z_cbase.p, cbase.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
-    if (lanes) HIPCHK(c, hipMemcpyAsync(c->z_vp.p, vp.data(), vp.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->ev[0], st));
-    if (lanes) launch_vinflate((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, (uint32_t)n, c->z_vp.p, (uint32_t)vp.size(), (uint64_t *)c->z_pb.p, (uint32_t *)c->z_mode.p,
-                               (uint32_t *)c->z_mode.p + n + 2, scan_g, (const uint8_t *)d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p, st);
+    int workspace_upload_and_lanes() {
+        const size_t n = b.n;
+        if (c->z_frames.ensure(n * sizeof(ZFrame)) || c->z_fx.ensure(n * sizeof(ZFrameX)) || c->z_blocks.ensure(nblk * sizeof(ZBlock)) ||
+            c->z_lit.ensure(out_span + 64) || c->z_seqs.ensure(nseq_cap * 8 + 64) || c->z_cbase.ensure((n + 1) * 4) || c->z_apart.ensure(pieces * 8 + 8) ||
+            c->z_mode.ensure(n * 4 + 8 + (lanes ? (size_t)n * scan_g * 4 : 0)) ||
+            (lanes && (c->z_vp.ensure(vp.size() * 8 + 8) || c->z_pb.ensure((nblk + n) * 8 + 8))))
+            return fail(c, PNA_E_NOMEM, "decoder workspace");
+        modes.assign(n, 1u);                                           // 1 = the wave-per-stream walk's (VM_SERIAL); the lane-per-piece decoder decides for itself when it runs
+        if (!lanes) HIPCHK(c, hipMemcpyAsync(c->z_mode.p, modes.data(), n * 4, hipMemcpyHostToDevice, b.st));
+        HIPCHK(c, hipMemcpyAsync(c->z_frames.p, frs.data(), n * sizeof(ZFrame), hipMemcpyHostToDevice, b.st));
+        HIPCHK(c, hipMemcpyAsync(c->z_fx.p, fxs.data(), n * sizeof(ZFrameX), hipMemcpyHostToDevice, b.st));
+        HIPCHK(c, hipMemcpyAsync(c->z_cbase.p, cbase.data(), (n + 1) * 4, hipMemcpyHostToDevice, b.st));
+        if (lanes) HIPCHK(c, hipMemcpyAsync(c->z_vp.p, vp.data(), vp.size() * 8, hipMemcpyHostToDevice, b.st));
+        HIPCHK(c, hipEventRecord(c->ev[0], b.st));
+        // the lane-per-piece decoder over every piece of the batch (in z_mode it says which streams it leaves to the wave-per-stream walk)
+        if (lanes) launch_vinflate(zframes(c), zfx(c), (uint32_t)b.n, c->z_vp.p, (uint32_t)vp.size(), (uint64_t *)c->z_pb.p, (uint32_t *)c->z_mode.p, (uint32_t *)c->z_mode.p + b.n + 2, scan_g,
+                                   src, zblocks(c), zlit(c), zseqs(c), b.st);
+        return PNA_OK;
+    }
     // ---- large foreign streams: chunks between block starts found by trial, walked side by side; what does not fit stays with the serial walk below
-    std::vector<std::pair<uint32_t, ZFrameX>> spec; std::vector<uint64_t> spec_len;
-    if (!cand.empty()) {
-        if (lanes) { HIPCHK(c, hipMemcpyAsync(modes.data(), c->z_mode.p, n * 4, hipMemcpyDeviceToHost, st)); HIPCHK(c, hipStreamSynchronize(st)); }
+    int decode_spec_candidates() {
+        if (cand.empty()) return PNA_OK;
+        if (lanes) { HIPCHK(c, hipMemcpyAsync(modes.data(), c->z_mode.p, b.n * 4, hipMemcpyDeviceToHost, b.st)); HIPCHK(c, hipStreamSynchronize(b.st)); }
         for (size_t k = 0; k < cand.size(); k++) {
             const uint32_t i = cand[k];
             if (modes[i] != 1u) continue;                              // this library's layout: the lane-per-piece decoder has it
             ZFrameX xs = fxs[i];
-            xs.blk_base = (uint32_t)cand_base[k]; xs.blk_cap = (uint32_t)((src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK); xs.nblk = 0; xs.pad = 0;
-            HIPCHK(c, hipMemcpyAsync((ZFrameX *)c->z_fx.p + i, &xs, sizeof xs, hipMemcpyHostToDevice, st));
+            xs.blk_base = (uint32_t)cand_base[k]; xs.blk_cap = (uint32_t)((b.src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK); xs.nblk = 0; xs.pad = 0;
+            HIPCHK(c, hipMemcpyAsync(zfx(c) + i, &xs, sizeof xs, hipMemcpyHostToDevice, b.st));
             bool ok = false; uint32_t m = 0; uint64_t olen = 0; SpecWhy reason;
-            const int rcs = inflate_spec_stream(c, i, frs[i], xs, d_src, st, &m, &ok, open, &olen, &reason);
-            if (rcs) return rcs;
-            if (!ok && (src_len[i] > 0xFFFFFFFFull || raw_len[i] > 0xFFFFFFFFull)) return big_unsplit(c, src_len[i], reason);   // (the serial walk counts in 32 bits)
-            static const uint32_t three = 3u;                           // (not 1: the serial walk leaves the stream alone)
+            const int rcs = inflate_spec_stream(c, i, frs[i], xs, b.d_src, b.st, &m, &ok, b.open, &olen, &reason); if (rcs) return rcs;
+            if (!ok && (b.src_len[i] > 0xFFFFFFFFull || b.raw_len[i] > 0xFFFFFFFFull)) return big_unsplit(c, b.src_len[i], reason);   // (the serial walk counts in 32 bits)
             if (ok) {
-                xs.nblk = m; xs.pad = 1; HIPCHK(c, hipMemcpyAsync((uint32_t *)c->z_mode.p + i, &three, 4, hipMemcpyHostToDevice, st));
-                if (open) {                                             // the size found: what the serial walk reports through ZFrame::dst_len
+                xs.nblk = m; xs.pad = 1; HIPCHK(c, poke32((uint32_t *)c->z_mode.p + i, 3u, b.st));   // (3, not 1: the serial walk leaves the stream alone)
+                if (b.open) {                                           // the size found: what the serial walk reports through ZFrame::dst_len
                     frs[i].dst_len = olen;
-                    HIPCHK(c, hipMemcpyAsync((uint8_t *)c->z_frames.p + (size_t)i * sizeof(ZFrame) + offsetof(ZFrame, dst_len), &frs[i].dst_len, 8, hipMemcpyHostToDevice, st));
+                    HIPCHK(c, hipMemcpyAsync(&zframes(c)[i].dst_len, &frs[i].dst_len, 8, hipMemcpyHostToDevice, b.st));
                 }
             }
             else xs = fxs[i];
-            HIPCHK(c, hipMemcpyAsync((ZFrameX *)c->z_fx.p + i, &xs, sizeof xs, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));                        // (xs is read by the copy until then)
+            HIPCHK(c, hipMemcpyAsync(zfx(c) + i, &xs, sizeof xs, hipMemcpyHostToDevice, b.st));
+            HIPCHK(c, hipStreamSynchronize(b.st));                      // (xs is read by the copy until then)
             if (ok) { spec.emplace_back(i, xs); spec_len.push_back(olen); }
         }
+        return PNA_OK;
     }
-    launch_inflate((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, (uint32_t)n, (const uint8_t *)d_src, (ZBlock *)c->z_blocks.p, (uint8_t *)c->z_lit.p,
-                   (uint64_t *)c->z_seqs.p, (const uint32_t *)c->z_mode.p, st);
-    HIPCHK(c, hipEventRecord(c->ev[2], st));
-    if (lanes) launch_zexec_groups((ZFrame *)c->z_frames.p, (const ZFrameX *)c->z_fx.p, (uint32_t)n, (ZBlock *)c->z_blocks.p, c->z_vp.p, (uint32_t)vp.size(), (const uint8_t *)d_src,
-                                   (const uint8_t *)c->z_lit.p, (const uint64_t *)c->z_seqs.p, (uint8_t *)d_dst, st);   // execution groups side by side (k_vfin)
-    else launch_zexec((ZFrame *)c->z_frames.p, (const ZFrameX *)c->z_fx.p, (uint32_t)n, (ZBlock *)c->z_blocks.p, (const uint8_t *)d_src,
-                      (const uint8_t *)c->z_lit.p, (const uint64_t *)c->z_seqs.p, (uint8_t *)d_dst, st);
-    for (size_t si = 0; si < spec.size(); si++) {                        // their chunks' records: pointer jumping over the stream's output positions (k_zexec_par.hip)
-        auto &sp = spec[si];
-        const uint32_t i = sp.first;
-        ZxFrame h{frs[i].dst_off, spec_len[si], sp.second.blk_base, sp.second.nblk, 0, 0};
-        std::vector<uint32_t> wblk; std::vector<uint64_t> woff; uint64_t wmax = 0;
-        { const int rw = zx_windows(c, h, st, wblk, woff, &wmax); if (rw) return rw; }
-        if (c->z_words.ensure(wmax * 4 + 4096) || c->z_rep.ensure((size_t)h.nblk * 24 + 64) || c->z_zxf.ensure(64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
-        HIPCHK(c, hipMemcpyAsync(c->z_zxf.p, &h, sizeof h, hipMemcpyHostToDevice, st));
-        uint32_t zst = 0, rounds = 0;
-        if (launch_zexec_par((ZxFrame *)c->z_zxf.p, h, (const ZBlock *)c->z_blocks.p, (const uint8_t *)d_src, (const uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p,
-                             (uint32_t *)c->z_rep.p, (uint32_t *)c->z_words.p, (uint8_t *)d_dst, &zst, &rounds, st, (uint32_t)wblk.size() - 1, wblk.data(), woff.data()) != 0) return fail(c, PNA_E_HIP, "parallel stream execution failed");
-        c->zexec_par_rounds = rounds;
-        if (zst) { static const uint32_t corrupt = 1u; HIPCHK(c, hipMemcpyAsync((uint8_t *)c->z_frames.p + (size_t)i * sizeof(ZFrame) + offsetof(ZFrame, status), &corrupt, 4, hipMemcpyHostToDevice, st)); }
-    }
-    c->inflate_spec_streams = (uint32_t)spec.size();
-    HIPCHK(c, hipEventRecord(c->ev[3], st));
-    launch_iadler((ZFrame *)c->z_frames.p, (const ZFrameX *)c->z_fx.p, (const ZBlock *)c->z_blocks.p, (uint32_t)n, (const uint32_t *)c->z_cbase.p,
-                  (uint32_t)pieces, (const uint8_t *)d_dst, c->z_apart.p, st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, n * sizeof(ZFrame), hipMemcpyDeviceToHost, st));
-    if (lanes) HIPCHK(c, hipStreamSynchronize(st));          // (vp is read by the copy above until then)
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0, ms_h = 0, ms_x = 0;
-    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]); (void)hipEventElapsedTime(&ms_h, c->ev[0], c->ev[2]); (void)hipEventElapsedTime(&ms_x, c->ev[2], c->ev[3]);
-    c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms; c->timing.ms_stats = ms_h; c->timing.ms_lit = ms_x;   // total, Huffman walk, execution
-    c->timing.lz_match_launches = spec.size();                      // (decode calls: the large foreign streams that went through the chunk decoder)
-    if (ent_status) for (size_t i = 0; i < n; i++) ent_status[i] = frs[i].status;     // verdict mode: every stream's own status, no call-level failure
-    for (size_t i = 0; i < n && !ent_status; i++)
-        if (frs[i].status) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "entry %zu: %s (produced %u of %llu bytes)", i,
-                     frs[i].status == 2 ? "unsupported stream" : (frs[i].status == 3 ? "size mismatch" : "corrupt stream"), frs[i].out_len, (unsigned long long)frs[i].dst_len);
-            return fail(c, frs[i].status == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, msg);
+    // the wave-per-stream walk over what is left to it, then the records' execution: execution groups side by side (k_vfin) behind the lanes, a wave per stream otherwise
+    int walk_and_execute() {
+        launch_inflate(zframes(c), zfx(c), (uint32_t)b.n, src, zblocks(c), zlit(c), zseqs(c), (const uint32_t *)c->z_mode.p, b.st);
+        HIPCHK(c, hipEventRecord(c->ev[2], b.st));
+        if (lanes) launch_zexec_groups(zframes(c), zfx(c), (uint32_t)b.n, zblocks(c), c->z_vp.p, (uint32_t)vp.size(), src, zlit(c), zseqs(c), dst, b.st);
+        else launch_zexec(zframes(c), zfx(c), (uint32_t)b.n, zblocks(c), src, zlit(c), zseqs(c), dst, b.st);
+        // the spec streams' chunks' records: pointer jumping over the stream's output positions (k_zexec_par.hip); a stream the executor gives up on is corrupt
+        for (size_t si = 0; si < spec.size(); si++) {
+            const uint32_t i = spec[si].first; const ZFrameX &x = spec[si].second;
+            uint32_t zst = 0;
+            const int rc = exec_par_frame(c, ZxFrame{frs[i].dst_off, spec_len[si], x.blk_base, x.nblk, 0, 0}, b.d_src, b.d_dst, b.st, &zst, "parallel stream execution failed"); if (rc) return rc;
+            if (zst) HIPCHK(c, poke32(&zframes(c)[i].status, 1u, b.st));
         }
-    if (open && raw_out) for (size_t i = 0; i < n; i++) raw_out[i] = frs[i].dst_len;
-    return PNA_OK;
-}
-
-// A zlib stream whose decoded size is recorded nowhere (deflate entries without fSIZ, deflate solid streams): decoded into dst_cap
-// bytes of room, the size found is reported (PNA_E_INVAL when it does not fit).
-extern "C" int pna_gpu_inflate_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
-                                           uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
-    if (!c || !d_src || !d_dst || !raw_len) return fail(c, PNA_E_INVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return inflate_batch_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &dst_cap, st, true, raw_len);
+        c->inflate_spec_streams = (uint32_t)spec.size();
+        HIPCHK(c, hipEventRecord(c->ev[3], b.st));
+        return PNA_OK;
+    }
+    // the Adler-32 trailers against the output, the streams' ZFrames back, the call's times
+    int check_and_read_back() {
+        launch_iadler(zframes(c), zfx(c), zblocks(c), (uint32_t)b.n, (const uint32_t *)c->z_cbase.p, (uint32_t)pieces, dst, c->z_apart.p, b.st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev[1], b.st));
+        HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, b.n * sizeof(ZFrame), hipMemcpyDeviceToHost, b.st));
+        HIPCHK(c, hipStreamSynchronize(b.st));                          // (frs is written by the copy above until then)
+        float ms = 0, ms_h = 0, ms_x = 0;
+        (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]); (void)hipEventElapsedTime(&ms_h, c->ev[0], c->ev[2]); (void)hipEventElapsedTime(&ms_x, c->ev[2], c->ev[3]);
+        c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms; c->timing.ms_stats = ms_h; c->timing.ms_lit = ms_x;   // total, Huffman walk, execution
+        c->timing.lz_match_launches = spec.size();                      // (decode calls: the large foreign streams that went through the chunk decoder)
+        return PNA_OK;
+    }
+    // what the caller gets: verdict mode -- every stream's own status, no call-level failure --, or the first bad stream as the call's failure; the sizes found
+    int settle() {
+        if (b.ent_status) for (size_t i = 0; i < b.n; i++) b.ent_status[i] = frs[i].status;
+        for (size_t i = 0; i < b.n && !b.ent_status; i++) if (frs[i].status) return fail_status(c, "entry " + std::to_string(i), frs[i], "size mismatch");
+        if (b.open && b.raw_out) for (size_t i = 0; i < b.n; i++) b.raw_out[i] = frs[i].dst_len;
+        return PNA_OK;
+    }
+};
+static int inflate_batch_device(pna_gpu_ctx *c, const DecodeBatch &b) {
+    InflateRun r{c, b, (const uint8_t *)b.d_src, (uint8_t *)b.d_dst};
+    int rc = r.count_pieces_and_plan(); if (rc) return rc;
+    rc = r.workspace_upload_and_lanes(); if (rc) return rc;
+    rc = r.decode_spec_candidates(); if (rc) return rc;
+    rc = r.walk_and_execute(); if (rc) return rc;
+    rc = r.check_and_read_back(); if (rc) return rc;
+    return r.settle();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -377,13 +401,13 @@ static int xz_scan_counts(pna_gpu_ctx *c, size_t n, const void *d_src, std::vect
     HIPCHK(c, hipStreamSynchronize(st));
     return PNA_OK;
 }
-// raw_len[i]: the decoded size (it must be the Index's total), or with `open` the room; raw_out: the sizes found; ent_status: verdict mode (decode_batch_status)
-static int xz_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off,
-                            const uint64_t *raw_len, bool open, uint64_t *raw_out, uint32_t *ent_status, hipStream_t st, XzFail *why = nullptr) {
+// raw_len[i]: the decoded size (it must be the Index's total), or with `open` the room; why: which stream failed and for what reason, for a caller that names its streams
+static int xz_decode_device(pna_gpu_ctx *c, const DecodeBatch &b, XzFail *why) {
+    const size_t n = b.n; const void *d_src = b.d_src; void *d_dst = b.d_dst; const uint64_t *raw_len = b.raw_len; const bool open = b.open; hipStream_t st = b.st;
     if (!xz_kernels_present()) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
     if (n > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
     std::vector<XzStreamInH> ins(n);
-    for (size_t i = 0; i < n; i++) ins[i] = XzStreamInH{src_off[i], src_len[i], dst_off[i], 0, 0, 0, 0};
+    for (size_t i = 0; i < n; i++) ins[i] = XzStreamInH{b.src_off[i], b.src_len[i], b.dst_off[i], 0, 0, 0, 0};
     std::vector<XzScan> sc;
     int rc = xz_scan_counts(c, n, d_src, ins, sc, st); if (rc) return rc;
     std::vector<uint32_t> status(n);
@@ -425,8 +449,8 @@ static int xz_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const u
         for (size_t i = 0; i < n; i++) if (!status[i]) status[i] = dev[i];
     }
     c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms_scan + ms_dec; c->timing.ms_stats = ms_scan; c->timing.ms_lit = ms_dec;   // the xz kernels, the first scan, the rest
-    if (ent_status) for (size_t i = 0; i < n; i++) ent_status[i] = status[i];
-    for (size_t i = 0; i < n && !ent_status; i++)
+    if (b.ent_status) for (size_t i = 0; i < n; i++) b.ent_status[i] = status[i];
+    for (size_t i = 0; i < n && !b.ent_status; i++)
         if (status[i]) {
             char reason[192];
             if (status[i] == XZ_UNSUPPORTED) snprintf(reason, sizeof reason, "%s", xz_unsup_text(sc[i].why));
@@ -436,23 +460,8 @@ static int xz_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const u
             if (why) { why->index = i; why->reason = reason; }
             return fail(c, status[i] == XZ_UNSUPPORTED ? PNA_E_UNSUPPORTED : PNA_E_INVAL, ("entry " + std::to_string(i) + ": " + reason).c_str());
         }
-    if (open && raw_out) for (size_t i = 0; i < n; i++) raw_out[i] = sc[i].total;
+    if (open && b.raw_out) for (size_t i = 0; i < n; i++) b.raw_out[i] = sc[i].total;
     return PNA_OK;
-}
-int pna::xz_open_decode(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t cap, uint64_t *got, hipStream_t st, XzFail *why) {
-    return xz_decode_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &cap, true, got, nullptr, st, why);
-}
-int pna::xz_decode_sized(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
-                         hipStream_t st, XzFail *why) {
-    return xz_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, nullptr, st, why);
-}
-// An xz stream whose decoded size is recorded nowhere (xz entries without fSIZ, xz solid streams): decoded into dst_cap bytes of room, the size -- the sum
-// of its Index records -- is reported (PNA_E_INVAL when it does not fit).
-extern "C" int pna_gpu_xz_decompress_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
-                                                 uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
-    if (!c || !d_src || !d_dst || !raw_len) return fail(c, PNA_E_INVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    return xz_open_decode(c, d_src, src_off, src_len, d_dst, dst_off, dst_cap, raw_len, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
 // the decoded size of one xz stream: the sum of its Index records, after the whole container walk -- exact, nothing is decoded
 static int xz_measure(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, hipStream_t st) {
@@ -501,36 +510,6 @@ extern "C" int pna_gpu_open_size_device(pna_gpu_ctx *c, int algo, const void *d_
     return PNA_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Read side: decompress_reader (lib/src/entry/read.rs:171-190); entries already in device memory.
-static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                              const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign = true,
-                              const OpenSize *plan = nullptr, uint32_t *ent_status = nullptr);
-
-extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off,
-                                               const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len,
-                                               void *hip_stream) {
-    if (!c || (n && (!d_src || !src_off || !src_len || !d_dst || !dst_off || !raw_len))) return fail(c, PNA_E_INVAL, "null argument");
-    const bool xz = algo == PNA_ALGO_XZ && xz_kernels_present();
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !xz) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
-    if (!n) return PNA_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (xz) return xz_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, nullptr, st);
-    if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, st);
-    return zstd_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, st);
-}
-
-// The same in verdict mode (`pna verify`): ent_status[i] = entry i's ZFrame status (0 good, 1 corrupt, 2 unsupported, 3 size mismatch) instead of a
-// failure of the call at the first bad entry; workspace, HIP and batch-shape errors still fail the call.
-int pna::decode_batch_status(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                             const uint64_t *dst_off, const uint64_t *raw_len, uint32_t *ent_status, hipStream_t st) {
-    if (!n) return PNA_OK;
-    if (algo == PNA_ALGO_XZ) return xz_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, ent_status, st);
-    if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, st, false, nullptr, ent_status);
-    return zstd_decode_device(c, n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, st, true, nullptr, ent_status);
-}
-
 // A zstd stream whose decoded size is not recorded anywhere (the SDAT stream of a solid entry: SHED carries no size): step 1 counts
 // its frames, the caller provides frames x 1 MiB (this library's segmentation; one frame of any size: `cap` bytes), step 2 decodes
 // and reports the size found.
@@ -547,34 +526,32 @@ extern "C" int pna_gpu_zstd_stream_frames_device(pna_gpu_ctx *c, const void *d_s
     if (*n_frames == 0 && src_len) return fail(c, PNA_E_INVAL, "not a sequence of zstd frames");
     return PNA_OK;
 }
-extern "C" int pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
-                                                   uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
-    if (!c || !d_src || !d_dst || !raw_len) return fail(c, PNA_E_INVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return zstd_decode_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &dst_cap, true, raw_len, st);
-}
-
-int pna::zstd_open_decode_planned(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, const OpenSize &m, uint64_t *got, hipStream_t st) {
-    const uint64_t dst_off = 0, cap = m.size;
-    return zstd_decode_device(c, 1, d_src, &src_off, &src_len, d_dst, &dst_off, &cap, true, got, st, true, &m);
-}
-
+// ---------------------------------------------------------------------------------------------------------
+// Read side: decompress_reader (lib/src/entry/read.rs:171-190); entries already in device memory.  allow_foreign: payloads k_zscan could not place go through zstd_decode_foreign
+// (which decodes their frames with this function again, allow_foreign off); b.plan: the measurement of an open stream (n = 1) -- how many frames it has, what the last one holds.
+static int zstd_decode_device(pna_gpu_ctx *c, const DecodeBatch &b, bool allow_foreign);
 // A payload k_zscan could not place -- frames of other sizes than this library's grid, skippable frames between them: anything zstd::stream::read::Decoder
 // reads (lib/src/entry/read.rs:171-190) --: its frames are listed (k_zlist), every run of frames whose headers carry a content size is decoded as one batch of
 // single-frame entries (the pipeline above, side by side), a frame without one on its own with an open size (its content's length is only known once it is
-// decoded), one after the other.  `room` = the entry's raw length (open: its capacity); *found = the bytes produced.
-static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t room, bool open,
-                               uint64_t *found, hipStream_t st, bool *size_mismatch = nullptr) {
+// decoded), one after the other.  Entry i of batch b: its room is raw_len[i] (open: its capacity); *found = the bytes produced.
+static int zstd_decode_foreign(pna_gpu_ctx *c, const DecodeBatch &b, size_t i, uint64_t *found, bool *size_mismatch) {
     struct Item { uint64_t off, len, fcs; };
     constexpr uint32_t CAP = 4096;
+    const uint64_t src_off = b.src_off[i], src_len = b.src_len[i], dst_off = b.dst_off[i], room = b.raw_len[i]; hipStream_t st = b.st;
     if (c->z_list.ensure(CAP * sizeof(Item) + 64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
     uint64_t *d_hdr = (uint64_t *)((uint8_t *)c->z_list.p + CAP * sizeof(Item));
     std::vector<Item> items(CAP);
     uint64_t ip = 0, produced = 0;
+    // (verdict mode, size_mismatch given: the frames' own statuses, so that a frame that overflows the entry's size is told from a corrupt one)
+    auto decode_frames = [&](DecodeBatch run) {
+        std::vector<uint32_t> fst(size_mismatch ? run.n : 0); if (size_mismatch) run.ent_status = fst.data();
+        const int rc = zstd_decode_device(c, run, false); if (rc) return rc;
+        for (uint32_t v : fst) if (v) { *size_mismatch = v == 3; return fail(c, v == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, "corrupt or mis-sized frame"); }
+        return (int)PNA_OK;
+    };
     for (;;) {
         uint64_t hdr[3] = {0, 0, 0};
-        launch_zlist((const uint8_t *)d_src, src_off, src_len, ip, c->z_list.p, CAP, d_hdr, st);
+        launch_zlist((const uint8_t *)b.d_src, src_off, src_len, ip, c->z_list.p, CAP, d_hdr, st);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -583,26 +560,17 @@ static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_o
         if (k) { HIPCHK(c, hipMemcpyAsync(items.data(), c->z_list.p, k * sizeof(Item), hipMemcpyDeviceToHost, st)); HIPCHK(c, hipStreamSynchronize(st)); }
         for (size_t a = 0; a < k;) {
             if (items[a].fcs != ~0ull) {                                  // a run of frames that say what they hold: one batch
-                size_t b = a; uint64_t pos = produced;
+                size_t e = a; uint64_t pos = produced;
                 std::vector<uint64_t> so, sl, dof, rl;
-                while (b < k && items[b].fcs != ~0ull) {
-                    if (items[b].fcs > room - pos) { if (size_mismatch) *size_mismatch = true; return fail(c, PNA_E_INVAL, "size mismatch: the frames hold more than the entry's size"); }
-                    so.push_back(items[b].off); sl.push_back(items[b].len); dof.push_back(dst_off + pos); rl.push_back(items[b].fcs); pos += items[b].fcs; b++;
+                while (e < k && items[e].fcs != ~0ull) {
+                    if (items[e].fcs > room - pos) { if (size_mismatch) *size_mismatch = true; return fail(c, PNA_E_INVAL, "size mismatch: the frames hold more than the entry's size"); }
+                    so.push_back(items[e].off); sl.push_back(items[e].len); dof.push_back(dst_off + pos); rl.push_back(items[e].fcs); pos += items[e].fcs; e++;
                 }
-                // (verdict mode, size_mismatch given: the frames' own statuses, so that a frame that overflows the entry's size is told from a corrupt one)
-                std::vector<uint32_t> fst(size_mismatch ? so.size() : 0);
-                int rc = zstd_decode_device(c, so.size(), d_src, so.data(), sl.data(), d_dst, dof.data(), rl.data(), false, nullptr, st, false, nullptr,
-                                            size_mismatch ? fst.data() : nullptr);
-                if (rc) return rc;
-                for (uint32_t v : fst) if (v) { *size_mismatch = v == 3; return fail(c, v == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, "corrupt or mis-sized frame"); }
-                produced = pos; a = b;
+                const int rc = decode_frames(DecodeBatch{so.size(), b.d_src, so.data(), sl.data(), b.d_dst, dof.data(), rl.data(), false, nullptr, nullptr, st}); if (rc) return rc;
+                produced = pos; a = e;
             } else {                                                      // no content size in the header: decoded with an open size
                 uint64_t cap = room - produced, got = 0, dof = dst_off + produced;
-                uint32_t fst = 0;
-                int rc = zstd_decode_device(c, 1, d_src, &items[a].off, &items[a].len, d_dst, &dof, &cap, true, &got, st, false, nullptr,
-                                            size_mismatch ? &fst : nullptr);
-                if (rc) return rc;
-                if (fst) { *size_mismatch = fst == 3; return fail(c, fst == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, "corrupt or mis-sized frame"); }
+                const int rc = decode_frames(DecodeBatch{1, b.d_src, &items[a].off, &items[a].len, b.d_dst, &dof, &cap, true, &got, nullptr, st}); if (rc) return rc;
                 produced += got; a++;
             }
         }
@@ -610,203 +578,239 @@ static int zstd_decode_foreign(pna_gpu_ctx *c, const void *d_src, uint64_t src_o
         if (ip >= src_len) break;
         if (k == 0) return fail(c, PNA_E_INVAL, "corrupt stream");        // (no progress: cannot happen with hdr[2] == 0)
     }
-    if (!open && produced != room) { if (size_mismatch) *size_mismatch = true; return fail(c, PNA_E_INVAL, "size mismatch (the frames do not add up to the entry's size)"); }
+    if (!b.open && produced != room) { if (size_mismatch) *size_mismatch = true; return fail(c, PNA_E_INVAL, "size mismatch (the frames do not add up to the entry's size)"); }
     *found = produced;
     return PNA_OK;
 }
 
-static int zstd_decode_device(pna_gpu_ctx *c, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                              const uint64_t *dst_off, const uint64_t *raw_len, bool open, uint64_t *raw_out, hipStream_t st, bool allow_foreign,
-                              const OpenSize *plan, uint32_t *ent_status) {
-    std::vector<ZEntry> ents(n);
-    uint64_t nfr = 0;
-    for (size_t i = 0; i < n; i++) {
-        uint64_t k = raw_len[i] ? (raw_len[i] + SEG_SIZE - 1) / SEG_SIZE : 1;
-        // a measured stream of several frames (plan: n = 1): one slot per frame, 1 MiB each but the last, which gets its own measured room -- a stream
-        // that does not have this library's shape goes through zstd_decode_foreign with all of raw_len
-        if (plan && plan->frames > 1) k = plan->frames;
-        if (nfr + k > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "too many frames");
-        const uint64_t room = plan && plan->frames > 1 ? std::min<uint64_t>(raw_len[i], (k - 1) * SEG_SIZE + plan->last) : raw_len[i];
-        ents[i] = ZEntry{src_off[i], src_len[i], dst_off[i], room, (uint32_t)nfr, (uint32_t)k, open ? 1u : 0u, 0u};
-        nfr += k;
-    }
-    // per-frame bounds of the lane-parallel pipeline (frames that exceed them fall back to the one-workgroup-per-frame kernel).  They are planned per MiB of
-    // content -- 260 block descriptors, 10 table sets, 262 160 sequence records -- and ONE frame that holds an entry gets the sum (k_zscan, each sum saturated
-    // at 2^31 - 1).  One frame of 8 GiB: 2.1 M descriptors for its 65 536 blocks of 128 KiB, 81 920 table sets (it needs a set per block at most), and
-    // 2^31 - 1 records: the records' sum saturates from 8 GiB of content on, so a frame with more sequences than that -- one per four bytes of 8 GiB -- goes
-    // to the fallback (k_zparse_a finds out).  The batch limit below, 2^30 - 1 descriptors, is 4 TiB of content.  The min() of a single slot only binds where a
-    // measured stream's last frame gets room of its own (plan): 2^20 descriptors = 128 GiB of 128 KiB blocks, 2^16 table sets.  Compressed bytes and literals
-    // are not bounded here: the header walk and the literal scratch (z_lit: as long as the output span) count in 64 bits.
-    std::vector<ZFrameX> fxs(nfr);
-    uint64_t nblk_cap = 0, nslot = 0, nseq_cap = 0, out_span = 0;
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t room = ents[i].raw_len;
-        out_span = std::max<uint64_t>(out_span, dst_off[i] + room);
-        for (uint32_t f = 0; f < ents[i].n_frames; f++) {
-            const uint64_t done = (uint64_t)f * SEG_SIZE;
-            const uint64_t dl = (f + 1 == ents[i].n_frames) ? (room > done ? room - done : 0) : SEG_SIZE;
-            ZFrameX &x = fxs[ents[i].first_frame + f];
-            x.blk_base = (uint32_t)nblk_cap; x.blk_cap = (uint32_t)std::min<uint64_t>((dl >> 12) + 4, 1u << 20);
-            x.slot_base = (uint32_t)nslot; x.slot_cap = (uint32_t)std::min<uint64_t>((dl >> 17) + 2, 1u << 16);
-            x.seq_base = nseq_cap; x.seq_cap = (uint32_t)std::min<uint64_t>(dl / 4 + 16, 0x7FFFFFFFu); x.nblk = 0;
-            nblk_cap += x.blk_cap; nslot += x.slot_cap; nseq_cap += x.seq_cap;
-            if (nblk_cap > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
+struct ZstdRun {
+    pna_gpu_ctx *c; const DecodeBatch &b; const uint8_t *src; uint8_t *dst; bool allow_foreign;
+    std::vector<ZEntry> ents; std::vector<ZFrameX> fxs, fxd;                             // the frames' shares of the workspace as planned; as read back behind k_zparse_a (the large frames' blocks)
+    std::vector<ZFrame> frs;                                         // the frames as the device has them, read back
+    uint64_t nfr = 0, nblk_cap = 0, nslot = 0, nseq_cap = 0, out_span = 0;
+    std::vector<uint32_t> big;                                       // large frames: parsed side by side, executed by the parallel executor
+    // host arithmetic: frames per entry, every frame's share of the workspace, the batch limits
+    int plan() {
+        ents.resize(b.n);
+        for (size_t i = 0; i < b.n; i++) {
+            uint64_t k = b.raw_len[i] ? (b.raw_len[i] + SEG_SIZE - 1) / SEG_SIZE : 1;
+            // a measured stream of several frames (b.plan: n = 1): one slot per frame, 1 MiB each but the last, which gets its own measured room -- a stream
+            // that does not have this library's shape goes through zstd_decode_foreign with all of raw_len
+            if (b.plan && b.plan->frames > 1) k = b.plan->frames;
+            if (nfr + k > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "too many frames");
+            const uint64_t room = b.plan && b.plan->frames > 1 ? std::min<uint64_t>(b.raw_len[i], (k - 1) * SEG_SIZE + b.plan->last) : b.raw_len[i];
+            ents[i] = ZEntry{b.src_off[i], b.src_len[i], b.dst_off[i], room, (uint32_t)nfr, (uint32_t)k, b.open ? 1u : 0u, 0u};
+            nfr += k;
         }
-    }
-    const bool serial_only = c->tun.zdec_serial != 0;                  // diagnostics: one workgroup per frame for everything
-    if (c->z_ents.ensure(n * sizeof(ZEntry)) || c->z_frames.ensure(nfr * sizeof(ZFrame)) || c->z_lit.ensure(out_span + 64) ||
-        c->z_fx.ensure(nfr * sizeof(ZFrameX)) || c->z_blocks.ensure(nblk_cap * sizeof(ZBlock)) || c->z_tabs.ensure(nslot * sizeof(ZTables)) ||
-        c->z_seqs.ensure(nseq_cap * 8 + 64) || c->z_hlist.ensure(nblk_cap * 16 + 16) || c->z_slist.ensure(nblk_cap * 4 + 16) || c->z_work.ensure(64))
-        return fail(c, PNA_E_NOMEM, "decoder workspace");
-    HIPCHK(c, hipMemcpyAsync(c->z_ents.p, ents.data(), n * sizeof(ZEntry), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->z_fx.p, fxs.data(), nfr * sizeof(ZFrameX), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(c->z_work.p, 0, 64, st));
-    launch_zscan((const ZEntry *)c->z_ents.p, (uint32_t)n, (const uint8_t *)d_src, (ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, st);
-    HIPCHK(c, hipEventRecord(c->ev[0], st));
-    std::vector<ZFrame> frs(nfr);
-    if (!serial_only) {
-        // Large frames (the reference writes ONE frame per entry whatever its size): k_zscan has found them -- a frame whose content takes zexec_par_min_mib
-        // and more, of any content, compressed and literal size (the executor works in windows, the header walk counts in 64 bits).  Their blocks are PARSED side by side (k_zparse_a: the header walk,
-        // k_zparse<true>: a wave per block for the tables) and their sequences EXECUTED in parallel by pointer jumping (k_zexec_par.hip) instead of by one
-        // wave each; the per-frame kernels skip them (ZFrameX::pad).
-        std::vector<uint32_t> big;
-        std::vector<ZFrameX> fxd;
-        const uint64_t big_min = (uint64_t)c->tun.zexec_par_min_mib << 20;
-        if (c->tun.zexec_par_min_mib > 0) {
-            bool any = false;
-            for (size_t i = 0; i < n && !any; i++) any = ents[i].raw_len >= big_min;
-            if (any) {
-                HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, nfr * sizeof(ZFrame), hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
-                for (uint64_t f = 0; f < nfr; f++)
-                    if (frs[f].status == 0 && frs[f].dst_len >= big_min) big.push_back((uint32_t)f);            // (any size: the executor works in windows of 1 GiB)
-                if (!big.empty()) {
-                    if (c->z_big.ensure(big.size() * 4 + 64) || c->z_one.ensure(nblk_cap * 4 + 64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
-                    static const uint32_t one = 1;                        // (static: the copy is asynchronous, the source must outlive this scope)
-                    for (uint32_t f : big) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->z_fx.p + (size_t)f * sizeof(ZFrameX) + offsetof(ZFrameX, pad), &one, 4, hipMemcpyHostToDevice, st));
-                    HIPCHK(c, hipMemcpyAsync(c->z_big.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, st));
-                }
+        // per-frame bounds of the lane-parallel pipeline (frames that exceed them fall back to the one-workgroup-per-frame kernel).  They are planned per MiB of
+        // content -- 260 block descriptors, 10 table sets, 262 160 sequence records -- and ONE frame that holds an entry gets the sum (k_zscan, each sum saturated
+        // at 2^31 - 1).  One frame of 8 GiB: 2.1 M descriptors for its 65 536 blocks of 128 KiB, 81 920 table sets (it needs a set per block at most), and
+        // 2^31 - 1 records: the records' sum saturates from 8 GiB of content on, so a frame with more sequences than that -- one per four bytes of 8 GiB -- goes
+        // to the fallback (k_zparse_a finds out).  The batch limit below, 2^30 - 1 descriptors, is 4 TiB of content.  The min() of a single slot only binds where a
+        // measured stream's last frame gets room of its own (b.plan): 2^20 descriptors = 128 GiB of 128 KiB blocks, 2^16 table sets.  Compressed bytes and literals
+        // are not bounded here: the header walk and the literal scratch (z_lit: as long as the output span) count in 64 bits.
+        fxs.resize(nfr);
+        for (size_t i = 0; i < b.n; i++) {
+            const uint64_t room = ents[i].raw_len;
+            out_span = std::max<uint64_t>(out_span, b.dst_off[i] + room);
+            for (uint32_t f = 0; f < ents[i].n_frames; f++) {
+                const uint64_t done = (uint64_t)f * SEG_SIZE;
+                const uint64_t dl = (f + 1 == ents[i].n_frames) ? (room > done ? room - done : 0) : SEG_SIZE;
+                ZFrameX &x = fxs[ents[i].first_frame + f];
+                x.blk_base = (uint32_t)nblk_cap; x.blk_cap = (uint32_t)std::min<uint64_t>((dl >> 12) + 4, 1u << 20);
+                x.slot_base = (uint32_t)nslot; x.slot_cap = (uint32_t)std::min<uint64_t>((dl >> 17) + 2, 1u << 16);
+                x.seq_base = nseq_cap; x.seq_cap = (uint32_t)std::min<uint64_t>(dl / 4 + 16, 0x7FFFFFFFu); x.nblk = 0;
+                nblk_cap += x.blk_cap; nslot += x.slot_cap; nseq_cap += x.seq_cap;
+                if (nblk_cap > 0x3FFFFFFFull) return fail(c, PNA_E_INVAL, "batch too large for one decode call");
             }
         }
+        return PNA_OK;
+    }
+    // the workspace, the plan's upload, and k_zscan: every frame's header walked, its ZFrame written
+    int workspace_and_scan() {
+        if (c->z_ents.ensure(b.n * sizeof(ZEntry)) || c->z_frames.ensure(nfr * sizeof(ZFrame)) || c->z_lit.ensure(out_span + 64) ||
+            c->z_fx.ensure(nfr * sizeof(ZFrameX)) || c->z_blocks.ensure(nblk_cap * sizeof(ZBlock)) || c->z_tabs.ensure(nslot * sizeof(ZTables)) ||
+            c->z_seqs.ensure(nseq_cap * 8 + 64) || c->z_hlist.ensure(nblk_cap * 16 + 16) || c->z_slist.ensure(nblk_cap * 4 + 16) || c->z_work.ensure(64))
+            return fail(c, PNA_E_NOMEM, "decoder workspace");
+        HIPCHK(c, hipMemcpyAsync(c->z_ents.p, ents.data(), b.n * sizeof(ZEntry), hipMemcpyHostToDevice, b.st));
+        HIPCHK(c, hipMemcpyAsync(c->z_fx.p, fxs.data(), nfr * sizeof(ZFrameX), hipMemcpyHostToDevice, b.st));
+        HIPCHK(c, hipMemsetAsync(c->z_work.p, 0, 64, b.st));
+        launch_zscan((const ZEntry *)c->z_ents.p, (uint32_t)b.n, src, zframes(c), zfx(c), b.st);
+        HIPCHK(c, hipEventRecord(c->ev[0], b.st));
+        frs.resize(nfr);
+        return PNA_OK;
+    }
+    // (not a stage: the frames as the device has them now; all_to_fallback -- diagnostics, zdec_serial, instead of the three stages below --: every well-formed frame is routed through the fallback)
+    int read_frames(bool all_to_fallback) {
+        HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, nfr * sizeof(ZFrame), hipMemcpyDeviceToHost, b.st));
+        HIPCHK(c, hipStreamSynchronize(b.st));
+        for (auto &fr : frs) if (all_to_fallback && fr.status == 0) fr.status = 2;
+        return PNA_OK;
+    }
+    // Large frames (the reference writes ONE frame per entry whatever its size): k_zscan has found them -- a frame whose content takes zexec_par_min_mib
+    // and more, of any content, compressed and literal size (the executor works in windows, the header walk counts in 64 bits).  Their blocks are PARSED side by side (k_zparse_a: the header walk,
+    // k_zparse<true>: a wave per block for the tables) and their sequences EXECUTED in parallel by pointer jumping (k_zexec_par.hip) instead of by one
+    // wave each; the per-frame kernels skip them (ZFrameX::pad).
+    int mark_large_frames() {
+        const uint64_t big_min = (uint64_t)c->tun.zexec_par_min_mib << 20;
+        bool any = false;
+        for (size_t i = 0; i < b.n && !any; i++) any = c->tun.zexec_par_min_mib > 0 && ents[i].raw_len >= big_min;
+        if (!any) return PNA_OK;
+        const int rc = read_frames(false); if (rc) return rc;
+        for (uint64_t f = 0; f < nfr; f++)
+            if (frs[f].status == 0 && frs[f].dst_len >= big_min) big.push_back((uint32_t)f);            // (any size: the executor works in windows of 1 GiB)
+        if (big.empty()) return PNA_OK;
+        if (c->z_big.ensure(big.size() * 4 + 64) || c->z_one.ensure(nblk_cap * 4 + 64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
+        for (uint32_t f : big) HIPCHK(c, poke32(&zfx(c)[f].pad, 1u, b.st));
+        HIPCHK(c, hipMemcpyAsync(c->z_big.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, b.st));
+        return PNA_OK;
+    }
+    // the bounded pipeline: block headers and tables (k_zparse; the large frames' by k_zparse_a / _b), literal and sequence streams (k_zstreams), execution (k_zexec)
+    int parse_and_execute() {
+        uint32_t *hlist = (uint32_t *)c->z_hlist.p, *slist = (uint32_t *)c->z_slist.p, *one = (uint32_t *)c->z_one.p; ZTables *tabs = (ZTables *)c->z_tabs.p;
         // sequence records of frame f start at seq_base: k_zparse adds it to the block's running count
-        launch_zparse((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, (uint32_t)nfr, (const uint8_t *)d_src, (ZBlock *)c->z_blocks.p, (ZTables *)c->z_tabs.p,
-                      (uint32_t *)c->z_hlist.p, (uint32_t *)c->z_slist.p, c->z_work.p, st);
+        launch_zparse(zframes(c), zfx(c), (uint32_t)nfr, src, zblocks(c), tabs, hlist, slist, c->z_work.p, b.st);
         uint32_t work[4] = {0, 0, 0, 0};
         if (!big.empty()) {
-            launch_zparse_big_a((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, (const uint32_t *)c->z_big.p, (uint32_t)big.size(), (const uint8_t *)d_src, (ZBlock *)c->z_blocks.p,
-                                (uint32_t *)c->z_one.p, c->z_work.p, st);
+            launch_zparse_big_a(zframes(c), zfx(c), (const uint32_t *)c->z_big.p, (uint32_t)big.size(), src, zblocks(c), one, c->z_work.p, b.st);
             fxd.resize(nfr);
-            HIPCHK(c, hipMemcpyAsync(work, c->z_work.p, 16, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipMemcpyAsync(fxd.data(), c->z_fx.p, nfr * sizeof(ZFrameX), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            launch_zparse_big_b((ZFrame *)c->z_frames.p, (ZFrameX *)c->z_fx.p, work[2], (const uint8_t *)d_src, (ZBlock *)c->z_blocks.p, (ZTables *)c->z_tabs.p,
-                                (uint32_t *)c->z_hlist.p, (uint32_t *)c->z_slist.p, c->z_work.p, (const uint32_t *)c->z_one.p, st);
+            HIPCHK(c, hipMemcpyAsync(work, c->z_work.p, 16, hipMemcpyDeviceToHost, b.st));
+            HIPCHK(c, hipMemcpyAsync(fxd.data(), c->z_fx.p, nfr * sizeof(ZFrameX), hipMemcpyDeviceToHost, b.st));
+            HIPCHK(c, hipStreamSynchronize(b.st));
+            launch_zparse_big_b(zframes(c), zfx(c), work[2], src, zblocks(c), tabs, hlist, slist, c->z_work.p, one, b.st);
         }
-        HIPCHK(c, hipMemcpyAsync(work, c->z_work.p, 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        launch_zstreams(work[0], work[1], (const uint32_t *)c->z_hlist.p, (const uint32_t *)c->z_slist.p, c->z_work.p, (ZBlock *)c->z_blocks.p,
-                        (const ZFrame *)c->z_frames.p, (const ZTables *)c->z_tabs.p, (const uint8_t *)d_src, (uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p, st);
-        launch_zexec((ZFrame *)c->z_frames.p, (const ZFrameX *)c->z_fx.p, (uint32_t)nfr, (ZBlock *)c->z_blocks.p, (const uint8_t *)d_src,
-                     (const uint8_t *)c->z_lit.p, (const uint64_t *)c->z_seqs.p, (uint8_t *)d_dst, st);
-        if (!big.empty()) {
-            HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, nfr * sizeof(ZFrame), hipMemcpyDeviceToHost, st));      // (k_zoff has fixed the sizes of open frames)
-            HIPCHK(c, hipStreamSynchronize(st));
-            for (uint32_t f : big) {
-                if (frs[f].status) continue;
-                ZxFrame h{frs[f].dst_off, frs[f].dst_len, fxd[f].blk_base, fxd[f].nblk, 0, 0};
-                std::vector<uint32_t> wblk; std::vector<uint64_t> woff; uint64_t wmax = 0;
-                { const int rw = zx_windows(c, h, st, wblk, woff, &wmax); if (rw) return rw; }
-                if (c->z_words.ensure(wmax * 4 + 4096) || c->z_rep.ensure((size_t)h.nblk * 24 + 64) || c->z_zxf.ensure(64)) return fail(c, PNA_E_NOMEM, "decoder workspace");
-                HIPCHK(c, hipMemcpyAsync(c->z_zxf.p, &h, sizeof h, hipMemcpyHostToDevice, st));
-                uint32_t zst = 0, rounds = 0;
-                if (launch_zexec_par((ZxFrame *)c->z_zxf.p, h, (const ZBlock *)c->z_blocks.p, (const uint8_t *)d_src, (const uint8_t *)c->z_lit.p, (uint64_t *)c->z_seqs.p,
-                                     (uint32_t *)c->z_rep.p, (uint32_t *)c->z_words.p, (uint8_t *)d_dst, &zst, &rounds, st, (uint32_t)wblk.size() - 1, wblk.data(), woff.data()) != 0) return fail(c, PNA_E_HIP, "parallel frame execution failed");
-                c->zexec_par_rounds = rounds;
-                if (zst) {                                            // 2: the serial kernel takes the frame (it decodes from the source again); 3: corrupt
-                    static const uint32_t codes[2] = {1u, 2u};            // (static: the copy is asynchronous)
-                    HIPCHK(c, hipMemcpyAsync((uint8_t *)c->z_frames.p + (size_t)f * sizeof(ZFrame) + offsetof(ZFrame, status), &codes[zst == 2 ? 1 : 0], 4, hipMemcpyHostToDevice, st));
-                }
-            }
+        HIPCHK(c, hipMemcpyAsync(work, c->z_work.p, 16, hipMemcpyDeviceToHost, b.st));
+        HIPCHK(c, hipStreamSynchronize(b.st));
+        launch_zstreams(work[0], work[1], hlist, slist, c->z_work.p, zblocks(c), zframes(c), tabs, src, zlit(c), zseqs(c), b.st);
+        launch_zexec(zframes(c), zfx(c), (uint32_t)nfr, zblocks(c), src, zlit(c), zseqs(c), dst, b.st);
+        return PNA_OK;
+    }
+    // the large frames' sequences through the parallel executor, one frame after the other; then the content checksums of the frames that carry one (k_zxxh), and the frames back
+    int execute_large_frames_and_checksum() {
+        int rc = big.empty() ? (int)PNA_OK : read_frames(false); if (rc) return rc;   // (k_zoff has fixed the sizes of open frames)
+        for (uint32_t f : big) {
+            if (frs[f].status) continue;
+            uint32_t zst = 0;
+            rc = exec_par_frame(c, ZxFrame{frs[f].dst_off, frs[f].dst_len, fxd[f].blk_base, fxd[f].nblk, 0, 0}, b.d_src, b.d_dst, b.st, &zst, "parallel frame execution failed"); if (rc) return rc;
+            if (zst) HIPCHK(c, poke32(&zframes(c)[f].status, zst == 2 ? 2u : 1u, b.st));   // 2: the serial kernel takes the frame (it decodes from the source again); 3: corrupt
         }
-        launch_zxxh((ZFrame *)c->z_frames.p, (uint32_t)nfr, (const uint8_t *)d_src, (const uint8_t *)d_dst, st);   // frames that carry a content checksum
+        launch_zxxh(zframes(c), (uint32_t)nfr, src, dst, b.st);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, nfr * sizeof(ZFrame), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, nfr * sizeof(ZFrame), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        for (auto &fr : frs) if (fr.status == 0) fr.status = 2;        // route every well-formed frame through the fallback below
+        return read_frames(false);
     }
     // ---- frames the bounded pipeline could not take: one workgroup per frame
-    std::vector<uint32_t> fb;
-    for (uint64_t f = 0; f < nfr; f++) if (frs[f].status == 2) fb.push_back((uint32_t)f);
-    if (c->tun.zdec_fallback_max_mib > 0)
-        for (uint32_t f : fb) if (frs[f].dst_len > ((uint64_t)c->tun.zdec_fallback_max_mib << 20)) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "frame %u: %llu bytes of content would be decoded by one workgroup (option zdec_fallback_max_mib)", f, (unsigned long long)frs[f].dst_len);
-            return fail(c, PNA_E_UNSUPPORTED, msg);
-        }
-    if (!fb.empty()) {
+    int fallback() {
+        std::vector<uint32_t> fb;
+        for (uint64_t f = 0; f < nfr; f++) if (frs[f].status == 2) fb.push_back((uint32_t)f);
+        if (c->tun.zdec_fallback_max_mib > 0)
+            for (uint32_t f : fb) if (frs[f].dst_len > ((uint64_t)c->tun.zdec_fallback_max_mib << 20)) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "frame %u: %llu bytes of content would be decoded by one workgroup (option zdec_fallback_max_mib)", f, (unsigned long long)frs[f].dst_len);
+                return fail(c, PNA_E_UNSUPPORTED, msg);
+            }
+        if (fb.empty()) return PNA_OK;
         std::vector<ZFrame> sub(fb.size());
         for (size_t k = 0; k < fb.size(); k++) { sub[k] = frs[fb[k]]; sub[k].status = 0; sub[k].out_len = 0; }
-        if (open)                                                 // the frame that closes a stream of unknown size keeps its flag
+        if (b.open)                                                   // the frame that closes a stream of unknown size keeps its flag
             for (size_t k = 0; k < fb.size(); k++)
-                for (size_t i = 0; i < n; i++) {
+                for (size_t i = 0; i < b.n; i++) {
                     const uint32_t f0 = ents[i].first_frame, f1 = f0 + ents[i].n_frames;
                     if (fb[k] >= f0 && fb[k] < f1 && (fb[k] + 1 == f1 || (fb[k] == f0 && f1 - f0 > 1 && frs[f0 + 1].status == 4))) sub[k].out_len = ZF_OPEN;
                 }
         if (c->z_fb.ensure(sub.size() * sizeof(ZFrame)) || c->z_lit.ensure(std::max<uint64_t>(out_span + 64, sub.size() * (uint64_t)(128u << 10) + 64)))
             return fail(c, PNA_E_NOMEM, "decoder workspace");
-        HIPCHK(c, hipMemcpyAsync(c->z_fb.p, sub.data(), sub.size() * sizeof(ZFrame), hipMemcpyHostToDevice, st));
-        launch_zdec((ZFrame *)c->z_fb.p, (uint32_t)sub.size(), (const uint8_t *)d_src, (uint8_t *)d_dst, (uint8_t *)c->z_lit.p, (uint32_t)c->tun.zdec_dbg, st);
-        launch_zxxh((ZFrame *)c->z_fb.p, (uint32_t)sub.size(), (const uint8_t *)d_src, (const uint8_t *)d_dst, st);
+        HIPCHK(c, hipMemcpyAsync(c->z_fb.p, sub.data(), sub.size() * sizeof(ZFrame), hipMemcpyHostToDevice, b.st));
+        launch_zdec((ZFrame *)c->z_fb.p, (uint32_t)sub.size(), src, dst, zlit(c), (uint32_t)c->tun.zdec_dbg, b.st);
+        launch_zxxh((ZFrame *)c->z_fb.p, (uint32_t)sub.size(), src, dst, b.st);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(sub.data(), c->z_fb.p, sub.size() * sizeof(ZFrame), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipMemcpyAsync(sub.data(), c->z_fb.p, sub.size() * sizeof(ZFrame), hipMemcpyDeviceToHost, b.st));
+        HIPCHK(c, hipStreamSynchronize(b.st));
         for (size_t k = 0; k < fb.size(); k++) frs[fb[k]] = sub[k];
+        return PNA_OK;
     }
-    HIPCHK(c, hipEventRecord(c->ev[1], st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-    c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms;            // decoder time reported in the first stage slot
-    std::vector<uint64_t> foreign_len(n, ~0ull);                  // entries that went through zstd_decode_foreign: the bytes they produced
-    const pna_gpu_timing outer_timing = c->timing;                // (the foreign path runs decode calls of its own: this call's timing stays what it measured)
-    if (ent_status) for (size_t i = 0; i < n; i++) ent_status[i] = 0;
-    for (size_t i = 0; i < n; i++)
-        for (uint32_t f = 0; f < ents[i].n_frames; f++) {
-            const ZFrame &fr = frs[ents[i].first_frame + f];
-            if (allow_foreign && (fr.status == 1 || fr.status == 3)) {
-                // not one of the two shapes k_zscan places (or a frame of the grid walk did not hold its MiB): the payload's frames as they are
-                uint64_t got = 0;
-                bool mism = false;
-                const int rcf = zstd_decode_foreign(c, d_src, src_off[i], src_len[i], d_dst, dst_off[i], raw_len[i], open, &got, st, ent_status ? &mism : nullptr);
-                c->timing = outer_timing;
-                if (rcf && ent_status && (rcf == PNA_E_INVAL || rcf == PNA_E_UNSUPPORTED)) { ent_status[i] = rcf == PNA_E_UNSUPPORTED ? 2u : (mism ? 3u : 1u); break; }
-                if (rcf) return rcf;
-                foreign_len[i] = got;
-                break;
+    // The call's time, then what the caller gets, entry by entry: the foreign path for a payload k_zscan could not place, verdict mode -- this entry's status, the
+    // others go on --, or the first bad frame as the call's failure; the sizes found.
+    int settle() {
+        const size_t n = b.n; HIPCHK(c, hipEventRecord(c->ev[1], b.st));
+        HIPCHK(c, hipStreamSynchronize(b.st));
+        float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+        c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms;            // decoder time reported in the first stage slot
+        std::vector<uint64_t> foreign_len(n, ~0ull);                  // entries that went through zstd_decode_foreign: the bytes they produced
+        const pna_gpu_timing outer_timing = c->timing;                // (the foreign path runs decode calls of its own: this call's timing stays what it measured)
+        if (b.ent_status) for (size_t i = 0; i < n; i++) b.ent_status[i] = 0;
+        for (size_t i = 0; i < n; i++)
+            for (uint32_t f = 0; f < ents[i].n_frames; f++) {
+                const ZFrame &fr = frs[ents[i].first_frame + f];
+                if (allow_foreign && (fr.status == 1 || fr.status == 3)) {
+                    // not one of the two shapes k_zscan places (or a frame of the grid walk did not hold its MiB): the payload's frames as they are
+                    uint64_t got = 0; bool mism = false;
+                    const int rcf = zstd_decode_foreign(c, b, i, &got, b.ent_status ? &mism : nullptr);
+                    c->timing = outer_timing;
+                    if (rcf && b.ent_status && (rcf == PNA_E_INVAL || rcf == PNA_E_UNSUPPORTED)) { b.ent_status[i] = rcf == PNA_E_UNSUPPORTED ? 2u : (mism ? 3u : 1u); break; }
+                    if (rcf) return rcf;
+                    foreign_len[i] = got; break;
+                }
+                if (fr.status && fr.status != 4 && b.ent_status) { b.ent_status[i] = fr.status; break; }
+                if (fr.status && fr.status != 4) return fail_status(c, "entry " + std::to_string(i) + " frame " + std::to_string(f), fr, "size mismatch (foreign multi-frame stream?)");   // 4: void slot behind a single frame that holds the whole entry
             }
-            if (fr.status && fr.status != 4 && ent_status) { ent_status[i] = fr.status; break; }     // verdict mode: this entry's status, the others go on
-            if (fr.status && fr.status != 4) {                    // 4: void slot behind a single frame that holds the whole entry
-                char msg[160];
-                snprintf(msg, sizeof msg, "entry %zu frame %u: %s (produced %u of %llu bytes)", i, f,
-                         fr.status == 2 ? "unsupported stream" : (fr.status == 3 ? "size mismatch (foreign multi-frame stream?)" : "corrupt stream"), fr.out_len, (unsigned long long)fr.dst_len);
-                return fail(c, fr.status == 2 ? PNA_E_UNSUPPORTED : PNA_E_INVAL, msg);
+        if (b.open && b.raw_out)
+            for (size_t i = 0; i < n; i++) {                          // sizes found by the decoder: frames in front hold SEG_SIZE each
+                if (foreign_len[i] != ~0ull) { b.raw_out[i] = foreign_len[i]; continue; }
+                uint64_t total = 0;
+                for (uint32_t f = 0; f < ents[i].n_frames; f++) { const ZFrame &fr = frs[ents[i].first_frame + f]; if (fr.status != 4) total += fr.dst_len; }
+                b.raw_out[i] = total;
             }
-        }
-    if (open && raw_out)
-        for (size_t i = 0; i < n; i++) {                          // sizes found by the decoder: frames in front hold SEG_SIZE each
-            if (foreign_len[i] != ~0ull) { raw_out[i] = foreign_len[i]; continue; }
-            uint64_t total = 0;
-            for (uint32_t f = 0; f < ents[i].n_frames; f++) { const ZFrame &fr = frs[ents[i].first_frame + f]; if (fr.status != 4) total += fr.dst_len; }
-            raw_out[i] = total;
-        }
-    return PNA_OK;
+        return PNA_OK;
+    }
+};
+static int zstd_decode_device(pna_gpu_ctx *c, const DecodeBatch &b, bool allow_foreign) {
+    ZstdRun r{c, b, (const uint8_t *)b.d_src, (uint8_t *)b.d_dst, allow_foreign};
+    int rc = r.plan(); if (rc) return rc;
+    rc = r.workspace_and_scan(); if (rc) return rc;
+    if (c->tun.zdec_serial != 0) { rc = r.read_frames(true); if (rc) return rc; }
+    else {
+        rc = r.mark_large_frames(); if (rc) return rc;
+        rc = r.parse_and_execute(); if (rc) return rc;
+        rc = r.execute_large_frames_and_checksum(); if (rc) return rc;
+    }
+    rc = r.fallback(); if (rc) return rc;
+    return r.settle();
+}
+// ---------------------------------------------------------------------------------------------------------
+// One batch to its codec's decoder (the caller has set the device).  Verdict mode (b.ent_status, `pna verify`): ent_status[i] = stream i's status (0 good,
+// 1 corrupt, 2 unsupported, 3 size mismatch) instead of a failure of the call at the first bad stream; workspace, HIP and batch-shape errors still fail the call.
+int pna::decode_batch(pna_gpu_ctx *c, int algo, const DecodeBatch &b, XzFail *why) {
+    if (!b.n) return PNA_OK;
+    if (algo == PNA_ALGO_XZ) return xz_decode_device(c, b, why);
+    if (algo == PNA_ALGO_DEFLATE) return inflate_batch_device(c, b);
+    return zstd_decode_device(c, b, true);
+}
+extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t n, const void *d_src, const uint64_t *src_off, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, const uint64_t *raw_len, void *hip_stream) {
+    if (!c || (n && (!d_src || !src_off || !src_len || !d_dst || !dst_off || !raw_len))) return fail(c, PNA_E_INVAL, "null argument");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !(algo == PNA_ALGO_XZ && xz_kernels_present())) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
+    if (!n) return PNA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return decode_batch(c, algo, DecodeBatch{n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream});
+}
+// One stream whose decoded size is recorded nowhere (entries without fSIZ, solid streams), decoded into dst_cap bytes of room; the size found is reported (PNA_E_INVAL when it does
+// not fit): zstd -- the caller provides frames x 1 MiB (pna_gpu_zstd_stream_frames_device; one frame of any size: its size) --, zlib, and xz (the size: the sum of its Index records).
+static int open_device(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
+    if (!c || !d_src || !d_dst || !raw_len) return fail(c, PNA_E_INVAL, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    return decode_batch(c, algo, DecodeBatch{1, d_src, &src_off, &src_len, d_dst, &dst_off, &dst_cap, true, raw_len, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream});
+}
+extern "C" int pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
+    return open_device(c, PNA_ALGO_ZSTD, d_src, src_off, src_len, d_dst, dst_off, dst_cap, raw_len, hip_stream);
+}
+extern "C" int pna_gpu_inflate_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
+    return open_device(c, PNA_ALGO_DEFLATE, d_src, src_off, src_len, d_dst, dst_off, dst_cap, raw_len, hip_stream);
+}
+extern "C" int pna_gpu_xz_decompress_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
+    return open_device(c, PNA_ALGO_XZ, d_src, src_off, src_len, d_dst, dst_off, dst_cap, raw_len, hip_stream);
 }
 
 // The same for payloads in host memory (extract / verify of an archive read from disk).
-extern "C" int pna_gpu_decompress_batch(pna_gpu_ctx *c, int algo, size_t n, const void *const *src, const size_t *src_len,
-                                        void *const *dst, const size_t *raw_len) {
+extern "C" int pna_gpu_decompress_batch(pna_gpu_ctx *c, int algo, size_t n, const void *const *src, const size_t *src_len, void *const *dst, const size_t *raw_len) {
     if (!c || (n && (!src || !src_len || !dst || !raw_len))) return fail(c, PNA_E_INVAL, "null argument");
     if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !(algo == PNA_ALGO_XZ && xz_kernels_present())) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
     HIPCHK(c, hipSetDevice(c->device));
@@ -815,8 +819,7 @@ extern "C" int pna_gpu_decompress_batch(pna_gpu_ctx *c, int algo, size_t n, cons
     for (size_t i = 0; i < n; i++) { so[i] = sp; sl[i] = src_len[i]; sp = (sp + src_len[i] + 15) & ~(uint64_t)15; dof[i] = dp; rl[i] = raw_len[i]; dp = (dp + raw_len[i] + 15) & ~(uint64_t)15; }
     if (c->stage_in.ensure(sp + 64) || c->stage_out.ensure(dp + 64)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
     for (size_t i = 0; i < n; i++) if (src_len[i]) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->stage_in.p + so[i], src[i], src_len[i], hipMemcpyHostToDevice, c->stream));
-    int rc = pna_gpu_decompress_batch_device(c, algo, n, c->stage_in.p, so.data(), sl.data(), c->stage_out.p, dof.data(), rl.data(), nullptr);
-    if (rc) return rc;
+    const int rc = pna_gpu_decompress_batch_device(c, algo, n, c->stage_in.p, so.data(), sl.data(), c->stage_out.p, dof.data(), rl.data(), nullptr); if (rc) return rc;
     for (size_t i = 0; i < n; i++) if (raw_len[i]) HIPCHK(c, hipMemcpyAsync(dst[i], (uint8_t *)c->stage_out.p + dof[i], raw_len[i], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return PNA_OK;

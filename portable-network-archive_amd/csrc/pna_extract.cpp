@@ -566,19 +566,22 @@ static int xz_named_error(pna_gpu_ctx *c, int rc, const XStream &s, const std::s
     if (rc == PNA_E_INVAL || rc == PNA_E_UNSUPPORTED) c->err = stream_label(s) + ": " + reason;
     return rc;
 }
+// the entries of one codec that `pick` chooses, as the lists of a decode call: (pk_off, pay_len, raw_off, raw_size), and which entries they are
+struct SizedLists { std::vector<uint64_t> so, sl, dof, rl; std::vector<size_t> idx; };
+template <class Pick> static SizedLists gather_sized(const std::vector<XEntry> &ents, int algo, Pick pick) {
+    SizedLists l;
+    for (size_t i = 0; i < ents.size(); i++) {
+        const XEntry &e = ents[i];
+        if (e.compression == algo && e.has_size && pick(i)) { l.so.push_back(e.pk_off); l.sl.push_back(e.pay_len); l.dof.push_back(e.raw_off); l.rl.push_back(e.raw_size); l.idx.push_back(i); }
+    }
+    return l;
+}
 static int decode_sized(pna_gpu_ctx *c, const std::vector<XEntry> &ents, int slot, hipStream_t st) {
     for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE, PNA_ALGO_XZ}) {
-        std::vector<uint64_t> so, sl, dof, rl; std::vector<const XEntry *> who;
-        for (const XEntry &e : ents) if (e.compression == algo && e.has_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); who.push_back(&e); }
-        if (so.empty()) continue;
-        if (algo == PNA_ALGO_XZ) {
-            XzFail why;
-            const int rc = xz_decode_sized(c, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[slot].p, dof.data(), rl.data(), st, &why);
-            if (rc) return why.index < who.size() ? xz_named_error(c, rc, *who[why.index], why.reason) : rc;
-            continue;
-        }
-        const int rc = pna_gpu_decompress_batch_device(c, algo, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[slot].p, dof.data(), rl.data(), st);
-        if (rc) return rc;
+        const SizedLists l = gather_sized(ents, algo, [](size_t) { return true; });
+        XzFail why;
+        const int rc = decode_batch(c, algo, DecodeBatch{l.idx.size(), c->x_pk.p, l.so.data(), l.sl.data(), c->x_raw[slot].p, l.dof.data(), l.rl.data(), false, nullptr, nullptr, st}, &why);
+        if (rc) return why.index < l.idx.size() ? xz_named_error(c, rc, ents[l.idx[why.index]], why.reason) : rc;
     }
     return PNA_OK;
 }
@@ -592,7 +595,7 @@ static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::
         int rc = open_size(c, s.compression, c->x_pk.p, s.pk_off, s.pay_len, &m, st);
         if (rc) return s.compression == PNA_ALGO_XZ ? xz_named_error(c, rc, s, std::string(c->err)) : rc;      // (the measurement's text carries no stream number)
         XzFail why;
-        const uint64_t cap = m.size; const int exact = m.exact;
+        const uint64_t cap = m.size, at0 = 0; const int exact = m.exact;      // (at0: the stream is decoded into solid_plain[0 ..]; zstd plans its frames from the measurement)
         auto nomem = [&]() {
             char msg[192];
             snprintf(msg, sizeof msg, "%s: the stream decodes to %s%llu bytes, more than the device's free memory takes (with the decoder's workspace)", what,
@@ -600,9 +603,7 @@ static int decode_open(pna_gpu_ctx *c, const XStream &s, const char *what, std::
             return fail(c, PNA_E_NOMEM, msg);
         };
         if (c->solid_plain.ensure(cap + 8192)) return nomem();
-        rc = s.compression == PNA_ALGO_ZSTD ? zstd_open_decode_planned(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, m, &got, st)
-           : s.compression == PNA_ALGO_XZ   ? xz_open_decode(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, 0, cap, &got, st, &why)
-                                            : pna_gpu_inflate_open_device(c, c->x_pk.p, s.pk_off, s.pay_len, c->solid_plain.p, 0, cap, &got, st);
+        rc = decode_batch(c, s.compression, DecodeBatch{1, c->x_pk.p, &s.pk_off, &s.pay_len, c->solid_plain.p, &at0, &cap, true, &got, nullptr, st, &m}, &why);
         if (rc == PNA_E_NOMEM) return nomem();
         if (rc) return why.index == 0 ? xz_named_error(c, rc, s, why.reason) : rc;
         d = c->solid_plain.p;
@@ -869,17 +870,12 @@ static int window_verdicts(XCall &x, const WinSrc &a, size_t span, std::vector<X
 static int decode_sized_status(pna_gpu_ctx *c, const std::vector<XEntry> &ents, std::vector<uint32_t> &vs, std::vector<uint64_t> &size, std::vector<size_t> &retry,
                                hipStream_t st, uint64_t *streams = nullptr) {
     for (int algo : {PNA_ALGO_ZSTD, PNA_ALGO_DEFLATE, PNA_ALGO_XZ}) {
-        std::vector<uint64_t> so, sl, dof, rl; std::vector<size_t> idx;
-        for (size_t i = 0; i < ents.size(); i++) {
-            const XEntry &e = ents[i];
-            if (!vs[i] && !e.nodecode && e.compression == algo && e.has_size && !e.odd_size) { so.push_back(e.pk_off); sl.push_back(e.pay_len); dof.push_back(e.raw_off); rl.push_back(e.raw_size); idx.push_back(i); }
-        }
-        if (so.empty()) continue;
-        if (streams) *streams += so.size();
-        std::vector<uint32_t> es(so.size(), 0);
-        const int rc = decode_batch_status(c, algo, so.size(), c->x_pk.p, so.data(), sl.data(), c->x_raw[0].p, dof.data(), rl.data(), es.data(), st); if (rc) return rc;
-        for (size_t k = 0; k < idx.size(); k++) {
-            const size_t i = idx[k];
+        const SizedLists l = gather_sized(ents, algo, [&](size_t i) { return !vs[i] && !ents[i].nodecode && !ents[i].odd_size; });
+        if (streams) *streams += l.idx.size();
+        std::vector<uint32_t> es(l.idx.size(), 0);
+        const int rc = decode_batch(c, algo, DecodeBatch{l.idx.size(), c->x_pk.p, l.so.data(), l.sl.data(), c->x_raw[0].p, l.dof.data(), l.rl.data(), false, nullptr, es.data(), st}); if (rc) return rc;
+        for (size_t k = 0; k < l.idx.size(); k++) {
+            const size_t i = l.idx[k];
             if (es[k] == 0) size[i] = ents[i].raw_size;
             else if (es[k] == 2) vs[i] = PNA_VERIFY_UNSUPPORTED;
             else if (es[k] == 3) retry.push_back(i);                     // the stream does not hold fSIZ bytes: measured and decoded without it
