@@ -342,7 +342,19 @@ int  pna_gpu_create_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n
  *       block that ends early or late or leaves compressed bytes unused, a range coder that does not start with a zero byte or end at zero.
  *     A single block is a serial chain on one wave (measured: 1.8 - 2.8 MiB/s per block, profiles/xz_rate.txt); the gain is entries and blocks side by side.  There is no xz encoder.
  * Errors: PNA_E_INVAL for corrupt / mismatching streams (pna_gpu_last_error names the entry), PNA_E_UNSUPPORTED for
- * dictionaries and other algorithms. */
+ * dictionaries and other algorithms.
+ *
+ * PLACEMENT (pna_gpu_decompress_batch_device; the open decoders and pna_gpu_open_size_device below follow the same rules).  d_src and d_dst may be any device
+ * addresses, aligned or not: only d_src + src_off[i] and d_dst + dst_off[i] matter (the entry points fold a base's low four bits into the offsets).  src_off[i] and dst_off[i] may be ANY byte offsets: no alignment, no padding, no order is asked for.
+ * Stream i is the bytes [src_off[i], src_off[i] + src_len[i]) of d_src, its room the bytes [dst_off[i], dst_off[i] + raw_len[i]) of d_dst (an open decoder's:
+ * dst_cap bytes).  Streams may touch; rooms may touch and may come in any order, but must not overlap each other or the
+ * streams.  Nothing outside the rooms is written, whether the call succeeds or fails: not the bytes in front of a room that share an aligned word with its
+ * first byte, not the bytes behind it.  After a failed call the rooms' contents are unspecified; after an open decoder's success so are the bytes of its room
+ * behind the size it reports.  d_src is never written.  Reads: the decoders read outside a stream's own bytes, and ignore what they find there -- the
+ * aligned 4-byte words (of d_src) that hold a stream's first and last byte (zlib), and up to 15 bytes behind a stream's end (zstd: the backward bit readers
+ * open with two 8-byte loads from the first byte of a bit stream, which may be the last byte of a frame).  So the 15 bytes behind the end of the LAST stream
+ * in d_src must be readable memory of any content; nothing in front of the 16-byte group that holds the first stream's first byte is read.  (pna_gpu_decompress_batch stages its payloads at 16-byte strides
+ * with 64 bytes behind the last: more than is needed.) */
 int  pna_gpu_decompress_batch(pna_gpu_ctx *ctx, int algo, size_t n, const void *const *src, const size_t *src_len,
                               void *const *dst, const size_t *raw_len);
 int  pna_gpu_decompress_batch_device(pna_gpu_ctx *ctx, int algo, size_t n, const void *d_src, const uint64_t *src_off,
@@ -351,7 +363,9 @@ int  pna_gpu_decompress_batch_device(pna_gpu_ctx *ctx, int algo, size_t n, const
 
 /* A zstd stream whose decoded size is recorded nowhere (the SDAT stream of a solid entry).  Step 1 counts its frames; the caller
  * provides frames x 1 MiB of room (this library's segmentation) -- for ONE frame, as the reference writes it, any capacity it sees fit;
- * step 2 decodes and reports the size found (PNA_E_INVAL when the stream does not fit). */
+ * step 2 decodes and reports the size found (PNA_E_INVAL when the stream does not fit).  src_off and dst_off of the open decoders and of
+ * pna_gpu_open_size_device: any byte offsets, the room [dst_off, dst_off + dst_cap) alone is written, 15 readable bytes behind the stream -- PLACEMENT at
+ * pna_gpu_decompress_batch_device. */
 int  pna_gpu_zstd_stream_frames_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t src_off, uint64_t src_len, uint32_t *n_frames, void *hip_stream);
 int  pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *ctx, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off,
                                          uint64_t dst_cap, uint64_t *raw_len, void *hip_stream);
@@ -371,8 +385,9 @@ int  pna_gpu_xz_decompress_open_device(pna_gpu_ctx *ctx, const void *d_src, uint
  * counted: k_inflate's count pass, one wave per chunk between block starts) and for zstd frames that carry Frame_Content_Size (this library's);
  * *exact = 0: an upper bound -- a zstd frame without a content size (what the reference's solid writer emits) counts its raw and RLE blocks exactly and
  * each compressed block as Block_Maximum_Size (min(window, 128 KiB)).  The open decoders report the true size.  PNA_E_INVAL for bytes that are not a
- * well-formed stream (truncated, reserved block types, a content size its blocks contradict, a corrupt zlib block); no read leaves the stream's bytes (zlib:
- * its aligned 4-byte words).  PNA_E_UNSUPPORTED: zlib streams of 4 GiB of compressed bytes and more, or of more than 4 GiB of content, that have no dynamic or
+ * well-formed stream (truncated, reserved block types, a content size its blocks contradict, a corrupt zlib block); reads as stated under PLACEMENT at
+ * pna_gpu_decompress_batch_device (measuring reads the headers only: no read leaves the stream's bytes; zlib: its aligned 4-byte words); src_off is any byte offset
+ * and the result does not depend on it.  PNA_E_UNSUPPORTED: zlib streams of 4 GiB of compressed bytes and more, or of more than 4 GiB of content, that have no dynamic or
  * stored blocks to split them at (fixed-Huffman blocks only). */
 int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, int *exact, void *hip_stream);
 
@@ -670,6 +685,18 @@ typedef struct {
     uint32_t lz_units;                                   /* latency mode: workgroups (units) of the LZ stage's launch; 0: one per segment       */
 } pna_gpu_timing;
 int  pna_gpu_last_timing(const pna_gpu_ctx *ctx, pna_gpu_timing *out);
+
+/* Which forms of the decoders the latest decode call of the context ran (tests assert that the form they are about was not re-routed).
+ * zstd calls fill the first three fields, deflate calls the last three, xz calls none; the others are 0. */
+typedef struct {
+    uint64_t zstd_executor_frames;    /* frames executed by the parallel executor (option zexec_par_min_mib)                                  */
+    uint64_t zstd_workgroup_frames;   /* frames decoded by the one-workgroup kernel (zdec_serial, or frames the bounded pipeline could not take) */
+    uint64_t zstd_listed_entries;     /* entries whose frames were listed one by one (frames off this library's grid, skippable frames)        */
+    uint64_t inflate_lane_pieces;     /* pieces the lane-per-piece decoder walked (0: it did not run: fewer than 1 024 pieces, inflate_serial)  */
+    uint64_t inflate_lane_streams;    /* streams it decoded (the others took the wave-per-stream walk or the chunk decoder)                    */
+    uint64_t inflate_chunk_streams;   /* large foreign streams decoded in chunks between block starts found by trial                           */
+} pna_gpu_decode_forms;
+int  pna_gpu_last_decode_forms(const pna_gpu_ctx *ctx, pna_gpu_decode_forms *out);
 
 /* LZ-stage outputs of the last device batch for one block (tests compare them with the oracle's pna_lz_block).
  * seqs: packed u64 (off:20 | ml:18<<20 | ll:18<<38). Copies at most cap_* items; returns counts. */

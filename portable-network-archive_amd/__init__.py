@@ -57,6 +57,12 @@ class Timing(ctypes.Structure):
                 ("lz_match_launches", ctypes.c_uint64), ("blk_log", ctypes.c_uint32), ("lz_units", ctypes.c_uint32)]
 
 
+class DecodeForms(ctypes.Structure):
+    """pna_gpu_decode_forms (include/pna_gpu.h): which forms of the decoders the latest decode call ran."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("zstd_executor_frames", "zstd_workgroup_frames", "zstd_listed_entries", "inflate_lane_pieces",
+                                                "inflate_lane_streams", "inflate_chunk_streams")]
+
+
 ENC_NONE, ENC_AES, ENC_CAMELLIA = 0, 1, 2          # Encryption::to_byte()
 MODE_CBC, MODE_CTR, MODE_GCM = 0, 1, 2             # CipherMode::to_byte()
 
@@ -173,7 +179,7 @@ EXPORTS = [
     "pna_gpu_host_alloc", "pna_gpu_host_free", "pna_gpu_gather_ordered", "pna_gpu_gather_ordered_start", "pna_gpu_gather_wait", "pna_gpu_gather_ticket", "pna_gpu_gather_wait_for", "pna_gather_verdict", "pna_gather_offsets", "pna_gpu_last_error", "pna_gpu_strerror", "pna_gpu_bound", "pna_gpu_clamp_level",
     "pna_gpu_compress_batch", "pna_gpu_compress_batch_device", "pna_gpu_stream_new", "pna_gpu_stream_write",
     "pna_gpu_stream_flush", "pna_gpu_stream_finish", "pna_gpu_stream_abort", "pna_gpu_compress_solid",
-    "pna_gpu_last_timing", "pna_gpu_debug_block", "pna_gpu_debug_lz_stamps", "pna_bench_corpus_fill_device",
+    "pna_gpu_last_timing", "pna_gpu_last_decode_forms", "pna_gpu_debug_block", "pna_gpu_debug_lz_stamps", "pna_bench_corpus_fill_device",
     "pna_gpu_archive_bound", "pna_gpu_create_archive_device", "pna_gpu_create_archive_host", "pna_gpu_debug_crc_schedule", "pna_gpu_debug_pinned_bytes",
     "pna_gpu_solid_archive_bound", "pna_gpu_solid_archive_enc_bound", "pna_gpu_create_solid_archive_device", "pna_gpu_create_solid_archive_host",
     "pna_gpu_create_archive_part_device", "pna_gpu_decompress_batch", "pna_gpu_decompress_batch_device",
@@ -279,6 +285,8 @@ def load_library() -> ctypes.CDLL:
     L.pna_gpu_compress_solid.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, SINK_FN, vp]
     L.pna_gpu_last_timing.restype = ctypes.c_int
     L.pna_gpu_last_timing.argtypes = [vp, ctypes.POINTER(Timing)]
+    L.pna_gpu_last_decode_forms.restype = ctypes.c_int
+    L.pna_gpu_last_decode_forms.argtypes = [vp, ctypes.POINTER(DecodeForms)]
     L.pna_gpu_debug_block.restype = ctypes.c_int
     L.pna_gpu_debug_block.argtypes = [vp, u32, u64p, u32, ctypes.POINTER(u32), ctypes.c_char_p, u32, ctypes.POINTER(u32)]
     L.pna_gpu_debug_lz_stamps.restype = ctypes.c_int
@@ -632,6 +640,11 @@ class Context:
         t = Timing()
         self._check(self._L.pna_gpu_last_timing(self._h, ctypes.byref(t)))
         return t
+
+    def decode_forms(self) -> DecodeForms:
+        f = DecodeForms()
+        self._check(self._L.pna_gpu_last_decode_forms(self._h, ctypes.byref(f)))
+        return f
 
     def debug_block(self, block: int):
         """LZ-stage output of one block of the last device batch: (list of (ll, ml, off), literal bytes)."""

@@ -134,7 +134,7 @@ void k_inflate(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint
     const uint32_t lane = threadIdx.x, f = chunks ? chunk_frame : blockIdx.x, ck = blockIdx.x;
     const bool l0 = lane == 0, emit_on = !chunks || emit != 0;
     if (IF_U(frames[f].status)) return;
-    if (!chunks && mode && IF_U(mode[f]) != 1u) return;                    // lane-per-piece decode (or the chunk mode) took this stream (VM_SERIAL = 1)
+    if (!chunks && mode && IF_U(mode[f]) != VM_SERIAL) return;             // lane-per-piece decode (or the chunk mode) took this stream
     const uint64_t src_off = (uint64_t)IF_U((uint32_t)frames[f].src_off) | ((uint64_t)IF_U((uint32_t)(frames[f].src_off >> 32)) << 32);
     const uint64_t dst_off = (uint64_t)IF_U((uint32_t)frames[f].dst_off) | ((uint64_t)IF_U((uint32_t)(frames[f].dst_off >> 32)) << 32);
     if (!chunks && IF_U((uint32_t)(frames[f].src_len >> 32)) | IF_U((uint32_t)(frames[f].dst_len >> 32))) {   // the whole-stream walk counts in 32 bits: streams of 4 GiB and more are decoded
@@ -618,7 +618,6 @@ void launch_ispec(const uint8_t *src, uint64_t src_off, uint64_t src_len, uint32
 // intermediate form as k_inflate -- literal bytes + (literal run, match length, distance + 3) records, one ZBlock per piece; k_zoff /
 // k_zexec / the Adler kernels run unchanged.
 constexpr uint32_t VI_LDS = 320 * 64 * 2;                               // 40 KiB per wave: four waves (one per SIMD) share a CU
-enum { VM_PIECES = 0, VM_SERIAL = 1 };
 
 struct VPiece { uint32_t frame, j; };
 

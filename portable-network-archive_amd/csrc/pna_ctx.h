@@ -319,6 +319,7 @@ struct pna_gpu_ctx {
     bool corpus_ready = false;
     std::string err;
     pna_gpu_timing timing = {};
+    pna_gpu_decode_forms forms = {};                // which forms of the decoders the latest decode call ran (pna_gpu_last_decode_forms)
     uint32_t last_nblk = 0;
     uint32_t plan_log = PNA_BLK_LOG;                // block size the current call's sub-batches are planned with (plan_call)
     size_t max_blocks = (size_t)1 << 17;            // blocks per sub-batch: what ~96 GiB of per-block workspace hold at that block size (16 GiB of input at 128 KiB)

@@ -241,7 +241,7 @@ struct InflateRun {
             c->z_mode.ensure(n * 4 + 8 + (lanes ? (size_t)n * scan_g * 4 : 0)) ||
             (lanes && (c->z_vp.ensure(vp.size() * 8 + 8) || c->z_pb.ensure((nblk + n) * 8 + 8))))
             return fail(c, PNA_E_NOMEM, "decoder workspace");
-        modes.assign(n, 1u);                                           // 1 = the wave-per-stream walk's (VM_SERIAL); the lane-per-piece decoder decides for itself when it runs
+        modes.assign(n, (uint32_t)VM_SERIAL);                          // the wave-per-stream walk's; the lane-per-piece decoder decides for itself when it runs
         if (!lanes) HIPCHK(c, hipMemcpyAsync(c->z_mode.p, modes.data(), n * 4, hipMemcpyHostToDevice, b.st));
         HIPCHK(c, hipMemcpyAsync(c->z_frames.p, frs.data(), n * sizeof(ZFrame), hipMemcpyHostToDevice, b.st));
         HIPCHK(c, hipMemcpyAsync(c->z_fx.p, fxs.data(), n * sizeof(ZFrameX), hipMemcpyHostToDevice, b.st));
@@ -259,7 +259,7 @@ struct InflateRun {
         if (lanes) { HIPCHK(c, hipMemcpyAsync(modes.data(), c->z_mode.p, b.n * 4, hipMemcpyDeviceToHost, b.st)); HIPCHK(c, hipStreamSynchronize(b.st)); }
         for (size_t k = 0; k < cand.size(); k++) {
             const uint32_t i = cand[k];
-            if (modes[i] != 1u) continue;                              // this library's layout: the lane-per-piece decoder has it
+            if (modes[i] != VM_SERIAL) continue;                              // this library's layout: the lane-per-piece decoder has it
             ZFrameX xs = fxs[i];
             xs.blk_base = (uint32_t)cand_base[k]; xs.blk_cap = (uint32_t)((b.src_len[i] + SPEC_CHUNK - 1) / SPEC_CHUNK); xs.nblk = 0; xs.pad = 0;
             HIPCHK(c, hipMemcpyAsync(zfx(c) + i, &xs, sizeof xs, hipMemcpyHostToDevice, b.st));
@@ -267,7 +267,7 @@ struct InflateRun {
             const int rcs = inflate_spec_stream(c, i, frs[i], xs, b.d_src, b.st, &m, &ok, b.open, &olen, &reason); if (rcs) return rcs;
             if (!ok && (b.src_len[i] > 0xFFFFFFFFull || b.raw_len[i] > 0xFFFFFFFFull)) return big_unsplit(c, b.src_len[i], reason);   // (the serial walk counts in 32 bits)
             if (ok) {
-                xs.nblk = m; xs.pad = 1; HIPCHK(c, poke32((uint32_t *)c->z_mode.p + i, 3u, b.st));   // (3, not 1: the serial walk leaves the stream alone)
+                xs.nblk = m; xs.pad = 1; HIPCHK(c, poke32((uint32_t *)c->z_mode.p + i, VM_CHUNKS, b.st));   // (not VM_SERIAL: the serial walk leaves the stream alone)
                 if (b.open) {                                           // the size found: what the serial walk reports through ZFrame::dst_len
                     frs[i].dst_len = olen;
                     HIPCHK(c, hipMemcpyAsync(&zframes(c)[i].dst_len, &frs[i].dst_len, 8, hipMemcpyHostToDevice, b.st));
@@ -303,11 +303,14 @@ struct InflateRun {
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(c->ev[1], b.st));
         HIPCHK(c, hipMemcpyAsync(frs.data(), c->z_frames.p, b.n * sizeof(ZFrame), hipMemcpyDeviceToHost, b.st));
+        if (lanes) HIPCHK(c, hipMemcpyAsync(modes.data(), c->z_mode.p, b.n * 4, hipMemcpyDeviceToHost, b.st));   // (which streams the lane-per-piece decoder kept: pna_gpu_last_decode_forms says how many)
         HIPCHK(c, hipStreamSynchronize(b.st));                          // (frs is written by the copy above until then)
         float ms = 0, ms_h = 0, ms_x = 0;
         (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]); (void)hipEventElapsedTime(&ms_h, c->ev[0], c->ev[2]); (void)hipEventElapsedTime(&ms_x, c->ev[2], c->ev[3]);
         c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms; c->timing.ms_stats = ms_h; c->timing.ms_lit = ms_x;   // total, Huffman walk, execution
         c->timing.lz_match_launches = spec.size();                      // (decode calls: the large foreign streams that went through the chunk decoder)
+        c->forms = pna_gpu_decode_forms{}; c->forms.inflate_chunk_streams = spec.size();
+        if (lanes) { c->forms.inflate_lane_pieces = vp.size(); for (uint32_t m : modes) c->forms.inflate_lane_streams += m == VM_PIECES; }
         return PNA_OK;
     }
     // what the caller gets: verdict mode -- every stream's own status, no call-level failure --, or the first bad stream as the call's failure; the sizes found
@@ -448,6 +451,7 @@ static int xz_decode_device(pna_gpu_ctx *c, const DecodeBatch &b, XzFail *why) {
         (void)hipEventElapsedTime(&ms_dec, c->ev[3], c->ev[1]);
         for (size_t i = 0; i < n; i++) if (!status[i]) status[i] = dev[i];
     }
+    c->forms = pna_gpu_decode_forms{};
     c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms_scan + ms_dec; c->timing.ms_stats = ms_scan; c->timing.ms_lit = ms_dec;   // the xz kernels, the first scan, the rest
     if (b.ent_status) for (size_t i = 0; i < n; i++) b.ent_status[i] = status[i];
     for (size_t i = 0; i < n && !b.ent_status; i++)
@@ -500,10 +504,14 @@ int pna::open_size(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off
     return PNA_OK;
 }
 
+// A caller's base address, aligned or not, as a 16-byte aligned base and what its low bits add to every offset: the kernels take their aligned words and
+// groups from base + offset, some from the offset alone (k_inflate), some from the address (k_zhuf, k_zx_emit) -- with an aligned base the two agree.
+template <class T> static uint64_t fold_base(T *&p) { const uint64_t m = (uint64_t)((uintptr_t)p & 15u); p = (T *)((uintptr_t)p - m); return m; }
 extern "C" int pna_gpu_open_size_device(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, uint64_t *size, int *exact, void *hip_stream) {
     if (!c || (!d_src && src_len) || !size || !exact) return fail(c, PNA_E_INVAL, "null argument");
     *size = 0; *exact = 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (d_src) src_off += fold_base(d_src);
     OpenSize m;
     const int rc = open_size(c, algo, d_src, src_off, src_len, &m, hip_stream ? (hipStream_t)hip_stream : c->stream); if (rc) return rc;
     *size = m.size; *exact = m.exact;
@@ -589,6 +597,7 @@ struct ZstdRun {
     std::vector<ZFrame> frs;                                         // the frames as the device has them, read back
     uint64_t nfr = 0, nblk_cap = 0, nslot = 0, nseq_cap = 0, out_span = 0;
     std::vector<uint32_t> big;                                       // large frames: parsed side by side, executed by the parallel executor
+    uint64_t n_par = 0, n_fallback = 0;                              // frames the parallel executor executed, frames the one-workgroup kernel decoded: pna_gpu_last_decode_forms
     // host arithmetic: frames per entry, every frame's share of the workspace, the batch limits
     int plan() {
         ents.resize(b.n);
@@ -692,6 +701,7 @@ struct ZstdRun {
             if (frs[f].status) continue;
             uint32_t zst = 0;
             rc = exec_par_frame(c, ZxFrame{frs[f].dst_off, frs[f].dst_len, fxd[f].blk_base, fxd[f].nblk, 0, 0}, b.d_src, b.d_dst, b.st, &zst, "parallel frame execution failed"); if (rc) return rc;
+            n_par += zst == 0;
             if (zst) HIPCHK(c, poke32(&zframes(c)[f].status, zst == 2 ? 2u : 1u, b.st));   // 2: the serial kernel takes the frame (it decodes from the source again); 3: corrupt
         }
         launch_zxxh(zframes(c), (uint32_t)nfr, src, dst, b.st);
@@ -709,6 +719,7 @@ struct ZstdRun {
                 return fail(c, PNA_E_UNSUPPORTED, msg);
             }
         if (fb.empty()) return PNA_OK;
+        n_fallback = fb.size();
         std::vector<ZFrame> sub(fb.size());
         for (size_t k = 0; k < fb.size(); k++) { sub[k] = frs[fb[k]]; sub[k].status = 0; sub[k].out_len = 0; }
         if (b.open)                                                   // the frame that closes a stream of unknown size keeps its flag
@@ -735,6 +746,8 @@ struct ZstdRun {
         HIPCHK(c, hipStreamSynchronize(b.st));
         float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
         c->timing = pna_gpu_timing{}; c->timing.ms_lz = ms;            // decoder time reported in the first stage slot
+        pna_gpu_decode_forms forms{}; forms.zstd_executor_frames = n_par; forms.zstd_workgroup_frames = n_fallback;   // (the frame list below runs decode calls of its own)
+        c->forms = forms;
         std::vector<uint64_t> foreign_len(n, ~0ull);                  // entries that went through zstd_decode_foreign: the bytes they produced
         const pna_gpu_timing outer_timing = c->timing;                // (the foreign path runs decode calls of its own: this call's timing stays what it measured)
         if (b.ent_status) for (size_t i = 0; i < n; i++) b.ent_status[i] = 0;
@@ -745,7 +758,7 @@ struct ZstdRun {
                     // not one of the two shapes k_zscan places (or a frame of the grid walk did not hold its MiB): the payload's frames as they are
                     uint64_t got = 0; bool mism = false;
                     const int rcf = zstd_decode_foreign(c, b, i, &got, b.ent_status ? &mism : nullptr);
-                    c->timing = outer_timing;
+                    c->timing = outer_timing; forms.zstd_listed_entries++; c->forms = forms;
                     if (rcf && b.ent_status && (rcf == PNA_E_INVAL || rcf == PNA_E_UNSUPPORTED)) { b.ent_status[i] = rcf == PNA_E_UNSUPPORTED ? 2u : (mism ? 3u : 1u); break; }
                     if (rcf) return rcf;
                     foreign_len[i] = got; break;
@@ -790,6 +803,9 @@ extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t 
     if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !(algo == PNA_ALGO_XZ && xz_kernels_present())) return fail(c, PNA_E_UNSUPPORTED, "only zstd and deflate streams are decoded on the device");
     if (!n) return PNA_OK;
     HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint64_t> so, dof;                                    // (only for a base that is not 16-byte aligned)
+    if (const uint64_t m = fold_base(d_src)) { so.assign(src_off, src_off + n); for (uint64_t &v : so) v += m; src_off = so.data(); }
+    if (const uint64_t m = fold_base(d_dst)) { dof.assign(dst_off, dst_off + n); for (uint64_t &v : dof) v += m; dst_off = dof.data(); }
     return decode_batch(c, algo, DecodeBatch{n, d_src, src_off, src_len, d_dst, dst_off, raw_len, false, nullptr, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream});
 }
 // One stream whose decoded size is recorded nowhere (entries without fSIZ, solid streams), decoded into dst_cap bytes of room; the size found is reported (PNA_E_INVAL when it does
@@ -797,6 +813,7 @@ extern "C" int pna_gpu_decompress_batch_device(pna_gpu_ctx *c, int algo, size_t 
 static int open_device(pna_gpu_ctx *c, int algo, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {
     if (!c || !d_src || !d_dst || !raw_len) return fail(c, PNA_E_INVAL, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
+    src_off += fold_base(d_src); dst_off += fold_base(d_dst);
     return decode_batch(c, algo, DecodeBatch{1, d_src, &src_off, &src_len, d_dst, &dst_off, &dst_cap, true, raw_len, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream});
 }
 extern "C" int pna_gpu_zstd_decompress_open_device(pna_gpu_ctx *c, const void *d_src, uint64_t src_off, uint64_t src_len, void *d_dst, uint64_t dst_off, uint64_t dst_cap, uint64_t *raw_len, void *hip_stream) {

@@ -249,6 +249,7 @@ __host__ __device__ inline uint64_t zrec_pack(uint32_t ll, uint32_t ml, uint64_t
 __host__ __device__ inline uint32_t zrec_ll(uint64_t s) { return (uint32_t)(s & 0x3FFFF); }
 __host__ __device__ inline uint32_t zrec_ml(uint64_t s) { return (uint32_t)((s >> 18) & 0x3FFFF); }
 __host__ __device__ inline uint32_t zrec_of(uint64_t s) { return (uint32_t)(s >> 36); }
+enum { VM_PIECES = 0, VM_SERIAL = 1, VM_CHUNKS = 3 };   // who decodes a zlib stream (k_inflate.hip, pna_decode.cpp): the lane-per-piece decoder, the wave-per-stream walk, the chunk decoder
 constexpr uint32_t ZF_OPEN = 0x80000000u;   // ZFrame.out_len on input: dst_len is a capacity, the decoder writes the size it found back to dst_len
 
 } // namespace pna

@@ -189,6 +189,10 @@ extern "C" int pna_gpu_last_timing(const pna_gpu_ctx *c, pna_gpu_timing *out) {
     if (!c || !out) return PNA_E_INVAL;
     *out = c->timing; out->blk_log = c->last_blk_log; out->lz_units = c->last_units; return PNA_OK;
 }
+extern "C" int pna_gpu_last_decode_forms(const pna_gpu_ctx *c, pna_gpu_decode_forms *out) {
+    if (!c || !out) return PNA_E_INVAL;
+    *out = c->forms; return PNA_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // ---- CRC-32 tables of the framing kernel (k_frame.hip explains the algebra)
