@@ -35,7 +35,8 @@ extern "C" {
 #define PNA_ALGO_STORE    0
 #define PNA_ALGO_DEFLATE  1
 #define PNA_ALGO_ZSTD     2
-#define PNA_ALGO_XZ       4     /* == Compression::XZ.to_byte(); DECODE ONLY (every compress entry point answers PNA_E_UNSUPPORTED) */
+#define PNA_ALGO_XZ       4     /* == Compression::XZ.to_byte(); decoded everywhere; WRITTEN only with option "xz_encode" = 1, by pna_gpu_compress_batch[_device] and the
+                                 * non-solid archive entry points (below: "XZ ON THE WRITE SIDE"); without the option every compress entry point answers PNA_E_UNSUPPORTED */
 
 /* encoder feature bits (pna_gpu_init flags, low byte); default = all of them */
 #define PNA_F_HUF   1u
@@ -117,6 +118,9 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
  *   "lazy2" [PNA_LAZY2]                   how far a start looks ahead before it is taken, beyond the next position: 2 (default), 1, 0
  *   "strong_gtab" [PNA_STRONG_GTAB]       zstd levels 10..22 with the hash table in global memory (1, default) or in LDS (0)
  *   "lit_beside_seq" [PNA_LIT_BESIDE_SEQ] large zstd batches: the literal coder on a second stream next to the sequence coder (1, default)
+ *   "xz_encode" [PNA_XZ_ENCODE]           0 (default): PNA_ALGO_XZ is PNA_E_UNSUPPORTED on every compress entry point; 1: the batch and the non-solid archive entry points write
+ *                                         xz.  An option because these streams are multi-block with per-chunk state resets: their bytes differ from the reference's encoder
+ *                                         (one block, one running model) and their ratio is lower -- a host chooses that knowingly ("XZ ON THE WRITE SIDE" below)
  *   "max_chunk_size" [PNA_MAX_CHUNK_SIZE] (FDAT chunk size of the entry points without such a parameter), "sub_mib" [PNA_SUB_MIB], "stage_threads" [PNA_STAGE_THREADS],
  *   "diff_slot_mib" [PNA_DIFF_SLOT_MIB]   pna_gpu_diff_archive_host: MiB of each of the two page-locked (and two device) slots the files' bytes travel through (256)
  *   "extract_win_mib" [PNA_EXTRACT_WIN_MIB], "batch_piece_mib" [PNA_BATCH_PIECE_MIB], "inflate_serial" [PNA_INFLATE_SERIAL],
@@ -124,12 +128,13 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
 int  pna_gpu_set_option(pna_gpu_ctx *ctx, const char *name, long value);
 const char *pna_gpu_strerror(int code);
 
-/* Worst-case compressed size of one entry (zstd: ZSTD_compressBound-like; zlib: deflateBound-like). */
+/* Worst-case compressed size of one entry (zstd: ZSTD_compressBound-like; zlib: deflateBound-like; xz: every chunk stored -- 3 bytes per 8 KiB, the smallest
+ * LZ block --, 24 bytes per 1 MiB block (header, end marker, padding, CRC64), 8 per Index record, 32 + the record count for stream header, Index framing and footer). */
 size_t pna_gpu_bound(int algo, size_t src_len);
 
 /* Level mapping of the reference, restated so callers can pass CompressionLevel values through unchanged:
  * lib/src/compress/zstandard.rs:43-57 (Default -> 3, clamp to min..max) and lib/src/compress/deflate.rs:89-101
- * (Default -> 6, clamp 0..9).  `level` < 0 with level == PNA_LEVEL_DEFAULT means default. */
+ * (Default -> 6, clamp 0..9), lib/src/compress/xz.rs:36-46 (Default -> 6, clamp 0..9).  `level` < 0 with level == PNA_LEVEL_DEFAULT means default. */
 /* The encoder has these parameter sets behind that scale ("Level sets"):
  *   stored   deflate 0 = Compression::none(): stored blocks only (zlib header 78 01)
  *   fast     zstd < 0 and 1, deflate 1..3: every position in the table, lazy deferral, look-back = the LDS window
@@ -137,9 +142,34 @@ size_t pna_gpu_bound(int algo, size_t src_len);
  *   default  zstd 0 and 3..5: light + a third adoption round (up to 7 positions back) and two-step lazy deferral;  deflate 4..8: even-position table,
  *            adoption, lazy deferral over three positions
  *   high     zstd 6..9: default on a 16 KiB window with 55 206 slots;  deflate 9: + the third adoption round and two-step lazy deferral
- *   max      zstd 10..22: + the hash table in global memory, 2^19 slots per segment */
+ *   max      zstd 10..22: + the hash table in global memory, 2^19 slots per segment
+ * xz runs zstd's LZ stage with matches of at most 273 bytes: xz 0 = the fast set (zstd 1), 1..3 = the default set (zstd 3), 4..6 = the high set (zstd 6..9),
+ * 7..9 = the max set (zstd 10..22). */
 #define PNA_LEVEL_DEFAULT  (-1000)
 int  pna_gpu_clamp_level(int algo, int level);
+
+/* XZ ON THE WRITE SIDE (option "xz_encode" = 1; the reference: XzEncoder::new(writer, level), lib/src/entry/write.rs:257-263).  Every stream is one that stock
+ * liblzma decodes; its bytes are NOT liblzma's:
+ *   per entry   one .xz stream: stream header (check = CRC64, liblzma's default), one block per 1 MiB segment of the entry, the Index, the stream footer; an empty
+ *               entry is the 32-byte stream without a block.
+ *   per block   a 12-byte header without size fields, one filter: LZMA2, dictionary-size byte 16 (1 MiB: the LZ stage never looks back beyond its segment); the
+ *               chunks, the 0x00 end marker, padding to 4, the CRC64 of the segment's input bytes.
+ *   per chunk   one LZMA2 chunk per LZ block of at most 64 KiB (option "blk_log": at most 16 here; a batch whose longest entry is shorter takes the power of two
+ *               that holds it, 8 KiB at least; a batch in LATENCY MODE takes zstd's blocks there, 16 KiB up to 32 MiB of input and 32 KiB beyond -- a chunk is one
+ *               serial chain --, but whole segments: the LZ stage's units are not used).  Every LZMA chunk resets the state and carries the properties lc 3, lp 0, pb 2 (control 0xE0 for a block's first
+ *               chunk, 0xC0 for the others); the dictionary is reset at a block's start only, so matches reach back over the segment's earlier chunks.  A chunk
+ *               whose LZMA form with its 6-byte header would not be smaller than its input with the 3-byte header of an uncompressed chunk is written as
+ *               the latter (0x01 at a block's start, 0x02 elsewhere): no chunk takes more than its input + 3 bytes, which pna_gpu_bound relies on.  Match lengths are at
+ *               most 273; a distance among the chunk's four latest is coded as a repeat.  The parse is the LZ stage's (greedy / lazy), not an optimal one.
+ *   That independence of the chunks is the parallelism (one wave per chunk, k_xzenc.hip), and what it costs in ratio.
+ * Entry points that take PNA_ALGO_XZ with the option: pna_gpu_compress_batch, pna_gpu_compress_batch_device, pna_gpu_create_archive_device and its _part, _enc,
+ *   _meta and _chunked forms, pna_gpu_create_archive_host and its _enc, _meta, _chunked and _part forms (FHED compression byte 4; the cipher stage and the chunk
+ *   cut work on payload bytes).  An entry is always coded inside one sub-batch -- its Index is sized over all its blocks --, so an entry whose workspace (about
+ *   3.5 bytes per input byte) cannot be allocated fails with PNA_E_NOMEM instead of being cut; pna_gpu_last_error then names this limit, the sub-batch's and its
+ *   longest entry's input bytes and the workspace they need.
+ * PNA_E_UNSUPPORTED with or without the option: the solid entry points (pna_gpu_create_solid_archive_*), pna_gpu_compress_solid, the streaming facade
+ *   (pna_gpu_stream_*) and pna_gpu_stream_entry_*; xz blocks smaller than a segment, other lc / lp / pb, an optimal parse: not built.
+ * pna_gpu_last_timing of an xz call: ms_lz the LZ stage, ms_stats the CRC64 kernel, ms_lit the chunk coder, ms_seq sizes and offsets. */
 
 /* ---- batch of independent entries: the data-parallel fan-out of spawn_entry_results()/create_entry()
  * (cli/src/command/core.rs:496-537,915-977).  Entry i becomes one independent stream in dst[i]
@@ -340,7 +370,8 @@ int  pna_gpu_create_archive_host(pna_gpu_ctx *ctx, int algo, int level, size_t n
  *       lc + lp <= 4.  Corrupt (PNA_E_INVAL): control bytes 0x03 .. 0x7F, a first chunk that does not reset the dictionary, a first LZMA chunk without
  *       properties, a match distance beyond min(dictionary size, bytes produced since the dictionary reset), an end-of-payload marker, a chunk or
  *       block that ends early or late or leaves compressed bytes unused, a range coder that does not start with a zero byte or end at zero.
- *     A single block is a serial chain on one wave (measured: 1.8 - 2.8 MiB/s per block, profiles/xz_rate.txt); the gain is entries and blocks side by side.  There is no xz encoder.
+ *     A single block is a serial chain on one wave (measured: 1.8 - 2.8 MiB/s per block, profiles/xz_rate.txt); the gain is entries and blocks side by side.
+ *     (Streams this library writes -- XZ ON THE WRITE SIDE -- carry one block per MiB, so they are read in parallel.)
  * Errors: PNA_E_INVAL for corrupt / mismatching streams (pna_gpu_last_error names the entry), PNA_E_UNSUPPORTED for
  * dictionaries and other algorithms.
  *

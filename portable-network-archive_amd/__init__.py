@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("PNA_GPU_LIB") or os.path.join(_HERE, "libpna_gpu.so")
 
 PNA_OK = 0
 ALGO_STORE, ALGO_DEFLATE, ALGO_ZSTD = 0, 1, 2
-ALGO_XZ = 4                                                      # Compression::XZ: decode only (decompress_batch, open_size_device, xz_open_device, the read-side drivers)
+ALGO_XZ = 4                                                      # Compression::XZ: decoded everywhere; written by compress_batch* and the non-solid create_archive* on a context with set_option("xz_encode", 1)
 LEVEL_DEFAULT = -1000
 # error codes of include/pna_gpu.h
 E_NODEVICE, E_INVAL, E_NOMEM, E_DSTSIZE, E_HIP, E_SINK, E_UNSUPPORTED = -1, -2, -3, -4, -5, -6, -7
@@ -393,7 +393,7 @@ def bound(algo: int, n: int) -> int:
 
 
 def clamp_level(algo: int, level: int = LEVEL_DEFAULT) -> int:
-    """From<CompressionLevel> mappings -- compress/zstandard.rs:43-57, compress/deflate.rs:89-101."""
+    """From<CompressionLevel> mappings -- compress/zstandard.rs:43-57, compress/deflate.rs:89-101, compress/xz.rs:36-46."""
     return load_library().pna_gpu_clamp_level(algo, level)
 
 

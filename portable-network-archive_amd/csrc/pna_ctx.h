@@ -78,6 +78,13 @@ __attribute__((weak)) void launch_xzscan(const void *streams, uint32_t n, const 
 __attribute__((weak)) void launch_lzma2(XzBlock *blocks, uint32_t nblk, const uint8_t *src, uint8_t *dst, uint32_t lclp, hipStream_t st);
 __attribute__((weak)) void launch_xzcheck(const void *pieces, uint32_t npieces, const XzBlock *blocks, uint32_t nblk, const uint8_t *src, const uint8_t *dst, uint64_t *acc,
                                           uint32_t *stream_status, hipStream_t st);
+// Compression::XZ on the write side (k_xzenc.hip; weak like the decoder's: the sanitizer build has no stand-ins for them, and without them PNA_ALGO_XZ stays unsupported
+// on the compress entry points).  max_seg: the longest segment's bytes; work: 2 * nseg 64-bit words (the blocks' unpadded sizes, the CRC64 accumulators)
+__attribute__((weak)) void launch_xzenc_stage(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint32_t max_seg, const uint32_t *blk_seg, uint32_t nblk, const uint64_t *seqs, BlkInfo *blk,
+                                              uint8_t *scratch, uint64_t *work, uint64_t *seg_size, uint64_t *seg_off, hipStream_t st, hipEvent_t *ev);
+__attribute__((weak)) void launch_xzenc_write(const uint8_t *src, const SegDesc *segs, const uint32_t *blk_seg, uint32_t nblk, const BlkInfo *blk, const uint64_t *seg_off,
+                                              const uint64_t *seg_size, const uint8_t *scratch, const uint64_t *work, uint32_t nseg, const uint32_t *entry_seg, uint32_t nentry,
+                                              uint8_t *dst, hipStream_t st, bool small_blocks);
 inline bool xz_kernels_present() { return launch_xzscan && launch_lzma2 && launch_xzcheck; }
 // pna_decode.cpp: which stream of an xz decode call failed and why (the call's error text is "entry <index>: <reason>"), for a caller that knows its streams by name
 struct XzFail { size_t index = ~(size_t)0; std::string reason; };
@@ -239,6 +246,7 @@ struct Tuning {
     long dev_layout = 1;             // PNA_DEV_LAYOUT: archive layout of plain one-chunk entries on the device (k_layout); 0: on the host, after a wait for the sizes
     long trace = 0;                  // PNA_TRACE: phase times of the host pipelines on stderr
     long d2h_wgs = 6;                // PNA_D2H_WGS: workgroups of the kernel that carries a sub-batch's archive bytes to the host (0: the copy engine / runtime's choice)
+    long xz_encode = 0;              // PNA_XZ_ENCODE: 1: pna_gpu_compress_batch[_device] and the non-solid archive entry points take PNA_ALGO_XZ (k_xzenc.hip: multi-block streams with per-chunk state resets -- their bytes differ from the reference's encoder and their ratio is lower, so a host chooses them knowingly); 0 (default): PNA_E_UNSUPPORTED, as before
     long hist_by_block = -1;         // PNA_HIST_BY_BLOCK: zstd entropy stage in its per-block form (1: k_hist, k_seqa, k_seqb) or its per-segment form (0: k_stats, k_seq); -1: by batch size
 };
 struct TuningName { const char *name, *env; long Tuning::*field; long lo, hi; };
@@ -258,6 +266,7 @@ struct pna_gpu_ctx {
     bool call_lazy3 = false;
     bool call_lazy2 = false;                         // two-step lazy deferral (FLAG_LAZY2 of the LZ kernels)
     uint32_t n_cus = 256;                           // compute units of the device (hipDeviceProp_t::multiProcessorCount): a full round of one-workgroup-per-CU kernels
+    bool call_xz = false;                           // the current call writes xz: LZ blocks of at most 64 KiB (one LZMA2 chunk each), matches of at most 273 bytes
     bool call_stored = false;                       // deflate level 0: stored blocks only (Compression::none())
     bool call_strong2 = false;                      // ... the high / max sets' fourth adoption round and 15 back bytes (FLAG_STRONG2: zstd 4 .. 22 on the packed 16 KiB geometry or the global table)
     uint32_t *lzp_hist = nullptr; bool lzp_hist_all = false;   // the current sub-batch: the counters the parse kernel adds the sequence codes to (null: none), and whether EVERY segment's parse did
@@ -383,6 +392,10 @@ struct GcmCallKeys { uint8_t kc[32], phsf_hash[32]; };
 inline uint32_t gcm_seg_size(const pna_gpu_cipher *ci) { return ci->gcm_segment_size ? ci->gcm_segment_size : (1u << 20); }
 
 void set_call_level(pna_gpu_ctx *c, int algo, int level);
+// what the compress entry points take: zstd, deflate and -- with option xz_encode, on the batch and the non-solid archive entry points -- xz
+inline bool encode_algo_ok(const pna_gpu_ctx *c, int algo) {
+    return algo == PNA_ALGO_ZSTD || algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_XZ && c && c->tun.xz_encode != 0 && launch_xzenc_stage && launch_xzenc_write);
+}
 inline size_t plan_blocks(const pna_gpu_ctx *c, uint64_t len) {
     return (size_t)((len + ((uint64_t)1 << c->plan_log) - 1) >> c->plan_log);
 }
@@ -402,8 +415,9 @@ struct CallTotalScope {
     CallTotalScope(const CallTotalScope &) = delete; CallTotalScope &operator=(const CallTotalScope &) = delete;
 };
 inline uint32_t blk_log_for_longest(const pna_gpu_ctx *c, uint64_t mx) {
-    if (c->tun.blk_log) return (uint32_t)c->tun.blk_log;
-    if (mx > 65536) return PNA_BLK_LOG;
+    const uint32_t cap = c->call_xz ? std::min<uint32_t>(16u, PNA_BLK_LOG) : (uint32_t)PNA_BLK_LOG;     // (xz: an LZ block is one LZMA2 chunk, 64 KiB at most)
+    if (c->tun.blk_log) return std::min<uint32_t>((uint32_t)c->tun.blk_log, cap);
+    if (mx > 65536) return cap;
     uint32_t lg = BLK_LOG_MIN;
     while (((uint64_t)1 << lg) < mx) lg++;
     return lg;

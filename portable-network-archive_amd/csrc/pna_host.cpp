@@ -2,6 +2,7 @@
 // device-resident entry points); the host pipelines, the read side and the streaming facade live in pna_pipeline.cpp, pna_extract.cpp, pna_decode.cpp and
 // pna_stream.cpp, what they share in pna_ctx.h.
 #include "pna_ctx.h"
+#include "xz_enc_core.h"
 static const TuningName TUNING_NAMES[] = {
     {"lz_split", "PNA_LZ_SPLIT", &Tuning::lz_split, 0, 2}, {"lz_split_blocks", "PNA_LZ_SPLIT_BLOCKS", &Tuning::lz_split_blocks, 8, 1 << 17},
     {"lz_split_min", "PNA_LZ_SPLIT_MIN", &Tuning::lz_split_min, 0, 1 << 30}, {"lz_pbuf_fail", "PNA_LZ_PBUF_FAIL", &Tuning::lz_pbuf_fail, 0, 1},
@@ -12,6 +13,7 @@ static const TuningName TUNING_NAMES[] = {
     {"blk_log", "PNA_BLK_LOG", &Tuning::blk_log, 0, PNA_BLK_LOG}, {"unit_log", "PNA_LZ_UNIT_LOG", &Tuning::unit_log, 0, 20},
     {"latency_max_mib", "PNA_LATENCY_MAX_MIB", &Tuning::latency_max_mib, 0, 1 << 20}, {"hist_by_block", "PNA_HIST_BY_BLOCK", &Tuning::hist_by_block, -1, 1},
     {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"mtile", "PNA_MTILE", &Tuning::mtile, 0, 2048}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
+    {"xz_encode", "PNA_XZ_ENCODE", &Tuning::xz_encode, 0, 1},
 };
 
 extern "C" const char *pna_gpu_strerror(int code) {
@@ -127,6 +129,8 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
 
 extern "C" size_t pna_gpu_bound(int algo, size_t n) {
     if (algo == PNA_ALGO_STORE) return n;
+    // xz: every chunk stored (3 bytes per block of the smallest size), 24 bytes per 1 MiB block, the stream's header, Index and footer (xz_enc_core.h)
+    if (algo == PNA_ALGO_XZ) return (size_t)xze_bound(n);
     // (per block of the SMALLEST size a batch may be cut into -- latency mode, BLK_LOG_MIN --: deflate 5 bytes of stored-block header + 5 of sync flush,
     // zstd 3 bytes of block header; per segment / 128 KiB the older, coarser allowances)
     constexpr size_t BMIN = (size_t)1 << BLK_LOG_MIN;
@@ -146,6 +150,10 @@ extern "C" int pna_gpu_clamp_level(int algo, int level) {
         if (level == PNA_LEVEL_DEFAULT) return 6;
         // Custom(n) => Compression::new((n as u32).clamp(0, 9)): a negative n wraps to a large u32 and clamps to 9 (deflate.rs:89-101)
         return (uint32_t)level > 9u ? 9 : level;
+    }
+    if (algo == PNA_ALGO_XZ) {              // lib/src/compress/xz.rs:36-46 (default 6, 0 .. 9)
+        if (level == PNA_LEVEL_DEFAULT) return 6;
+        return level < 0 ? 0 : (level > 9 ? 9 : level);
     }
     return 0;
 }
@@ -171,7 +179,11 @@ static uint32_t level_flags(const pna_gpu_ctx *c, int algo, int level) {
     if (strong && (c->flags & F_ADOPT) && (c->flags & F_LAZY)) return c->flags | F_STRONG;
     return c->flags;
 }
+// xz runs the LZ stage of a zstd level (matches capped at LZMA's 273 bytes): xz 0 the fast set, 1..3 the default set, 4..6 the high set, 7..9 the max set
+static const int XZ_LZ_LEVEL[10] = {1, 3, 3, 3, 6, 6, 6, 10, 10, 10};
 void set_call_level(pna_gpu_ctx *c, int algo, int level) {
+    c->call_xz = algo == PNA_ALGO_XZ;
+    if (c->call_xz) { level = XZ_LZ_LEVEL[pna_gpu_clamp_level(PNA_ALGO_XZ, level)]; algo = PNA_ALGO_ZSTD; }
     c->call_flags = level_flags(c, algo, level);
     const bool zstd = algo != PNA_ALGO_DEFLATE;
     c->call_gtab = zstd && pna_gpu_clamp_level(algo, level) >= 10 && (c->call_flags & F_STRONG) && (c->call_flags & F_ADOPT) && c->tun.strong_gtab != 0;
@@ -638,7 +650,12 @@ struct SubPlan {
 static void plan_geometry(const pna_gpu_ctx *c, int algo, uint64_t in_total, uint64_t nseg_est, SubPlan &p) {
     const bool latency = c->tun.latency_max_mib > 0 && in_total <= ((uint64_t)c->tun.latency_max_mib << 20) && nseg_est <= 1024 && !(c->call_flags & 0x100u);
     uint32_t blk_log = blk_log_for_longest(c, p.max_len), unit_log = 20;
-    if (blk_log == PNA_BLK_LOG && algo != PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & 0x100u) && !(latency && in_total <= (64ull << 20))) {
+    if (algo == PNA_ALGO_XZ) {
+        // xz: an LZ block is an LZMA2 chunk, 64 KiB at most (a shorter longest entry: the power of two that holds it), and a chunk is one wave's serial chain.  In
+        // latency mode the blocks are zstd's there -- 16 KiB up to 32 MiB of input, 32 KiB beyond --, a quarter or half of the chain for a model that starts anew
+        // more often.  Whole segments always: the LZ stage's units are not used, the coder behind it is what an xz call waits for.
+        if (latency && blk_log == 16 && !c->tun.blk_log) blk_log = std::max<uint64_t>(in_total, c->call_total) <= (32ull << 20) ? 14u : 15u;
+    } else if (blk_log == PNA_BLK_LOG && algo != PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & 0x100u) && !(latency && in_total <= (64ull << 20))) {
         // deflate beyond 64 MiB of input: whole segments, and 64 KiB blocks up to 384 MiB of the call's input (96 / 192 / 256 MiB: 1.78 / 2.19 / 2.52 -> 1.66 / 1.99 / 2.20 ms;
         // ratio 2.540 -> 2.536: every dynamic block repeats the code description, so the blocks stay larger than zstd's)
         if (std::max<uint64_t>(in_total, c->call_total) <= (384ull << 20)) blk_log = 16;
@@ -768,8 +785,14 @@ static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
         c->seqs.ensure((size_t)(nblk + 1) * seq_cap_of(blk_log) * 8) || c->lits.ensure((size_t)(nblk + 1) << blk_log) ||
         c->litc.ensure((size_t)(nblk + 1) << blk_log) || (algo == PNA_ALGO_ZSTD && c->seqc.ensure((size_t)(nblk + 1) << blk_log)) ||
         (algo == PNA_ALGO_ZSTD && c->seqw.ensure(hist_on ? (size_t)(nblk + 1) * seq_cap_of(blk_log) * 8 : 64)) ||
-        c->seg_size.ensure((size_t)nseg * 8) || c->seg_off.ensure(((size_t)nseg + 1 + 2 * ((size_t)nseg / 4096 + 2)) * 8))       // (+ the scratch of the hierarchical scan)
-        return fail(c, PNA_E_NOMEM, "workspace allocation failed");
+        c->seg_size.ensure((size_t)nseg * 8) || c->seg_off.ensure(((size_t)nseg + 1 + 2 * ((size_t)nseg / 4096 + 2)) * 8)) {     // (+ the scratch of the hierarchical scan)
+        if (!c->call_xz) return fail(c, PNA_E_NOMEM, "workspace allocation failed");
+        // xz: the sub-batch cannot be made smaller than its longest entry (the entry's Index is sized over all its blocks), so name that limit
+        char msg[256];
+        snprintf(msg, sizeof msg, "workspace allocation failed: an xz entry must fit one sub-batch -- this one holds %llu input bytes (longest entry %llu) and needs about %llu bytes of device workspace",
+                 (unsigned long long)in_total, (unsigned long long)max_len, (unsigned long long)((size_t)(nblk + 1) * (seq_cap_of(blk_log) * 8 + (2ull << blk_log))));
+        return fail(c, PNA_E_NOMEM, msg);
+    }
     uint8_t *hp = (uint8_t *)c->h_plan.p, *dp = (uint8_t *)c->plan.p;
     c->d_segs = (SegDesc *)dp; c->d_units = (SegDesc *)(dp + o_units); c->d_blk_seg = (uint32_t *)(dp + o_blkseg); c->d_entry_seg = (uint32_t *)(dp + o_entry);
     c->d_hist = (uint32_t *)((uint8_t *)c->blk.p + o_hist);
@@ -805,7 +828,7 @@ static int compress_subbatch(const SubBatch &sb, const SubPlan &p) {
                               (uint64_t *)c->seg_size.p, (uint64_t *)c->seg_off.p, st, timed ? &c->ev[2] : nullptr, c->call_flags, c->call_stored,
                               /* a wave per segment: many small entries */ p.wave_blk);
     } else {
-        // zstd: everything stays on `st` -- a hand-over to the auxiliary stream and back costs ~45 us of idle device, a tenth of a small batch --, except the
+        // zstd (and xz, whose LZ stage is zstd's with matches of at most 273 bytes): everything stays on `st` -- a hand-over to the auxiliary stream and back costs ~45 us of idle device, a tenth of a small batch --, except the
         // literal coder of large batches, which runs on the auxiliary stream next to the sequence coder (option lit_beside_seq)
         if (!c->aux) {
             { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // (lowest priority: what runs here fills in beside the main stream's kernels)
@@ -816,6 +839,8 @@ static int compress_subbatch(const SubBatch &sb, const SubPlan &p) {
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         }
         HIPCHK(c, hipEventRecord(c->ev_lz[0], st));
+        const bool xz = sb.algo == PNA_ALGO_XZ;
+        const uint32_t zlen = xz ? (uint32_t)XZE_MAX_LEN : 0xFFFFFFFFu;
         const uint32_t zfl = (c->call_flags & 0x3FFu) | (c->call_w32 ? (c->call_w16 ? FLAG_W16 : FLAG_W32) : 0u) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | (c->call_gtab ? 0u : FLAG_LEN36) | (c->call_tab3 ? FLAG_TAB3 : 0u) | ((c->call_tab3 && !c->call_w16 && c->tun.far1) ? FLAG_FAR1 : 0u) | (c->call_strong2 ? FLAG_STRONG2 : 0u) | p.small_fl;
         const uint32_t zmax = (c->call_flags & F_FAR) ? (c->call_gtab ? MAX_OFF : MAX_OFF_W3) : NEAR_OFF;   // (3-byte words keep 19 bits of offset)
         if (p.unit_mode) {
@@ -825,15 +850,24 @@ static int compress_subbatch(const SubBatch &sb, const SubPlan &p) {
             if (gt && (c->pbuf.ensure(((size_t)nblk << blk_log) * 4) || c->gtab.ensure((size_t)nunits << (lz_gtab_log() + 2)))) return fail(c, PNA_E_NOMEM, "no room for the strong level set's hash tables");
             if (gt || !(zfl & FLAG_ALL_SMALL))
             launch_lz(d_src, c->d_units, nunits, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, nullptr, zfl,
-                      zmax, 0xFFFFFFFFu, st, gt ? (uint32_t *)c->pbuf.p : nullptr, 0, nullptr, gt ? (uint32_t *)c->gtab.p : nullptr, gt ? &pgu : nullptr);
-            if (!gt && (zfl & FLAG_HAS_SMALL)) { const int rc = lz_small_pass(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, 0xFFFFFFFFu, st); if (rc) return rc; }   // (the split form above takes them itself)
+                      zmax, zlen, st, gt ? (uint32_t *)c->pbuf.p : nullptr, 0, nullptr, gt ? (uint32_t *)c->gtab.p : nullptr, gt ? &pgu : nullptr);
+            if (!gt && (zfl & FLAG_HAS_SMALL)) { const int rc = lz_small_pass(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, zlen, st); if (rc) return rc; }   // (the split form above takes them itself)
         }
         else {
             c->lzp_hist = p.seq_hist ? c->d_hist : nullptr; c->lzp_hist_all = c->lzp_hist != nullptr;
-            const int rc = lz_stage(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, zmax, 0xFFFFFFFFu, st, timed); if (rc) return rc;
+            const int rc = lz_stage(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, zmax, zlen, st, timed); if (rc) return rc;
         }
         HIPCHK(c, hipEventRecord(c->ev_lz[1], st));
         HIPCHK(c, hipEventRecord(c->ev_en[0], st));
+        if (xz) {
+            // xz: the segments' CRC64 (timed as the statistics stage), the chunk coder (as the literal stage), sizes and offsets (as the sequence stage); the scratch is the literal
+            // coder's (a slot of the block's size per block), the sizes and accumulators live where the zstd tables would
+            launch_xzenc_stage(d_src, c->d_segs, nseg, (uint32_t)std::min<uint64_t>(p.max_len, SEG_SIZE), c->d_blk_seg, nblk, (const uint64_t *)c->seqs.p, (BlkInfo *)c->blk.p, (uint8_t *)c->litc.p, (uint64_t *)c->tabs.p,
+                               (uint64_t *)c->seg_size.p, (uint64_t *)c->seg_off.p, st, &c->ev_en[1]);
+            if (timed) { HIPCHK(c, hipEventRecord(c->ev[4], st)); HIPCHK(c, hipEventRecord(c->ev[5], st)); }
+            HIPCHK(c, hipGetLastError());
+            return PNA_OK;
+        }
         launch_entropy_chunk(c->d_segs, 0, nseg, c->d_blk_seg, 0, nblk, (const uint64_t *)c->seqs.p,
                              (const uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (SegTables *)c->tabs.p, (uint8_t *)c->litc.p, (uint8_t *)c->seqc.p,
                              (uint32_t *)c->seqw.p, c->call_flags, blk_log, p.hist_on ? c->d_hist : nullptr, st, &c->ev_en[1],
@@ -1089,6 +1123,8 @@ static int write_stage(const SubBatch &sb, const SubPlan &p, const SubLayout &L,
         launch_deflate_write_run(sb.d_src, c->d_segs, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p,
                                  (const uint8_t *)c->litc.p, c->d_entry_seg, wbase, st, c->call_stored, /* a wave per block */ p.wave_blk, sb.fj->adler_carry, sb.fj->run);
     }
+    else if (sb.algo == PNA_ALGO_XZ) launch_xzenc_write(sb.d_src, c->d_segs, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p, (const uint8_t *)c->litc.p,
+                                                        (const uint64_t *)c->tabs.p, p.nseg, c->d_entry_seg, (uint32_t)(sb.e1 - sb.e0), wbase, st, p.wave_blk);
     else if (sb.algo == PNA_ALGO_DEFLATE) launch_deflate_write(sb.d_src, c->d_segs, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, d_segdst, (const uint64_t *)c->seg_size.p,
                                                                (const uint8_t *)c->litc.p, c->d_entry_seg, (uint32_t)(sb.e1 - sb.e0), wbase, st, c->call_stored, p.wave_blk);
     else launch_write(sb.d_src, c->d_segs, p.nseg, c->d_blk_seg, p.nblk, (const BlkInfo *)c->blk.p, (const SegTables *)c->tabs.p, d_segdst, (const uint8_t *)c->lits.p,
@@ -1230,7 +1266,7 @@ extern "C" int pna_gpu_compress_batch_device(pna_gpu_ctx *c, int algo, int level
                                              const uint64_t *src_off, const uint64_t *src_len, void *d_dst, size_t dst_cap,
                                              uint64_t *dst_off, void *hip_stream) {
     if (!c || !src_off || !src_len || !dst_off || (!d_src && n) || (!d_dst && n)) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     set_call_level(c, algo, level);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -1348,7 +1384,7 @@ int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, co
                                       uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream) {
     { int rcm = check_meta(c, meta, n); if (rcm) return rcm; }
     if (!c || !archive_len || (n && (!names || !src_off || !src_len || !d_src)) || !d_dst) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     if ((uintptr_t)d_dst & 15) return fail(c, PNA_E_INVAL, "archive buffer must be 16-byte aligned");
     if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
     const auto t_call0 = std::chrono::steady_clock::now();
@@ -1487,7 +1523,7 @@ extern "C" int pna_gpu_create_solid_archive_enc_device(pna_gpu_ctx *c, int algo,
     if (cipher) { int rc0 = resolve_ivs(c, cipher, 1, own_ivs, &ivs); if (rc0) return rc0; }
     if (cipher && cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
     if (!c || !archive_len || (n && (!names || !src_off || !src_len || !d_src)) || !d_dst) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
     if ((uintptr_t)d_dst & 15) return fail(c, PNA_E_INVAL, "archive buffer must be 16-byte aligned");
     set_call_level(c, algo, level);
     HIPCHK(c, hipSetDevice(c->device));

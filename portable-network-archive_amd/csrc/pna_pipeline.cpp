@@ -236,7 +236,7 @@ extern "C" int pna_gpu_create_solid_archive_enc_host(pna_gpu_ctx *c, int algo, i
     const uint8_t *ivs = nullptr;
     int rc = resolve_ivs(c, cipher, 1, own_ivs, &ivs); if (rc) return rc;
     if (cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
     HIPCHK(c, hipSetDevice(c->device));
     pna_gpu_cipher ci = *cipher; ci.ivs = ivs;                  // (IVs drawn here: the one-shot form must not draw others)
     if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, &ci, ivs, sink, user);
@@ -414,7 +414,7 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
     const auto t_entry = std::chrono::steady_clock::now();
     { int rcm = check_meta(c, meta, n); if (rcm) return rcm; }
     if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     set_call_level(c, algo, level);
     if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
     std::vector<uint8_t> own_ivs;
@@ -611,7 +611,7 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
 extern "C" int pna_gpu_compress_batch(pna_gpu_ctx *c, int algo, int level, size_t n, const void *const *src,
                                       const size_t *src_len, void *const *dst, const size_t *dst_cap, size_t *dst_len) {
     if (!c || (n && (!src || !src_len || !dst || !dst_cap || !dst_len))) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented");
+    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<uint64_t> off(n + 1), len(n), doff(n + 1), obase(n + 1);       // obase: running sum of the entries' bounds
     uint64_t pos = 0, bound = 0;
