@@ -10,6 +10,7 @@ import lzma
 import pytest
 
 import xz_enc_cases as E
+from xz_enc_cases import _check_archive, _entries
 
 pytestmark = pytest.mark.gpu
 
@@ -106,30 +107,6 @@ def test_device_batch_guard_bands(pna, ctx):
     assert host[:G] == b"\xA5" * G and host[G + offs[2]:] == b"\xA5" * (len(host) - G - offs[2])
     assert lzma.decompress(host[G + offs[0]:G + offs[1]]) == a
     assert lzma.decompress(host[G + offs[1]:G + offs[2]]) == b
-
-
-def _entries():
-    text = dict(E.inputs())["text1m12345"]
-    rnd = dict(E.inputs())["random70000"]
-    return ["a/text.txt", "a/empty", "b/random.bin", "b/big.txt"], [text[:5000], b"", rnd[:40000], text[:(1 << 20) + 100]]
-
-
-def _check_archive(pna, pf, codec, ctx, arc, names, ents, password=None):
-    """the archive through the existing read-side drivers, through the oracle's container parser, and its payloads through liblzma"""
-    got = pna.extract_archive(ctx, arc, password)
-    assert [(n, d) for n, _, d in got] == list(zip(names, ents))
-    recs, summ = pna.verify_archive(ctx, arc, password)
-    assert summ["rc"] == 0 and len(recs) == len(names) and all(r[2] == pna.VERIFY_OK for r in recs)
-    _, items = pf.read_archive(arc)
-    assert len(items) == len(names)
-    for it, n, e in zip(items, names, ents):
-        assert (it.name, it.compression, it.raw_file_size) == (n, pna.ALGO_XZ, len(e))     # FHED compression byte 4
-        payload = it.data
-        if it.encryption:
-            phsf = [d for ty, d in it.chunks if ty == b"PHSF"][0].decode()
-            payload = codec.decrypt_payload(it.encryption, it.cipher_mode, codec.derive_key_from_phsf(phsf, password), it.data)
-        assert lzma.decompress(payload, format=lzma.FORMAT_XZ) == e, n
-    return items
 
 
 def test_archive_plain_host_and_device(pna, pf, codec, ctx):

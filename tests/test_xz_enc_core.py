@@ -111,6 +111,84 @@ def test_levels_round_trip():
     assert sizes[0] > sizes[2]                                           # (the fast set finds less than the high set)
 
 
+def _decodes(stream, data):
+    """liblzma and xz_core.h's decoder give the data back; the stream fits the bound and no chunk of it costs more than stored"""
+    lib = E.core()
+    assert stream, "the stream did not fit xze_bound"
+    assert len(stream) <= lib.xze_host_bound(len(data))
+    assert lzma.decompress(stream, format=lzma.FORMAT_XZ) == data
+    buf, got = ctypes.create_string_buffer(max(len(data), 1)), ctypes.c_size_t()
+    assert lib.xze_host_decode(stream, len(stream), buf, len(data), ctypes.byref(got)) == 0
+    assert buf.raw[:got.value] == data
+    _no_chunk_beyond_stored(stream)
+
+
+def test_hand_made_parses():
+    """parses the LZ stage never writes -- every length around the 273 cap and its multiples, distances of every slot, a pool of four distances -- and
+    parses with one wrong sequence: valid streams all the same"""
+    for data, blk_log, counts, packed in E.hand_made_cases():
+        _decodes(E.stream_of_parse(data, blk_log, counts, packed), data)
+    for what, data, blk_log, counts, packed, _, _ in E.broken_sequence_cases():
+        _decodes(E.stream_of_parse(data, blk_log, counts, packed), data)
+
+
+def test_census():
+    """What the inputs are there for, each at least once, by the event decoder of xz_enc_cases (which rebuilds the bytes as well).  As measured:
+    rep_cycle (level 6, 64 KiB blocks): rep0 121, rep1 450, rep2 479, rep3 325, replen_low 188, replen_mid 377, replen_high 810, lit_matched 2 501;
+    far (level 9): slot39 301 (slot38 0), len273 299, rep0 521;
+    the 21 hand-made parses together: every key but shortrep, the rarest slot15 1, slot6 2, slot9 3, slot11 3, slot10 4 -- rep0 33 652, rep1 5 980, rep2 5 141,
+    rep3 4 375, lenstate0 2 184, lenstate1 2 210, lenstate2 2 151, slot0 .. slot3 1 228 / 1 368 / 1 239 / 1 502, slot38 806, slot39 481, len273 27 228, stored 4;
+    the six broken parses: 1 527, 1 869, 1 735, 1 602, 1 924 and 8 192 literals between the wrong sequence and its chunk's end, nothing else."""
+    d = dict(E.inputs())["rep_cycle"]
+    ev = E.events(E.cpu_stream("rep_cycle", 6, 16))
+    assert ev.data == d
+    for k in ("rep0", "rep1", "rep2", "rep3", "replen_low", "replen_mid", "replen_high", "lit_matched"):
+        assert ev[k] >= 1, (k, dict(ev))
+    ev = E.events(E.cpu_stream_of(E.far(), 9, 16))
+    assert ev.data == E.far()
+    assert ev["slot38"] + ev["slot39"] >= 1 and ev["len273"] >= 1, dict(ev)
+    total = E.Events()
+    for data, blk_log, counts, packed in E.hand_made_cases():
+        ev = E.events(E.stream_of_parse(data, blk_log, counts, packed))
+        assert ev.data == data
+        total.update(ev)
+    assert sorted(total) == sorted(k for k in E.EVENT_KEYS if k != "shortrep") and all(total[k] >= 1 for k in total), dict(total)
+    assert total["shortrep"] == 0                                       # (the coder never writes one)
+    for what, data, blk_log, counts, packed, pos, end in E.broken_sequence_cases():
+        ev = E.events(E.stream_of_parse(data, blk_log, counts, packed))
+        assert ev.data == data
+        inside = [(at, kind) for at, kind, _ in ev.trace if pos <= at < end]
+        assert inside == [(at, "lit") for at in range(pos, end)], what   # (an LZMA chunk, so every byte of it has its event)
+        assert any(kind != "lit" for at, kind, _ in ev.trace if end <= at < end + 8192), what      # (... and the next chunk is parsed as given)
+
+
+def test_split_above_273():
+    """single matches of 274, 275, 546, 547, 63 579 and 65 000 bytes: pieces of 273 with a rest of 2 .. 273, or of 272 + 2 where 273 would leave one byte
+    -- the first piece a match at the sequence's distance, the others repeats of it (rep0) --, and each sequence's pieces add up to its length"""
+    data, blk_log, counts, packed, matches = E.split_case()
+    stream = E.stream_of_parse(data, blk_log, counts, packed)
+    _decodes(stream, data)
+    ev = E.events(stream)
+    assert ev.data == data
+    pieces = {}
+    for at, kind, n in ev.trace:
+        if kind != "lit":
+            start = max(p for p, _ in matches if p <= at)
+            pieces.setdefault(start, []).append((at, kind, n))
+    assert ev["shortrep"] == 0 and sorted(pieces) == [p for p, _ in matches]
+    for start, ml in matches:
+        got = pieces[start]
+        want = [273] * (ml // 273) + ([ml % 273] if ml % 273 else [])
+        if want[-1] == 1:
+            want[-2:] = [272, 2]
+        assert [n for _, _, n in got] == want, (ml, got[-3:])
+        assert [at for at, _, _ in got] == [start + sum(want[:i]) for i in range(len(want))] and sum(n for _, _, n in got) == ml
+        assert [kind for _, kind, _ in got] == ["match"] + ["rep0"] * (len(want) - 1), ml
+        assert min(n for _, _, n in got) >= 2
+    assert [n for _, _, n in pieces[matches[0][0]]] == [272, 2] and [n for _, _, n in pieces[matches[1][0]]] == [273, 2]
+    assert [n for _, _, n in pieces[matches[3][0]]] == [273, 272, 2]
+
+
 def test_sanitizer_program(tmp_path):
     out = E.built()
     lines = []
@@ -123,7 +201,13 @@ def test_sanitizer_program(tmp_path):
         p = str(tmp_path / ("edge_%d.case" % i))
         E.literal_case_file(p, data, blk_log)
         lines.append(p)
-    man =tmp_path / "manifest"
+    parses = [c for c in E.hand_made_cases()] + [c[1:5] for c in E.broken_sequence_cases()] + [E.split_case()[:4]]
+    parses.append((E.far(), 16) + tuple(E.model_sequences_of(E.far(), 9, 16)))
+    for i, (data, blk_log, counts, packed) in enumerate(parses):
+        p = str(tmp_path / ("parse_%d.case" % i))
+        E.parse_case_file(p, data, blk_log, counts, packed)
+        lines.append(p)
+    man = tmp_path / "manifest"
     man.write_text("\n".join(lines) + "\n")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([os.path.join(out, "xz_enc_host_san"), str(man)], capture_output=True, text=True, env=env)
