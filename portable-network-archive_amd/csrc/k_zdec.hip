@@ -10,144 +10,19 @@
 //   (bit windows in registers, next word prefetched), lane 0 of wave 0 runs the serial FSE chain in batches of 64 sequences and
 //   the wave executes each batch one sequence per lane: positions by a wave scan, literal runs in parallel, matches in
 //   dependency passes with a workgroup-scope fence between them.
+//
+// What the bytes of a header say is parsed in one place, zstd_parse_core.h (bit readers, table builders, one parser per header: also built and tested
+// on the CPU); the kernels here turn those facts into their statuses and keep the decoding loops.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "pna_dev.h"
+#include "zstd_parse_core.h"
 
 namespace pna {
 
 constexpr uint32_t ZD_THREADS = 256;
-constexpr int ZD_HUF_MAX = 11;
 constexpr uint32_t ZD_STAGE_W = 6144;                 // 48 KiB
 constexpr uint32_t ZD_BATCH = 64;                     // sequences decoded by lane 0, then executed one per lane
-enum { ZD_OK = 0, ZD_CORRUPT = 1, ZD_UNSUPPORTED = 2, ZD_DSTSIZE = 3 };
-
-typedef unsigned long long zd_u64u __attribute__((aligned(1)));
-
-__constant__ int16_t ZD_LL_DEF[36] = {4,3,2,2,2,2,2,2,2,2,2,2,2,1,1,1,2,2,2,2,2,2,2,2,2,3,2,1,1,1,1,1,-1,-1,-1,-1};
-__constant__ int16_t ZD_ML_DEF[53] = {1,4,3,2,2,2,2,2,2,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,-1,-1,-1,-1,-1,-1,-1};
-__constant__ int16_t ZD_OF_DEF[29] = {1,1,1,1,1,1,2,2,2,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,-1,-1,-1,-1,-1};
-__constant__ uint32_t ZD_LL_BASE[36] = {0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,18,20,22,24,28,32,40,48,64,128,256,512,1024,2048,4096,8192,16384,32768,65536};
-__constant__ uint8_t  ZD_LL_BITS[36] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,1,1,1,1,2,2,3,3,4,6,7,8,9,10,11,12,13,14,15,16};
-__constant__ uint32_t ZD_ML_BASE[53] = {3,4,5,6,7,8,9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,26,27,28,29,30,31,32,33,34,35,37,39,41,43,47,51,59,67,83,99,131,259,515,1027,2051,4099,8195,16387,32771,65539};
-__constant__ uint8_t  ZD_ML_BITS[53] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,1,1,1,1,2,2,3,3,4,4,5,7,8,9,10,11,12,13,14,15,16};
-
-__device__ __forceinline__ int zd_hb(uint32_t v) { return 31 - (int)__builtin_clz(v); }           // v != 0
-
-// n bits (<= 56) at bit offset off >= 0 of the little-endian bit string p; reads 8 bytes at p + off / 8 (the source buffer
-// carries 8 bytes of slack behind its last stream)
-__device__ __forceinline__ uint64_t zd_bits(const uint8_t *p, int64_t off, uint32_t n) {
-    const uint64_t v = *(const zd_u64u *)(p + (off >> 3)) >> (off & 7);
-    return v & (((uint64_t)1 << n) - 1);
-}
-// backward reader: `off` = number of unread bits below the cursor; bits below the start of the string read as zero
-struct ZdBits { const uint8_t *p; int64_t off; };
-__device__ __forceinline__ bool zd_binit(ZdBits &b, const uint8_t *p, uint32_t len) {
-    if (len == 0) return false;
-    const uint32_t last = p[len - 1];
-    if (last == 0) return false;
-    b.p = p; b.off = (int64_t)len * 8 - (8 - zd_hb(last));
-    return true;
-}
-__device__ __forceinline__ uint64_t zd_bread(ZdBits &b, uint32_t n) {
-    if (n == 0) return 0;
-    b.off -= n;
-    if (b.off >= 0) return zd_bits(b.p, b.off, n);
-    const int64_t have = (int64_t)n + b.off;                       // bits that exist
-    if (have <= 0) return 0;
-    return zd_bits(b.p, 0, (uint32_t)have) << (uint32_t)(-b.off);
-}
-
-// The same reader with a 128-bit window in registers (words k, k+1 of the string, 8 bytes each) and word k-1 already requested.
-// `fetch(j)` returns word j of the string: from the LDS copy of the stream when it fits (the serial Huffman / FSE chains then
-// never wait for HBM), else straight from global memory.
-struct ZdWin { int64_t off; int64_t k; uint64_t lo, hi, pre; };
-template <class F> __device__ __forceinline__ bool zd_winit(ZdWin &w, F &&fetch, uint32_t last_byte, uint32_t len) {
-    if (len == 0 || last_byte == 0) return false;
-    w.off = (int64_t)len * 8 - (8 - zd_hb(last_byte));
-    w.k = ((w.off + 63) >> 6) - 2; if (w.k < 0) w.k = 0;
-    w.lo = fetch(w.k); w.hi = fetch(w.k + 1); w.pre = w.k > 0 ? fetch(w.k - 1) : 0;
-    return true;
-}
-// the n (<= 57) bits below the cursor, not consumed
-template <class F> __device__ __forceinline__ uint64_t zd_wpeek(ZdWin &w, F &&fetch, uint32_t n) {
-    const int64_t lo_bit = w.off - (int64_t)n;
-    const int64_t need = lo_bit < 0 ? 0 : lo_bit;
-    while (need < 64 * w.k) { w.hi = w.lo; w.lo = w.pre; w.k--; w.pre = w.k > 0 ? fetch(w.k - 1) : 0; }
-    const uint32_t sft = (uint32_t)(need - 64 * w.k);              // 0..127
-    uint64_t v = sft < 64 ? (w.lo >> sft) | (sft ? w.hi << (64 - sft) : 0) : w.hi >> (sft - 64);
-    if (lo_bit < 0) {                                              // part of the field lies below the start: zero there
-        if (w.off <= 0) return 0;
-        v = (v & (((uint64_t)1 << (uint32_t)w.off) - 1)) << (uint32_t)(-lo_bit);
-    }
-    return v & (((uint64_t)1 << n) - 1);
-}
-template <class F> __device__ __forceinline__ uint64_t zd_wread(ZdWin &w, F &&fetch, uint32_t n) {
-    if (n == 0) return 0;
-    const uint64_t v = zd_wpeek(w, fetch, n);
-    w.off -= n;
-    return v;
-}
-
-// FSE decoding table (sym | nbits << 8 | base << 16) from a normalised distribution; serial (one thread)
-__device__ bool zd_fse_build(uint32_t *tab, const int16_t *norm, int nsym, int alog, uint16_t *next /* [256] scratch */) {
-    if (alog > 9) return false;
-    const int size = 1 << alog;
-    int high = size - 1;
-    for (int s = 0; s < nsym; s++) {
-        if (norm[s] == -1) { tab[high--] = (uint32_t)s; next[s] = 1; }
-        else next[s] = (uint16_t)norm[s];
-    }
-    const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    int pos = 0;
-    for (int s = 0; s < nsym; s++)
-        for (int i = 0; i < norm[s]; i++) { tab[pos] = (uint32_t)s; do { pos = (pos + step) & mask; } while (pos > high); }
-    if (pos != 0) return false;
-    for (int u = 0; u < size; u++) {
-        const uint32_t s = tab[u] & 0xFF;
-        const uint32_t ns = next[s]++;
-        const uint32_t nb = (uint32_t)(alog - zd_hb(ns));
-        tab[u] = s | (nb << 8) | ((((ns << nb) - (uint32_t)size) & 0xFFFF) << 16);
-    }
-    return true;
-}
-
-// FSE table description (forward bits); returns bytes consumed, 0 on error
-__device__ uint32_t zd_fse_desc(const uint8_t *src, uint32_t len, int16_t *norm, int *nsym_out, int *alog_out, int max_sym, int max_alog) {
-    if (len < 1) return 0;
-    uint64_t bitpos = 0;
-    auto peek = [&](uint32_t n) -> uint32_t {
-        uint64_t v = 0; const uint64_t byte = bitpos >> 3;
-        for (int i = 0; i < 5; i++) if (byte + i < len) v |= (uint64_t)src[byte + i] << (8 * i);
-        return (uint32_t)((v >> (bitpos & 7)) & (((uint64_t)1 << n) - 1));
-    };
-    const int alog = (int)peek(4) + 5; bitpos += 4;
-    if (alog > max_alog) return 0;
-    int remaining = (1 << alog) + 1, threshold = 1 << alog, nbits = alog + 1, sym = 0;
-    for (int i = 0; i <= max_sym; i++) norm[i] = 0;
-    while (remaining > 1 && sym <= max_sym) {
-        const int mx = (2 * threshold - 1) - remaining;
-        int count;
-        const uint32_t v = peek((uint32_t)nbits);
-        if ((int)(v & (uint32_t)(threshold - 1)) < mx) { count = (int)(v & (uint32_t)(threshold - 1)); bitpos += (uint32_t)(nbits - 1); }
-        else { count = (int)(v & (uint32_t)(2 * threshold - 1)); if (count >= threshold) count -= mx; bitpos += (uint32_t)nbits; }
-        count--;
-        remaining -= count < 0 ? -count : count;
-        norm[sym++] = (int16_t)count;
-        if (count == 0) {
-            for (;;) {
-                const uint32_t rep = peek(2); bitpos += 2;
-                for (uint32_t i = 0; i < rep && sym <= max_sym; i++) norm[sym++] = 0;
-                if (rep != 3) break;
-            }
-        }
-        while (remaining < threshold) { nbits--; threshold >>= 1; }
-        if ((bitpos + 7) / 8 > len) return 0;
-    }
-    if (remaining != 1 || sym > max_sym + 1) return 0;
-    *nsym_out = sym; *alog_out = alog;
-    return (uint32_t)((bitpos + 7) / 8);
-}
 
 struct ZdBlk {                 // what thread 0 tells the workgroup about the current block
     uint32_t status;           // ZD_*
@@ -190,28 +65,22 @@ void k_zdec(ZFrame *__restrict__ frames, const uint8_t *__restrict__ src, uint8_
 
     // ---- frame header (uniform)
     {
-        if (in_len < 6) status = ZD_CORRUPT;
+        ZdFrameHdr h;
+        zd_frame_header(in, in_len, h);
+        if (in_len < 6 || !h.magic) status = ZD_CORRUPT;
         else {
-            const uint32_t magic = in[0] | (in[1] << 8) | (in[2] << 16) | ((uint32_t)in[3] << 24);
-            if (magic != 0xFD2FB528u) status = ZD_CORRUPT;
+            if (h.reserved) status = ZD_CORRUPT;
+            if (h.dict_bytes) status = ZD_UNSUPPORTED;
+            // (the window descriptor: the whole frame is addressable here.  A dictionary id is not stepped over: the content size of such a frame is looked for in
+            // the id's place, and the later answers below replace the earlier ones -- both as they always were here; the lane-parallel route refuses first)
+            const uint32_t at = h.len - h.dict_bytes - h.fcs_bytes;
+            if (at + h.fcs_bytes > in_len) status = ZD_CORRUPT;
             else {
-                const uint32_t fhd = in[4];
-                const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3;
-                ip = 5;
-                if (fhd & 0x08) status = ZD_CORRUPT;
-                if (!single) ip += 1;                                    // window descriptor: the whole frame is addressable here
-                if (dict) status = ZD_UNSUPPORTED;
-                const uint32_t fsz = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-                if (ip + fsz > in_len) status = ZD_CORRUPT;
-                else {
-                    uint64_t fcs = 0;
-                    for (uint32_t i = 0; i < fsz; i++) fcs |= (uint64_t)in[ip + i] << (8 * i);
-                    if (fsz == 2) fcs += 256;
-                    if (fsz && (open ? fcs > fr.dst_len : fcs != fr.dst_len)) status = ZD_DSTSIZE;
-                    ip += fsz;
-                }
-                if ((fhd >> 2) & 1) { /* content checksum: 4 bytes after the last block, verified by k_zxxh once the content is there */ }
+                const uint64_t fcs = zd_fcs(in + at, h.fcs_bytes);
+                if (h.fcs_bytes && (open ? fcs > fr.dst_len : fcs != fr.dst_len)) status = ZD_DSTSIZE;
+                ip = at + h.fcs_bytes;
             }
+            // (content checksum: 4 bytes after the last block, verified by k_zxxh once the content is there)
         }
     }
     __syncthreads();
@@ -230,115 +99,36 @@ void k_zdec(ZFrame *__restrict__ frames, const uint8_t *__restrict__ src, uint8_
             b.seq_off = 0; b.seq_len = 0; b.nweights = 0; b.maxbits = 0; b.alog[0] = b.alog[1] = b.alog[2] = 0;
             b.last = 1; b.type = 0; b.size = 0;
             do {
-                if (ip + 3 > in_len) { b.status = ZD_CORRUPT; break; }
-                const uint32_t bh = in[ip] | (in[ip + 1] << 8) | ((uint32_t)in[ip + 2] << 16);
-                b.last = bh & 1; b.type = (bh >> 1) & 3; b.size = bh >> 3;
-                if (b.type == 3 || b.size > (128u << 10)) { b.status = ZD_CORRUPT; break; }
-                const uint32_t body = ip + 3;
-                if (b.type == 1) { if (body + 1 > in_len) b.status = ZD_CORRUPT; break; }
-                if (body + b.size > in_len) { b.status = ZD_CORRUPT; break; }
-                if (b.type == 0) break;
+                ZdBlockHdr bh;
+                zd_block_header(in + ip, in_len - ip, bh);
+                if (!bh.have) { b.status = ZD_CORRUPT; break; }
+                b.last = bh.last; b.type = bh.type; b.size = bh.size;
+                if (bh.type == 3 || bh.size > ZD_BLOCK_MAX || !bh.fits) { b.status = ZD_CORRUPT; break; }
+                if (b.type != 2) break;
                 // ---- compressed block: literals section
-                const uint8_t *p = in + body; const uint32_t len = b.size;
-                if (len < 1) { b.status = ZD_CORRUPT; break; }
-                const uint32_t ltype = p[0] & 3, sf = (p[0] >> 2) & 3;
-                uint32_t regen, comp = 0, hdr, streams = 1;
-                if (ltype < 2) {
-                    if (sf == 0 || sf == 2) { regen = p[0] >> 3; hdr = 1; }
-                    else if (sf == 1) { if (len < 2) { b.status = ZD_CORRUPT; break; } regen = (p[0] >> 4) + ((uint32_t)p[1] << 4); hdr = 2; }
-                    else { if (len < 3) { b.status = ZD_CORRUPT; break; } regen = (p[0] >> 4) + ((uint32_t)p[1] << 4) + ((uint32_t)p[2] << 12); hdr = 3; }
-                } else {
-                    if (len < 5) { b.status = ZD_CORRUPT; break; }
-                    uint64_t v = 0; for (int i = 0; i < 5; i++) v |= (uint64_t)p[i] << (8 * i);
-                    if (sf == 0) { streams = 1; hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-                    else if (sf == 1) { streams = 4; hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-                    else if (sf == 2) { streams = 4; hdr = 4; regen = (v >> 4) & 0x3FFF; comp = (v >> 18) & 0x3FFF; }
-                    else { streams = 4; hdr = 5; regen = (v >> 4) & 0x3FFFF; comp = (v >> 22) & 0x3FFFF; }
-                }
-                if (regen > (128u << 10) || regen > cap) { b.status = ZD_CORRUPT; break; }
-                b.ltype = ltype; b.regen = regen; b.streams = streams;
-                uint32_t pos = hdr;
-                if (ltype == 0) { if (pos + regen > len) { b.status = ZD_CORRUPT; break; } b.lit_off = pos; pos += regen; }
-                else if (ltype == 1) { if (pos + 1 > len) { b.status = ZD_CORRUPT; break; } b.lit_off = pos; pos += 1; }
-                else {
-                    if (pos + comp > len) { b.status = ZD_CORRUPT; break; }
-                    const uint8_t *cs = p + pos; uint32_t cl = comp, used = 0;
-                    if (ltype == 2) {
-                        // ---- Huffman tree description -> weights[0 .. nw), the last weight is implied
-                        if (cl < 1) { b.status = ZD_CORRUPT; break; }
-                        const uint32_t hbyte = cs[0];
-                        uint32_t nw = 0;
-                        if (hbyte >= 128) {
-                            nw = hbyte - 127;
-                            const uint32_t bytes = (nw + 1) / 2;
-                            if (1 + bytes > cl) { b.status = ZD_CORRUPT; break; }
-                            for (uint32_t i = 0; i < nw; i++) { const uint32_t by = cs[1 + i / 2]; weights[i] = (uint8_t)((i & 1) ? (by & 15) : (by >> 4)); }
-                            used = 1 + bytes;
-                        } else {
-                            const uint32_t csize = hbyte;
-                            if (csize == 0 || 1 + csize > cl) { b.status = ZD_CORRUPT; break; }
-                            int nsym, alog;
-                            const uint32_t dl = zd_fse_desc(cs + 1, csize, norm, &nsym, &alog, 255, 6);
-                            if (!dl || dl >= csize || !zd_fse_build(wtab, norm, nsym, alog, nexts)) { b.status = ZD_CORRUPT; break; }
-                            ZdBits bb;
-                            if (!zd_binit(bb, cs + 1 + dl, csize - dl)) { b.status = ZD_CORRUPT; break; }
-                            uint32_t s1 = (uint32_t)zd_bread(bb, (uint32_t)alog), s2 = (uint32_t)zd_bread(bb, (uint32_t)alog);
-                            bool bad = false;
-                            for (;;) {
-                                if (nw >= 255) { bad = true; break; }
-                                weights[nw++] = (uint8_t)(wtab[s1] & 0xFF);
-                                s1 = (wtab[s1] >> 16) + (uint32_t)zd_bread(bb, (wtab[s1] >> 8) & 0xFF);
-                                if (bb.off < 0) { if (nw >= 255) { bad = true; break; } weights[nw++] = (uint8_t)(wtab[s2] & 0xFF); break; }
-                                if (nw >= 255) { bad = true; break; }
-                                weights[nw++] = (uint8_t)(wtab[s2] & 0xFF);
-                                s2 = (wtab[s2] >> 16) + (uint32_t)zd_bread(bb, (wtab[s2] >> 8) & 0xFF);
-                                if (bb.off < 0) { if (nw >= 255) { bad = true; break; } weights[nw++] = (uint8_t)(wtab[s1] & 0xFF); break; }
-                            }
-                            if (bad) { b.status = ZD_CORRUPT; break; }
-                            used = 1 + csize;
-                        }
-                        uint32_t total = 0; bool badw = false;
-                        for (uint32_t i = 0; i < nw; i++) { if (weights[i] > ZD_HUF_MAX) badw = true; else if (weights[i]) total += 1u << (weights[i] - 1); }
-                        if (badw || total == 0 || nw < 1) { b.status = ZD_CORRUPT; break; }
-                        const uint32_t maxbits = (uint32_t)zd_hb(total) + 1;
-                        const uint32_t rest = (1u << maxbits) - total;
-                        if (maxbits > (uint32_t)ZD_HUF_MAX || rest == 0 || (rest & (rest - 1))) { b.status = ZD_CORRUPT; break; }
-                        weights[nw] = (uint8_t)(zd_hb(rest) + 1);
-                        b.new_tree = 1; b.nweights = nw + 1; b.maxbits = maxbits; s_huf_ok = 1; s_hufbits = maxbits;
+                const uint8_t *p = in + ip + 3; const uint32_t len = b.size;
+                ZdLitHdr l;
+                if (!zd_literals_header(p, len, l) || l.regen > ZD_BLOCK_MAX || l.regen > cap || l.size > len) { b.status = ZD_CORRUPT; break; }
+                b.ltype = l.ltype; b.regen = l.regen; b.streams = l.streams; b.lit_off = l.hdr;
+                if (l.ltype >= 2) {
+                    uint32_t used = 0;
+                    if (l.ltype == 2) {
+                        if (!zd_huf_weights(p + l.hdr, l.comp, weights, norm, nexts, wtab, b.nweights, b.maxbits, used)) { b.status = ZD_CORRUPT; break; }
+                        b.new_tree = 1; s_huf_ok = 1; s_hufbits = b.maxbits;
                     } else if (!s_huf_ok) { b.status = ZD_CORRUPT; break; }
-                    if (used > cl) { b.status = ZD_CORRUPT; break; }
-                    b.lit_off = pos + used; b.lit_csize = cl - used;
-                    pos += comp;
+                    if (used > l.comp) { b.status = ZD_CORRUPT; break; }
+                    b.lit_off = l.hdr + used; b.lit_csize = l.comp - used;
                 }
                 // ---- sequences section
-                if (pos >= len) { b.status = ZD_CORRUPT; break; }
-                uint32_t nseq; const uint32_t b0 = p[pos++];
-                if (b0 < 128) nseq = b0;
-                else if (b0 < 255) { if (pos >= len) { b.status = ZD_CORRUPT; break; } nseq = ((b0 - 128) << 8) + p[pos++]; }
-                else { if (pos + 2 > len) { b.status = ZD_CORRUPT; break; } nseq = p[pos] + ((uint32_t)p[pos + 1] << 8) + 0x7F00; pos += 2; }
-                b.nseq = nseq;
-                if (nseq == 0) { if (pos != len) b.status = ZD_CORRUPT; break; }
-                if (pos >= len) { b.status = ZD_CORRUPT; break; }
-                const uint32_t modes = p[pos++];
+                uint32_t pos = l.size, modes;
+                if (!zd_seq_header(p, len, pos, b.nseq, modes)) { b.status = ZD_CORRUPT; break; }
+                if (b.nseq == 0) { if (pos != len) b.status = ZD_CORRUPT; break; }
                 if (modes & 3) { b.status = ZD_CORRUPT; break; }
                 bool ok = true;
                 for (int k = 0; k < 3 && ok; k++) {                         // LL, OF, ML in stream order
-                    const uint32_t mode = (modes >> (6 - 2 * k)) & 3;
-                    const int16_t *def = k == 0 ? ZD_LL_DEF : (k == 1 ? ZD_OF_DEF : ZD_ML_DEF);
-                    const int def_n = k == 0 ? 36 : (k == 1 ? 29 : 53), def_log = k == 1 ? 5 : 6;
-                    const int max_sym = k == 0 ? 35 : (k == 1 ? 31 : 52), max_log = k == 1 ? 8 : 9;
-                    if (mode == 0) {
-                        for (int i = 0; i < def_n; i++) norm[i] = def[i];
-                        ok = zd_fse_build(fse_tab[k], norm, def_n, def_log, nexts); s_ok[k] = 1; s_alog[k] = (uint32_t)def_log;
-                    } else if (mode == 1) {
-                        if (pos >= len || p[pos] > max_sym) { ok = false; break; }
-                        fse_tab[k][0] = p[pos]; pos++; s_ok[k] = 1; s_alog[k] = 0;
-                    } else if (mode == 2) {
-                        int nsym, alog;
-                        const uint32_t used = zd_fse_desc(p + pos, len - pos, norm, &nsym, &alog, max_sym, max_log);
-                        if (!used) { ok = false; break; }
-                        ok = zd_fse_build(fse_tab[k], norm, nsym, alog, nexts); pos += used; s_ok[k] = 1; s_alog[k] = (uint32_t)alog;
-                    } else if (!s_ok[k]) ok = false;
+                    const uint32_t mode = zd_seq_mode(modes, k);
+                    if (mode == 3) ok = s_ok[k] != 0;                       // repeat: the table of an earlier block
+                    else { ok = zd_seq_table(k, mode, p, len, pos, fse_tab[k], norm, nexts, s_alog[k]); s_ok[k] = 1; }
                     b.alog[k] = s_alog[k];
                 }
                 if (!ok || pos >= len) { b.status = ZD_CORRUPT; break; }
@@ -362,16 +152,7 @@ void k_zdec(ZFrame *__restrict__ frames, const uint8_t *__restrict__ src, uint8_
         const uint8_t *p = in + body;
         // ================= Huffman table (all threads): symbol s of weight w owns 2^(w-1) cells behind all symbols of smaller
         // weight and the lower-numbered symbols of its own weight
-        if (b.new_tree) {
-            for (uint32_t s = tid; s < b.nweights; s += ZD_THREADS) {
-                const uint32_t w = weights[s];
-                if (!w) continue;
-                uint32_t pos = 0;
-                for (uint32_t o = 0; o < b.nweights; o++) { const uint32_t wo = weights[o]; if (wo && (wo < w || (wo == w && o < s))) pos += 1u << (wo - 1); }
-                const uint32_t n = 1u << (w - 1), cell = s | ((b.maxbits + 1 - w) << 8);
-                for (uint32_t i = 0; i < n; i++) huf_tab[pos + i] = (uint16_t)cell;
-            }
-        }
+        if (b.new_tree) zd_huf_fill(huf_tab, weights, b.nweights, b.maxbits, tid, ZD_THREADS);
         __syncthreads();
         // ================= literals -> tail of the frame's output region
         uint8_t *lit_stage = lit_scratch + (size_t)blockIdx.x * (128u << 10);   // this frame's slot for decoded literals
@@ -379,20 +160,13 @@ void k_zdec(ZFrame *__restrict__ frames, const uint8_t *__restrict__ src, uint8_
             const uint32_t mb = s_hufbits;
             const uint8_t *cs = p + b.lit_off; const uint32_t cl = b.lit_csize;
             // stream s: bytes [s_off, s_off + s_len) of the section, regenerates o_len bytes at o_off
-            uint32_t sof4[4] = {0, 0, 0, 0}, sln4[4] = {cl, 0, 0, 0}, oof4[4] = {0, 0, 0, 0}, oln4[4] = {b.regen, 0, 0, 0};
+            uint32_t sof4[4], sln4[4], oof4[4], oln4[4];
             bool okh = true;
-            if (b.streams == 4) {
-                if (cl < 6) okh = false;
-                else {
-                    const uint32_t l1 = cs[0] | (cs[1] << 8), l2 = cs[2] | (cs[3] << 8), l3 = cs[4] | (cs[5] << 8);
-                    const uint32_t seg = (b.regen + 3) / 4;
-                    if (6 + l1 + l2 + l3 > cl || seg * 3 > b.regen) okh = false;
-                    else {
-                        sof4[0] = 6; sln4[0] = l1; sof4[1] = 6 + l1; sln4[1] = l2; sof4[2] = 6 + l1 + l2; sln4[2] = l3;
-                        sof4[3] = 6 + l1 + l2 + l3; sln4[3] = cl - sof4[3];
-                        for (int q = 0; q < 4; q++) { oof4[q] = q * seg; oln4[q] = q < 3 ? seg : b.regen - 3 * seg; }
-                    }
-                }
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++) {
+                ZdStream hs;
+                okh = zd_huf_streams(cs, cl, b.regen, b.streams, q, hs) && okh;
+                sof4[q] = hs.off; sln4[q] = hs.len; oof4[q] = hs.out_off; oln4[q] = hs.out_len;
             }
             // LDS copies of the streams (each starts on an 8-byte boundary, 16 bytes of slack behind the last)
             uint32_t lw4[4] = {0, 0, 0, 0}, words = 0;
@@ -589,6 +363,17 @@ struct ZWork { uint32_t n_huf, n_seq, pad0, pad1; };
 // ONE (round 4): the frame's blocks were laid out by k_zparse_a (a serial walk of the headers only: positions, sizes, table slots) and every wave of this
 // launch parses ONE of them -- blockIdx.x = index into `one_list` of block numbers --: what took the single wave of a 2 048-block frame 0.6 s (0.29 ms of
 // weight decoding and table building per block on lane 0) runs side by side.  Same code, the running state comes from the block's descriptor.
+// the frame header as the lane-parallel route answers it; *at: where the first block starts
+__device__ __forceinline__ uint32_t zparse_frame_header(const uint8_t *in, uint64_t in_len, bool open, uint64_t want, uint32_t *at) {
+    ZdFrameHdr h;
+    zd_frame_header(in, in_len, h);
+    if (in_len < 6 || !h.magic || h.reserved) return ZD_CORRUPT;
+    if (h.dict_bytes) return ZD_UNSUPPORTED;
+    if (!h.complete) return ZD_CORRUPT;
+    *at = h.len;
+    return h.fcs_bytes && (open ? h.fcs > want : h.fcs != want) ? ZD_DSTSIZE : ZD_OK;
+}
+
 template <bool ONE>
 __global__ __launch_bounds__(64)
 void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8_t *__restrict__ src, ZBlock *__restrict__ blocks,
@@ -621,28 +406,7 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
     uint32_t status = fr.status, ip = 0;
     if (!ONE && status == ZD_OK && fr.src_len > 0xFFFFFFFFull) status = ZD_UNSUPPORTED;
     // ---- frame header
-    if (!ONE && status == ZD_OK) {
-        if (in_len < 6) status = ZD_CORRUPT;
-        else {
-            const uint32_t magic = in[0] | (in[1] << 8) | (in[2] << 16) | ((uint32_t)in[3] << 24);
-            const uint32_t fhd = in[4];
-            const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3;
-            if (magic != 0xFD2FB528u || (fhd & 0x08)) status = ZD_CORRUPT;
-            else if (dict) status = ZD_UNSUPPORTED;
-            else {
-                ip = 5 + (single ? 0 : 1);
-                const uint32_t fsz = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-                if (ip + fsz > in_len) status = ZD_CORRUPT;
-                else {
-                    uint64_t fcs = 0;
-                    for (uint32_t i = 0; i < fsz; i++) fcs |= (uint64_t)in[ip + i] << (8 * i);
-                    if (fsz == 2) fcs += 256;
-                    if (fsz && (open ? fcs > fcs_want : fcs != fcs_want)) status = ZD_DSTSIZE;
-                    ip += fsz;
-                }
-            }
-        }
-    }
+    if (!ONE && status == ZD_OK) status = zparse_frame_header(in, in_len, open, fcs_want, &ip);
     uint32_t nblk = 0, next_slot = 0, huf_slot = 0xFFFFFFFFu, slot3[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     uint64_t lit_pos = 0, seq_pos = 0;                                  // (per block, on lane 0: the literal scratch of a frame is as long as its content)
     if (ONE) {                                                          // the walk's state in front of this block
@@ -666,103 +430,42 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
         if (lane == 0) {
             do {
                 if (nblk >= x.blk_cap) { bstat = ZD_UNSUPPORTED; break; }
-                if (ip + 3 > in_len) { bstat = ZD_CORRUPT; break; }
-                const uint32_t bh = in[ip] | (in[ip + 1] << 8) | ((uint32_t)in[ip + 2] << 16);
-                b.type = (bh >> 1) & 3; b.size = bh >> 3; b.pad[0] = bh & 1;
+                ZdBlockHdr bh;
+                zd_block_header(in + ip, in_len - ip, bh);
+                if (!bh.have) { bstat = ZD_CORRUPT; break; }
+                b.type = bh.type; b.size = bh.size; b.pad[0] = bh.last;
                 b.body = in_abs + ip + 3;
-                if (b.type == 3 || b.size > (128u << 10)) { bstat = ZD_CORRUPT; break; }
-                if (b.type == 1) { if (ip + 4 > in_len) bstat = ZD_CORRUPT; b.out_len = b.size; break; }
-                if (ip + 3 + b.size > in_len) { bstat = ZD_CORRUPT; break; }
-                if (b.type == 0) { b.out_len = b.size; break; }
+                if (bh.type == 3 || bh.size > ZD_BLOCK_MAX || !bh.fits) { bstat = ZD_CORRUPT; break; }
+                if (b.type != 2) { b.out_len = b.size; break; }
                 const uint8_t *p = in + ip + 3; const uint32_t len = b.size;
-                if (len < 1) { bstat = ZD_CORRUPT; break; }
-                const uint32_t ltype = p[0] & 3, sf = (p[0] >> 2) & 3;
-                uint32_t regen, comp = 0, hdr, streams = 1;
-                if (ltype < 2) {
-                    if (sf == 0 || sf == 2) { regen = p[0] >> 3; hdr = 1; }
-                    else if (sf == 1) { if (len < 2) { bstat = ZD_CORRUPT; break; } regen = (p[0] >> 4) + ((uint32_t)p[1] << 4); hdr = 2; }
-                    else { if (len < 3) { bstat = ZD_CORRUPT; break; } regen = (p[0] >> 4) + ((uint32_t)p[1] << 4) + ((uint32_t)p[2] << 12); hdr = 3; }
-                } else {
-                    if (len < 5) { bstat = ZD_CORRUPT; break; }
-                    uint64_t v = 0; for (int i = 0; i < 5; i++) v |= (uint64_t)p[i] << (8 * i);
-                    if (sf == 0) { streams = 1; hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-                    else if (sf == 1) { streams = 4; hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-                    else if (sf == 2) { streams = 4; hdr = 4; regen = (v >> 4) & 0x3FFF; comp = (v >> 18) & 0x3FFF; }
-                    else { streams = 4; hdr = 5; regen = (v >> 4) & 0x3FFFF; comp = (v >> 22) & 0x3FFFF; }
-                }
-                if (regen > (128u << 10) || lit_pos + regen > cap) { bstat = regen > (128u << 10) ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
-                b.ltype = ltype; b.regen = regen; b.streams = streams;
-                uint32_t pos = hdr;
-                if (ltype == 0) { if (pos + regen > len) { bstat = ZD_CORRUPT; break; } b.lit_off = pos; pos += regen; }
-                else if (ltype == 1) { if (pos + 1 > len) { bstat = ZD_CORRUPT; break; } b.lit_off = pos; pos += 1; }
-                else {
-                    if (pos + comp > len) { bstat = ZD_CORRUPT; break; }
-                    const uint8_t *cs = p + pos; const uint32_t cl = comp; uint32_t used = 0;
-                    if (ltype == 2) {
-                        if (cl < 1) { bstat = ZD_CORRUPT; break; }
-                        const uint32_t hbyte = cs[0];
-                        uint32_t nw = 0;
-                        if (hbyte >= 128) {
-                            nw = hbyte - 127;
-                            const uint32_t bytes = (nw + 1) / 2;
-                            if (1 + bytes > cl) { bstat = ZD_CORRUPT; break; }
-                            for (uint32_t i = 0; i < nw; i++) { const uint32_t by = cs[1 + i / 2]; weights[i] = (uint8_t)((i & 1) ? (by & 15) : (by >> 4)); }
-                            used = 1 + bytes;
-                        } else {
-                            const uint32_t csize = hbyte;
-                            if (csize == 0 || 1 + csize > cl) { bstat = ZD_CORRUPT; break; }
-                            int nsym, alog;
-                            const uint32_t dl = zd_fse_desc(cs + 1, csize, norm, &nsym, &alog, 255, 6);
-                            if (!dl || dl >= csize || !zd_fse_build(wtab, norm, nsym, alog, nexts)) { bstat = ZD_CORRUPT; break; }
-                            ZdBits bb;
-                            if (!zd_binit(bb, cs + 1 + dl, csize - dl)) { bstat = ZD_CORRUPT; break; }
-                            uint32_t s1 = (uint32_t)zd_bread(bb, (uint32_t)alog), s2 = (uint32_t)zd_bread(bb, (uint32_t)alog);
-                            bool bad = false;
-                            for (;;) {
-                                if (nw >= 255) { bad = true; break; }
-                                weights[nw++] = (uint8_t)(wtab[s1] & 0xFF);
-                                s1 = (wtab[s1] >> 16) + (uint32_t)zd_bread(bb, (wtab[s1] >> 8) & 0xFF);
-                                if (bb.off < 0) { if (nw >= 255) { bad = true; break; } weights[nw++] = (uint8_t)(wtab[s2] & 0xFF); break; }
-                                if (nw >= 255) { bad = true; break; }
-                                weights[nw++] = (uint8_t)(wtab[s2] & 0xFF);
-                                s2 = (wtab[s2] >> 16) + (uint32_t)zd_bread(bb, (wtab[s2] >> 8) & 0xFF);
-                                if (bb.off < 0) { if (nw >= 255) { bad = true; break; } weights[nw++] = (uint8_t)(wtab[s1] & 0xFF); break; }
-                            }
-                            if (bad) { bstat = ZD_CORRUPT; break; }
-                            used = 1 + csize;
-                        }
-                        uint32_t total = 0; bool badw = false;
-                        for (uint32_t i = 0; i < nw; i++) { if (weights[i] > ZD_HUF_MAX) badw = true; else if (weights[i]) total += 1u << (weights[i] - 1); }
-                        if (badw || total == 0 || nw < 1) { bstat = ZD_CORRUPT; break; }
-                        const uint32_t maxbits = (uint32_t)zd_hb(total) + 1;
-                        const uint32_t rest = (1u << maxbits) - total;
-                        if (maxbits > (uint32_t)ZD_HUF_MAX || rest == 0 || (rest & (rest - 1))) { bstat = ZD_CORRUPT; break; }
-                        weights[nw] = (uint8_t)(zd_hb(rest) + 1);
+                ZdLitHdr l;
+                if (!zd_literals_header(p, len, l)) { bstat = ZD_CORRUPT; break; }
+                if (l.regen > ZD_BLOCK_MAX || lit_pos + l.regen > cap) { bstat = l.regen > ZD_BLOCK_MAX ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
+                b.ltype = l.ltype; b.regen = l.regen; b.streams = l.streams;
+                if (l.size > len) { bstat = ZD_CORRUPT; break; }
+                b.lit_off = l.hdr;
+                if (l.ltype >= 2) {
+                    uint32_t used = 0;
+                    if (l.ltype == 2) {
+                        uint32_t nwt = 0, mbits = 0;
+                        if (!zd_huf_weights(p + l.hdr, l.comp, weights, norm, nexts, wtab, nwt, mbits, used)) { bstat = ZD_CORRUPT; break; }
                         if (next_slot >= x.slot_cap) { bstat = ZD_UNSUPPORTED; break; }
                         huf_slot = x.slot_base + next_slot;             // this block's own slot (shared with its FSE tables below)
-                        p1_tree = 1; s_cmd[3] = maxbits; s_cmd[4] = nw + 1;
+                        p1_tree = 1; s_cmd[3] = mbits; s_cmd[4] = nwt;
                     } else if (huf_slot == 0xFFFFFFFFu) { bstat = ZD_CORRUPT; break; }
-                    if (used > cl) { bstat = ZD_CORRUPT; break; }
-                    b.lit_off = pos + used; b.lit_csize = cl - used;
-                    pos += comp;
+                    if (used > l.comp) { bstat = ZD_CORRUPT; break; }
+                    b.lit_off = l.hdr + used; b.lit_csize = l.comp - used;
                 }
-                b.seq_off = pos;                                          // provisional: start of the sequences section
+                b.seq_off = l.size;                                       // provisional: start of the sequences section
             } while (false);
             s_cmd[0] = p1_tree; s_cmd[5] = bstat;
         }
         __builtin_amdgcn_wave_barrier();
         bstat = s_cmd[5];
         if (s_cmd[0]) {
-            // ---- Huffman table: all lanes (same construction as k_zdec)
+            // ---- Huffman table: all lanes
             const uint32_t nwt = s_cmd[4], mbits = s_cmd[3];
-            for (uint32_t sy = lane; sy < nwt; sy += 64) {
-                const uint32_t w = weights[sy];
-                if (!w) continue;
-                uint32_t pos = 0;
-                for (uint32_t o = 0; o < nwt; o++) { const uint32_t wo = weights[o]; if (wo && (wo < w || (wo == w && o < sy))) pos += 1u << (wo - 1); }
-                const uint32_t n = 1u << (w - 1), cell = sy | ((mbits + 1 - w) << 8);
-                for (uint32_t i = 0; i < n; i++) huf_tab[pos + i] = (uint16_t)cell;
-            }
+            zd_huf_fill(huf_tab, weights, nwt, mbits, lane, 64);
             __builtin_amdgcn_wave_barrier();
             const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)huf_slot);
             ZTables *T = tabs + sl;
@@ -777,41 +480,18 @@ void k_zparse(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx, const uint8
             const uint8_t *p = in + ip + 3;
             if (lane == 0) {
                 len = b.size; pos = b.seq_off;
-                do {
-                    if (pos >= len) { bstat = ZD_CORRUPT; break; }
-                    const uint32_t b0 = p[pos++];
-                    if (b0 < 128) nseq = b0;
-                    else if (b0 < 255) { if (pos >= len) { bstat = ZD_CORRUPT; break; } nseq = ((b0 - 128) << 8) + p[pos++]; }
-                    else { if (pos + 2 > len) { bstat = ZD_CORRUPT; break; } nseq = p[pos] + ((uint32_t)p[pos + 1] << 8) + 0x7F00; pos += 2; }
-                    if (nseq == 0) { if (pos != len) bstat = ZD_CORRUPT; break; }
-                    if (pos >= len) { bstat = ZD_CORRUPT; break; }
-                    modes = p[pos++];
-                    if (modes & 3) bstat = ZD_CORRUPT;
-                } while (false);
+                if (!zd_seq_header(p, len, pos, nseq, modes) || (nseq == 0 && pos != len) || (modes & 3)) bstat = ZD_CORRUPT;
                 s_cmd[5] = bstat; s_cmd[6] = nseq; s_cmd[7] = modes;
             }
             __builtin_amdgcn_wave_barrier();
             bstat = s_cmd[5]; nseq = s_cmd[6]; modes = s_cmd[7];
             for (int k = 0; k < 3 && bstat == ZD_OK && nseq; k++) {        // LL, OF, ML in stream order
-                const uint32_t mode = (modes >> (6 - 2 * k)) & 3;
+                const uint32_t mode = zd_seq_mode(modes, k);
                 if (mode == 3) { if (slot3[k] == 0xFFFFFFFFu) bstat = ZD_CORRUPT; continue; }
                 if (lane == 0) {
                     uint32_t st2 = ZD_OK, alog_out = 0;
-                    const int16_t *def = k == 0 ? ZD_LL_DEF : (k == 1 ? ZD_OF_DEF : ZD_ML_DEF);
-                    const int def_n = k == 0 ? 36 : (k == 1 ? 29 : 53), def_log = k == 1 ? 5 : 6;
-                    const int max_sym = k == 0 ? 35 : (k == 1 ? 31 : 52), max_log = k == 1 ? 8 : 9;
                     if (!own_slot && next_slot >= x.slot_cap) st2 = ZD_UNSUPPORTED;
-                    else if (mode == 0) {
-                        for (int i = 0; i < def_n; i++) norm[i] = def[i];
-                        if (!zd_fse_build(fse_tab, norm, def_n, def_log, nexts)) st2 = ZD_CORRUPT;
-                        alog_out = (uint32_t)def_log;
-                    } else if (mode == 1) {
-                        if (pos >= len || p[pos] > max_sym) st2 = ZD_CORRUPT; else { fse_tab[0] = p[pos]; pos++; alog_out = 0; }
-                    } else {
-                        int nsym, alog;
-                        const uint32_t used = zd_fse_desc(p + pos, len - pos, norm, &nsym, &alog, max_sym, max_log);
-                        if (!used || !zd_fse_build(fse_tab, norm, nsym, alog, nexts)) st2 = ZD_CORRUPT; else { pos += used; alog_out = (uint32_t)alog; }
-                    }
+                    else if (!zd_seq_table(k, mode, p, len, pos, fse_tab, norm, nexts, alog_out)) st2 = ZD_CORRUPT;
                     s_cmd[5] = st2; s_cmd[3] = alog_out;
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -882,85 +562,46 @@ __global__ void k_zparse_a(ZFrame *__restrict__ frames, ZFrameX *__restrict__ fx
     const uint64_t fcs_want = fr.dst_len;
     const bool open = (fr.out_len & ZF_OPEN) != 0;
     uint32_t status = fr.status; uint64_t ip = 0;
-    if (status == ZD_OK) {
-        if (in_len < 6) status = ZD_CORRUPT;
-        else {
-            const uint32_t magic = in[0] | (in[1] << 8) | (in[2] << 16) | ((uint32_t)in[3] << 24);
-            const uint32_t fhd = in[4];
-            const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3;
-            if (magic != 0xFD2FB528u || (fhd & 0x08)) status = ZD_CORRUPT;
-            else if (dict) status = ZD_UNSUPPORTED;
-            else {
-                ip = 5 + (single ? 0 : 1);
-                const uint32_t fsz = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-                if (ip + fsz > in_len) status = ZD_CORRUPT;
-                else {
-                    uint64_t fcs = 0;
-                    for (uint32_t i = 0; i < fsz; i++) fcs |= (uint64_t)in[ip + i] << (8 * i);
-                    if (fsz == 2) fcs += 256;
-                    if (fsz && (open ? fcs > fcs_want : fcs != fcs_want)) status = ZD_DSTSIZE;
-                    ip += fsz;
-                }
-            }
-        }
-    }
+    if (status == ZD_OK) { uint32_t at = 0; status = zparse_frame_header(in, in_len, open, fcs_want, &at); ip = at; }
     uint32_t nblk = 0, next_slot = 0, huf_slot = 0xFFFFFFFFu, slot3[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     uint64_t lit_pos = 0, seq_pos = 0;
     bool last = status != ZD_OK;
     while (!last) {
         if (nblk >= x.blk_cap) { status = ZD_UNSUPPORTED; break; }
-        if (ip + 3 > in_len) { status = ZD_CORRUPT; break; }
-        const uint32_t bh = in[ip] | (in[ip + 1] << 8) | ((uint32_t)in[ip + 2] << 16);
-        const uint32_t type = (bh >> 1) & 3, size = bh >> 3;
-        if (type == 3 || size > (128u << 10)) { status = ZD_CORRUPT; break; }
-        if (type == 1 ? ip + 4 > in_len : ip + 3 + size > in_len) { status = ZD_CORRUPT; break; }
+        ZdBlockHdr bh;
+        zd_block_header(in + ip, in_len - ip, bh);
+        if (!bh.have || bh.type == 3 || bh.size > ZD_BLOCK_MAX || !bh.fits) { status = ZD_CORRUPT; break; }
+        const uint32_t type = bh.type, size = bh.size;
         ZBlock b;
         b.body = fr.src_off + ip + 3; b.out_off = 0; b.seq_pos = x.seq_base + seq_pos; b.size = size; b.type = type; b.ltype = 0; b.regen = 0; b.streams = 1; b.lit_off = 0; b.lit_csize = 0;
         b.lit_pos = (uint32_t)lit_pos; b.huf_slot = huf_slot; b.slot[0] = slot3[0]; b.slot[1] = slot3[1]; b.slot[2] = slot3[2];
         b.nseq = 0; b.seq_off = 0; b.seq_len = 0; b.frame = f; b.out_len = type < 2 ? size : 0; b.status = 0; b.uses_rep = 0;
         for (int i = 0; i < 7; i++) b.pad[i] = 0;
-        b.pad[0] = bh & 1; b.pad[2] = (uint32_t)(lit_pos >> 32); b.pad[3] = next_slot;
+        b.pad[0] = bh.last; b.pad[2] = (uint32_t)(lit_pos >> 32); b.pad[3] = next_slot;
         uint32_t regen = 0, nseq = 0;
         if (type == 2) {
             const uint8_t *p = in + ip + 3; const uint32_t len = size;
-            if (len < 1) { status = ZD_CORRUPT; break; }
-            const uint32_t ltype = p[0] & 3, sf = (p[0] >> 2) & 3;
-            uint32_t comp = 0, hdr;
-            if (ltype < 2) {
-                if (sf == 0 || sf == 2) { regen = p[0] >> 3; hdr = 1; }
-                else if (sf == 1) { if (len < 2) { status = ZD_CORRUPT; break; } regen = (p[0] >> 4) + ((uint32_t)p[1] << 4); hdr = 2; }
-                else { if (len < 3) { status = ZD_CORRUPT; break; } regen = (p[0] >> 4) + ((uint32_t)p[1] << 4) + ((uint32_t)p[2] << 12); hdr = 3; }
-            } else {
-                if (len < 5) { status = ZD_CORRUPT; break; }
-                uint64_t v = 0; for (int i = 0; i < 5; i++) v |= (uint64_t)p[i] << (8 * i);
-                if (sf == 0) { hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-                else if (sf == 1) { hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-                else if (sf == 2) { hdr = 4; regen = (v >> 4) & 0x3FFF; comp = (v >> 18) & 0x3FFF; }
-                else { hdr = 5; regen = (v >> 4) & 0x3FFFF; comp = (v >> 22) & 0x3FFFF; }
-            }
-            if (regen > (128u << 10) || lit_pos + regen > cap) { status = regen > (128u << 10) ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
-            uint32_t pos = hdr + (ltype == 0 ? regen : (ltype == 1 ? 1u : comp));
-            if (pos >= len) { status = ZD_CORRUPT; break; }                 // (the sequences section holds at least its count)
-            const uint32_t b0 = p[pos++];
-            if (b0 < 128) nseq = b0;
-            else if (b0 < 255) { if (pos >= len) { status = ZD_CORRUPT; break; } nseq = ((b0 - 128) << 8) + p[pos++]; }
-            else { if (pos + 2 > len) { status = ZD_CORRUPT; break; } nseq = p[pos] + ((uint32_t)p[pos + 1] << 8) + 0x7F00; pos += 2; }
-            uint32_t modes = 0xFF;                                          // (no sequences: nothing is defined)
-            if (nseq) { if (pos >= len) { status = ZD_CORRUPT; break; } modes = p[pos]; }
+            ZdLitHdr l;
+            if (!zd_literals_header(p, len, l)) { status = ZD_CORRUPT; break; }
+            regen = l.regen;
+            if (regen > ZD_BLOCK_MAX || lit_pos + regen > cap) { status = regen > ZD_BLOCK_MAX ? ZD_CORRUPT : (fcs_want > cap ? ZD_UNSUPPORTED : ZD_DSTSIZE); break; }
+            const uint32_t ltype = l.ltype;
+            uint32_t pos = l.size, modes;                                   // (no sequences: modes 0, nothing is defined)
+            if (!zd_seq_header(p, len, pos, nseq, modes)) { status = ZD_CORRUPT; break; }
             if (seq_pos + nseq > x.seq_cap) { status = ZD_UNSUPPORTED; break; }
             const bool def_tree = ltype == 2;
             bool own = def_tree;
-            for (int k = 0; k < 3; k++) if (nseq && ((modes >> (6 - 2 * k)) & 3) != 3) own = true;
+            for (int k = 0; k < 3; k++) if (nseq && zd_seq_mode(modes, k) != 3) own = true;
             if (own && next_slot >= x.slot_cap) { status = ZD_UNSUPPORTED; break; }
             if (ltype == 3 && huf_slot == 0xFFFFFFFFu) { status = ZD_CORRUPT; break; }
             if (def_tree) huf_slot = x.slot_base + next_slot;
-            for (int k = 0; k < 3; k++) if (nseq && ((modes >> (6 - 2 * k)) & 3) != 3) slot3[k] = x.slot_base + next_slot;
+            for (int k = 0; k < 3; k++) if (nseq && zd_seq_mode(modes, k) != 3) slot3[k] = x.slot_base + next_slot;
             if (own) next_slot++;
         }
         const uint32_t bi = x.blk_base + nblk;
         blocks[bi] = b;
         one_list[atomicAdd(one_count, 1u)] = bi;
-        last = (bh & 1) != 0;
+        last = bh.last != 0;
         ip += 3 + (type == 1 ? 1 : size);
         if (type == 2) { lit_pos += regen; seq_pos += nseq; }
         nblk++;
@@ -999,21 +640,9 @@ void k_zhuf(const uint32_t *__restrict__ huf_list, const ZWork *__restrict__ wor
     if (!valid) return;
     const uint8_t *cs = src + b.body + b.lit_off;
     const uint32_t cl = b.lit_csize;
-    uint32_t s_off = 0, s_len = cl, o_off = 0, o_len = b.regen;
-    bool ok = true;
-    if (b.streams == 4) {
-        if (cl < 6) ok = false;
-        else {
-            const uint32_t l1 = cs[0] | (cs[1] << 8), l2 = cs[2] | (cs[3] << 8), l3 = cs[4] | (cs[5] << 8);
-            const uint32_t seg = (b.regen + 3) / 4;
-            if (6 + l1 + l2 + l3 > cl || seg * 3 > b.regen) ok = false;
-            else {
-                s_off = 6 + (sidx > 0 ? l1 : 0) + (sidx > 1 ? l2 : 0) + (sidx > 2 ? l3 : 0);
-                s_len = sidx == 0 ? l1 : (sidx == 1 ? l2 : (sidx == 2 ? l3 : cl - 6 - l1 - l2 - l3));
-                o_off = sidx * seg; o_len = sidx < 3 ? seg : b.regen - 3 * seg;
-            }
-        }
-    }
+    ZdStream hs;
+    bool ok = zd_huf_streams(cs, cl, b.regen, b.streams, sidx, hs);
+    const uint32_t s_off = hs.off, s_len = hs.len, o_off = hs.out_off, o_len = hs.out_len;
     if (ok) {
         const ZTables *T = tabs + b.huf_slot;
         const uint32_t mb = T->hufbits;
@@ -1407,23 +1036,20 @@ void launch_zexec_groups(ZFrame *frames, const ZFrameX *fx, uint32_t n, ZBlock *
 // SEG_SIZE bytes (a single-frame entry -- what the reference writes -- holds all of it); k_zdec verifies the sizes.
 // walk one frame starting at p[ip]: header, blocks, optional checksum; returns its end or 0 when it is malformed / truncated
 __device__ uint64_t zscan_frame_end(const uint8_t *p, uint64_t ip, uint64_t len) {
-    uint64_t q = ip;
-    if (q + 6 > len) return 0;
-    const uint32_t magic = p[q] | (p[q + 1] << 8) | (p[q + 2] << 16) | ((uint32_t)p[q + 3] << 24);
-    if (magic != 0xFD2FB528u) return 0;
-    const uint32_t fhd = p[q + 4];
-    const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3;
-    q += 5 + (single ? 0 : 1) + (dict == 0 ? 0 : (dict == 1 ? 1 : (dict == 2 ? 2 : 4)));
-    q += fcs_flag == 0 ? single : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8));
+    if (ip + 6 > len) return 0;
+    ZdFrameHdr h;
+    zd_frame_header(p + ip, len - ip, h);
+    if (!h.magic) return 0;
+    uint64_t q = ip + h.len;                   // (a dictionary id is stepped over and the reserved bit not looked at: the kernel that decodes the frame answers for both)
     for (;;) {
         if (q + 3 > len) return 0;
-        const uint32_t bh = p[q] | (p[q + 1] << 8) | ((uint32_t)p[q + 2] << 16);
-        const uint32_t type = (bh >> 1) & 3, size = bh >> 3;
-        q += 3 + (type == 1 ? 1 : size);
-        if (type == 3 || q > len) return 0;
-        if (bh & 1) break;
+        ZdBlockHdr b;
+        zd_block_header(p + q, len - q, b);
+        if (b.type == 3 || !b.fits) return 0;
+        q += 3 + b.body;
+        if (b.last) break;
     }
-    if ((fhd >> 2) & 1) q += 4;
+    if (h.checksum) q += 4;
     return q > len ? 0 : q;
 }
 
@@ -1441,7 +1067,7 @@ __global__ void k_zscan(const ZEntry *__restrict__ ents, uint32_t n, const uint8
     // frame slots planned for the entry are void.
     if (nfr > 1 && zscan_frame_end(p, 0, len) == len) {
         ZFrame fr; fr.src_off = en.src_off; fr.dst_off = en.dst_off; fr.src_len = len; fr.out_len = en.open ? ZF_OPEN : 0u;
-        fr.dst_len = en.raw_len; fr.status = 2u;
+        fr.dst_len = en.raw_len; fr.status = ZD_UNSUPPORTED;
         if (fx) {                                                    // (content and compressed bytes of any size: the header walk and the literal scratch count in 64 bits, the executor works in windows)
             ZFrameX x = fx[en.first_frame];
             uint64_t nb = 0, ns = 0, nq = 0;
@@ -1449,27 +1075,27 @@ __global__ void k_zscan(const ZEntry *__restrict__ ents, uint32_t n, const uint8
             x.blk_cap = (uint32_t)(nb < 0x7FFFFFFFull ? nb : 0x7FFFFFFFull); x.slot_cap = (uint32_t)(ns < 0x7FFFFFFFull ? ns : 0x7FFFFFFFull);
             x.seq_cap = (uint32_t)(nq < 0x7FFFFFFFull ? nq : 0x7FFFFFFFull);
             fx[en.first_frame] = x;
-            fr.status = 0u;
+            fr.status = ZD_OK;
         }
         frames[en.first_frame] = fr;
-        fr.src_len = 0; fr.dst_len = 0; fr.status = 4;              // ZD_VOID
+        fr.src_len = 0; fr.dst_len = 0; fr.status = ZD_VOID;
         for (uint32_t g = 1; g < nfr; g++) frames[en.first_frame + g] = fr;
         return;
     }
     uint64_t ip = 0;
     for (uint32_t f = 0; f < nfr; f++) {
-        ZFrame fr; fr.src_off = en.src_off + ip; fr.dst_off = en.dst_off + (uint64_t)f * SEG_SIZE; fr.status = 0; fr.out_len = 0;
+        ZFrame fr; fr.src_off = en.src_off + ip; fr.dst_off = en.dst_off + (uint64_t)f * SEG_SIZE; fr.status = ZD_OK; fr.out_len = 0;
         const uint64_t done = (uint64_t)f * SEG_SIZE;
         fr.dst_len = (uint32_t)(en.raw_len - done < SEG_SIZE || f + 1 == nfr ? (en.raw_len > done ? en.raw_len - done : 0) : SEG_SIZE);
-        if (en.raw_len - done > 0xFFFFFFFFull && f + 1 == nfr) fr.status = 2;
+        if (en.raw_len - done > 0xFFFFFFFFull && f + 1 == nfr) fr.status = ZD_UNSUPPORTED;
         const uint64_t q = zscan_frame_end(p, ip, len);
-        if (!q) { fr.status = 1; fr.src_len = 0; frames[en.first_frame + f] = fr; for (uint32_t g = f + 1; g < nfr; g++) { fr.src_off = 0; frames[en.first_frame + g] = fr; } return; }
+        if (!q) { fr.status = ZD_CORRUPT; fr.src_len = 0; frames[en.first_frame + f] = fr; for (uint32_t g = f + 1; g < nfr; g++) { fr.src_off = 0; frames[en.first_frame + g] = fr; } return; }
         fr.src_len = q - ip;                                          // (4 GiB and more, with at most 1 MiB of content: k_zparse leaves it to the one-workgroup kernel)
         if (en.open && f + 1 == nfr) fr.out_len = ZF_OPEN;             // the last frame of a stream of unknown size
         frames[en.first_frame + f] = fr;
         ip = q;
     }
-    if (ip != len && nfr) frames[en.first_frame + nfr - 1].status = 1;      // bytes left over behind the last frame
+    if (ip != len && nfr) frames[en.first_frame + nfr - 1].status = ZD_CORRUPT;   // bytes left over behind the last frame
 }
 
 // number of frames of every entry's payload (0: malformed) -- the planning step for streams that carry no size (solid)
@@ -1480,13 +1106,10 @@ __global__ void k_zcount(const ZEntry *__restrict__ ents, uint32_t n, const uint
     const uint8_t *p = src + en.src_off;
     uint64_t ip = 0; uint32_t cnt = 0;
     while (ip < en.src_len) {
-        if (ip + 8 <= en.src_len && ((p[ip] | (p[ip + 1] << 8) | (p[ip + 2] << 16) | ((uint32_t)p[ip + 3] << 24)) & 0xFFFFFFF0u) == 0x184D2A50u) {   // a skippable frame: not counted
-            const uint64_t sz = (uint64_t)p[ip + 4] | ((uint64_t)p[ip + 5] << 8) | ((uint64_t)p[ip + 6] << 16) | ((uint64_t)p[ip + 7] << 24);
-            if (ip + 8 + sz > en.src_len) { cnt = 0; break; }
-            ip += 8 + sz;
-            continue;
-        }
-        const uint64_t q = zscan_frame_end(p, ip, en.src_len);
+        uint64_t skip = 0;
+        const int sk = zd_skippable(p + ip, en.src_len - ip, &skip);
+        if (sk == ZD_SKIP_WHOLE) { ip += skip; continue; }              // a skippable frame: not counted
+        const uint64_t q = sk ? 0 : zscan_frame_end(p, ip, en.src_len);
         if (!q) { cnt = 0; break; }
         ip = q; cnt++;
         if (cnt == 0x7FFFFFFFu) { cnt = 0; break; }
@@ -1509,24 +1132,14 @@ __global__ void k_zlist(const uint8_t *__restrict__ src, uint64_t base, uint64_t
     const uint8_t *p = src + base;
     uint64_t ip = ip0; uint32_t cnt = 0; uint64_t bad = 0;
     while (ip < len && cnt < cap) {
-        if (ip + 4 > len) { bad = 1; break; }
-        const uint32_t magic = p[ip] | (p[ip + 1] << 8) | (p[ip + 2] << 16) | ((uint32_t)p[ip + 3] << 24);
-        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
-            if (ip + 8 > len) { bad = 1; break; }
-            const uint64_t sz = (uint64_t)p[ip + 4] | ((uint64_t)p[ip + 5] << 8) | ((uint64_t)p[ip + 6] << 16) | ((uint64_t)p[ip + 7] << 24);
-            if (ip + 8 + sz > len) { bad = 1; break; }
-            ip += 8 + sz;
-            continue;
-        }
-        const uint64_t q = zscan_frame_end(p, ip, len);
+        uint64_t skip = 0;
+        const int sk = zd_skippable(p + ip, len - ip, &skip);
+        if (sk == ZD_SKIP_WHOLE) { ip += skip; continue; }
+        const uint64_t q = sk ? 0 : zscan_frame_end(p, ip, len);
         if (!q) { bad = 1; break; }
-        const uint32_t fhd = p[ip + 4];
-        const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3;
-        const uint64_t fp = ip + 5 + (single ? 0 : 1) + (dict == 0 ? 0 : (dict == 1 ? 1 : (dict == 2 ? 2 : 4)));
-        const uint32_t fb = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-        uint64_t fcs = ~0ull;
-        if (fb) { fcs = 0; for (uint32_t i = 0; i < fb; i++) fcs |= (uint64_t)p[fp + i] << (8 * i); if (fb == 2) fcs += 256; }
-        items[cnt].off = base + ip; items[cnt].len = q - ip; items[cnt].fcs = fcs;
+        ZdFrameHdr h;
+        zd_frame_header(p + ip, len - ip, h);                           // (whole: the walk went through it)
+        items[cnt].off = base + ip; items[cnt].len = q - ip; items[cnt].fcs = h.fcs_bytes ? h.fcs : ~0ull;
         cnt++; ip = q;
     }
     hdr[0] = cnt; hdr[1] = ip; hdr[2] = bad;
@@ -1548,51 +1161,26 @@ __global__ void k_zsize(const uint8_t *__restrict__ src, uint64_t base, uint64_t
     uint64_t ip = 0, total = 0, nfr = 0, last = 0;
     uint32_t exact = 1, bad = 0;
     while (ip < len && !bad) {
-        if (len - ip < 4) { bad = 1; break; }
-        const uint32_t magic = p[ip] | (p[ip + 1] << 8) | (p[ip + 2] << 16) | ((uint32_t)p[ip + 3] << 24);
-        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
-            if (len - ip < 8) { bad = 1; break; }
-            const uint64_t sz = (uint64_t)p[ip + 4] | ((uint64_t)p[ip + 5] << 8) | ((uint64_t)p[ip + 6] << 16) | ((uint64_t)p[ip + 7] << 24);
-            if (sz > len - ip - 8) { bad = 1; break; }
-            ip += 8 + sz;
-            continue;
-        }
-        if (magic != 0xFD2FB528u || len - ip < 5) { bad = 1; break; }
-        const uint32_t fhd = p[ip + 4];
-        const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, dict = fhd & 3, cksum = (fhd >> 2) & 1;
-        if (fhd & 8) { bad = 1; break; }                                    // reserved bit
-        uint64_t q = ip + 5, wsize = 0;
-        if (!single) {
-            if (q >= len) { bad = 1; break; }
-            const uint32_t wd = p[q++];
-            const uint64_t wbase = 1ull << (10 + (wd >> 3));
-            wsize = wbase + (wbase >> 3) * (wd & 7);
-        }
-        q += dict == 0 ? 0 : (dict == 1 ? 1 : (dict == 2 ? 2 : 4));
-        const uint32_t fb = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-        if (q > len || len - q < fb) { bad = 1; break; }
-        uint64_t fcs = 0;
-        for (uint32_t i = 0; i < fb; i++) fcs |= (uint64_t)p[q + i] << (8 * i);
-        if (fb == 2) fcs += 256;
-        q += fb;
-        if (single) wsize = fcs;
-        const uint64_t bms = wsize < (128u << 10) ? wsize : (128u << 10);
+        uint64_t skip = 0;
+        const int sk = zd_skippable(p + ip, len - ip, &skip);
+        if (sk == ZD_SKIP_WHOLE) { ip += skip; continue; }
+        ZdFrameHdr h;
+        zd_frame_header(p + ip, len - ip, h);
+        if (sk || !h.have || !h.magic || h.reserved || !h.complete) { bad = 1; break; }
+        uint64_t q = ip + h.len;
+        const uint64_t bms = h.window < ZD_BLOCK_MAX ? h.window : ZD_BLOCK_MAX;
         uint64_t ex = 0, bnd = 0;                                           // raw + RLE content; compressed blocks' bound
         for (;;) {
-            if (len - q < 3) { bad = 1; break; }
-            const uint32_t bh = p[q] | (p[q + 1] << 8) | ((uint32_t)p[q + 2] << 16);
-            const uint32_t type = (bh >> 1) & 3, size = bh >> 3;
-            q += 3;
-            if (type == 3) { bad = 1; break; }
-            const uint64_t body = type == 1 ? 1u : size;
-            if (body > len - q) { bad = 1; break; }
-            if (type == 2) bnd += bms; else ex += size;
-            q += body;
-            if (bh & 1) break;
+            ZdBlockHdr b;
+            zd_block_header(p + q, len - q, b);
+            if (!b.have || b.type == 3 || !b.fits) { bad = 1; break; }
+            if (b.type == 2) bnd += bms; else ex += b.size;
+            q += 3 + b.body;
+            if (b.last) break;
         }
         if (bad) break;
-        if (cksum) { if (len - q < 4) { bad = 1; break; } q += 4; }
-        if (fb) { if (fcs < ex || fcs - ex > bnd) { bad = 1; break; } last = fcs; }
+        if (h.checksum) { if (len - q < 4) { bad = 1; break; } q += 4; }
+        if (h.fcs_bytes) { if (h.fcs < ex || h.fcs - ex > bnd) { bad = 1; break; } last = h.fcs; }
         else { last = ex + bnd; if (bnd) exact = 0; }
         total += last;
         ip = q; nfr++;
@@ -1650,7 +1238,7 @@ void k_zxxh(ZFrame *__restrict__ frames, uint32_t n, const uint8_t *__restrict__
     h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
     const uint8_t *c4 = src + fr.src_off + fr.src_len - 4;
     const uint32_t stored = (uint32_t)c4[0] | ((uint32_t)c4[1] << 8) | ((uint32_t)c4[2] << 16) | ((uint32_t)c4[3] << 24);
-    if (stored != (uint32_t)h) frames[f].status = 1;                   // corrupt: the content does not match its checksum
+    if (stored != (uint32_t)h) frames[f].status = ZD_CORRUPT;          // the content does not match its checksum
 }
 void launch_zxxh(ZFrame *frames, uint32_t n, const uint8_t *src, const uint8_t *dst, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_zxxh, dim3((n + 15) / 16), dim3(64), 0, st, frames, n, src, dst);
