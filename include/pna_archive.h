@@ -80,6 +80,11 @@ int  pna_kdf_derive(int kdf, const void *password, size_t password_len, const vo
 int  pna_create_archive_encrypted_ex(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
                                      const void *const *src, const size_t *src_len, const void *password, size_t password_len,
                                      int cipher_mode, int kdf, uint32_t rounds, pna_sink_fn sink, void *user);
+/* ... with the block cipher named as well (`--aes` / `--camellia`): encryption PNA_ENC_AES -- the call above -- or PNA_ENC_CAMELLIA, which is
+ * PNA_E_UNSUPPORTED unless the context has option "camellia" = 1 (include/pna_gpu.h). */
+int  pna_create_archive_encrypted_with(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
+                                       const void *const *src, const size_t *src_len, const void *password, size_t password_len,
+                                       int encryption, int cipher_mode, int kdf, uint32_t rounds, pna_sink_fn sink, void *user);
 
 /* `pna create --split`: re-frame ONE archive image into parts of at most max_part_bytes (SplitParts, lib/src/archive/split_parts.rs:
  * signature + AHED(archive number) ... [ANXT] AEND per part; chunks that fit keep their bytes, FDAT / SDAT chunks are cut at the budget

@@ -121,6 +121,10 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
  *   "xz_encode" [PNA_XZ_ENCODE]           0 (default): PNA_ALGO_XZ is PNA_E_UNSUPPORTED on every compress entry point; 1: the batch and the non-solid archive entry points write
  *                                         xz.  An option because these streams are multi-block with per-chunk state resets: their bytes differ from the reference's encoder
  *                                         (one block, one running model) and their ratio is lower -- a host chooses that knowingly ("XZ ON THE WRITE SIDE" below)
+ *   "camellia" [PNA_CAMELLIA]             0 (default): PNA_ENC_CAMELLIA is PNA_E_UNSUPPORTED on every entry point that takes a cipher, and the read side refuses / reports
+ *                                         PNA_VERIFY_UNSUPPORTED for Camellia entries; 1: Camellia-256 in CTR, CBC and GCM STREAM wherever AES-256 is taken -- the archive
+ *                                         entry points (solid: CTR and GCM), pna_gpu_cipher_apply_device (CTR, CBC encryption), and extract / verify / diff / extract-select
+ *                                         (k_camellia.hip).  An option so that a host which keeps the reference's CipherWriter for Camellia sees no change
  *   "max_chunk_size" [PNA_MAX_CHUNK_SIZE] (FDAT chunk size of the entry points without such a parameter), "sub_mib" [PNA_SUB_MIB], "stage_threads" [PNA_STAGE_THREADS],
  *   "diff_slot_mib" [PNA_DIFF_SLOT_MIB]   pna_gpu_diff_archive_host: MiB of each of the two page-locked (and two device) slots the files' bytes travel through (256)
  *   "extract_win_mib" [PNA_EXTRACT_WIN_MIB], "batch_piece_mib" [PNA_BATCH_PIECE_MIB], "inflate_serial" [PNA_INFLATE_SERIAL],
@@ -224,14 +228,14 @@ int  pna_gpu_create_archive_device(pna_gpu_ctx *ctx, int algo, int level, size_t
  * FDAT(ciphertext) | FEND (lib/src/entry.rs:895-911; the IV is its own data piece: prepend_data_prefix, lib/src/entry/builder.rs:62-69). */
 #define PNA_ENC_NONE      0     /* == Encryption::to_byte(), lib/src/entry/options.rs */
 #define PNA_ENC_AES       1
-#define PNA_ENC_CAMELLIA  2     /* not offered: PNA_E_UNSUPPORTED */
+#define PNA_ENC_CAMELLIA  2     /* Camellia-256, in the modes and on the entry points of AES-256 -- on a context with option "camellia" = 1; PNA_E_UNSUPPORTED unless option "camellia" is set */
 #define PNA_MODE_CBC      0     /* == CipherMode::to_byte() */
 #define PNA_MODE_CTR      1
 #define PNA_MODE_GCM      2     /* "GCM STREAM": lib/src/cipher/aead.rs, lib/src/cipher/gcm.rs */
 typedef struct {
     int encryption;             /* PNA_ENC_* */
     int cipher_mode;            /* PNA_MODE_* */
-    uint8_t key[32];            /* AES-256 key; GCM: K_master, the per-entry stream keys are derived from it (HKDF) */
+    uint8_t key[32];            /* AES-256 / Camellia-256 key; GCM: K_master, the per-entry stream keys are derived from it (HKDF) */
     const char *phsf;           /* body of the PHSF chunk */
     const uint8_t *ivs;         /* CBC / CTR: n x 16 bytes; GCM: n x 39 bytes (salt[32] || nonce_prefix[7] per entry); or NULL */
     uint32_t gcm_segment_size;  /* GCM: segment size written into the stream header (0 = 1 MiB, the reference's DEFAULT_SEGMENT_SIZE; at most 64 MiB) */
@@ -327,7 +331,7 @@ int  pna_gpu_create_solid_archive_host(pna_gpu_ctx *ctx, int algo, int level, si
  * cut from the whole compressed stream (GcmEncryptWriter, lib/src/cipher/gcm.rs:45-90) -- each window but the last holds back, in device memory, the
  * 1 .. gcm_segment_size bytes of its output not yet known to form a non-final segment and puts them in front of the next window's output.  Page-locked
  * memory (pna_gpu_debug_pinned_bytes): about four windows, plus two GCM segments (the output slots hold the carry); device memory: one segment of carry
- * on top of the plain form.  cipher == NULL or PNA_ENC_NONE: pna_gpu_create_solid_archive_host.  CBC and Camellia: PNA_E_UNSUPPORTED. */
+ * on top of the plain form.  cipher == NULL or PNA_ENC_NONE: pna_gpu_create_solid_archive_host.  CBC: PNA_E_UNSUPPORTED; Camellia: PNA_E_UNSUPPORTED unless option "camellia" = 1 (then CTR and GCM, like AES). */
 int  pna_gpu_create_solid_archive_enc_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
                                            const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
                                            pna_sink_fn sink, void *user);
@@ -430,7 +434,7 @@ int  pna_gpu_open_size_device(pna_gpu_ctx *ctx, int algo, const void *d_src, uin
  * and zstd / deflate / xz / store decoding run on the device; entries without fSIZ are sized by the decoder.  cb is called once per entry in archive order (kind =
  * DataKind::to_byte(): 0 file, 1 directory, ...); `data` is valid during the call.  PNA_E_INVAL: structural damage, CRC mismatch, corrupt
  * stream, wrong password (GCM key confirmation, CBC padding), authentication failure; PNA_E_UNSUPPORTED: multipart archives,
- * Camellia, xz streams outside the scope stated at pna_gpu_decompress_batch, solid streams with inner entries that are not stored.  Solid entries (SHED [PHSF] SDAT* SEND; plain or AES CTR / CBC / GCM):
+ * Camellia unless option "camellia" = 1 (then decrypted like AES, in the same windows), xz streams outside the scope stated at pna_gpu_decompress_batch, solid streams with inner entries that are not stored.  Solid entries (SHED [PHSF] SDAT* SEND; plain or AES CTR / CBC / GCM):
  * SDAT CRCs and the inner FDAT CRCs on the device.  A solid stream or an entry without fSIZ has no recorded size: it is measured first
  * (pna_gpu_open_size_device), decoded into device memory of that size and copied once to host memory (an N-GiB solid stream: N GiB of host memory,
  * besides the archive); PNA_E_NOMEM, naming the size, when the device cannot hold it. */
@@ -468,10 +472,10 @@ int  pna_gpu_extract_archive_host(pna_gpu_ctx *ctx, const void *archive, size_t 
 #define PNA_VERIFY_BAD_AUTH        4    /* GCM: key confirmation or a segment tag */
 #define PNA_VERIFY_BAD_DECRYPT     5    /* CBC length / PKCS#7 padding */
 #define PNA_VERIFY_BAD_STREAM      6    /* corrupt zstd / zlib stream, content checksum, Adler-32 */
-#define PNA_VERIFY_UNSUPPORTED     7    /* Camellia, an xz stream with a SHA-256 check or a filter chain, ...: what this build does not decode */
+#define PNA_VERIFY_UNSUPPORTED     7    /* Camellia unless option "camellia" = 1, an xz stream with a SHA-256 check or a filter chain, ...: what this build does not decode */
 /* flags of one record */
 #define PNA_VERIFY_SIZE_HINT       1u   /* fSIZ present and != the decoded size (a warning; status stays OK) */
-#define PNA_VERIFY_UNAUTHENTICATED 2u   /* AES CBC / CTR: a wrong password cannot be told from damage (verify.rs is_unauthenticated) */
+#define PNA_VERIFY_UNAUTHENTICATED 2u   /* AES / Camellia CBC / CTR: a wrong password cannot be told from damage (verify.rs is_unauthenticated) */
 #define PNA_VERIFY_KIND_SOLID  (-1)     /* record of a whole solid block (fast mode, skipped, or failed) */
 #define PNA_VERIFY_KIND_BROKEN (-2)     /* chunks that belong to no readable entry header */
 typedef struct { uint64_t total, ok, failed, skipped, unsupported; uint32_t unauthenticated_failure, broken; } pna_verify_summary;

@@ -63,7 +63,7 @@ class DecodeForms(ctypes.Structure):
                                                 "inflate_lane_streams", "inflate_chunk_streams")]
 
 
-ENC_NONE, ENC_AES, ENC_CAMELLIA = 0, 1, 2          # Encryption::to_byte()
+ENC_NONE, ENC_AES, ENC_CAMELLIA = 0, 1, 2          # Encryption::to_byte(); ENC_CAMELLIA: written and read on a context with set_option("camellia", 1), E_UNSUPPORTED otherwise
 MODE_CBC, MODE_CTR, MODE_GCM = 0, 1, 2             # CipherMode::to_byte()
 
 
@@ -190,7 +190,7 @@ EXPORTS = [
     # include/pna_archive.h
     "pna_crc32", "pna_archive_new", "pna_archive_add_file", "pna_archive_add_dir", "pna_archive_add_solid",
     "pna_archive_inner_entry_bytes", "pna_archive_finalize", "pna_archive_abort", "pna_create_archive",
-    "pna_kdf_pbkdf2_sha256", "pna_create_archive_encrypted", "pna_create_archive_encrypted_ex", "pna_kdf_derive", "pna_kdf_argon2", "pna_split_archive", "pna_join_parts",
+    "pna_kdf_pbkdf2_sha256", "pna_create_archive_encrypted", "pna_create_archive_encrypted_ex", "pna_create_archive_encrypted_with", "pna_kdf_derive", "pna_kdf_argon2", "pna_split_archive", "pna_join_parts",
     "pna_archive_seek_to_end", "pna_archive_list_entries",
     # streaming entries, parts, append (include/pna_gpu.h)
     "pna_gpu_create_archive_part_host", "pna_gpu_create_archive_multi_host", "pna_gpu_append_archive_host", "pna_gpu_stream_entry_begin", "pna_gpu_stream_entry_write",
@@ -358,6 +358,9 @@ def load_library() -> ctypes.CDLL:
     L.pna_create_archive_encrypted_ex.restype = ctypes.c_int
     L.pna_create_archive_encrypted_ex.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
                                                   ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_int, ctypes.c_int, u32, SINK_FN, vp]
+    L.pna_create_archive_encrypted_with.restype = ctypes.c_int
+    L.pna_create_archive_encrypted_with.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
+                                                    ctypes.POINTER(sz), ctypes.c_char_p, sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32, SINK_FN, vp]
     L.pna_kdf_derive.restype = ctypes.c_int
     L.pna_kdf_derive.argtypes = [ctypes.c_int, ctypes.c_char_p, sz, ctypes.c_char_p, sz, u32, ctypes.c_char_p, ctypes.c_char_p, sz]
     L.pna_gpu_create_solid_archive_enc_host.restype = ctypes.c_int
@@ -1034,8 +1037,10 @@ def kdf_derive(kdf: str, password: bytes, salt: bytes, rounds: int = 0):
 
 def create_archive_encrypted(ctx: Context, names: Sequence[str], entries: Sequence[bytes], password: bytes, algo: int = ALGO_ZSTD,
                              level: int = LEVEL_DEFAULT, mode: int = MODE_CTR, rounds: int = 0, cipher: Optional[Cipher] = None,
-                             solid: bool = False, kdf: str = "pbkdf2") -> bytes:
+                             solid: bool = False, kdf: str = "pbkdf2", encryption: int = ENC_AES) -> bytes:
     """`pna create [--solid] --aes [ctr|cbc|gcm] [--argon2 | --pbkdf2]`: key derivation on the host, compression + cipher + framing on the device.
+    encryption: ENC_AES (default) or ENC_CAMELLIA (`--camellia`; on a context with set_option("camellia", 1), PNA_E_UNSUPPORTED otherwise); with
+    `cipher` it is the cipher's own that counts.
     kdf: "pbkdf2" (PBKDF2-SHA256, `rounds`, 0 = 600 000) or "argon2id" (m=19456, t=2, p=1, the reference's default).  solid: one cipher stream
     over the solid stream, CTR or GCM (pna_gpu_create_solid_archive_enc_host).  With `cipher` the caller supplies key / PHSF / IVs itself
     (pna_gpu_create_archive_enc_host, or the solid form: one IV / one salt || nonce prefix)."""
@@ -1059,6 +1064,9 @@ def create_archive_encrypted(ctx: Context, names: Sequence[str], entries: Sequen
     elif cipher is not None:
         cs = cipher.struct(n)
         rc = L.pna_gpu_create_archive_enc_host(ctx._h, algo, level, n, a_names, a_src, a_len, ctypes.byref(cs), cb, None)
+    elif encryption != ENC_AES:
+        rc = L.pna_create_archive_encrypted_with(ctx._h, algo, level, 1 if solid else 0, n, a_names, a_src, a_len, bytes(password), len(password),
+                                                 encryption, mode, KDFS[kdf], rounds, cb, None)
     elif solid or kdf != "pbkdf2":
         rc = L.pna_create_archive_encrypted_ex(ctx._h, algo, level, 1 if solid else 0, n, a_names, a_src, a_len, bytes(password), len(password),
                                                mode, KDFS[kdf], rounds, cb, None)
@@ -1071,7 +1079,8 @@ def create_archive_encrypted(ctx: Context, names: Sequence[str], entries: Sequen
 
 def extract_archive(ctx: Context, archive: bytes, password: Optional[bytes] = None):
     """`pna extract` for a non-solid archive (pna_gpu_extract_archive_host): returns [(name, kind, data)] in archive order; chunk CRCs
-    are verified (data chunks on the device), entries and solid streams are decrypted (AES CTR / CBC / GCM STREAM) and decoded on the device."""
+    are verified (data chunks on the device), entries and solid streams are decrypted (AES -- with option "camellia" also Camellia -- in CTR / CBC /
+    GCM STREAM) and decoded on the device."""
     out = []
 
     def _cb(_u, idx, name, kind, data, n):

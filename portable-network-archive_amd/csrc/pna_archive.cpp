@@ -610,12 +610,18 @@ extern "C" int pna_kdf_derive(int kdf, const void *password, size_t password_len
 extern "C" int pna_create_archive_encrypted_ex(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
                                                const void *const *src, const size_t *src_len, const void *password, size_t password_len,
                                                int cipher_mode, int kdf, uint32_t rounds, pna_sink_fn sink, void *user) {
+    return pna_create_archive_encrypted_with(ctx, algo, level, solid, n, names, src, src_len, password, password_len, PNA_ENC_AES, cipher_mode, kdf, rounds, sink, user);
+}
+// ... with the block cipher named too: `--aes` or `--camellia` (PNA_ENC_CAMELLIA: on a context with option "camellia" = 1)
+extern "C" int pna_create_archive_encrypted_with(pna_gpu_ctx *ctx, int algo, int level, int solid, size_t n, const char *const *names,
+                                                 const void *const *src, const size_t *src_len, const void *password, size_t password_len,
+                                                 int encryption, int cipher_mode, int kdf, uint32_t rounds, pna_sink_fn sink, void *user) {
     if (!ctx) return PNA_E_NODEVICE;
     if (!sink || (!password && password_len)) return PNA_E_INVAL;
     uint8_t salt[16];
     if (getrandom(salt, sizeof salt, 0) != (ssize_t)sizeof salt) return PNA_E_INVAL;
     pna_gpu_cipher ci{};
-    ci.encryption = PNA_ENC_AES; ci.cipher_mode = cipher_mode; ci.ivs = nullptr;
+    ci.encryption = encryption; ci.cipher_mode = cipher_mode; ci.ivs = nullptr;
     char phsf[128];
     int rc = pna_kdf_derive(kdf, password, password_len, salt, sizeof salt, rounds, ci.key, phsf, sizeof phsf);
     if (rc) return rc;

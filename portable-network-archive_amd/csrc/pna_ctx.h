@@ -21,6 +21,7 @@
 #include <memory>
 #include <sys/random.h>
 #include "pna_dev.h"
+#include "camellia_core.h"
 #include "../../include/pna_gpu.h"
 #include "../../include/pna_archive.h"
 
@@ -166,6 +167,11 @@ void launch_aes_cbc_dec(const CipherUnit *units, uint32_t n, const uint8_t *ivs,
 size_t frame_entry_prefix_enc_bound(const char *name, const char *phsf);
 void launch_aes_ctr(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *tabs, uint8_t *buf, const AesKey &key, const AesKey *keys, hipStream_t st);
 void launch_aes_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *tabs, uint8_t *buf, const AesKey &key, hipStream_t st);
+// Camellia-256 in the cipher stage (k_camellia.hip; weak like the xz launchers: the sanitizer build has no stand-ins for them and a build without the file still links --
+// Camellia then stays PNA_E_UNSUPPORTED whatever option "camellia" says)
+__attribute__((weak)) void launch_cam_ctr(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const CamTabs *tabs, uint8_t *buf, const CamKey &key, const CamKey *keys, hipStream_t st);
+__attribute__((weak)) void launch_cam_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const CamTabs *tabs, uint8_t *buf, const CamKey &key, hipStream_t st);
+__attribute__((weak)) void launch_cam_cbc_dec(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const CamTabs *tabs, uint8_t *buf, const CamKey &dkey, uint32_t *plain_len, hipStream_t st);
 void launch_corpus(int kind, uint64_t first_file, uint64_t n_files, uint64_t file_len, uint64_t stride,
                    const uint8_t *vocab, const uint64_t *cum, const uint32_t *phrases, uint8_t *dst, hipStream_t st);
 }
@@ -247,6 +253,7 @@ struct Tuning {
     long trace = 0;                  // PNA_TRACE: phase times of the host pipelines on stderr
     long d2h_wgs = 6;                // PNA_D2H_WGS: workgroups of the kernel that carries a sub-batch's archive bytes to the host (0: the copy engine / runtime's choice)
     long xz_encode = 0;              // PNA_XZ_ENCODE: 1: pna_gpu_compress_batch[_device] and the non-solid archive entry points take PNA_ALGO_XZ (k_xzenc.hip: multi-block streams with per-chunk state resets -- their bytes differ from the reference's encoder and their ratio is lower, so a host chooses them knowingly); 0 (default): PNA_E_UNSUPPORTED, as before
+    long camellia = 0;               // PNA_CAMELLIA: 1: Encryption::CAMELLIA (Camellia-256 in CTR, CBC and GCM STREAM; k_camellia.hip) is written by the entry points that take a cipher and read by extract / verify / diff / extract-select; 0 (default): PNA_E_UNSUPPORTED / PNA_VERIFY_UNSUPPORTED, as before
     long hist_by_block = -1;         // PNA_HIST_BY_BLOCK: zstd entropy stage in its per-block form (1: k_hist, k_seqa, k_seqb) or its per-segment form (0: k_stats, k_seq); -1: by batch size
 };
 struct TuningName { const char *name, *env; long Tuning::*field; long lo, hi; };
@@ -307,6 +314,7 @@ struct pna_gpu_ctx {
     DevBuf ci_spread, ci_spread_desc;                          // GCM entries of several segments: their compact payloads, the pieces to move
     DevBuf aes_tabs, ci_units, ci_ivs, ci_keys, ci_gcm;        // cipher stage: round tables, unit descriptors, IVs; GCM: per-entry round keys, segment descriptors
     bool aes_ready = false;
+    DevBuf cam_tabs, ci_ckeys; bool cam_ready = false;         // ... for Camellia (option camellia): its four tables, GCM's per-segment schedules
     hipEvent_t ev_ci[2] = {};
     DevBuf solid_plain, solid_desc, solid_blob, solid_place;   // serialised inner entries of a solid archive
     DevBuf solid_adler;                                        // deflate solid from host memory: the stream's Adler-32 carried from window to window
@@ -386,7 +394,7 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
 // front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  layout_solid advances
 // pos, seg and carry_len past the window.
 struct SolidCipherRun { uint64_t pos = 0, seg = 0, carry_len = 0; uint8_t *carry = nullptr; bool final_win = false; };
-struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4]; };     // a stream's header, round keys and hash subkey
+struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4]; int enc = PNA_ENC_AES; CamKey ck; };     // a stream's header, round keys (rk: AES, ck: Camellia -- by enc) and hash subkey
 struct GcmCallKeys { uint8_t kc[32], phsf_hash[32]; };
 // GCM STREAM segment size of a cipher job (0: the reference's DEFAULT_SEGMENT_SIZE, 1 MiB)
 inline uint32_t gcm_seg_size(const pna_gpu_cipher *ci) { return ci->gcm_segment_size ? ci->gcm_segment_size : (1u << 20); }
@@ -494,13 +502,16 @@ uint32_t crc_gf2_mulmod(uint32_t a, uint32_t b);       // a * b mod P of the CRC
 uint32_t crc_gf2_xpow(uint64_t e);
 int  ensure_aes(pna_gpu_ctx *c);
 int  ensure_aes_dec(pna_gpu_ctx *c);
+int  ensure_cam(pna_gpu_ctx *c);
+// Encryption::CAMELLIA is taken: option camellia is on and the library holds k_camellia.hip's launchers
+inline bool camellia_on(const pna_gpu_ctx *c) { return c && c->tun.camellia != 0 && launch_cam_ctr && launch_cam_cbc_enc && launch_cam_cbc_dec; }
 int  check_cipher(pna_gpu_ctx *c, const pna_gpu_cipher *ci);
 void aes256_expand(const uint8_t key[32], AesKey &k);
 void aes256_dec_key(const AesKey &k, AesKey &d);
 void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]);
 int  resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs);
 GcmCallKeys gcm_call_keys(const uint8_t key[32], const char *phsf, size_t phsf_len);
-void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], AesKey &rk, uint32_t h[4]);
+void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], int encryption, GcmMaterial &m);
 void gcm_segment(const GcmMaterial &m, uint32_t counter, bool fin, GcmEntry &ge, uint8_t iv[16]);
 void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const uint8_t salt_prefix[39], uint32_t seg_size, const char *name, int compression,
                         GcmMaterial &m);

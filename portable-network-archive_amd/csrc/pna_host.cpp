@@ -13,7 +13,7 @@ static const TuningName TUNING_NAMES[] = {
     {"blk_log", "PNA_BLK_LOG", &Tuning::blk_log, 0, PNA_BLK_LOG}, {"unit_log", "PNA_LZ_UNIT_LOG", &Tuning::unit_log, 0, 20},
     {"latency_max_mib", "PNA_LATENCY_MAX_MIB", &Tuning::latency_max_mib, 0, 1 << 20}, {"hist_by_block", "PNA_HIST_BY_BLOCK", &Tuning::hist_by_block, -1, 1},
     {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"mtile", "PNA_MTILE", &Tuning::mtile, 0, 2048}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
-    {"xz_encode", "PNA_XZ_ENCODE", &Tuning::xz_encode, 0, 1},
+    {"xz_encode", "PNA_XZ_ENCODE", &Tuning::xz_encode, 0, 1}, {"camellia", "PNA_CAMELLIA", &Tuning::camellia, 0, 1},
 };
 
 extern "C" const char *pna_gpu_strerror(int code) {
@@ -117,7 +117,7 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     for (auto &e : c->df_ev_k) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->df_tev) if (e) (void)hipEventDestroy(e);
     c->xs_pieces.release();
-    for (DevBuf *b : {&c->xz_in, &c->xz_scan, &c->xz_blocks, &c->xz_pieces, &c->xz_acc}) b->release();
+    for (DevBuf *b : {&c->xz_in, &c->xz_scan, &c->xz_blocks, &c->xz_pieces, &c->xz_acc, &c->cam_tabs, &c->ci_ckeys}) b->release();
     for (auto &e : c->xs_tev) if (e) (void)hipEventDestroy(e);
     if (c->x_cp) (void)hipStreamDestroy(c->x_cp);
     for (auto &e : c->x_ev) if (e) (void)hipEventDestroy(e);
@@ -342,9 +342,18 @@ int ensure_aes(pna_gpu_ctx *c) {
     c->aes_ready = true;
     return PNA_OK;
 }
+// Camellia's tables on the device (option camellia); the cipher stage's events are ensure_aes's
+int ensure_cam(pna_gpu_ctx *c) {
+    int rc = ensure_aes(c); if (rc) return rc;
+    if (c->cam_ready) return PNA_OK;
+    if (c->cam_tabs.ensure(sizeof(CamTabs))) return fail(c, PNA_E_NOMEM, "camellia tables");
+    HIPCHK(c, hipMemcpy(c->cam_tabs.p, &cam_host_tabs(), sizeof(CamTabs), hipMemcpyHostToDevice));
+    c->cam_ready = true;
+    return PNA_OK;
+}
 int check_cipher(pna_gpu_ctx *c, const pna_gpu_cipher *ci) {
-    if (ci->encryption == PNA_ENC_CAMELLIA) return fail(c, PNA_E_UNSUPPORTED, "Camellia is not offered on the device path");
-    if (ci->encryption != PNA_ENC_AES) return fail(c, PNA_E_INVAL, "unknown encryption");
+    if (ci->encryption == PNA_ENC_CAMELLIA && !camellia_on(c)) return fail(c, PNA_E_UNSUPPORTED, "Camellia is not offered on the device path");
+    if (ci->encryption != PNA_ENC_AES && ci->encryption != PNA_ENC_CAMELLIA) return fail(c, PNA_E_INVAL, "unknown encryption");
     if (ci->cipher_mode != PNA_MODE_CTR && ci->cipher_mode != PNA_MODE_CBC && ci->cipher_mode != PNA_MODE_GCM) return fail(c, PNA_E_UNSUPPORTED, "cipher mode not offered on the device path");
     if (ci->cipher_mode == PNA_MODE_GCM && ci->gcm_segment_size > (64u << 20)) return fail(c, PNA_E_INVAL, "GCM segment size beyond 64 MiB");
     return PNA_OK;
@@ -364,19 +373,24 @@ void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]) {
         t[i] = (sb(s[i]) | (sb(s[(i + 1) & 3] >> 8) << 8) | (sb(s[(i + 2) & 3] >> 16) << 16) | (sb(s[(i + 3) & 3] >> 24) << 24)) ^ k.rk[56 + i];
     for (int i = 0; i < 4; i++) { out[4 * i] = (uint8_t)t[i]; out[4 * i + 1] = (uint8_t)(t[i] >> 8); out[4 * i + 2] = (uint8_t)(t[i] >> 16); out[4 * i + 3] = (uint8_t)(t[i] >> 24); }
 }
+// one block under a GCM stream's key, by the block cipher of the stream
+static void gcm_block_host(const GcmMaterial &m, const uint8_t in[16], uint8_t out[16]) {
+    if (m.enc == PNA_ENC_CAMELLIA) cam_block_host(m.ck, in, out); else aes256_block_host(m.rk, in, out);
+}
 // The stream key of a GCM STREAM (derive_stream_key, lib/src/cipher/aead.rs:184-199), bound to the PHSF string and to the header chunk of the entry
 // that carries the stream: FHED or SHED (entry_context, aead.rs:167-190).  `header`: salt || nonce prefix || segment size of the stream header.
-void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], AesKey &rk, uint32_t h[4]) {
+void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], int encryption, GcmMaterial &m) {
     uint8_t info[88], ks[32];
     memcpy(info, "PNA-STREAM-v1", 13);
     sha256_bytes(htype, 4, hbody.data(), hbody.size(), info + 13);
     memcpy(info + 45, phsf_hash, 32);
     memcpy(info + 77, header + 32, 11);
     hkdf_sha256_32(master, 32, header, 32, info, 88, ks);
-    aes256_expand(ks, rk);
+    m.enc = encryption;
+    if (encryption == PNA_ENC_CAMELLIA) cam_expand_host(ks, m.ck); else aes256_expand(ks, m.rk);
     uint8_t zero[16] = {0}, hb[16];
-    aes256_block_host(rk, zero, hb);
-    for (int i = 0; i < 4; i++) h[i] = rd_be32(hb + 4 * i);
+    gcm_block_host(m, zero, hb);
+    for (int i = 0; i < 4; i++) m.h[i] = rd_be32(hb + 4 * i);
 }
 // Segment `counter` of a stream (segment_nonce, lib/src/cipher/gcm.rs): J0 = nonce prefix || counter || final flag || 0 0 0 1.  Gives the tag
 // descriptor's H and E(K, J0) and the counter-mode IV of the segment's first data block (counter 2).
@@ -384,7 +398,7 @@ void gcm_segment(const GcmMaterial &m, uint32_t counter, bool fin, GcmEntry &ge,
     uint8_t j0[16], eb[16];
     memcpy(j0, m.header + 32, 7); put_be32(j0 + 7, counter); j0[11] = fin ? 1 : 0;
     put_be32(j0 + 12, 1);
-    aes256_block_host(m.rk, j0, eb);
+    gcm_block_host(m, j0, eb);
     memcpy(ge.h, m.h, 16);
     for (int i = 0; i < 4; i++) ge.ej0[i] = rd_be32(eb + 4 * i);
     memcpy(iv, j0, 16); iv[15] = 2;
@@ -398,7 +412,7 @@ void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const
     memcpy(m.header + 43, keys.kc, 32);
     const std::vector<uint8_t> fh = name ? frame_fhed_bytes(name, compression, ci->encryption, PNA_MODE_GCM)
                                          : std::vector<uint8_t>{0, 0, (uint8_t)compression, (uint8_t)ci->encryption, (uint8_t)PNA_MODE_GCM};
-    gcm_stream_key(ci->key, m.header, name ? "FHED" : "SHED", fh, keys.phsf_hash, m.rk, m.h);
+    gcm_stream_key(ci->key, m.header, name ? "FHED" : "SHED", fh, keys.phsf_hash, ci->encryption, m);
 }
 // what the GCM STREAMs under one key and PHSF string share: the key confirmation (key_confirmation, aead.rs:161-163) and the hash of the PHSF string
 GcmCallKeys gcm_call_keys(const uint8_t key[32], const char *phsf, size_t phsf_len) {
@@ -890,7 +904,7 @@ struct SubLayout {
     std::vector<GcmMaterial> gmat; std::vector<GcmEntry> gents;
     // GCM STREAM segments of this sub-batch, in order (an entry has ceil(payload / segment_size) of them, at least one): counter-mode IV
     // (nonce || 2) and the round keys of the stream they belong to; `spread`: pieces of the compact payload that move to their place between the tags
-    std::vector<uint8_t> giv; std::vector<AesKey> gkeys;
+    std::vector<uint8_t> giv; std::vector<AesKey> gkeys; std::vector<CamKey> gckeys;     // (a call has one cipher: gkeys under AES, gckeys under Camellia)
     struct SpreadPiece { uint64_t src, dst; uint32_t len; };
     std::vector<SpreadPiece> spread; uint64_t spread_bytes = 0;
     std::vector<std::pair<uint64_t, uint64_t>> spread_copy;     // (archive offset, length) of the compact payloads to save first
@@ -909,11 +923,12 @@ struct SubLayout {
     void gcm_segments(const GcmMaterial &gm, uint64_t first, uint64_t K, bool final_last, uint64_t plen, uint64_t G, uint64_t base, uint64_t stride) {
         for (uint64_t k = 0; k < K; k++) {
             const uint64_t sl = std::min<uint64_t>(G, plen - k * G), so = base + k * stride, q = first + k;     // q: the segment's counter in the stream
-            const uint32_t si = (uint32_t)gkeys.size();
+            const uint32_t si = (uint32_t)(giv.size() / 16);
             GcmEntry ge{so, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
             uint8_t iv[16];
             gcm_segment(gm, (uint32_t)q, final_last && k + 1 == K, ge, iv);
-            giv.insert(giv.end(), iv, iv + 16); gkeys.push_back(gm.rk);
+            giv.insert(giv.end(), iv, iv + 16);
+            if (gm.enc == PNA_ENC_CAMELLIA) gckeys.push_back(gm.ck); else gkeys.push_back(gm.rk);
             for (uint64_t o = 0; o < sl; o += CTR_UNIT) cunits.push_back(CipherUnit{so + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
             gents.push_back(ge);
             if (k >= 1) move(k * G, so, sl);
@@ -1177,20 +1192,26 @@ static int cipher_stage(const SubBatch &sb, const SubLayout &L) {
     pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const hipStream_t st = sb.st; const size_t e0 = sb.e0, e1 = sb.e1;
     const bool gcm = fj->cipher->cipher_mode == PNA_MODE_GCM;
     if (fj->solid && fj->cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
-    int rc = ensure_aes(c); if (rc) return rc;
+    const bool cam = fj->cipher->encryption == PNA_ENC_CAMELLIA;
+    int rc = cam ? ensure_cam(c) : ensure_aes(c); if (rc) return rc;
     if (c->ci_units.ensure(L.cunits.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure((e1 - e0) * 16 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
-    AesKey key; aes256_expand(fj->cipher->key, key);
+    AesKey key{}; CamKey ckey{};
+    if (cam) cam_expand_host(fj->cipher->key, ckey); else aes256_expand(fj->cipher->key, key);
     HIPCHK(c, hipMemcpyAsync(c->ci_units.p, L.cunits.data(), L.cunits.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
     if (gcm) {
-        if (c->ci_keys.ensure(L.gkeys.size() * sizeof(AesKey) + 16) || c->ci_gcm.ensure(L.gents.size() * sizeof(GcmEntry) + 16) || c->ci_ivs.ensure(L.giv.size() + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+        if (c->ci_keys.ensure(L.gkeys.size() * sizeof(AesKey) + 16) || c->ci_ckeys.ensure(L.gckeys.size() * sizeof(CamKey) + 16) || c->ci_gcm.ensure(L.gents.size() * sizeof(GcmEntry) + 16) || c->ci_ivs.ensure(L.giv.size() + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
         HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, L.giv.data(), L.giv.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, L.gkeys.data(), L.gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
+        if (cam) HIPCHK(c, hipMemcpyAsync(c->ci_ckeys.p, L.gckeys.data(), L.gckeys.size() * sizeof(CamKey), hipMemcpyHostToDevice, st));
+        else HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, L.gkeys.data(), L.gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(c->ci_gcm.p, L.gents.data(), L.gents.size() * sizeof(GcmEntry), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipStreamSynchronize(st));                  // (the copies read host vectors)
     } else HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, fj->ivs + 16 * e0, (e1 - e0) * 16, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->ev_ci[0], st));
     const CipherUnit *units = (const CipherUnit *)c->ci_units.p; const uint32_t nu = (uint32_t)L.cunits.size(); const uint8_t *ivs = (const uint8_t *)c->ci_ivs.p;
-    if (fj->cipher->cipher_mode == PNA_MODE_CBC) launch_aes_cbc_enc(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, st);
+    if (cam) {
+        if (fj->cipher->cipher_mode == PNA_MODE_CBC) launch_cam_cbc_enc(units, nu, ivs, (const CamTabs *)c->cam_tabs.p, sb.d_dst, ckey, st);
+        else launch_cam_ctr(units, nu, ivs, (const CamTabs *)c->cam_tabs.p, sb.d_dst, ckey, gcm ? (const CamKey *)c->ci_ckeys.p : nullptr, st);
+    } else if (fj->cipher->cipher_mode == PNA_MODE_CBC) launch_aes_cbc_enc(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, st);
     else launch_aes_ctr(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, gcm ? (const AesKey *)c->ci_keys.p : nullptr, st);   // (GCM: per-segment keys)
     if (gcm) launch_gcm_tag((const GcmEntry *)c->ci_gcm.p, (uint32_t)L.gents.size(), sb.d_dst, st);
     HIPCHK(c, hipEventRecord(c->ev_ci[1], st));
@@ -1454,7 +1475,8 @@ extern "C" int pna_gpu_cipher_apply_device(pna_gpu_ctx *c, const pna_gpu_cipher 
     if (n == 0) return PNA_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    rc = ensure_aes(c); if (rc) return rc;
+    const bool cam = cipher->encryption == PNA_ENC_CAMELLIA;
+    rc = cam ? ensure_cam(c) : ensure_aes(c); if (rc) return rc;
     std::vector<CipherUnit> units;
     for (size_t i = 0; i < n; i++) {
         if (len[i] >= 0xFFFFFFF0ull) return fail(c, PNA_E_INVAL, "cipher range too long");
@@ -1462,12 +1484,15 @@ extern "C" int pna_gpu_cipher_apply_device(pna_gpu_ctx *c, const pna_gpu_cipher 
         else for (uint64_t o = 0; o < len[i]; o += CTR_UNIT) units.push_back(CipherUnit{off[i] + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, len[i] - o), (uint32_t)i});
     }
     if (c->ci_units.ensure(units.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure(n * 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
-    AesKey key; aes256_expand(cipher->key, key);
+    AesKey key{}; CamKey ckey{};
+    if (cam) cam_expand_host(cipher->key, ckey); else aes256_expand(cipher->key, key);
     c->timing = pna_gpu_timing{};
     HIPCHK(c, hipMemcpyAsync(c->ci_units.p, units.data(), units.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, cipher->ivs, n * 16, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->ev_ci[0], st));
-    if (cbc) launch_aes_cbc_enc((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)d_buf, key, st);
+    if (cam && cbc) launch_cam_cbc_enc((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const CamTabs *)c->cam_tabs.p, (uint8_t *)d_buf, ckey, st);
+    else if (cam) launch_cam_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const CamTabs *)c->cam_tabs.p, (uint8_t *)d_buf, ckey, nullptr, st);
+    else if (cbc) launch_aes_cbc_enc((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)d_buf, key, st);
     else launch_aes_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)d_buf, key, nullptr, st);
     HIPCHK(c, hipEventRecord(c->ev_ci[1], st));
     HIPCHK(c, hipGetLastError());
