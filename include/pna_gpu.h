@@ -124,7 +124,7 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
  *   "camellia" [PNA_CAMELLIA]             0 (default): PNA_ENC_CAMELLIA is PNA_E_UNSUPPORTED on every entry point that takes a cipher, and the read side refuses / reports
  *                                         PNA_VERIFY_UNSUPPORTED for Camellia entries; 1: Camellia-256 in CTR, CBC and GCM STREAM wherever AES-256 is taken -- the archive
  *                                         entry points (solid: CTR and GCM), pna_gpu_cipher_apply_device (CTR, CBC encryption), and extract / verify / diff / extract-select
- *                                         (k_camellia.hip).  An option so that a host which keeps the reference's CipherWriter for Camellia sees no change
+ *                                         (k_cipher.hip).  An option so that a host which keeps the reference's CipherWriter for Camellia sees no change
  *   "max_chunk_size" [PNA_MAX_CHUNK_SIZE] (FDAT chunk size of the entry points without such a parameter), "sub_mib" [PNA_SUB_MIB], "stage_threads" [PNA_STAGE_THREADS],
  *   "diff_slot_mib" [PNA_DIFF_SLOT_MIB]   pna_gpu_diff_archive_host: MiB of each of the two page-locked (and two device) slots the files' bytes travel through (256)
  *   "extract_win_mib" [PNA_EXTRACT_WIN_MIB], "batch_piece_mib" [PNA_BATCH_PIECE_MIB], "inflate_serial" [PNA_INFLATE_SERIAL],

@@ -1,4 +1,4 @@
-// camellia_core.h -- Camellia-256 (RFC 3713) in one place, for the host code and the kernels of k_camellia.hip: key schedule, the decrypt-order
+// camellia_core.h -- Camellia-256 (RFC 3713) in one place, for the host code and the kernels of k_cipher.hip: key schedule, the decrypt-order
 // schedule, and the block function in two forms -- a byte-wise one straight from the RFC's text (host only: what the tests hold the other against) and
 // the table form the kernels run.  Builds with g++ alone (tests/camellia_core); no HIP header is needed.
 //

@@ -167,8 +167,8 @@ void launch_aes_cbc_dec(const CipherUnit *units, uint32_t n, const uint8_t *ivs,
 size_t frame_entry_prefix_enc_bound(const char *name, const char *phsf);
 void launch_aes_ctr(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *tabs, uint8_t *buf, const AesKey &key, const AesKey *keys, hipStream_t st);
 void launch_aes_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const AesTabs *tabs, uint8_t *buf, const AesKey &key, hipStream_t st);
-// Camellia-256 in the cipher stage (k_camellia.hip; weak like the xz launchers: the sanitizer build has no stand-ins for them and a build without the file still links --
-// Camellia then stays PNA_E_UNSUPPORTED whatever option "camellia" says)
+// Camellia-256 in the cipher stage (k_cipher.hip; weak like the xz launchers: the sanitizer build has no stand-ins for them and still links -- Camellia
+// then stays PNA_E_UNSUPPORTED whatever option "camellia" says).  Only pna_cipher.cpp calls the six cipher launchers.
 __attribute__((weak)) void launch_cam_ctr(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const CamTabs *tabs, uint8_t *buf, const CamKey &key, const CamKey *keys, hipStream_t st);
 __attribute__((weak)) void launch_cam_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const CamTabs *tabs, uint8_t *buf, const CamKey &key, hipStream_t st);
 __attribute__((weak)) void launch_cam_cbc_dec(const CipherUnit *units, uint32_t n, const uint8_t *ivs, const CamTabs *tabs, uint8_t *buf, const CamKey &dkey, uint32_t *plain_len, hipStream_t st);
@@ -253,7 +253,7 @@ struct Tuning {
     long trace = 0;                  // PNA_TRACE: phase times of the host pipelines on stderr
     long d2h_wgs = 6;                // PNA_D2H_WGS: workgroups of the kernel that carries a sub-batch's archive bytes to the host (0: the copy engine / runtime's choice)
     long xz_encode = 0;              // PNA_XZ_ENCODE: 1: pna_gpu_compress_batch[_device] and the non-solid archive entry points take PNA_ALGO_XZ (k_xzenc.hip: multi-block streams with per-chunk state resets -- their bytes differ from the reference's encoder and their ratio is lower, so a host chooses them knowingly); 0 (default): PNA_E_UNSUPPORTED, as before
-    long camellia = 0;               // PNA_CAMELLIA: 1: Encryption::CAMELLIA (Camellia-256 in CTR, CBC and GCM STREAM; k_camellia.hip) is written by the entry points that take a cipher and read by extract / verify / diff / extract-select; 0 (default): PNA_E_UNSUPPORTED / PNA_VERIFY_UNSUPPORTED, as before
+    long camellia = 0;               // PNA_CAMELLIA: 1: Encryption::CAMELLIA (Camellia-256 in CTR, CBC and GCM STREAM; k_cipher.hip) is written by the entry points that take a cipher and read by extract / verify / diff / extract-select; 0 (default): PNA_E_UNSUPPORTED / PNA_VERIFY_UNSUPPORTED, as before
     long hist_by_block = -1;         // PNA_HIST_BY_BLOCK: zstd entropy stage in its per-block form (1: k_hist, k_seqa, k_seqb) or its per-segment form (0: k_stats, k_seq); -1: by batch size
 };
 struct TuningName { const char *name, *env; long Tuning::*field; long lo, hi; };
@@ -312,9 +312,9 @@ struct pna_gpu_ctx {
     DevBuf xz_in, xz_scan, xz_blocks, xz_pieces, xz_acc;       // xz decode: stream descriptors, scan results, block descriptors, check pieces, accumulators + stream statuses
     DevBuf z_vp, z_pb, z_mode;                                 // lane-per-piece inflate: piece list, piece boundaries, per-stream mode
     DevBuf ci_spread, ci_spread_desc;                          // GCM entries of several segments: their compact payloads, the pieces to move
-    DevBuf aes_tabs, ci_units, ci_ivs, ci_keys, ci_gcm;        // cipher stage: round tables, unit descriptors, IVs; GCM: per-entry round keys, segment descriptors
+    DevBuf aes_tabs, ci_units, ci_ivs, ci_keys, ci_gcm;        // cipher stage: round tables, unit descriptors, IVs; GCM: per-segment round keys (SegKeys), segment descriptors
     bool aes_ready = false;
-    DevBuf cam_tabs, ci_ckeys; bool cam_ready = false;         // ... for Camellia (option camellia): its four tables, GCM's per-segment schedules
+    DevBuf cam_tabs, ci_ckeys; bool cam_ready = false;         // ... for Camellia (option camellia): its four tables, GCM's per-segment schedules (SegKeys)
     hipEvent_t ev_ci[2] = {};
     DevBuf solid_plain, solid_desc, solid_blob, solid_place;   // serialised inner entries of a solid archive
     DevBuf solid_adler;                                        // deflate solid from host memory: the stream's Adler-32 carried from window to window
@@ -394,7 +394,25 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
 // front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  layout_solid advances
 // pos, seg and carry_len past the window.
 struct SolidCipherRun { uint64_t pos = 0, seg = 0, carry_len = 0; uint8_t *carry = nullptr; bool final_win = false; };
-struct GcmMaterial { uint8_t header[75]; AesKey rk; uint32_t h[4]; int enc = PNA_ENC_AES; CamKey ck; };     // a stream's header, round keys (rk: AES, ck: Camellia -- by enc) and hash subkey
+// A block cipher's key schedule as a value (pna_cipher.cpp): which cipher (a PNA_ENC_* id) and its schedule.  cipher_ctr / cipher_cbc_enc / cipher_cbc_dec
+// turn the id into a kernel, block() into the host's block function; nobody else asks which cipher it is.
+struct BlockKey {
+    int enc = PNA_ENC_AES;
+    union { AesKey aes; CamKey cam = {}; };                        // (zeroed through its larger member)
+    void expand(int encryption, const uint8_t key32[32]);          // the encryption schedule of a 256-bit key
+    BlockKey dec() const;                                          // ... its counterpart for decryption (CBC)
+    void block(const uint8_t in[16], uint8_t out[16]) const;       // one block on the host
+};
+// GCM STREAM: the schedule of every segment's stream by segment index, as the CTR kernels read them (keys[unit.iv_idx]) -- one array per cipher, a
+// segment's slot in the other one unused.  A window of the read side may mix AES and Camellia streams: sort_units puts the AES segments' units first,
+// and cipher_ctr runs each cipher's kernel over its part.  (A list that is not sorted holds one cipher only.)
+struct SegKeys {
+    std::vector<AesKey> aes; std::vector<CamKey> cam; std::vector<uint8_t> is_cam; size_t aes_units = 0;
+    void push(uint32_t segment, const BlockKey &k);
+    void sort_units(std::vector<CipherUnit> &units);
+    int upload(pna_gpu_ctx *c, hipStream_t st) const;              // to c->ci_keys / c->ci_ckeys
+};
+struct GcmMaterial { uint8_t header[75]; BlockKey key; uint32_t h[4]; };     // a stream's header, the schedule of its stream key and the hash subkey
 struct GcmCallKeys { uint8_t kc[32], phsf_hash[32]; };
 // GCM STREAM segment size of a cipher job (0: the reference's DEFAULT_SEGMENT_SIZE, 1 MiB)
 inline uint32_t gcm_seg_size(const pna_gpu_cipher *ci) { return ci->gcm_segment_size ? ci->gcm_segment_size : (1u << 20); }
@@ -500,15 +518,17 @@ inline void plan_call(pna_gpu_ctx *c, const L *src_len, size_t n) {
 int  ensure_crc(pna_gpu_ctx *c);
 uint32_t crc_gf2_mulmod(uint32_t a, uint32_t b);       // a * b mod P of the CRC-32 (reflected bit order), x^e mod P: what chains the raw registers of a chunk's pieces
 uint32_t crc_gf2_xpow(uint64_t e);
-int  ensure_aes(pna_gpu_ctx *c);
-int  ensure_aes_dec(pna_gpu_ctx *c);
-int  ensure_cam(pna_gpu_ctx *c);
-// Encryption::CAMELLIA is taken: option camellia is on and the library holds k_camellia.hip's launchers
-inline bool camellia_on(const pna_gpu_ctx *c) { return c && c->tun.camellia != 0 && launch_cam_ctr && launch_cam_cbc_enc && launch_cam_cbc_dec; }
+// The cipher stage's dispatch (pna_cipher.cpp), in place over `buf`: units and ivs are device arrays, `key` a by-value kernel argument; each readies its
+// cipher's tables on first use.  cipher_ctr: stream_keys != null -- GCM STREAM, every unit under the schedule of its segment (uploaded before).
+// cipher_mark: records event `i` of the pair around the stage (ms_cipher) -- event 0 by the three functions themselves, once their tables are on the
+// device, event 1 by the caller.
+int  cipher_ctr(pna_gpu_ctx *c, const CipherUnit *units, uint32_t n, const uint8_t *ivs, uint8_t *buf, const BlockKey &key, const SegKeys *stream_keys, hipStream_t st);
+int  cipher_cbc_enc(pna_gpu_ctx *c, const CipherUnit *units, uint32_t n, const uint8_t *ivs, uint8_t *buf, const BlockKey &key, hipStream_t st);
+int  cipher_cbc_dec(pna_gpu_ctx *c, const CipherUnit *units, uint32_t n, const uint8_t *ivs, uint8_t *buf, const BlockKey &dkey, uint32_t *plain_len, hipStream_t st);
+int  cipher_mark(pna_gpu_ctx *c, int i, hipStream_t st);
+// Encryption::CAMELLIA is taken: option camellia is on and the library holds the Camellia launchers
+bool camellia_on(const pna_gpu_ctx *c);
 int  check_cipher(pna_gpu_ctx *c, const pna_gpu_cipher *ci);
-void aes256_expand(const uint8_t key[32], AesKey &k);
-void aes256_dec_key(const AesKey &k, AesKey &d);
-void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]);
 int  resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs);
 GcmCallKeys gcm_call_keys(const uint8_t key[32], const char *phsf, size_t phsf_len);
 void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], int encryption, GcmMaterial &m);

@@ -433,8 +433,6 @@ static int upload_window(pna_gpu_ctx *c, const WinSrc &a, size_t archive_len, co
 // window's CBC groups share x_plen), and no stream fails the call.
 static constexpr uint64_t CBC_UNIT = 16u << 20;
 static int decrypt_cbc(pna_gpu_ctx *c, int encryption, const uint8_t *key, const std::vector<XStream *> &grp_in, hipStream_t st, bool verdict = false, uint32_t *unit0 = nullptr) {
-    const bool cam = encryption == PNA_ENC_CAMELLIA;
-    int rc = cam ? ensure_cam(c) : ensure_aes_dec(c); if (rc) return rc;
     std::vector<XStream *> grp;
     for (XStream *s : grp_in) { if (verdict && (s->pay_len == 0 || (s->pay_len & 15))) s->vst = PNA_VERIFY_BAD_DECRYPT; else grp.push_back(s); }
     if (grp.empty()) return PNA_OK;
@@ -459,15 +457,9 @@ static int decrypt_cbc(pna_gpu_ctx *c, int encryption, const uint8_t *key, const
           } }
     std::vector<uint32_t> plen(units.size());
     HIPCHK(c, hipMemcpyAsync(c->ci_units.p, units.data(), units.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
-    if (cam) {
-        CamKey ek, dk; cam_expand_host(key, ek); cam_dec_key(ek, dk);
-        launch_cam_cbc_dec((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const CamTabs *)c->cam_tabs.p,
-                           (uint8_t *)c->x_pk.p, dk, (uint32_t *)c->x_plen.p + u0, st);
-    } else {
-        AesKey ek, dk; aes256_expand(key, ek); aes256_dec_key(ek, dk);
-        launch_aes_cbc_dec((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesDecTabs *)c->aes_dtabs.p,
-                           (uint8_t *)c->x_pk.p, dk, (uint32_t *)c->x_plen.p + u0, st);
-    }
+    BlockKey ek; ek.expand(encryption, key);
+    int rc = cipher_cbc_dec(c, (const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (uint8_t *)c->x_pk.p, ek.dec(), (uint32_t *)c->x_plen.p + u0, st);
+    if (rc) return rc;
     rc = read_back(c, plen.data(), (uint32_t *)c->x_plen.p + u0, units.size() * 4, st); if (rc) return rc;
     if (unit0) *unit0 += (uint32_t)units.size();
     for (size_t q = 0; q < grp.size(); q++) {
@@ -512,10 +504,10 @@ static int decrypt_ctr_cbc(XCall &x, const std::vector<XStream *> &enc_list, hip
 // for k_verdict, and the keystream is applied to every segment all the same (a record that failed is not decoded).
 static int decrypt_gcm(XCall &x, const WinSrc &a, const std::vector<XStream *> &gcm_list, uint32_t flag[2], hipStream_t st) {
     pna_gpu_ctx *c = x.c;
-    int rc = ensure_aes(c); if (rc) return rc;
-    // a window may hold AES and Camellia streams together: one segment list (tags, IVs, verdict words), the CTR units partitioned by cipher -- each
-    // family's kernel runs over its own list, with a key array indexed by segment like the IVs (the other family's slots stay unused)
-    std::vector<GcmEntry> gents; std::vector<uint8_t> tags, giv; std::vector<AesKey> gkeys; std::vector<CamKey> gckeys; std::vector<CipherUnit> units, cunits;
+    int rc;
+    // a window may hold AES and Camellia streams together: one segment list (tags, IVs, verdict words, keys), one unit list that the key list sorts by
+    // cipher for cipher_ctr
+    std::vector<GcmEntry> gents; std::vector<uint8_t> tags, giv; SegKeys gkeys; std::vector<CipherUnit> units;
     for (XStream *e : gcm_list) {
         XStream &s = *e;
         const uint8_t *km = nullptr;
@@ -526,8 +518,6 @@ static int decrypt_gcm(XCall &x, const WinSrc &a, const std::vector<XStream *> &
           if (diff && x.verdict) { s.vst = PNA_VERIFY_BAD_AUTH; continue; }
           if (diff) return fail(c, PNA_E_INVAL, "GCM STREAM: key confirmation failed (wrong password)"); }
         s.g0 = (uint32_t)gents.size();
-        const bool cam = s.encryption == PNA_ENC_CAMELLIA;
-        if (cam) { rc = ensure_cam(c); if (rc) return rc; }
         gcm_stream_key(km, m.header, s.htype, s.hdr, ck.phsf_hash, s.encryption, m);
         uint64_t rest = s.stream_len - 75, at = 75, outp = s.pk_off; uint32_t counter = 0;
         while (rest) {
@@ -539,26 +529,24 @@ static int decrypt_gcm(XCall &x, const WinSrc &a, const std::vector<XStream *> &
             stream_read(a, s.pieces, at + ctl, 16, tag);             // the stored tag, wherever the chunk boundaries fall
             const uint32_t idx = (uint32_t)gents.size();
             gents.push_back(ge); tags.insert(tags.end(), tag, tag + 16);
-            if (cam) { gckeys.resize(idx + 1, CamKey{}); gckeys[idx] = m.ck; } else { gkeys.resize(idx + 1, AesKey{}); gkeys[idx] = m.rk; }
+            gkeys.push(idx, m.key);
             giv.insert(giv.end(), iv, iv + 16);
-            for (uint64_t o = 0; o < ctl; o += CTR_UNIT) (cam ? cunits : units).push_back(CipherUnit{outp + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, ctl - o), idx});
+            for (uint64_t o = 0; o < ctl; o += CTR_UNIT) units.push_back(CipherUnit{outp + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, ctl - o), idx});
             outp += ctl; at += segl; rest -= segl; counter++;
             if (!fin && segl != (uint64_t)s.gcm_seg + 16) return fail(c, PNA_E_INVAL, "GCM STREAM: short non-final segment");
         }
         s.g1 = (uint32_t)gents.size();
     }
     if (gents.empty()) return PNA_OK;                                  // (verdict mode: every stream failed its key confirmation)
-    if (c->ci_gcm.ensure(gents.size() * sizeof(GcmEntry) + 16) || c->x_tags.ensure(tags.size() + 16) || c->ci_keys.ensure(gkeys.size() * sizeof(AesKey) + 16) ||
-        c->ci_ckeys.ensure(gckeys.size() * sizeof(CamKey) + 16) ||
-        c->ci_ivs.ensure(giv.size() + 16) || c->ci_units.ensure((units.size() + cunits.size()) * sizeof(CipherUnit) + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+    gkeys.sort_units(units);
+    if (c->ci_gcm.ensure(gents.size() * sizeof(GcmEntry) + 16) || c->x_tags.ensure(tags.size() + 16) ||
+        c->ci_ivs.ensure(giv.size() + 16) || c->ci_units.ensure(units.size() * sizeof(CipherUnit) + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
     HIPCHK(c, hipMemcpyAsync(c->x_flag.p, flag0, 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->ci_gcm.p, gents.data(), gents.size() * sizeof(GcmEntry), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->x_tags.p, tags.data(), tags.size(), hipMemcpyHostToDevice, st));
-    if (!gkeys.empty()) HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, gkeys.data(), gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
-    if (!gckeys.empty()) HIPCHK(c, hipMemcpyAsync(c->ci_ckeys.p, gckeys.data(), gckeys.size() * sizeof(CamKey), hipMemcpyHostToDevice, st));
+    rc = gkeys.upload(c, st); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, giv.data(), giv.size(), hipMemcpyHostToDevice, st));
     if (!units.empty()) HIPCHK(c, hipMemcpyAsync(c->ci_units.p, units.data(), units.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
-    if (!cunits.empty()) HIPCHK(c, hipMemcpyAsync((CipherUnit *)c->ci_units.p + units.size(), cunits.data(), cunits.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
     if (x.verdict) {
         if (c->v_seg.ensure(gents.size() * 4 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
         launch_gcm_verdict((const GcmEntry *)c->ci_gcm.p, (uint32_t)gents.size(), (const uint8_t *)c->x_pk.p, (const uint8_t *)c->x_tags.p, (uint32_t *)c->v_seg.p, st);
@@ -567,12 +555,8 @@ static int decrypt_gcm(XCall &x, const WinSrc &a, const std::vector<XStream *> &
         rc = read_back(c, flag, c->x_flag.p, 8, st); if (rc) return rc;
         if (flag[0]) return fail(c, PNA_E_INVAL, "GCM STREAM: authentication failure (a segment tag does not match)");
     }
-    AesKey k0{};
-    launch_aes_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)c->x_pk.p, k0, (const AesKey *)c->ci_keys.p, st);
-    if (!cunits.empty()) {
-        CamKey ck0{};
-        launch_cam_ctr((const CipherUnit *)c->ci_units.p + units.size(), (uint32_t)cunits.size(), (const uint8_t *)c->ci_ivs.p, (const CamTabs *)c->cam_tabs.p, (uint8_t *)c->x_pk.p, ck0, (const CamKey *)c->ci_ckeys.p, st);
-    }
+    rc = cipher_ctr(c, (const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (uint8_t *)c->x_pk.p, BlockKey{}, &gkeys, st);
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));
     return PNA_OK;

@@ -270,188 +270,6 @@ extern "C" uint32_t pna_gpu_debug_crc_schedule(const void *payload, size_t len) 
     return ~lane[0];
 }
 
-// ---- cipher stage: AES-256 key schedule and round tables (FIPS-197), built on the host once per context / per call
-static void aes_sbox(uint8_t sb[256]) {
-    uint8_t p = 1, q = 1;                                      // p walks the multiplicative group of GF(2^8), q is its inverse
-    do {
-        p = (uint8_t)(p ^ (p << 1) ^ ((p & 0x80) ? 0x1B : 0));
-        q ^= (uint8_t)(q << 1); q ^= (uint8_t)(q << 2); q ^= (uint8_t)(q << 4); if (q & 0x80) q ^= 0x09;
-        const uint8_t r1 = (uint8_t)((q << 1) | (q >> 7)), r2 = (uint8_t)((q << 2) | (q >> 6)), r3 = (uint8_t)((q << 3) | (q >> 5)), r4 = (uint8_t)((q << 4) | (q >> 4));
-        sb[p] = (uint8_t)(q ^ r1 ^ r2 ^ r3 ^ r4 ^ 0x63);
-    } while (p != 1);
-    sb[0] = 0x63;
-}
-static void build_aes_tabs(AesTabs &t) {
-    uint8_t sb[256]; aes_sbox(sb);
-    for (uint32_t x = 0; x < 256; x++) {
-        const uint32_t s1 = sb[x], s2 = ((s1 << 1) ^ ((s1 & 0x80) ? 0x1B : 0)) & 0xFF, s3 = s2 ^ s1;
-        const uint32_t w = s2 | (s1 << 8) | (s1 << 16) | (s3 << 24);
-        t.Te[0][x] = w; t.Te[1][x] = (w << 8) | (w >> 24); t.Te[2][x] = (w << 16) | (w >> 16); t.Te[3][x] = (w << 24) | (w >> 8);
-    }
-}
-void aes256_expand(const uint8_t key[32], AesKey &k) {
-    uint8_t sb[256]; aes_sbox(sb);
-    uint8_t w[60][4]; uint8_t rc = 1;
-    memcpy(w, key, 32);
-    for (int i = 8; i < 60; i++) {
-        uint8_t t[4]; memcpy(t, w[i - 1], 4);
-        if (i % 8 == 0) { const uint8_t t0 = t[0]; t[0] = (uint8_t)(sb[t[1]] ^ rc); t[1] = sb[t[2]]; t[2] = sb[t[3]]; t[3] = sb[t0]; rc = (uint8_t)((rc << 1) ^ ((rc & 0x80) ? 0x1B : 0)); }
-        else if (i % 8 == 4) for (int j = 0; j < 4; j++) t[j] = sb[t[j]];
-        for (int j = 0; j < 4; j++) w[i][j] = (uint8_t)(w[i - 8][j] ^ t[j]);
-    }
-    for (int i = 0; i < 60; i++) k.rk[i] = (uint32_t)w[i][0] | ((uint32_t)w[i][1] << 8) | ((uint32_t)w[i][2] << 16) | ((uint32_t)w[i][3] << 24);
-}
-static uint8_t gf_mul8(uint8_t a, uint8_t b) { uint8_t r = 0; while (b) { if (b & 1) r ^= a; a = (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1B : 0)); b >>= 1; } return r; }
-// equivalent inverse cipher (FIPS-197 5.3.5): tables of InvSubBytes + InvMixColumns, round keys reversed with InvMixColumns applied to
-// the middle ones
-static void build_aes_dec_tabs(AesDecTabs &t) {
-    uint8_t sb[256], si[256]; aes_sbox(sb);
-    for (int x = 0; x < 256; x++) si[sb[x]] = (uint8_t)x;
-    for (uint32_t x = 0; x < 256; x++) {
-        const uint8_t v = si[x];
-        const uint32_t w = (uint32_t)gf_mul8(v, 14) | ((uint32_t)gf_mul8(v, 9) << 8) | ((uint32_t)gf_mul8(v, 13) << 16) | ((uint32_t)gf_mul8(v, 11) << 24);
-        t.Td[0][x] = w; t.Td[1][x] = (w << 8) | (w >> 24); t.Td[2][x] = (w << 16) | (w >> 16); t.Td[3][x] = (w << 24) | (w >> 8);
-        t.Sd[x] = v;
-    }
-}
-void aes256_dec_key(const AesKey &k, AesKey &d) {
-    for (int c4 = 0; c4 < 4; c4++) { d.rk[c4] = k.rk[56 + c4]; d.rk[56 + c4] = k.rk[c4]; }
-    for (int r = 1; r < 14; r++)
-        for (int c4 = 0; c4 < 4; c4++) {
-            const uint32_t w = k.rk[4 * (14 - r) + c4];
-            const uint8_t a0 = (uint8_t)w, a1 = (uint8_t)(w >> 8), a2 = (uint8_t)(w >> 16), a3 = (uint8_t)(w >> 24);
-            const uint8_t r0 = gf_mul8(a0, 14) ^ gf_mul8(a1, 11) ^ gf_mul8(a2, 13) ^ gf_mul8(a3, 9), r1 = gf_mul8(a0, 9) ^ gf_mul8(a1, 14) ^ gf_mul8(a2, 11) ^ gf_mul8(a3, 13);
-            const uint8_t r2 = gf_mul8(a0, 13) ^ gf_mul8(a1, 9) ^ gf_mul8(a2, 14) ^ gf_mul8(a3, 11), r3 = gf_mul8(a0, 11) ^ gf_mul8(a1, 13) ^ gf_mul8(a2, 9) ^ gf_mul8(a3, 14);
-            d.rk[4 * r + c4] = (uint32_t)r0 | ((uint32_t)r1 << 8) | ((uint32_t)r2 << 16) | ((uint32_t)r3 << 24);
-        }
-}
-int ensure_aes_dec(pna_gpu_ctx *c) {
-    if (c->aes_dec_ready) return PNA_OK;
-    static AesDecTabs t; build_aes_dec_tabs(t);
-    if (c->aes_dtabs.ensure(sizeof(t))) return fail(c, PNA_E_NOMEM, "aes tables");
-    HIPCHK(c, hipMemcpy(c->aes_dtabs.p, &t, sizeof(t), hipMemcpyHostToDevice));
-    c->aes_dec_ready = true;
-    return PNA_OK;
-}
-int ensure_aes(pna_gpu_ctx *c) {
-    if (c->aes_ready) return PNA_OK;
-    AesTabs t; build_aes_tabs(t);
-    if (c->aes_tabs.ensure(sizeof(t))) return fail(c, PNA_E_NOMEM, "aes tables");
-    HIPCHK(c, hipMemcpy(c->aes_tabs.p, &t, sizeof(t), hipMemcpyHostToDevice));
-    for (auto &e : c->ev_ci) HIPCHK(c, hipEventCreate(&e));
-    c->aes_ready = true;
-    return PNA_OK;
-}
-// Camellia's tables on the device (option camellia); the cipher stage's events are ensure_aes's
-int ensure_cam(pna_gpu_ctx *c) {
-    int rc = ensure_aes(c); if (rc) return rc;
-    if (c->cam_ready) return PNA_OK;
-    if (c->cam_tabs.ensure(sizeof(CamTabs))) return fail(c, PNA_E_NOMEM, "camellia tables");
-    HIPCHK(c, hipMemcpy(c->cam_tabs.p, &cam_host_tabs(), sizeof(CamTabs), hipMemcpyHostToDevice));
-    c->cam_ready = true;
-    return PNA_OK;
-}
-int check_cipher(pna_gpu_ctx *c, const pna_gpu_cipher *ci) {
-    if (ci->encryption == PNA_ENC_CAMELLIA && !camellia_on(c)) return fail(c, PNA_E_UNSUPPORTED, "Camellia is not offered on the device path");
-    if (ci->encryption != PNA_ENC_AES && ci->encryption != PNA_ENC_CAMELLIA) return fail(c, PNA_E_INVAL, "unknown encryption");
-    if (ci->cipher_mode != PNA_MODE_CTR && ci->cipher_mode != PNA_MODE_CBC && ci->cipher_mode != PNA_MODE_GCM) return fail(c, PNA_E_UNSUPPORTED, "cipher mode not offered on the device path");
-    if (ci->cipher_mode == PNA_MODE_GCM && ci->gcm_segment_size > (64u << 20)) return fail(c, PNA_E_INVAL, "GCM segment size beyond 64 MiB");
-    return PNA_OK;
-}
-// one AES-256 block on the host (FIPS-197 with the round tables of the kernels): hash subkey and E(K, J0) of a GCM segment
-void aes256_block_host(const AesKey &k, const uint8_t in[16], uint8_t out[16]) {
-    static const AesTabs T = [] { AesTabs x; build_aes_tabs(x); return x; }();      // called from several host threads: C++11 static initialisation is thread-safe
-    uint32_t s[4], t[4];
-    for (int i = 0; i < 4; i++) s[i] = ((uint32_t)in[4 * i] | ((uint32_t)in[4 * i + 1] << 8) | ((uint32_t)in[4 * i + 2] << 16) | ((uint32_t)in[4 * i + 3] << 24)) ^ k.rk[i];
-    for (int r = 1; r < 14; r++) {
-        for (int i = 0; i < 4; i++)
-            t[i] = T.Te[0][s[i] & 0xFF] ^ T.Te[1][(s[(i + 1) & 3] >> 8) & 0xFF] ^ T.Te[2][(s[(i + 2) & 3] >> 16) & 0xFF] ^ T.Te[3][s[(i + 3) & 3] >> 24] ^ k.rk[4 * r + i];
-        memcpy(s, t, sizeof s);
-    }
-    auto sb = [&](uint32_t v) { return (T.Te[0][v & 0xFF] >> 8) & 0xFF; };
-    for (int i = 0; i < 4; i++)
-        t[i] = (sb(s[i]) | (sb(s[(i + 1) & 3] >> 8) << 8) | (sb(s[(i + 2) & 3] >> 16) << 16) | (sb(s[(i + 3) & 3] >> 24) << 24)) ^ k.rk[56 + i];
-    for (int i = 0; i < 4; i++) { out[4 * i] = (uint8_t)t[i]; out[4 * i + 1] = (uint8_t)(t[i] >> 8); out[4 * i + 2] = (uint8_t)(t[i] >> 16); out[4 * i + 3] = (uint8_t)(t[i] >> 24); }
-}
-// one block under a GCM stream's key, by the block cipher of the stream
-static void gcm_block_host(const GcmMaterial &m, const uint8_t in[16], uint8_t out[16]) {
-    if (m.enc == PNA_ENC_CAMELLIA) cam_block_host(m.ck, in, out); else aes256_block_host(m.rk, in, out);
-}
-// The stream key of a GCM STREAM (derive_stream_key, lib/src/cipher/aead.rs:184-199), bound to the PHSF string and to the header chunk of the entry
-// that carries the stream: FHED or SHED (entry_context, aead.rs:167-190).  `header`: salt || nonce prefix || segment size of the stream header.
-void gcm_stream_key(const uint8_t master[32], const uint8_t header[43], const char htype[4], const std::vector<uint8_t> &hbody, const uint8_t phsf_hash[32], int encryption, GcmMaterial &m) {
-    uint8_t info[88], ks[32];
-    memcpy(info, "PNA-STREAM-v1", 13);
-    sha256_bytes(htype, 4, hbody.data(), hbody.size(), info + 13);
-    memcpy(info + 45, phsf_hash, 32);
-    memcpy(info + 77, header + 32, 11);
-    hkdf_sha256_32(master, 32, header, 32, info, 88, ks);
-    m.enc = encryption;
-    if (encryption == PNA_ENC_CAMELLIA) cam_expand_host(ks, m.ck); else aes256_expand(ks, m.rk);
-    uint8_t zero[16] = {0}, hb[16];
-    gcm_block_host(m, zero, hb);
-    for (int i = 0; i < 4; i++) m.h[i] = rd_be32(hb + 4 * i);
-}
-// Segment `counter` of a stream (segment_nonce, lib/src/cipher/gcm.rs): J0 = nonce prefix || counter || final flag || 0 0 0 1.  Gives the tag
-// descriptor's H and E(K, J0) and the counter-mode IV of the segment's first data block (counter 2).
-void gcm_segment(const GcmMaterial &m, uint32_t counter, bool fin, GcmEntry &ge, uint8_t iv[16]) {
-    uint8_t j0[16], eb[16];
-    memcpy(j0, m.header + 32, 7); put_be32(j0 + 7, counter); j0[11] = fin ? 1 : 0;
-    put_be32(j0 + 12, 1);
-    gcm_block_host(m, j0, eb);
-    memcpy(ge.h, m.h, 16);
-    for (int i = 0; i < 4; i++) ge.ej0[i] = rd_be32(eb + 4 * i);
-    memcpy(iv, j0, 16); iv[15] = 2;
-}
-// GCM STREAM material of one entry (lib/src/entry/write.rs:81-107 to_hashed; lib/src/cipher/aead.rs): stream header, round keys and hash subkey of
-// the stream key (name == nullptr: the solid entry's SHED)
-void gcm_entry_material(const pna_gpu_cipher *ci, const GcmCallKeys &keys, const uint8_t salt_prefix[39], uint32_t seg_size, const char *name, int compression,
-                        GcmMaterial &m) {
-    memcpy(m.header, salt_prefix, 39);
-    put_be32(m.header + 39, seg_size);
-    memcpy(m.header + 43, keys.kc, 32);
-    const std::vector<uint8_t> fh = name ? frame_fhed_bytes(name, compression, ci->encryption, PNA_MODE_GCM)
-                                         : std::vector<uint8_t>{0, 0, (uint8_t)compression, (uint8_t)ci->encryption, (uint8_t)PNA_MODE_GCM};
-    gcm_stream_key(ci->key, m.header, name ? "FHED" : "SHED", fh, keys.phsf_hash, ci->encryption, m);
-}
-// what the GCM STREAMs under one key and PHSF string share: the key confirmation (key_confirmation, aead.rs:161-163) and the hash of the PHSF string
-GcmCallKeys gcm_call_keys(const uint8_t key[32], const char *phsf, size_t phsf_len) {
-    GcmCallKeys k;
-    hkdf_sha256_32(key, 32, nullptr, 0, "PNA-KC-v1", 9, k.kc);
-    sha256_bytes(phsf, phsf_len, nullptr, 0, k.phsf_hash);
-    return k;
-}
-// ... the material of a solid archive's one stream (bound to its SHED chunk)
-void gcm_solid_material(const pna_gpu_cipher *ci, const uint8_t salt_prefix[39], int compression, GcmMaterial &m) {
-    gcm_entry_material(ci, gcm_call_keys(ci->key, ci->phsf, strlen(ci->phsf)), salt_prefix, gcm_seg_size(ci), nullptr, compression, m);
-}
-// The head of a solid archive: signature + AHED, then SHED; with a cipher PHSF and the stream's first write, a chunk of its own -- the IV (CTR) or
-// the stream header (GCM: salt || nonce prefix || segment size || key confirmation, 75 bytes)
-void solid_archive_head(std::vector<uint8_t> &head, int compression, const pna_gpu_cipher *ci, const uint8_t *ivs) {
-    frame_archive_head(head, 0);
-    if (!ci) { frame_solid_head(head, compression); return; }
-    if (ci->cipher_mode != PNA_MODE_GCM) { frame_solid_head_enc(head, compression, ci->encryption, ci->cipher_mode, ci->phsf, ivs, 16); return; }
-    GcmMaterial gm;
-    gcm_solid_material(ci, ivs, compression, gm);
-    frame_solid_head_enc(head, compression, ci->encryption, ci->cipher_mode, ci->phsf, gm.header, 75);
-}
-// the per-entry IVs of a cipher job: the caller's, or random ones (random::random_vec(block_size) per entry, lib/src/entry/write.rs:108-112)
-int resolve_ivs(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, size_t n, std::vector<uint8_t> &own, const uint8_t **ivs) {
-    int rc = check_cipher(c, cipher); if (rc) return rc;
-    if (!cipher->phsf) return fail(c, PNA_E_INVAL, "cipher without a PHSF string");
-    *ivs = cipher->ivs;
-    if (*ivs) return PNA_OK;
-    const size_t per = cipher->cipher_mode == PNA_MODE_GCM ? 39 : 16;  // GCM: salt(32) || nonce_prefix(7) per stream (to_hashed, write.rs:83-86)
-    own.resize(n * per + 16);
-    for (size_t o = 0; o < n * per;) {
-        const ssize_t got = getrandom(own.data() + o, std::min<size_t>(n * per - o, 1u << 20), 0);
-        if (got <= 0) return fail(c, PNA_E_INVAL, "getrandom failed");
-        o += (size_t)got;
-    }
-    *ivs = own.data();
-    return PNA_OK;
-}
-
 // names[e] for the batch's global entry index e; solid: one SDAT chunk per segment of the (single) entry; cipher + ivs (16 bytes per
 // global entry index): the payloads are encrypted in place before their CRC-32 is taken
 // largest FDAT chunk the device paths write: the CRC kernel takes "FDAT" || data as one message of at most 2^32 - 1 bytes (the reference's default cuts
@@ -904,7 +722,7 @@ struct SubLayout {
     std::vector<GcmMaterial> gmat; std::vector<GcmEntry> gents;
     // GCM STREAM segments of this sub-batch, in order (an entry has ceil(payload / segment_size) of them, at least one): counter-mode IV
     // (nonce || 2) and the round keys of the stream they belong to; `spread`: pieces of the compact payload that move to their place between the tags
-    std::vector<uint8_t> giv; std::vector<AesKey> gkeys; std::vector<CamKey> gckeys;     // (a call has one cipher: gkeys under AES, gckeys under Camellia)
+    std::vector<uint8_t> giv; SegKeys gkeys;
     struct SpreadPiece { uint64_t src, dst; uint32_t len; };
     std::vector<SpreadPiece> spread; uint64_t spread_bytes = 0;
     std::vector<std::pair<uint64_t, uint64_t>> spread_copy;     // (archive offset, length) of the compact payloads to save first
@@ -928,7 +746,7 @@ struct SubLayout {
             uint8_t iv[16];
             gcm_segment(gm, (uint32_t)q, final_last && k + 1 == K, ge, iv);
             giv.insert(giv.end(), iv, iv + 16);
-            if (gm.enc == PNA_ENC_CAMELLIA) gckeys.push_back(gm.ck); else gkeys.push_back(gm.rk);
+            gkeys.push(si, gm.key);
             for (uint64_t o = 0; o < sl; o += CTR_UNIT) cunits.push_back(CipherUnit{so + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
             gents.push_back(ge);
             if (k >= 1) move(k * G, so, sl);
@@ -1192,30 +1010,23 @@ static int cipher_stage(const SubBatch &sb, const SubLayout &L) {
     pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const hipStream_t st = sb.st; const size_t e0 = sb.e0, e1 = sb.e1;
     const bool gcm = fj->cipher->cipher_mode == PNA_MODE_GCM;
     if (fj->solid && fj->cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
-    const bool cam = fj->cipher->encryption == PNA_ENC_CAMELLIA;
-    int rc = cam ? ensure_cam(c) : ensure_aes(c); if (rc) return rc;
     if (c->ci_units.ensure(L.cunits.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure((e1 - e0) * 16 + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
-    AesKey key{}; CamKey ckey{};
-    if (cam) cam_expand_host(fj->cipher->key, ckey); else aes256_expand(fj->cipher->key, key);
+    BlockKey key; key.expand(fj->cipher->encryption, fj->cipher->key);
     HIPCHK(c, hipMemcpyAsync(c->ci_units.p, L.cunits.data(), L.cunits.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
+    int rc;
     if (gcm) {
-        if (c->ci_keys.ensure(L.gkeys.size() * sizeof(AesKey) + 16) || c->ci_ckeys.ensure(L.gckeys.size() * sizeof(CamKey) + 16) || c->ci_gcm.ensure(L.gents.size() * sizeof(GcmEntry) + 16) || c->ci_ivs.ensure(L.giv.size() + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
+        if (c->ci_gcm.ensure(L.gents.size() * sizeof(GcmEntry) + 16) || c->ci_ivs.ensure(L.giv.size() + 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
         HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, L.giv.data(), L.giv.size(), hipMemcpyHostToDevice, st));
-        if (cam) HIPCHK(c, hipMemcpyAsync(c->ci_ckeys.p, L.gckeys.data(), L.gckeys.size() * sizeof(CamKey), hipMemcpyHostToDevice, st));
-        else HIPCHK(c, hipMemcpyAsync(c->ci_keys.p, L.gkeys.data(), L.gkeys.size() * sizeof(AesKey), hipMemcpyHostToDevice, st));
+        rc = L.gkeys.upload(c, st); if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(c->ci_gcm.p, L.gents.data(), L.gents.size() * sizeof(GcmEntry), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipStreamSynchronize(st));                  // (the copies read host vectors)
     } else HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, fj->ivs + 16 * e0, (e1 - e0) * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->ev_ci[0], st));
     const CipherUnit *units = (const CipherUnit *)c->ci_units.p; const uint32_t nu = (uint32_t)L.cunits.size(); const uint8_t *ivs = (const uint8_t *)c->ci_ivs.p;
-    if (cam) {
-        if (fj->cipher->cipher_mode == PNA_MODE_CBC) launch_cam_cbc_enc(units, nu, ivs, (const CamTabs *)c->cam_tabs.p, sb.d_dst, ckey, st);
-        else launch_cam_ctr(units, nu, ivs, (const CamTabs *)c->cam_tabs.p, sb.d_dst, ckey, gcm ? (const CamKey *)c->ci_ckeys.p : nullptr, st);
-    } else if (fj->cipher->cipher_mode == PNA_MODE_CBC) launch_aes_cbc_enc(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, st);
-    else launch_aes_ctr(units, nu, ivs, (const AesTabs *)c->aes_tabs.p, sb.d_dst, key, gcm ? (const AesKey *)c->ci_keys.p : nullptr, st);   // (GCM: per-segment keys)
+    rc = fj->cipher->cipher_mode == PNA_MODE_CBC ? cipher_cbc_enc(c, units, nu, ivs, sb.d_dst, key, st)
+                                                 : cipher_ctr(c, units, nu, ivs, sb.d_dst, key, gcm ? &L.gkeys : nullptr, st);   // (GCM: per-segment keys)
+    if (rc) return rc;
     if (gcm) launch_gcm_tag((const GcmEntry *)c->ci_gcm.p, (uint32_t)L.gents.size(), sb.d_dst, st);
-    HIPCHK(c, hipEventRecord(c->ev_ci[1], st));
-    return PNA_OK;
+    return cipher_mark(c, 1, st);
 }
 // One sub-batch: entries [e0, e1) -> segments -> kernels; output appended at d_dst + out_base.
 int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
@@ -1464,45 +1275,6 @@ int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, co
     return PNA_OK;
 }
 
-// The cipher stage alone over byte ranges of a device buffer (read side: DecryptReader::CtrAes, lib/src/entry/read.rs:83-88).
-extern "C" int pna_gpu_cipher_apply_device(pna_gpu_ctx *c, const pna_gpu_cipher *cipher, int decrypt, size_t n, void *d_buf,
-                                           const uint64_t *off, const uint64_t *len, void *hip_stream) {
-    if (!c || !cipher || (n && (!d_buf || !off || !len || !cipher->ivs))) return fail(c, PNA_E_INVAL, "null argument");
-    int rc = check_cipher(c, cipher); if (rc) return rc;
-    const bool cbc = cipher->cipher_mode == PNA_MODE_CBC;
-    if (cipher->cipher_mode == PNA_MODE_GCM) return fail(c, PNA_E_UNSUPPORTED, "GCM STREAM is offered by the archive entry points only");
-    if (cbc && decrypt) return fail(c, PNA_E_UNSUPPORTED, "CBC decryption is not offered on the device path");
-    if (n == 0) return PNA_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const bool cam = cipher->encryption == PNA_ENC_CAMELLIA;
-    rc = cam ? ensure_cam(c) : ensure_aes(c); if (rc) return rc;
-    std::vector<CipherUnit> units;
-    for (size_t i = 0; i < n; i++) {
-        if (len[i] >= 0xFFFFFFF0ull) return fail(c, PNA_E_INVAL, "cipher range too long");
-        if (cbc) units.push_back(CipherUnit{off[i], 0, (uint32_t)len[i], (uint32_t)i});
-        else for (uint64_t o = 0; o < len[i]; o += CTR_UNIT) units.push_back(CipherUnit{off[i] + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, len[i] - o), (uint32_t)i});
-    }
-    if (c->ci_units.ensure(units.size() * sizeof(CipherUnit) + 16) || c->ci_ivs.ensure(n * 16)) return fail(c, PNA_E_NOMEM, "cipher workspace");
-    AesKey key{}; CamKey ckey{};
-    if (cam) cam_expand_host(cipher->key, ckey); else aes256_expand(cipher->key, key);
-    c->timing = pna_gpu_timing{};
-    HIPCHK(c, hipMemcpyAsync(c->ci_units.p, units.data(), units.size() * sizeof(CipherUnit), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->ci_ivs.p, cipher->ivs, n * 16, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(c->ev_ci[0], st));
-    if (cam && cbc) launch_cam_cbc_enc((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const CamTabs *)c->cam_tabs.p, (uint8_t *)d_buf, ckey, st);
-    else if (cam) launch_cam_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const CamTabs *)c->cam_tabs.p, (uint8_t *)d_buf, ckey, nullptr, st);
-    else if (cbc) launch_aes_cbc_enc((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)d_buf, key, st);
-    else launch_aes_ctr((const CipherUnit *)c->ci_units.p, (uint32_t)units.size(), (const uint8_t *)c->ci_ivs.p, (const AesTabs *)c->aes_tabs.p, (uint8_t *)d_buf, key, nullptr, st);
-    HIPCHK(c, hipEventRecord(c->ev_ci[1], st));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(st));
-    float mc = 0; (void)hipEventElapsedTime(&mc, c->ev_ci[0], c->ev_ci[1]);
-    c->timing.ms_cipher = mc;
-    for (size_t i = 0; i < n; i++) c->timing.in_bytes += len[i];
-    return PNA_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // `pna create --solid` with the archive assembled in HBM (create_archive_file's solid branch, cli/src/command/create.rs:594-598,
 // 603-617; SolidArchive / SolidEntryBuilder, lib/src/archive/write.rs:443-470,575-580,716-727):
@@ -1684,3 +1456,6 @@ extern "C" int pna_gpu_debug_lz_stamps(pna_gpu_ctx *c, unsigned long long *out8)
     return PNA_OK;
 }
 
+// The cipher stage's host side is a file of its own in this translation unit: whatever builds pna_host.cpp -- the library, the sanitizer build of the
+// host code -- has it, under one list of sources.
+#include "pna_cipher.cpp"

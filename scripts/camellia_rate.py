@@ -1,4 +1,4 @@
-"""Camellia-256 against AES-256 in the cipher stage, on the GPU box: python scripts/camellia_rate.py [files] [runs] [--parent DIR]
+"""Camellia-256 against AES-256 in the cipher stage, on the GPU box: python scripts/camellia_rate.py [files] [runs] [--parent DIR] [--out FILE]
   (a) k_cam_ctr against k_aes_ctr over the same bytes with the same units: the compressed payloads of a files x 1 MiB (10 000 by default) zstd-3 archive,
       where they stand in the archive image in HBM, through pna_gpu_cipher_apply_device -- the kernel's HIP-event time (pna_gpu_last_timing: ms_cipher);
   (b) the create step (pna_gpu_create_archive_enc_device, inputs in HBM, archive left in HBM) with AES-CTR and with Camellia-CTR: wall time of the call
@@ -6,7 +6,7 @@
   (c) with --parent DIR (a built checkout of the parent commit): bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end --no-verify,
       `runs` times from DIR and `runs` times from this tree, alternating, each in a process of its own -- both lists, and whether this build's median
       lies inside the parent's min - max.
-`runs` (6) timed runs after a warm-up; median and min - max.  Writes profiles/camellia_rate.txt and prints one JSON line."""
+`runs` (6) timed runs after a warm-up; median and min - max.  Writes FILE (default: profiles/camellia_rate.txt) and prints one JSON line."""
 import importlib, json, os, statistics, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,6 +16,9 @@ args = [a for a in sys.argv[1:]]
 parent = None
 if "--parent" in args:
     i = args.index("--parent"); parent = args[i + 1]; del args[i:i + 2]
+out_path = os.path.join(ROOT, "profiles", "camellia_rate.txt")
+if "--out" in args:
+    i = args.index("--out"); out_path = os.path.abspath(args[i + 1]); del args[i:i + 2]
 n = int(args[0]) if len(args) > 0 else 10000
 runs = int(args[1]) if len(args) > 1 else 6
 L = 1 << 20
@@ -111,7 +114,7 @@ if parent:
     say(f"    this build's median lies {'inside' if inside else 'OUTSIDE'} the parent's min - max ({min(vals['parent'])} - {max(vals['parent'])})")
     res["bench_default_path"] = {"parent": vals["parent"], "this": vals["this"], "this_median_inside_parent_range": inside}
 say("not measured: another table layout for k_cam_ctr; the CBC kernels; GCM STREAM with Camellia (k_cam_ctr plus the GHASH kernels it shares with AES); the read side")
-os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-with open(os.path.join(ROOT, "profiles", "camellia_rate.txt"), "w") as f:
+os.makedirs(os.path.dirname(out_path), exist_ok=True)
+with open(out_path, "w") as f:
     f.write("\n".join(lines) + "\n" + json.dumps(res) + "\n")
 print(json.dumps(res))

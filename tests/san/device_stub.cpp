@@ -8,10 +8,8 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
-#include "pna_dev.h"
+#include "pna_dev.h"                                             // (with aes_core.h: the host code's key schedule, aes256_expand)
 #include "../../include/pna_archive.h"
-
-void aes256_expand(const uint8_t key[32], pna::AesKey &k);      // the host code's key schedule (pna_host.cpp)
 
 namespace pna {
 [[noreturn]] static void nostub(const char *what) { fprintf(stderr, "device_stub: %s is not stubbed\n", what); abort(); }
@@ -170,7 +168,7 @@ void launch_aes_cbc_enc(const CipherUnit *units, uint32_t n, const uint8_t *ivs,
         }
     }
 }
-// The encryption round keys behind a decryption schedule.  aes256_dec_key (pna_host.cpp) builds the equivalent inverse cipher's schedule: the
+// The encryption round keys behind a decryption schedule.  aes256_dec_key (aes_core.h) builds the equivalent inverse cipher's schedule: the
 // encryption round keys in reverse order, d.rk[4 r + c] = InvMixColumns(k.rk[4 (14 - r) + c]) for rounds 1 .. 13, rounds 0 and 14 swapped as they
 // are.  AES-256's round keys 0 and 1 are the key itself: round 0 is d.rk[56 .. 59], round 1 is MixColumns(d.rk[52 .. 55]); the expansion gives the
 // rest.  (The stub's CBC encryption folds the encryption schedule, and its bytes are pinned by the framing matrix.)
@@ -182,7 +180,7 @@ static AesKey enc_key_of(const AesKey &dk) {
         for (int j = 0; j < 4; j++) { key[4 * c4 + j] = (uint8_t)(dk.rk[56 + c4] >> (8 * j)); a[j] = (uint8_t)(dk.rk[52 + c4] >> (8 * j)); }
         for (int j = 0; j < 4; j++) key[16 + 4 * c4 + j] = x2(a[j]) ^ x2(a[(j + 1) & 3]) ^ a[(j + 1) & 3] ^ a[(j + 2) & 3] ^ a[(j + 3) & 3];
     }
-    AesKey ek; ::aes256_expand(key, ek);
+    AesKey ek; aes256_expand(key, ek);
     return ek;
 }
 // the exact inverse of launch_aes_cbc_enc, in place; plain_len: a unit's plaintext length, 0xFFFFFFFF on a bad length or PKCS#7 padding (k_aes_cbc_dec)

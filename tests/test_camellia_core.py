@@ -1,5 +1,5 @@
 """Camellia-256 on the CPU (csrc/camellia_core.h: key schedule, decrypt-order schedule, the byte-wise block form of RFC 3713 and the table form the
-kernels of k_camellia.hip run, the CTR / CBC helpers) -- the model tests/test_gpu_camellia.py leans on.  Built with g++ alone by
+Camellia kernels of k_cipher.hip run, the CTR / CBC helpers) -- the model tests/test_gpu_camellia.py leans on.  Built with g++ alone by
 tests/camellia_core/Makefile, once as a shared object (tests/camellia_cases.py loads it), once as a stand-alone program under
 -fsanitize=address,undefined that runs the known answers with buffers of exactly the needed sizes (never loaded into this process).
 

@@ -1,4 +1,4 @@
-"""Camellia-256 on the device (k_camellia.hip; option "camellia" = 1): CTR, CBC and GCM STREAM on the write and the read side, against the CPU core
+"""Camellia-256 on the device (k_cipher.hip's k_cam_* kernels; option "camellia" = 1): CTR, CBC and GCM STREAM on the write and the read side, against the CPU core
 (csrc/camellia_core.h through tests/camellia_cases.py, which tests/test_camellia_core.py pins to openssl's answers and the reference's archives) and
 against the reference's six Camellia fixtures.  Integer work: bit-exact.  A context of its own with the option set, closed afterwards; the session's
 default context shows that nothing changes without the option."""
