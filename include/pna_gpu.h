@@ -125,6 +125,11 @@ const char *pna_gpu_last_error(const pna_gpu_ctx *ctx);
  *                                         PNA_VERIFY_UNSUPPORTED for Camellia entries; 1: Camellia-256 in CTR, CBC and GCM STREAM wherever AES-256 is taken -- the archive
  *                                         entry points (solid: CTR and GCM), pna_gpu_cipher_apply_device (CTR, CBC encryption), and extract / verify / diff / extract-select
  *                                         (k_cipher.hip).  An option so that a host which keeps the reference's CipherWriter for Camellia sees no change
+ *   "kdf_device" [PNA_KDF_DEVICE]         0 (default): extract / verify / diff / extract-select derive every key on the host, one PHSF string after the other, as before;
+ *                                         N >= 1: a window's distinct, not yet derived PHSF strings go through pna_gpu_kdf_batch when there are at least N of them (fewer:
+ *                                         the host).  pna_gpu_kdf_batch called directly does not look at it ("KEY DERIVATION ON THE DEVICE" below)
+ *   "kdf_mem_mib" [PNA_KDF_MEM_MIB]       MiB that pna_gpu_kdf_batch's Argon2 block memory may take (one allocation, kept by the context); 0 (default): a quarter of the
+ *                                         device's free memory at the first batch, at most 32 GiB.  A batch runs in as many rounds as its jobs need to fit
  *   "max_chunk_size" [PNA_MAX_CHUNK_SIZE] (FDAT chunk size of the entry points without such a parameter), "sub_mib" [PNA_SUB_MIB], "stage_threads" [PNA_STAGE_THREADS],
  *   "diff_slot_mib" [PNA_DIFF_SLOT_MIB]   pna_gpu_diff_archive_host: MiB of each of the two page-locked (and two device) slots the files' bytes travel through (256)
  *   "extract_win_mib" [PNA_EXTRACT_WIN_MIB], "batch_piece_mib" [PNA_BATCH_PIECE_MIB], "inflate_serial" [PNA_INFLATE_SERIAL],
@@ -589,6 +594,34 @@ int  pna_gpu_extract_select_host(pna_gpu_ctx *ctx, const void *const *parts, con
 #define PNA_EXTRACT_GAP_MAX  65536u
 int  pna_extract_plan_runs(const uint64_t *rec_off, const uint64_t *rec_len, const uint8_t *wanted, size_t n,
                            uint64_t gap_max, uint64_t *run_off, uint64_t *run_len, size_t *n_runs);
+/* KEY DERIVATION ON THE DEVICE.  An encrypted entry's key is the password hash its PHSF chunk names: Argon2 (RFC 9106, version 0x13; the reference's
+ * default is argon2id m=19456,t=2,p=1) or PBKDF2-HMAC-SHA256 (600 000 rounds), 32 bytes.  pna_gpu_kdf_batch derives n keys from ONE password and n salts /
+ * parameter sets, all in host memory: Argon2's block fill and PBKDF2's chain run on the device (k_kdf.hip: one Argon2 lane per 32 wave lanes, one PBKDF2
+ * job per wave lane), H0, the seed blocks, the final H' and HMAC's key set-up on the host.  keys receives n x 32 bytes.
+ *   The device takes: Argon2 with lanes <= 16, t_cost <= 64, 8 lanes <= m_cost_kib <= 2^20, whose blocks fit the block memory (option "kdf_mem_mib"); PBKDF2
+ *   with any rounds >= 1; password_len <= 1024, salt_len <= 64.  Any other job of the batch is derived by pna_kdf_argon2 / pna_kdf_pbkdf2_sha256 in the same
+ *   call.  kind: PNA_KDF_ARGON2D / PNA_KDF_ARGON2I / PNA_KDF_ARGON2ID_JOB (t_cost, m_cost_kib, lanes; rounds ignored) or PNA_KDF_PBKDF2_SHA256_JOB (rounds; the others ignored).
+ *   status (n ints, may be NULL): PNA_OK, or the code with which the host function refuses the job's parameters (PNA_E_INVAL: m < 8 lanes, t = 0, rounds = 0,
+ *   an unknown kind, ...) -- the other jobs still run and the call returns PNA_OK.  With status == NULL the first such job fails the call.
+ *   Drains hip_stream (NULL: the context's).  Keys are byte-equal to the host functions' whatever path a job took.
+ * pna_phsf_parse (host code, no device): a PHSF string -- "$argon2id$v=19$m=<KiB>,t=<passes>,p=<lanes>$<salt>" (argon2d / argon2i alike, "v=19$" optional,
+ * absent parameters at the argon2 crate's defaults 19456 / 2 / 1) or "$pbkdf2-sha256$i=<rounds>,l=<len>$<salt>" (600 000) -- as a job.  The salt's bytes
+ * (B64 without padding, what follows it from the next '$' on ignored) go to salt_buf, *salt_len receives their number and job->salt / salt_len name them.
+ * PNA_E_INVAL: malformed; PNA_E_UNSUPPORTED: another hash, an Argon2 version other than 0x13, or a cost beyond what the read side accepts from an archive
+ * (m <= 4 GiB, t <= 64, p <= 256, rounds <= 10 000 000); PNA_E_DSTSIZE: salt_cap too small.
+ * pna_gpu_debug_kdf_stats: the context's latest pna_gpu_kdf_batch (any pointer may be NULL) -- jobs the kernels derived, jobs the host functions derived,
+ * rounds of the block memory (0: no Argon2 job on the device), HIP-event time of the kernels.  After a driver call under "kdf_device" that had a key to
+ * derive: the sums over that call's batches, one per window at most -- all zero when every window stayed below the threshold and the keys came from the host
+ * one by one.  Not on any product path. */
+#define PNA_KDF_ARGON2D           0
+#define PNA_KDF_ARGON2I           1
+#define PNA_KDF_ARGON2ID_JOB      2   /* (pna_archive.h's PNA_KDF_ARGON2ID = 0 names a choice of pna_kdf_derive, as PNA_KDF_PBKDF2_SHA256 does) */
+#define PNA_KDF_PBKDF2_SHA256_JOB 3
+typedef struct { int kind; uint32_t t_cost, m_cost_kib, lanes, rounds; const void *salt; size_t salt_len; } pna_kdf_job;
+int  pna_gpu_kdf_batch(pna_gpu_ctx *ctx, const void *password, size_t password_len, size_t n, const pna_kdf_job *jobs,
+                       uint8_t *keys, int *status, void *hip_stream);
+int  pna_phsf_parse(const char *phsf, size_t len, pna_kdf_job *job, uint8_t *salt_buf, size_t salt_cap, size_t *salt_len);
+int  pna_gpu_debug_kdf_stats(pna_gpu_ctx *ctx, uint64_t *device_jobs, uint64_t *host_jobs, uint64_t *rounds, double *ms_kernels);
 /* The latest pna_gpu_extract_select_host call of the context (any pointer may be NULL): bytes of its H2D archive copies; streams taken through the decode
  * stage (every selected entry that has data -- a stored one's decode is the identity -- and every solid stream); key derivations; bytes k_pick moved and
  * its HIP-event time.  Not on any product path. */

@@ -171,6 +171,14 @@ class ExtractSummary(ctypes.Structure):
 EXTRACT_SELECT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ExtractDest))
 EXTRACT_RECORD_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64)
 
+class KdfJob(ctypes.Structure):
+    """pna_kdf_job (include/pna_gpu.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("t_cost", ctypes.c_uint32), ("m_cost_kib", ctypes.c_uint32), ("lanes", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
+                ("salt", ctypes.c_void_p), ("salt_len", ctypes.c_size_t)]
+
+
+KDF_ARGON2D, KDF_ARGON2I, KDF_ARGON2ID_JOB, KDF_PBKDF2_SHA256_JOB = 0, 1, 2, 3      # pna_kdf_job.kind
+
 _lib = None
 
 EXPORTS = [
@@ -201,6 +209,8 @@ EXPORTS = [
     "pna_gpu_diff_archive_host", "pna_gpu_debug_diff_stats",
     # extract of chosen entries, to host or device (include/pna_gpu.h)
     "pna_gpu_extract_select_host", "pna_extract_plan_runs", "pna_gpu_debug_extract_stats", "pna_gpu_debug_pick_device",
+    # key derivation on the device (include/pna_gpu.h)
+    "pna_gpu_kdf_batch", "pna_phsf_parse", "pna_gpu_debug_kdf_stats",
 ]
 
 
@@ -334,6 +344,12 @@ def load_library() -> ctypes.CDLL:
                                               EXTRACT_SELECT_FN, EXTRACT_RECORD_FN, vp, ctypes.POINTER(ExtractSummary)]
     L.pna_extract_plan_runs.restype = ctypes.c_int
     L.pna_extract_plan_runs.argtypes = [u64p, u64p, ctypes.POINTER(ctypes.c_uint8), sz, ctypes.c_uint64, u64p, u64p, ctypes.POINTER(sz)]
+    L.pna_gpu_kdf_batch.restype = ctypes.c_int
+    L.pna_gpu_kdf_batch.argtypes = [vp, ctypes.c_char_p, sz, sz, ctypes.POINTER(KdfJob), ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), vp]
+    L.pna_phsf_parse.restype = ctypes.c_int
+    L.pna_phsf_parse.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(KdfJob), ctypes.c_char_p, sz, ctypes.POINTER(sz)]
+    L.pna_gpu_debug_kdf_stats.restype = ctypes.c_int
+    L.pna_gpu_debug_kdf_stats.argtypes = [vp, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
     L.pna_gpu_debug_extract_stats.restype = ctypes.c_int
     L.pna_gpu_debug_extract_stats.argtypes = [vp, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
     L.pna_gpu_debug_pick_device.restype = ctypes.c_int
@@ -1298,6 +1314,44 @@ def pick_device(ctx: Context, src, src_off: Sequence[int], dsts: Sequence[int], 
     so, ln = (ctypes.c_uint64 * max(n, 1))(*src_off), (ctypes.c_uint64 * max(n, 1))(*lens)
     dd = (ctypes.c_void_p * max(n, 1))(*dsts)
     ctx._check(ctx._L.pna_gpu_debug_pick_device(ctx._h, n, src.data_ptr(), so, dd, ln, stream or None))
+
+
+def kdf_batch(ctx: Context, password: bytes, jobs, stream: int = 0, with_status: bool = True):
+    """pna_gpu_kdf_batch: one password, many salts and parameter sets -> (keys, statuses).  A job is a dict -- {"kind": KDF_ARGON2D / KDF_ARGON2I /
+    KDF_ARGON2ID_JOB, "t_cost", "m_cost_kib", "lanes", "salt"} or {"kind": KDF_PBKDF2_SHA256_JOB, "rounds", "salt"} -- or a tuple (kind, t_cost,
+    m_cost_kib, lanes, rounds, salt).  Argon2's fill and PBKDF2's chain run on the device for every job the device takes (kdf_stats tells).
+    with_status = False passes status = NULL: the first job whose parameters are refused fails the call."""
+    n = len(jobs)
+    arr, salts = (KdfJob * max(n, 1))(), []
+    for i, j in enumerate(jobs):
+        if isinstance(j, dict):
+            j = (j["kind"], j.get("t_cost", 0), j.get("m_cost_kib", 0), j.get("lanes", 0), j.get("rounds", 0), j["salt"])
+        kind, t, m, p, rounds, salt = j
+        buf = ctypes.create_string_buffer(bytes(salt), max(len(salt), 1))
+        salts.append(buf)
+        arr[i] = KdfJob(kind, t, m, p, rounds, ctypes.cast(buf, ctypes.c_void_p), len(salt))
+    keys = ctypes.create_string_buffer(32 * max(n, 1))
+    st = (ctypes.c_int * max(n, 1))()
+    ctx._check(ctx._L.pna_gpu_kdf_batch(ctx._h, bytes(password), len(password), n, arr, keys, st if with_status else None, stream or None))
+    return [keys.raw[32 * i:32 * i + 32] for i in range(n)], list(st)[:n]
+
+
+def phsf_parse(phsf) -> dict:
+    """pna_phsf_parse: a PHSF string as a kdf_batch job (a dict).  PnaGpuError: E_INVAL (malformed) or E_UNSUPPORTED (another hash, a cost beyond the caps)."""
+    raw = phsf.encode() if isinstance(phsf, str) else bytes(phsf)
+    j, salt, n = KdfJob(), ctypes.create_string_buffer(max(len(raw), 1)), ctypes.c_size_t()
+    rc = load_library().pna_phsf_parse(raw, len(raw), ctypes.byref(j), salt, len(raw), ctypes.byref(n))
+    if rc:
+        raise PnaGpuError(rc, load_library().pna_gpu_strerror(rc).decode())
+    return {"kind": j.kind, "t_cost": j.t_cost, "m_cost_kib": j.m_cost_kib, "lanes": j.lanes, "rounds": j.rounds, "salt": salt.raw[:n.value]}
+
+
+def kdf_stats(ctx: Context):
+    """(jobs the kernels derived, jobs the host functions derived, rounds of the Argon2 block memory, the kernels' HIP-event milliseconds) of the context's
+    latest kdf_batch -- or, after a read-side driver's call under option kdf_device, the sums over that call's batches."""
+    d, h, r, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
+    ctx._check(ctx._L.pna_gpu_debug_kdf_stats(ctx._h, ctypes.byref(d), ctypes.byref(h), ctypes.byref(r), ctypes.byref(ms)))
+    return d.value, h.value, r.value, ms.value
 
 
 def kdf_argon2(kind: int, password: bytes, salt: bytes, t_cost: int, m_cost_kib: int, lanes: int, key_len: int = 32) -> bytes:

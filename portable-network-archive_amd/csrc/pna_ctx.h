@@ -26,6 +26,7 @@
 #include "../../include/pna_archive.h"
 
 struct XzScan; struct XzBlock;     // xz_core.h
+struct KdfArgonJob; struct KdfPbkdf2Job;     // kdf_core.h
 namespace pna {
 void launch_lz_small(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
                      uint32_t flags, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, const LzParseGrid *pg, bool w3);
@@ -86,6 +87,11 @@ __attribute__((weak)) void launch_xzenc_stage(const uint8_t *src, const SegDesc 
 __attribute__((weak)) void launch_xzenc_write(const uint8_t *src, const SegDesc *segs, const uint32_t *blk_seg, uint32_t nblk, const BlkInfo *blk, const uint64_t *seg_off,
                                               const uint64_t *seg_size, const uint8_t *scratch, const uint64_t *work, uint32_t nseg, const uint32_t *entry_seg, uint32_t nentry,
                                               uint8_t *dst, hipStream_t st, bool small_blocks);
+// pna_gpu_kdf_batch's kernels (k_kdf.hip; weak like launch_diff: the entry point refuses to run without them).  jobs: of ONE Argon2 lane count p
+__attribute__((weak)) void launch_argon2_fill(const KdfArgonJob *jobs, uint32_t njobs, uint32_t p, uint64_t *mem, const uint64_t *seeds, uint64_t *fin, hipStream_t st);
+__attribute__((weak)) void launch_pbkdf2_sha256(const KdfPbkdf2Job *jobs, uint32_t njobs, uint32_t *out, hipStream_t st);
+// pna_kdf.cpp: pna_gpu_kdf_batch without the argument checks; add: the counters of pna_gpu_debug_kdf_stats go on from where they stand (weak: the sanitizer build of the host code does not hold it; the drivers derive on the host there)
+__attribute__((weak)) int kdf_batch(pna_gpu_ctx *c, const void *password, size_t password_len, size_t n, const pna_kdf_job *jobs, uint8_t *keys, int *status, hipStream_t st, bool add);
 inline bool xz_kernels_present() { return launch_xzscan && launch_lzma2 && launch_xzcheck; }
 // pna_decode.cpp: which stream of an xz decode call failed and why (the call's error text is "entry <index>: <reason>"), for a caller that knows its streams by name
 struct XzFail { size_t index = ~(size_t)0; std::string reason; };
@@ -254,6 +260,8 @@ struct Tuning {
     long d2h_wgs = 6;                // PNA_D2H_WGS: workgroups of the kernel that carries a sub-batch's archive bytes to the host (0: the copy engine / runtime's choice)
     long xz_encode = 0;              // PNA_XZ_ENCODE: 1: pna_gpu_compress_batch[_device] and the non-solid archive entry points take PNA_ALGO_XZ (k_xzenc.hip: multi-block streams with per-chunk state resets -- their bytes differ from the reference's encoder and their ratio is lower, so a host chooses them knowingly); 0 (default): PNA_E_UNSUPPORTED, as before
     long camellia = 0;               // PNA_CAMELLIA: 1: Encryption::CAMELLIA (Camellia-256 in CTR, CBC and GCM STREAM; k_cipher.hip) is written by the entry points that take a cipher and read by extract / verify / diff / extract-select; 0 (default): PNA_E_UNSUPPORTED / PNA_VERIFY_UNSUPPORTED, as before
+    long kdf_device = 0;             // PNA_KDF_DEVICE: 0 (default): the read-side drivers derive every key on the host, one PHSF string after the other; N >= 1: a window's not yet derived PHSF strings go through pna_gpu_kdf_batch (k_kdf.hip) when there are at least N of them
+    long kdf_mem_mib = 0;            // PNA_KDF_MEM_MIB: the cap of pna_gpu_kdf_batch's Argon2 block memory; 0 (default): a quarter of the device's free memory at the first batch, at most 32 GiB
     long hist_by_block = -1;         // PNA_HIST_BY_BLOCK: zstd entropy stage in its per-block form (1: k_hist, k_seqa, k_seqb) or its per-segment form (0: k_stats, k_seq); -1: by batch size
 };
 struct TuningName { const char *name, *env; long Tuning::*field; long lo, hi; };
@@ -307,6 +315,9 @@ struct pna_gpu_ctx {
     // taken through the decode stage, key derivations, bytes k_pick moved, its HIP-event time
     DevBuf xs_pieces; std::vector<hipEvent_t> xs_tev; size_t xs_tused = 0;
     uint64_t xs_uploaded = 0, xs_streams = 0, xs_kdf = 0, xs_picked = 0; double xs_ms = 0;
+    // pna_gpu_kdf_batch (pna_kdf.cpp): Argon2's block memory (one allocation, at most kdf_cap bytes), the jobs, seed blocks and results of a round; the latest batch's counts
+    DevBuf kdf_mem, kdf_jobs, kdf_seeds, kdf_fin; size_t kdf_cap = 0; hipEvent_t kdf_ev[2] = {};
+    uint64_t kdf_dev_jobs = 0, kdf_host_jobs = 0, kdf_rounds = 0; double kdf_ms = 0;
     hipStream_t x_cp = nullptr; hipEvent_t x_ev[2] = {}, x_done = nullptr;   // extract driver: D2H of window k on x_cp next to window k+1's work
     bool aes_dec_ready = false;        // read side (pna_gpu_extract_archive_host): archive image, packed payloads, decoded entries
     DevBuf xz_in, xz_scan, xz_blocks, xz_pieces, xz_acc;       // xz decode: stream descriptors, scan results, block descriptors, check pieces, accumulators + stream statuses

@@ -63,6 +63,7 @@ struct XCall {
     std::vector<std::pair<std::string, std::vector<uint8_t>>> keys; size_t index = 0;
     bool verdict = false, fast = false;                        // `pna verify` (pna_gpu_verify_archive_host): failures become records; --fast: chunk structure and CRCs only
     uint64_t kdf_runs = 0;                                     // key derivations of the call (one per distinct PHSF string that a stream needed)
+    bool kdf_counted = false;                                  // option kdf_device: the context's batch counters were set to zero for this call
 };
 // a window's layout: packed payloads and decoded bytes, the gather of the data streams, the streams each cipher stage takes
 struct XPlan {
@@ -105,52 +106,115 @@ void stream_read(const WinSrc &a, const std::vector<XPiece> &pieces, uint64_t lo
 }
 }
 
-// The key of a PHSF string, derived once per call: "$argon2id$v=19$m=<KiB>,t=<passes>,p=<lanes>$<salt>" (argon2 0.5: Params::try_from(&PasswordHash),
-// lib/src/hash.rs:56-70) or "$pbkdf2-sha256$i=<rounds>,l=<len>$<salt>" (derive_password_hash, lib/src/hash.rs:47-88)
-static int phsf_key(XCall &x, const std::string &phsf, const uint8_t **out) {
-    pna_gpu_ctx *c = x.c;
-    for (auto &k : x.keys) if (k.first == phsf) { *out = k.second.data(); return PNA_OK; }
+// A PHSF string as a key derivation job: "$argon2id$v=19$m=<KiB>,t=<passes>,p=<lanes>$<salt>" (argon2 0.5: Params::try_from(&PasswordHash),
+// lib/src/hash.rs:56-70) or "$pbkdf2-sha256$i=<rounds>,l=<len>$<salt>" (derive_password_hash, lib/src/hash.rs:47-88).  *why: what the caller's error text says
+static int phsf_parse(const std::string &phsf, pna_kdf_job &job, std::vector<uint8_t> &salt, const char **why) {
+    auto bad = [&](int code, const char *what) { *why = what; return code; };
     int kind = -1; size_t p1 = 15, p2 = 0;                        // kind: the argon2 variant, -1 for pbkdf2-sha256
     uint32_t m = 19456, t = 2, lanes = 1, rounds = 600000;      // argon2 0.5 and pbkdf2 0.12 defaults
     if (phsf.rfind("$argon2", 0) == 0) {
         if (phsf.rfind("$argon2id$", 0) == 0) { kind = 2; p1 = 10; } else if (phsf.rfind("$argon2i$", 0) == 0) { kind = 1; p1 = 9; } else if (phsf.rfind("$argon2d$", 0) == 0) { kind = 0; p1 = 9; }
-        if (kind < 0) return fail(c, PNA_E_INVAL, "malformed PHSF");
-        if (phsf.compare(p1, 2, "v=") == 0) { const size_t q = phsf.find('$', p1); if (q == std::string::npos || strtoul(phsf.c_str() + p1 + 2, nullptr, 10) != 19) return fail(c, PNA_E_UNSUPPORTED, "argon2 version other than 0x13"); p1 = q + 1; }
+        if (kind < 0) return bad(PNA_E_INVAL, "malformed PHSF");
+        if (phsf.compare(p1, 2, "v=") == 0) { const size_t q = phsf.find('$', p1); if (q == std::string::npos || strtoul(phsf.c_str() + p1 + 2, nullptr, 10) != 19) return bad(PNA_E_UNSUPPORTED, "argon2 version other than 0x13"); p1 = q + 1; }
         p2 = phsf.find('$', p1);
-        if (p2 == std::string::npos) return fail(c, PNA_E_INVAL, "malformed PHSF");
+        if (p2 == std::string::npos) return bad(PNA_E_INVAL, "malformed PHSF");
         const std::string prm = phsf.substr(p1, p2 - p1);
         for (size_t q = 0; q < prm.size();) {
             const size_t e2 = prm.find(',', q); const std::string kv = prm.substr(q, e2 == std::string::npos ? std::string::npos : e2 - q);
             if (kv.size() > 2 && kv[1] == '=') {
                 char *endp = nullptr; const unsigned long long v = strtoull(kv.c_str() + 2, &endp, 10);
-                if (!endp || *endp || endp == kv.c_str() + 2) return fail(c, PNA_E_INVAL, "malformed argon2 parameter in PHSF");
+                if (!endp || *endp || endp == kv.c_str() + 2) return bad(PNA_E_INVAL, "malformed argon2 parameter in PHSF");
                 // the parameters come from an untrusted archive: refuse costs that only serve to stall / exhaust the host
-                if ((kv[0] == 'm' && v > (4ull << 20)) || (kv[0] == 't' && v > 64) || (kv[0] == 'p' && v > 256)) return fail(c, PNA_E_UNSUPPORTED, "argon2 cost beyond the accepted maximum (m <= 4 GiB, t <= 64, p <= 256)");
+                if ((kv[0] == 'm' && v > (4ull << 20)) || (kv[0] == 't' && v > 64) || (kv[0] == 'p' && v > 256)) return bad(PNA_E_UNSUPPORTED, "argon2 cost beyond the accepted maximum (m <= 4 GiB, t <= 64, p <= 256)");
                 if (kv[0] == 'm') m = (uint32_t)v; else if (kv[0] == 't') t = (uint32_t)v; else if (kv[0] == 'p') lanes = (uint32_t)v;
             }
             if (e2 == std::string::npos) break; q = e2 + 1;
         }
     } else {
-        if (phsf.rfind("$pbkdf2-sha256$", 0) != 0) return fail(c, PNA_E_UNSUPPORTED, "password hash other than argon2 / pbkdf2-sha256");
+        if (phsf.rfind("$pbkdf2-sha256$", 0) != 0) return bad(PNA_E_UNSUPPORTED, "password hash other than argon2 / pbkdf2-sha256");
         p2 = phsf.find('$', p1);
-        if (p2 == std::string::npos) return fail(c, PNA_E_INVAL, "malformed PHSF");
+        if (p2 == std::string::npos) return bad(PNA_E_INVAL, "malformed PHSF");
         const std::string prm = phsf.substr(p1, p2 - p1);
         const size_t ip = prm.find("i=");
         if (ip != std::string::npos) {
             char *endp = nullptr; const unsigned long long v = strtoull(prm.c_str() + ip + 2, &endp, 10);
-            if (!endp || (*endp && *endp != ',') || v == 0) return fail(c, PNA_E_INVAL, "malformed pbkdf2 round count in PHSF");
-            if (v > 10000000ull) return fail(c, PNA_E_UNSUPPORTED, "pbkdf2 round count beyond the accepted maximum (10 000 000)");
+            if (!endp || (*endp && *endp != ',') || v == 0) return bad(PNA_E_INVAL, "malformed pbkdf2 round count in PHSF");
+            if (v > 10000000ull) return bad(PNA_E_UNSUPPORTED, "pbkdf2 round count beyond the accepted maximum (10 000 000)");
             rounds = (uint32_t)v;
         }
     }
     std::string sb = phsf.substr(p2 + 1); const size_t p3 = sb.find('$'); if (p3 != std::string::npos) sb.resize(p3);
-    std::vector<uint8_t> key(32), salt;
-    if (!b64_decode_nopad(sb, salt)) return fail(c, PNA_E_INVAL, "malformed PHSF");
-    const int rc = kind >= 0 ? pna_kdf_argon2(kind, x.password, x.password_len, salt.data(), salt.size(), t, m, lanes, key.data(), 32)
-                             : pna_kdf_pbkdf2_sha256(x.password, x.password_len, salt.data(), salt.size(), rounds, key.data(), 32, nullptr, 0);
-    if (rc) return fail(c, rc, kind >= 0 ? "key derivation failed (argon2 parameters)" : "key derivation failed");
+    salt.clear();
+    if (!b64_decode_nopad(sb, salt)) return bad(PNA_E_INVAL, "malformed PHSF");
+    job = pna_kdf_job{kind >= 0 ? kind : PNA_KDF_PBKDF2_SHA256_JOB, t, m, lanes, rounds, salt.data(), salt.size()};
+    return PNA_OK;
+}
+extern "C" int pna_phsf_parse(const char *phsf, size_t len, pna_kdf_job *job, uint8_t *salt_buf, size_t salt_cap, size_t *salt_len) {
+    if ((!phsf && len) || !job || (!salt_buf && salt_cap)) return PNA_E_INVAL;
+    std::vector<uint8_t> salt; const char *why = nullptr; pna_kdf_job j{};
+    const int rc = phsf_parse(std::string(phsf ? phsf : "", len), j, salt, &why);
+    if (rc) return rc;
+    if (salt_len) *salt_len = salt.size();
+    if (salt.size() > salt_cap) return PNA_E_DSTSIZE;
+    if (!salt.empty()) memcpy(salt_buf, salt.data(), salt.size());
+    j.salt = salt_buf; *job = j;
+    return PNA_OK;
+}
+// The key of a PHSF string, derived once per call: the cache, or -- for a string that derive_ahead did not take -- one derivation on the host
+static int phsf_key(XCall &x, const std::string &phsf, const uint8_t **out) {
+    pna_gpu_ctx *c = x.c;
+    for (auto &k : x.keys) if (k.first == phsf) { *out = k.second.data(); return PNA_OK; }
+    pna_kdf_job j{}; std::vector<uint8_t> key(32), salt; const char *why = nullptr;
+    int rc = phsf_parse(phsf, j, salt, &why);
+    if (rc) return fail(c, rc, why);
+    const bool argon = j.kind != PNA_KDF_PBKDF2_SHA256_JOB;
+    rc = argon ? pna_kdf_argon2(j.kind, x.password, x.password_len, salt.data(), salt.size(), j.t_cost, j.m_cost_kib, j.lanes, key.data(), 32)
+               : pna_kdf_pbkdf2_sha256(x.password, x.password_len, salt.data(), salt.size(), j.rounds, key.data(), 32, nullptr, 0);
+    if (rc) return fail(c, rc, argon ? "key derivation failed (argon2 parameters)" : "key derivation failed");
     x.keys.emplace_back(phsf, std::move(key)); *out = x.keys.back().second.data(); x.kdf_runs++;
     return PNA_OK;
+}
+// Option kdf_device = N >= 1: the distinct PHSF strings that the streams of `need` will ask phsf_key for and that the call has not derived yet, as ONE
+// batch of pna_gpu_kdf_batch's -- if there are at least N of them.  A string that does not parse, or a job the algorithm refuses, is left out of the
+// cache: phsf_key meets it where its key is asked for and reports it as it always did.
+static int derive_ahead(XCall &x, const std::vector<const XStream *> &need) {
+    pna_gpu_ctx *c = x.c;
+    if (c->tun.kdf_device < 1 || !kdf_batch || need.empty()) return PNA_OK;
+    std::vector<const std::string *> todo; std::vector<pna_kdf_job> jobs; std::vector<std::vector<uint8_t>> salts;
+    {
+        std::vector<const std::string *> seen;
+        for (auto &k : x.keys) seen.push_back(&k.first);
+        auto less = [](const std::string *a, const std::string *b) { return *a < *b; };
+        std::sort(seen.begin(), seen.end(), less);
+        std::vector<const std::string *> cand;
+        for (const XStream *s : need) cand.push_back(&s->phsf);
+        std::stable_sort(cand.begin(), cand.end(), less);
+        for (size_t i = 0; i < cand.size(); i++) {
+            if (i && *cand[i] == *cand[i - 1]) continue;
+            if (std::binary_search(seen.begin(), seen.end(), cand[i], less)) continue;
+            pna_kdf_job j{}; std::vector<uint8_t> salt; const char *why = nullptr;
+            if (phsf_parse(*cand[i], j, salt, &why)) continue;
+            todo.push_back(cand[i]); jobs.push_back(j); salts.push_back(std::move(salt));
+        }
+    }
+    if (todo.empty()) return PNA_OK;
+    if (!x.kdf_counted) { c->kdf_dev_jobs = c->kdf_host_jobs = c->kdf_rounds = 0; c->kdf_ms = 0; x.kdf_counted = true; }      // pna_gpu_debug_kdf_stats: the batches of this call
+    if (todo.size() < (size_t)c->tun.kdf_device) return PNA_OK;     // below the threshold: phsf_key derives them on the host
+    for (size_t i = 0; i < jobs.size(); i++) jobs[i].salt = salts[i].data();
+    std::vector<uint8_t> keys(32 * jobs.size()); std::vector<int> status(jobs.size(), PNA_OK);
+    const int rc = kdf_batch(c, x.password, x.password_len, jobs.size(), jobs.data(), keys.data(), status.data(), c->stream, true);
+    if (rc) return rc;
+    for (size_t i = 0; i < jobs.size(); i++) {
+        if (status[i]) continue;
+        x.keys.emplace_back(*todo[i], std::vector<uint8_t>(keys.begin() + 32 * i, keys.begin() + 32 * i + 32)); x.kdf_runs++;
+    }
+    return PNA_OK;
+}
+// ... for the streams a window's cipher stages will take (every mode but verdict, where plan_window has derived them already)
+static int derive_ahead_plan(XCall &x, const std::vector<XStream *> &enc_list, const std::vector<XStream *> &gcm_list) {
+    std::vector<const XStream *> need(enc_list.begin(), enc_list.end());
+    need.insert(need.end(), gcm_list.begin(), gcm_list.end());
+    return derive_ahead(x, need);
 }
 
 // ---- 1. the chunk walk (host): structure, small-chunk CRCs, data-chunk descriptors.  Verdict mode (`pna verify`, x.verdict) goes on after damage:
@@ -350,6 +414,16 @@ static bool decoded_here(int compression) {
 static int plan_window(XCall &x, const WinSrc &a, std::vector<XEntry> &ents, std::vector<XSolid> &solids, XPlan &P) {
     pna_gpu_ctx *c = x.c;
     if (x.fast) return PNA_OK;                                        // verify --fast: chunk structure and CRCs, nothing gathered, decrypted or decoded
+    if (x.verdict && x.password) {                                    // plan_stream asks for every encrypted stream's key: those it will ask for, derived as one batch (option kdf_device)
+        std::vector<const XStream *> need;
+        auto want = [&](const XStream &s) {
+            if (s.vst || !decoded_here(s.compression) || s.encryption == PNA_ENC_NONE || s.phsf.empty()) return;
+            if (s.encryption == PNA_ENC_AES || (s.encryption == PNA_ENC_CAMELLIA && camellia_on(c))) need.push_back(&s);
+        };
+        for (const XEntry &e : ents) if (!e.nodecode) want(e);
+        for (const XSolid &so : solids) want(so);
+        const int r = derive_ahead(x, need); if (r) return r;
+    }
     for (size_t i = 0; i < ents.size(); i++) {
         XEntry &e = ents[i];
         if (x.verdict && (e.vst || e.nodecode)) continue;              // (a structural fault found by the walk, or `pna diff` needs no byte of it: nothing to decode)
@@ -737,6 +811,7 @@ static int extract_window(XCall &x, const WinSrc &a, size_t archive_len, std::ve
     // as one after the other -- and the kernels would again run with the link idle.)
     if (prev && *prev && !prev->issued) { prev->issued = true; const int r = prev->issue(); if (r) return r; }
     if (flag[0]) { c->err = "data chunk CRC mismatch (" + std::to_string(flag[0]) + " FDAT / SDAT chunks)"; return PNA_E_INVAL; }
+    rc = derive_ahead_plan(x, P.enc_list, P.gcm_list); if (rc) return rc;
     if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
     if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
     rc = decode_sized(c, ents, slot, st); if (rc) return rc;
@@ -850,6 +925,7 @@ static int window_verdicts(XCall &x, const WinSrc &a, size_t span, std::vector<X
     pna_gpu_ctx *c = x.c;
     int rc = plan_window(x, a, ents, solids, P); if (rc) return rc;
     rc = upload_window(c, a, span, dchunks, schunks, P, 0, flag, st, true); if (rc) return rc;
+    rc = derive_ahead_plan(x, P.enc_list, P.gcm_list); if (rc) return rc;
     if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
     if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
     // the fold: one VerdictEnt per record (the window's entries, or its solid entry), one status word back per record
@@ -1439,6 +1515,7 @@ int select_window(XCall &x, SCall &s, const WinSrc &a, uint64_t win_len, std::ve
     uint32_t flag[2] = {0, 0};
     rc = upload_window(c, a, (size_t)win_len, chunks, no_sdat, P, 0, flag, st); if (rc) return rc;
     if (flag[0]) { c->err = "data chunk CRC mismatch (" + std::to_string(flag[0]) + " FDAT chunks)"; return PNA_E_INVAL; }
+    rc = derive_ahead_plan(x, P.enc_list, P.gcm_list); if (rc) return rc;
     if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
     if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
     rc = decode_sized(c, ents, 0, st); if (rc) return rc;
@@ -1479,6 +1556,7 @@ int select_solid(XCall &x, SCall &s, const WinSrc &a, size_t span, std::vector<F
     uint32_t flag[2] = {0, 0};
     rc = upload_window(c, a, span, no_fdat, schunks, P, 0, flag, st); if (rc) return rc;
     if (flag[0]) { c->err = "data chunk CRC mismatch (" + std::to_string(flag[0]) + " SDAT chunks)"; return PNA_E_INVAL; }
+    rc = derive_ahead_plan(x, P.enc_list, P.gcm_list); if (rc) return rc;
     if (!P.enc_list.empty()) { rc = decrypt_ctr_cbc(x, P.enc_list, st); if (rc) return rc; }
     if (!P.gcm_list.empty()) { rc = decrypt_gcm(x, a, P.gcm_list, flag, st); if (rc) return rc; }
     const XSolid &so = solids[0];

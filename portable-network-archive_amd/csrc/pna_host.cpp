@@ -14,6 +14,7 @@ static const TuningName TUNING_NAMES[] = {
     {"latency_max_mib", "PNA_LATENCY_MAX_MIB", &Tuning::latency_max_mib, 0, 1 << 20}, {"hist_by_block", "PNA_HIST_BY_BLOCK", &Tuning::hist_by_block, -1, 1},
     {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"mtile", "PNA_MTILE", &Tuning::mtile, 0, 2048}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
     {"xz_encode", "PNA_XZ_ENCODE", &Tuning::xz_encode, 0, 1}, {"camellia", "PNA_CAMELLIA", &Tuning::camellia, 0, 1},
+    {"kdf_device", "PNA_KDF_DEVICE", &Tuning::kdf_device, 0, 1 << 30}, {"kdf_mem_mib", "PNA_KDF_MEM_MIB", &Tuning::kdf_mem_mib, 0, 32768},
 };
 
 extern "C" const char *pna_gpu_strerror(int code) {
@@ -117,7 +118,8 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     for (auto &e : c->df_ev_k) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->df_tev) if (e) (void)hipEventDestroy(e);
     c->xs_pieces.release();
-    for (DevBuf *b : {&c->xz_in, &c->xz_scan, &c->xz_blocks, &c->xz_pieces, &c->xz_acc, &c->cam_tabs, &c->ci_ckeys}) b->release();
+    for (DevBuf *b : {&c->xz_in, &c->xz_scan, &c->xz_blocks, &c->xz_pieces, &c->xz_acc, &c->cam_tabs, &c->ci_ckeys, &c->kdf_mem, &c->kdf_jobs, &c->kdf_seeds, &c->kdf_fin}) b->release();
+    for (auto &e : c->kdf_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->xs_tev) if (e) (void)hipEventDestroy(e);
     if (c->x_cp) (void)hipStreamDestroy(c->x_cp);
     for (auto &e : c->x_ev) if (e) (void)hipEventDestroy(e);
