@@ -555,3 +555,51 @@ int  check_meta(pna_gpu_ctx *c, const pna_gpu_entry_meta *meta, size_t n);
 int  run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
                   size_t e0, size_t e1, uint8_t *d_dst, size_t dst_cap, uint64_t out_base, uint64_t *dst_off,
                   hipStream_t st, bool timed, const FrameJob *fj = nullptr);
+
+// ---- the staging and copy layer of the host pipelines (pna_pipeline.cpp, pna_stream.cpp, the diff driver): thread count, parallel memcpy, copy streams,
+// sink calls and slot reservation, each written once.
+// Host threads that copy entries to or from page-locked memory: option stage_threads, or min(8, cores / 2)
+inline unsigned staging_threads(const pna_gpu_ctx *c) {
+    if (c && c->tun.stage_threads > 0) return (unsigned)c->tun.stage_threads;
+    return std::min(8u, std::max(1u, std::thread::hardware_concurrency() / 2));
+}
+// n copies, job(i) = {dst, src, len}, on up to `threads` threads: on the calling thread when there is one job, one thread or less than `serial_below` bytes;
+// otherwise the list is cut into CONTIGUOUS ranges balanced by bytes (adjacent small entries stay on one thread, a range ends behind the job that fills its
+// share).  The threads are the call's own, not host_pool()'s: the stager thread copies while run_subbatch's per-entry loops hold the pool on the main thread,
+// and a loop that finds the pool taken starts threads of its own (~0.5 ms a loop, DESIGN §5 "Many small entries").
+struct CopyJob { uint8_t *dst; const uint8_t *src; uint64_t len; };
+template <class J>
+inline void parallel_copy(size_t n, unsigned threads, uint64_t serial_below, J &&job) {
+    auto run = [&job](size_t a, size_t b) { for (size_t i = a; i < b; i++) { const CopyJob j = job(i); if (j.len) memcpy(j.dst, j.src, j.len); } };
+    uint64_t total = 0;
+    if (threads > 1 && n > 1) for (size_t i = 0; i < n; i++) total += job(i).len;
+    if (threads <= 1 || n <= 1 || total < serial_below) { run(0, n); return; }
+    std::vector<std::thread> th;
+    const uint64_t per = (total + threads - 1) / threads;
+    size_t e = 0;
+    for (unsigned t = 0; t < threads && e < n; t++) {
+        const size_t b = e; uint64_t acc = 0;
+        while (e < n && (acc < per || t + 1 == threads)) acc += job(e++).len;
+        th.emplace_back([&run, b, e]() { run(b, e); });
+    }
+    for (auto &x : th) x.join();
+}
+// the copy streams and slot events of the pipelined host paths, created on first use (the device is set)
+inline int ensure_copy_lanes(pna_gpu_ctx *c) {
+    if (c->cp_in) return PNA_OK;
+    HIPCHK(c, hipStreamCreate(&c->cp_in)); HIPCHK(c, hipStreamCreate(&c->cp_out));
+    for (auto &e : c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : c->ev_out) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return PNA_OK;
+}
+// a piece of the archive to the caller's sink (an empty piece is not handed on)
+inline int sink_put(pna_gpu_ctx *c, pna_sink_fn sink, void *user, const void *p, size_t n) {
+    return !n || sink(user, p, n) == 0 ? PNA_OK : fail(c, PNA_E_SINK, "sink failed");
+}
+// A pipeline's staging memory: every buffer (or array of slots) with its size, stated once; done() is the one PNA_E_NOMEM exit.
+struct Reserve {
+    pna_gpu_ctx *c; bool bad = false;
+    template <class B> Reserve &add(B &buf, size_t bytes) { bad = bad || buf.ensure(bytes); return *this; }
+    template <class B> Reserve &add(B *slots, size_t count, size_t bytes) { for (size_t s = 0; s < count; s++) add(slots[s], bytes); return *this; }
+    int done() const { return bad ? fail(c, PNA_E_NOMEM, "staging allocation failed") : PNA_OK; }
+};

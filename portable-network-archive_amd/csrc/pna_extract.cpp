@@ -1139,9 +1139,7 @@ struct DiffFeed {
             }
         }
         if (!jobs.empty()) {
-            const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-            const unsigned T = c->tun.stage_threads > 0 ? (unsigned)c->tun.stage_threads : std::min(8u, std::max(1u, hw / 2));
-            const unsigned nt = (unsigned)std::min<uint64_t>(T, std::max<uint64_t>(1, bytes >> 22));
+            const unsigned nt = (unsigned)std::min<uint64_t>(staging_threads(c), std::max<uint64_t>(1, bytes >> 22));
             par_ranges(jobs.size(), nt, [&](unsigned, size_t a0, size_t a1) { for (size_t j = a0; j < a1; j++) memcpy(jobs[j].dst, jobs[j].src, jobs[j].n); });
             HIPCHK(c, hipMemcpyAsync(c->df_dev[s].p, c->df_pin[s].p, extent, hipMemcpyHostToDevice, c->df_cp));
         }

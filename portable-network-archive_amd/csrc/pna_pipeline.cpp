@@ -1,9 +1,13 @@
 // pna_pipeline.cpp -- the host-memory create pipelines of libpna_gpu.so: bounded staging || H2D || kernels || D2H (pna_gpu_create_archive_host and its
-// forms, solid, multi-context, append, zero-staging host slots) and pna_gpu_compress_batch from host buffers.
+// forms, solid, multi-context, append, zero-staging host slots) and pna_gpu_compress_batch from host buffers.  Each pipeline is a row of stages over a
+// call struct (what the stages share) and a plan; thread counts, parallel copies, copy streams, sink calls and slot reservation come from pna_ctx.h.
+//   solid_stream (pna_gpu_create_solid_archive[_enc]_host in windows): solid_layout -> solid_sizes (window sizes, slots) -> per window: SolidAssembler::assemble
+//     (on a thread beside the window before) -> solid_window_in (H2D, the pieces' CRC registers, chaining, patches) -> solid_window_compress (kernels, D2H, sink).
+//   create_archive_host_impl (pna_gpu_create_archive_host and its forms): create_check -> capacity_terms -> cut_subbatches -> reserve_create_slots ->
+//     Stager (lend_subbatch / stage_subbatch on its thread) || drain_subbatches (kernels, copy_out, hand_over of the sub-batch before) -> create_finish.
+//   pna_gpu_compress_batch: cut_pieces -> BatchRun::stage(k + 1) || BatchRun::compress(k) || BatchRun::scatter(k - 1); BatchRun::drain on an error exit.
 #include "pna_ctx.h"
 #include <memory>
-#include <atomic>
-static void parallel_stage(uint8_t *dst, const void *const *src, const size_t *src_len, const uint64_t *off, size_t e0, size_t e1, unsigned threads);
 
 // `pna create --solid` from host memory (SolidArchive::add_entry streams the entries into ONE encoder, lib/src/archive/write.rs:575-580), zstd and deflate:
 // the serialised inner entries -- FHED | fSIZ | FDAT(data, crc) | FEND per entry, stored -- reach the device in WINDOWS of solid_win_mib MiB of that stream
@@ -21,160 +25,187 @@ static void parallel_stage(uint8_t *dst, const void *const *src, const size_t *s
 namespace {
 struct SolidSpan { uint64_t pos, len; uint32_t kind; uint32_t chunk; uint64_t a, b; };     // kind 0: blob[a ..), 1: entry a from byte b on, 2: the CRC of chunk `chunk`
 struct SolidChunk { uint32_t state = 0, crc = 0; uint64_t end = 0; bool started = false, done = false; };   // end: stream position behind the chunk's data
-}
-static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
-                        const pna_gpu_cipher *cipher, const uint8_t *ivs, pna_sink_fn sink, void *user) {
-    set_call_level(c, algo, level);
-    hipStream_t st = c->stream;
-    // ---- the stream's layout
-    std::vector<uint8_t> blob; std::vector<SolidSpan> spans; std::vector<SolidChunk> chunks;
-    const uint64_t CH = 0xFFFFFFFBull;
-    uint64_t pos = 0;
-    uint8_t fend[12] = {0, 0, 0, 0, 'F', 'E', 'N', 'D', 0, 0, 0, 0};
-    { const uint32_t fc = frame_fend_crc(); fend[8] = (uint8_t)(fc >> 24); fend[9] = (uint8_t)(fc >> 16); fend[10] = (uint8_t)(fc >> 8); fend[11] = (uint8_t)fc; }
-    auto lit = [&](size_t from) { const uint64_t l = blob.size() - from; spans.push_back(SolidSpan{pos, l, 0u, 0u, (uint64_t)from, 0}); pos += l; };
-    for (size_t i = 0; i < n; i++) {
-        const size_t b0 = blob.size();
-        if (src_len[i] == 0) { frame_inner_entry_empty(blob, names[i]); lit(b0); continue; }
-        const uint64_t L = src_len[i];
-        for (uint64_t o = 0; o < L; o += CH) {
-            const uint64_t cl = std::min<uint64_t>(CH, L - o);
-            const size_t b1 = blob.size();
-            if (o == 0) frame_entry_prefix(blob, names[i], PNA_ALGO_STORE, L, (uint32_t)cl);
-            else { const uint8_t h[8] = {(uint8_t)(cl >> 24), (uint8_t)(cl >> 16), (uint8_t)(cl >> 8), (uint8_t)cl, 'F', 'D', 'A', 'T'}; blob.insert(blob.end(), h, h + 8); }
-            lit(b1);
-            const uint32_t ci = (uint32_t)chunks.size();
-            chunks.emplace_back();
-            spans.push_back(SolidSpan{pos, cl, 1u, ci, (uint64_t)i, o}); pos += cl;
-            chunks[ci].end = pos;
-            spans.push_back(SolidSpan{pos, 4, 2u, ci, 0, 0}); pos += 4;
-            if (chunks.size() > 0x7FFFFFF0u) return fail(c, PNA_E_INVAL, "too many data chunks");
-        }
-        const size_t b2 = blob.size();
-        blob.insert(blob.end(), fend, fend + 12); lit(b2);
-    }
-    const uint64_t plain_len = pos;
-    // ---- the fixed chunks around the stream
-    std::vector<uint8_t> head, tail;
-    const bool gcm = cipher && cipher->cipher_mode == PNA_MODE_GCM;
-    const uint64_t G = gcm ? gcm_seg_size(cipher) : 0;
-    solid_archive_head(head, algo, cipher, ivs);                // (GCM: the stream header is the stream's first SDAT chunk, as in the device form)
-    frame_solid_tail(tail); frame_archive_tail(tail);
-    if (sink(user, head.data(), head.size()) != 0) return fail(c, PNA_E_SINK, "sink failed");
-    const uint64_t W = std::max<uint64_t>(1, (uint64_t)c->tun.solid_win_mib) << 20;           // a multiple of SEG_SIZE
-    const uint64_t nwin = (plain_len + W - 1) / W;
-    const uint64_t wcap_in = std::min<uint64_t>(W, plain_len) + 8192;
-    uint64_t wcap_out = pna_gpu_bound(algo, (size_t)std::min<uint64_t>(W, plain_len)) + (std::min<uint64_t>(W, plain_len) / SEG_SIZE + 2) * 16 + 4096;
-    if (gcm) wcap_out += G + 28 * ((wcap_out + G) / G + 2);    // GCM: the carry in front, a tag and SDAT framing per segment
-    int rc = ensure_crc(c); if (rc) return rc;
-    const uint64_t slot_in = (wcap_in + 255) & ~(uint64_t)255, slot_out = (wcap_out + 255) & ~(uint64_t)255;   // the two device slots each way
-    if (c->stage_in.ensure(2 * slot_in + 64) || c->stage_out.ensure(2 * slot_out + 64) || c->hp_in[0].ensure(wcap_in) || c->hp_in[1].ensure(wcap_in) ||
-        c->hp_out[0].ensure(wcap_out) || c->hp_out[1].ensure(wcap_out)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
-    const bool defl = algo == PNA_ALGO_DEFLATE;
-    if (defl && c->solid_adler.ensure(64)) return fail(c, PNA_E_NOMEM, "solid workspace");                  // the stream's Adler-32 (A, B) between windows
-    if (gcm && c->solid_carry.ensure(G + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");              // the GCM carry between windows
-    SolidCipherRun crun;
-    crun.carry = (uint8_t *)c->solid_carry.p;
-    const CallTotalScope call_total(c, plain_len);                                            // every window picks the block size of the whole stream
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned T = c->tun.stage_threads > 0 ? (unsigned)c->tun.stage_threads : std::min(8u, std::max(1u, hw / 2));
-    // assemble window k in its page-locked slot: framing bytes, entry bytes, the CRCs that are known; the pieces of data chunks inside it
-    struct Win { std::vector<FrameDesc> pieces; std::vector<uint32_t> piece_chunk; std::vector<uint64_t> piece_len; std::vector<uint32_t> crc_spans; uint64_t w0 = 0, w1 = 0; };
+struct SolidLayout { std::vector<uint8_t> blob; std::vector<SolidSpan> spans; std::vector<SolidChunk> chunks; uint64_t plain_len = 0; };
+// what a window's stages share: its pieces of data chunks, the CRC spans that are not known yet, its place [w0, w1) in the stream
+struct SolidWin { std::vector<FrameDesc> pieces; std::vector<uint32_t> piece_chunk; std::vector<uint64_t> piece_len; std::vector<uint32_t> crc_spans; uint64_t w0 = 0, w1 = 0; };
+struct SolidRun {
+    pna_gpu_ctx *c; int algo; const pna_gpu_cipher *cipher; const uint8_t *ivs; pna_sink_fn sink; void *user;
+    SolidLayout L; SolidCipherRun crun;
+    uint64_t W = 0, nwin = 0, wcap_in = 0, wcap_out = 0, slot_in = 0, slot_out = 0;          // window bytes, windows, a window's room each way, the device slots' stride
+    uint8_t *d_in(uint64_t k) const { return (uint8_t *)c->stage_in.p + (k & 1) * slot_in; }
+    uint8_t *d_out(uint64_t k) const { return (uint8_t *)c->stage_out.p + (k & 1) * slot_out; }
+};
+// ---- assemble window k in its page-locked slot: framing bytes, entry bytes, the CRCs that are known; the pieces of data chunks inside it
+struct SolidAssembler {
+    const SolidRun &r; const void *const *src; unsigned threads;
     size_t cursor = 0;                                                                         // first span that reaches into the window
-    auto assemble = [&](uint64_t k, Win &w) {
+    void assemble(uint64_t k, SolidWin &w) {
+        const SolidLayout &L = r.L;
         w.pieces.clear(); w.piece_chunk.clear(); w.piece_len.clear(); w.crc_spans.clear();
-        w.w0 = k * W; w.w1 = std::min(plain_len, w.w0 + W);
-        uint8_t *slot = (uint8_t *)c->hp_in[k & 1].p;
-        struct Job { uint8_t *d; const uint8_t *s; uint64_t l; };
-        std::vector<Job> jobs;
-        while (cursor < spans.size() && spans[cursor].pos + spans[cursor].len <= w.w0) cursor++;
-        for (size_t j = cursor; j < spans.size() && spans[j].pos < w.w1; j++) {
-            const SolidSpan &sp = spans[j];
+        w.w0 = k * r.W; w.w1 = std::min(L.plain_len, w.w0 + r.W);
+        uint8_t *slot = (uint8_t *)r.c->hp_in[k & 1].p;
+        std::vector<CopyJob> jobs;
+        while (cursor < L.spans.size() && L.spans[cursor].pos + L.spans[cursor].len <= w.w0) cursor++;
+        for (size_t j = cursor; j < L.spans.size() && L.spans[j].pos < w.w1; j++) {
+            const SolidSpan &sp = L.spans[j];
             const uint64_t a = std::max(sp.pos, w.w0), b = std::min(sp.pos + sp.len, w.w1);
             if (a >= b) continue;
             uint8_t *d = slot + (a - w.w0);
-            if (sp.kind == 0) memcpy(d, blob.data() + sp.a + (a - sp.pos), b - a);
+            if (sp.kind == 0) memcpy(d, L.blob.data() + sp.a + (a - sp.pos), b - a);
             else if (sp.kind == 1) {
                 const uint8_t *sbase = (const uint8_t *)src[sp.a] + sp.b + (a - sp.pos);
-                for (uint64_t o = 0; o < b - a; o += (8u << 20)) jobs.push_back(Job{d + o, sbase + o, std::min<uint64_t>(8u << 20, b - a - o)});
+                for (uint64_t o = 0; o < b - a; o += (8u << 20)) jobs.push_back(CopyJob{d + o, sbase + o, std::min<uint64_t>(8u << 20, b - a - o)});
                 w.pieces.push_back(FrameDesc{a - w.w0, (uint32_t)(b - a), 0u, 0u, 4u | (a == sp.pos ? 0u : 8u)});
                 w.piece_chunk.push_back(sp.chunk); w.piece_len.push_back(b - a);
             } else {
-                const SolidChunk &cc = chunks[sp.chunk];
+                const SolidChunk &cc = L.chunks[sp.chunk];
                 if (cc.done) for (uint64_t q = a; q < b; q++) slot[q - w.w0] = (uint8_t)(cc.crc >> (24 - 8 * (q - sp.pos)));
                 else { memset(d, 0, b - a); w.crc_spans.push_back((uint32_t)j); }
             }
         }
-        if (w.w1 - w.w0 < wcap_in) memset(slot + (w.w1 - w.w0), 0, std::min<uint64_t>(64, wcap_in - (w.w1 - w.w0)));
-        if (jobs.size() <= 1 || T <= 1) { for (const Job &jb : jobs) memcpy(jb.d, jb.s, jb.l); }
-        else {
-            std::atomic<size_t> next{0};
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < std::min<size_t>(T, jobs.size()); t++)
-                th.emplace_back([&]() { for (size_t q; (q = next.fetch_add(1)) < jobs.size();) memcpy(jobs[q].d, jobs[q].s, jobs[q].l); });
-            for (auto &x : th) x.join();
-        }
-    };
-    Win win[2];
-    if (nwin) assemble(0, win[0]);
-    DevBuf &dp = c->solid_place, &dd = c->solid_desc;                                          // patches, piece descriptors + states
-    for (uint64_t k = 0; k < nwin && rc == PNA_OK; k++) {
-        Win &w = win[k & 1];
-        const uint64_t wl = w.w1 - w.w0;
-        uint8_t *d_in = (uint8_t *)c->stage_in.p + (k & 1) * slot_in;
-        uint8_t *d_out = (uint8_t *)c->stage_out.p + (k & 1) * slot_out;
-        HIPCHK(c, hipMemcpyAsync(d_in, c->hp_in[k & 1].p, wl + std::min<uint64_t>(64, wcap_in - wl), hipMemcpyHostToDevice, st));
-        // the CRC registers of the window's pieces
-        const size_t np = w.pieces.size();
-        std::vector<uint32_t> states(np);
-        if (np) {
-            if (dd.ensure(np * (sizeof(FrameDesc) + 4) + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");
-            uint32_t *d_states = (uint32_t *)((uint8_t *)dd.p + np * sizeof(FrameDesc));
-            HIPCHK(c, hipMemcpyAsync(dd.p, w.pieces.data(), np * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
-            launch_frame_pieces((const FrameDesc *)dd.p, (uint32_t)np, (const CrcTabs *)c->crc_tabs.p, d_in, wcap_in & ~(uint64_t)15, "FDAT", d_states, st);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(states.data(), d_states, np * 4, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(c, hipStreamSynchronize(st));
-        for (size_t q = 0; q < np; q++) {
-            SolidChunk &cc = chunks[w.piece_chunk[q]];
-            cc.state = cc.started ? (crc_gf2_mulmod(crc_gf2_xpow(8 * w.piece_len[q]), cc.state) ^ states[q]) : states[q];
-            cc.started = true;
-            if (w.w0 + w.pieces[q].arc_off + w.piece_len[q] == cc.end) { cc.crc = ~cc.state; cc.done = true; }
-        }
-        std::vector<CrcPatchH> patches;
-        for (uint32_t j : w.crc_spans) {
-            const SolidSpan &sp = spans[j];
-            const SolidChunk &cc = chunks[sp.chunk];
-            if (!cc.done) return fail(c, PNA_E_INVAL, "internal: a chunk's CRC is due before its data is through");
-            uint32_t mask = 0;
-            for (int q = 0; q < 4; q++) if (sp.pos + q >= w.w0 && sp.pos + q < w.w1) mask |= 1u << q;
-            patches.push_back(CrcPatchH{(int64_t)sp.pos - (int64_t)w.w0, cc.crc, mask});
-        }
-        if (!patches.empty()) {
-            if (dp.ensure(patches.size() * sizeof(CrcPatchH) + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");
-            HIPCHK(c, hipMemcpyAsync(dp.p, patches.data(), patches.size() * sizeof(CrcPatchH), hipMemcpyHostToDevice, st));
-            launch_crc_patch(dp.p, (uint32_t)patches.size(), d_in, st);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipStreamSynchronize(st));                                               // (`patches` is read by the copy)
-        }
-        // the next window is assembled on a thread of its own while the device compresses this one
-        std::thread next;
-        if (k + 1 < nwin) next = std::thread([&, k]() { assemble(k + 1, win[(k + 1) & 1]); });
-        const uint64_t off0 = 0, len0 = wl; uint64_t offs[2] = {0, 0};
-        FrameJob fj{nullptr, 1, cipher, ivs};
-        fj.stream_len = plain_len;
-        if (cipher) { crun.final_win = k + 1 == nwin; fj.crun = &crun; }
-        if (defl) { fj.run = (k > 0 ? DRUN_CONT : 0u) | (k + 1 < nwin ? DRUN_OPEN : 0u); fj.adler_carry = (uint32_t *)c->solid_adler.p; }
-        rc = run_subbatch(c, algo, d_in, &off0, &len0, 0, 1, d_out, wcap_out, 0, offs, st, false, &fj);
-        if (rc == PNA_OK && hipMemcpyAsync(c->hp_out[k & 1].p, d_out, offs[1], hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
-        if (rc == PNA_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
-        if (next.joinable()) next.join();
-        if (rc == PNA_OK && offs[1] && sink(user, c->hp_out[k & 1].p, (size_t)offs[1]) != 0) rc = fail(c, PNA_E_SINK, "sink failed");
+        if (w.w1 - w.w0 < r.wcap_in) memset(slot + (w.w1 - w.w0), 0, std::min<uint64_t>(64, r.wcap_in - (w.w1 - w.w0)));
+        // entry bytes in jobs of at most 8 MiB, taken one by one by the threads: parallel_copy's fixed ranges measured 1.5 % slower on this path
+        // (2 048 x 1 MiB: 87.6 against 86.2 ms, profiles/host_pipeline_stages_rate.txt), so the window keeps its own pool
+        if (jobs.size() <= 1 || threads <= 1) { for (const CopyJob &jb : jobs) memcpy(jb.dst, jb.src, jb.len); return; }
+        std::atomic<size_t> next{0};
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < std::min<size_t>(threads, jobs.size()); t++)
+            th.emplace_back([&]() { for (size_t q; (q = next.fetch_add(1)) < jobs.size();) memcpy(jobs[q].dst, jobs[q].src, jobs[q].len); });
+        for (auto &x : th) x.join();
     }
+};
+}
+// ---- the stream's layout
+static SolidLayout solid_layout(size_t n, const char *const *names, const size_t *src_len) {
+    SolidLayout L;
+    std::vector<uint8_t> &blob = L.blob;
+    const uint64_t CH = 0xFFFFFFFBull;
+    uint64_t pos = 0;
+    uint8_t fend[12] = {0, 0, 0, 0, 'F', 'E', 'N', 'D', 0, 0, 0, 0};
+    { const uint32_t fc = frame_fend_crc(); fend[8] = (uint8_t)(fc >> 24); fend[9] = (uint8_t)(fc >> 16); fend[10] = (uint8_t)(fc >> 8); fend[11] = (uint8_t)fc; }
+    auto lit = [&](size_t from) { const uint64_t l = blob.size() - from; L.spans.push_back(SolidSpan{pos, l, 0u, 0u, (uint64_t)from, 0}); pos += l; };
+    for (size_t i = 0; i < n && L.chunks.size() <= 0x7FFFFFF0u; i++) {                         // (more chunks than that: refused by the caller)
+        const size_t b0 = blob.size();
+        if (src_len[i] == 0) { frame_inner_entry_empty(blob, names[i]); lit(b0); continue; }
+        const uint64_t len = src_len[i];
+        for (uint64_t o = 0; o < len; o += CH) {
+            const uint64_t cl = std::min<uint64_t>(CH, len - o);
+            const size_t b1 = blob.size();
+            if (o == 0) frame_entry_prefix(blob, names[i], PNA_ALGO_STORE, len, (uint32_t)cl);
+            else { const uint8_t h[8] = {(uint8_t)(cl >> 24), (uint8_t)(cl >> 16), (uint8_t)(cl >> 8), (uint8_t)cl, 'F', 'D', 'A', 'T'}; blob.insert(blob.end(), h, h + 8); }
+            lit(b1);
+            const uint32_t ci = (uint32_t)L.chunks.size();
+            L.chunks.emplace_back();
+            L.spans.push_back(SolidSpan{pos, cl, 1u, ci, (uint64_t)i, o}); pos += cl;
+            L.chunks[ci].end = pos;
+            L.spans.push_back(SolidSpan{pos, 4, 2u, ci, 0, 0}); pos += 4;
+        }
+        const size_t b2 = blob.size();
+        blob.insert(blob.end(), fend, fend + 12); lit(b2);
+    }
+    L.plain_len = pos;
+    return L;
+}
+// ---- window sizes, the two slots each way (page-locked and device), the workspaces that live from window to window
+static int solid_sizes(SolidRun &r) {
+    pna_gpu_ctx *c = r.c;
+    const bool gcm = r.cipher && r.cipher->cipher_mode == PNA_MODE_GCM;
+    const uint64_t G = gcm ? gcm_seg_size(r.cipher) : 0, plain_len = r.L.plain_len;
+    r.W = std::max<uint64_t>(1, (uint64_t)c->tun.solid_win_mib) << 20;                        // a multiple of SEG_SIZE
+    r.nwin = (plain_len + r.W - 1) / r.W;
+    r.wcap_in = std::min<uint64_t>(r.W, plain_len) + 8192;
+    r.wcap_out = pna_gpu_bound(r.algo, (size_t)std::min<uint64_t>(r.W, plain_len)) + (std::min<uint64_t>(r.W, plain_len) / SEG_SIZE + 2) * 16 + 4096;
+    if (gcm) r.wcap_out += G + 28 * ((r.wcap_out + G) / G + 2);    // GCM: the carry in front, a tag and SDAT framing per segment
+    int rc = ensure_crc(c); if (rc) return rc;
+    r.slot_in = (r.wcap_in + 255) & ~(uint64_t)255; r.slot_out = (r.wcap_out + 255) & ~(uint64_t)255;   // the two device slots each way
+    rc = Reserve{c}.add(c->stage_in, 2 * r.slot_in + 64).add(c->stage_out, 2 * r.slot_out + 64).add(c->hp_in, 2, r.wcap_in).add(c->hp_out, 2, r.wcap_out).done();
     if (rc) return rc;
-    if (sink(user, tail.data(), tail.size()) != 0) return fail(c, PNA_E_SINK, "sink failed");
+    if (r.algo == PNA_ALGO_DEFLATE && c->solid_adler.ensure(64)) return fail(c, PNA_E_NOMEM, "solid workspace");   // the stream's Adler-32 (A, B) between windows
+    if (gcm && c->solid_carry.ensure(G + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");              // the GCM carry between windows
+    r.crun.carry = (uint8_t *)c->solid_carry.p;
     return PNA_OK;
+}
+// ---- window k to the device and its CRC step: the raw CRC registers of its pieces to the host, chained into their chunks' (crc_gf2_mulmod / crc_gf2_xpow),
+// the CRCs that are complete now patched into the window.  An error exit leaves the window's H2D copy and kernels on the stream: solid_stream waits for them.
+static int solid_window_in(SolidRun &r, uint64_t k, const SolidWin &w) {
+    pna_gpu_ctx *c = r.c; hipStream_t st = c->stream;
+    DevBuf &dp = c->solid_place, &dd = c->solid_desc;                                          // patches, piece descriptors + states
+    const uint64_t wl = w.w1 - w.w0;
+    uint8_t *d_in = r.d_in(k);
+    HIPCHK(c, hipMemcpyAsync(d_in, c->hp_in[k & 1].p, wl + std::min<uint64_t>(64, r.wcap_in - wl), hipMemcpyHostToDevice, st));
+    const size_t np = w.pieces.size();
+    std::vector<uint32_t> states(np);
+    if (np) {
+        if (dd.ensure(np * (sizeof(FrameDesc) + 4) + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");
+        uint32_t *d_states = (uint32_t *)((uint8_t *)dd.p + np * sizeof(FrameDesc));
+        HIPCHK(c, hipMemcpyAsync(dd.p, w.pieces.data(), np * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+        launch_frame_pieces((const FrameDesc *)dd.p, (uint32_t)np, (const CrcTabs *)c->crc_tabs.p, d_in, r.wcap_in & ~(uint64_t)15, "FDAT", d_states, st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(states.data(), d_states, np * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (size_t q = 0; q < np; q++) {
+        SolidChunk &cc = r.L.chunks[w.piece_chunk[q]];
+        cc.state = cc.started ? (crc_gf2_mulmod(crc_gf2_xpow(8 * w.piece_len[q]), cc.state) ^ states[q]) : states[q];
+        cc.started = true;
+        if (w.w0 + w.pieces[q].arc_off + w.piece_len[q] == cc.end) { cc.crc = ~cc.state; cc.done = true; }
+    }
+    std::vector<CrcPatchH> patches;
+    for (uint32_t j : w.crc_spans) {
+        const SolidSpan &sp = r.L.spans[j];
+        const SolidChunk &cc = r.L.chunks[sp.chunk];
+        if (!cc.done) return fail(c, PNA_E_INVAL, "internal: a chunk's CRC is due before its data is through");
+        uint32_t mask = 0;
+        for (int q = 0; q < 4; q++) if (sp.pos + q >= w.w0 && sp.pos + q < w.w1) mask |= 1u << q;
+        patches.push_back(CrcPatchH{(int64_t)sp.pos - (int64_t)w.w0, cc.crc, mask});
+    }
+    if (!patches.empty()) {
+        if (dp.ensure(patches.size() * sizeof(CrcPatchH) + 64)) return fail(c, PNA_E_NOMEM, "solid workspace");
+        HIPCHK(c, hipMemcpyAsync(dp.p, patches.data(), patches.size() * sizeof(CrcPatchH), hipMemcpyHostToDevice, st));
+        launch_crc_patch(dp.p, (uint32_t)patches.size(), d_in, st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(st));                                                   // (`patches` is read by the copy)
+    }
+    return PNA_OK;
+}
+// ---- compress window k and hand it back; the next window is assembled on a thread of its own while the device compresses this one.  Every exit has joined
+// that thread; an error exit may leave kernels or the D2H copy on the stream: solid_stream waits for them.
+static int solid_window_compress(SolidRun &r, uint64_t k, const SolidWin &w, SolidAssembler &as, SolidWin &next_win) {
+    pna_gpu_ctx *c = r.c; hipStream_t st = c->stream;
+    struct Joined { std::thread t; ~Joined() { if (t.joinable()) t.join(); } } next;
+    if (k + 1 < r.nwin) next.t = std::thread([&, k]() { as.assemble(k + 1, next_win); });
+    const uint64_t off0 = 0, len0 = w.w1 - w.w0; uint64_t offs[2] = {0, 0};
+    FrameJob fj{nullptr, 1, r.cipher, r.ivs};
+    fj.stream_len = r.L.plain_len;
+    if (r.cipher) { r.crun.final_win = k + 1 == r.nwin; fj.crun = &r.crun; }
+    if (r.algo == PNA_ALGO_DEFLATE) { fj.run = (k > 0 ? DRUN_CONT : 0u) | (k + 1 < r.nwin ? DRUN_OPEN : 0u); fj.adler_carry = (uint32_t *)c->solid_adler.p; }
+    int rc = run_subbatch(c, r.algo, r.d_in(k), &off0, &len0, 0, 1, r.d_out(k), r.wcap_out, 0, offs, st, false, &fj);
+    if (rc == PNA_OK && hipMemcpyAsync(c->hp_out[k & 1].p, r.d_out(k), offs[1], hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
+    if (rc == PNA_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
+    if (next.t.joinable()) next.t.join();
+    return rc ? rc : sink_put(c, r.sink, r.user, c->hp_out[k & 1].p, (size_t)offs[1]);
+}
+static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
+                        const pna_gpu_cipher *cipher, const uint8_t *ivs, pna_sink_fn sink, void *user) {
+    set_call_level(c, algo, level);
+    SolidRun r{c, algo, cipher, ivs, sink, user, solid_layout(n, names, src_len), {}};
+    if (r.L.chunks.size() > 0x7FFFFFF0u) return fail(c, PNA_E_INVAL, "too many data chunks");
+    // the fixed chunks around the stream (GCM: the stream header is the stream's first SDAT chunk, as in the device form)
+    std::vector<uint8_t> head, tail;
+    solid_archive_head(head, algo, cipher, ivs);
+    frame_solid_tail(tail); frame_archive_tail(tail);
+    int rc = sink_put(c, sink, user, head.data(), head.size()); if (rc) return rc;
+    if ((rc = solid_sizes(r))) return rc;
+    const CallTotalScope call_total(c, r.L.plain_len);                                        // every window picks the block size of the whole stream
+    SolidAssembler as{r, src, staging_threads(c)};
+    SolidWin win[2];
+    if (r.nwin) as.assemble(0, win[0]);
+    for (uint64_t k = 0; k < r.nwin && rc == PNA_OK; k++) {
+        rc = solid_window_in(r, k, win[k & 1]);
+        if (rc == PNA_OK) rc = solid_window_compress(r, k, win[k & 1], as, win[(k + 1) & 1]);
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }                             // (no thread is left; what the window left on the stream is waited for: its slots are the next call's)
+    return sink_put(c, sink, user, tail.data(), tail.size());                                 // (nothing in flight)
 }
 
 // Page-locked staging memory the context holds right now (the slots of the host pipelines; plan blobs and tables excluded): what tests/ pin the
@@ -188,6 +219,10 @@ extern "C" uint64_t pna_gpu_debug_pinned_bytes(pna_gpu_ctx *c) {
     return t;
 }
 
+// the entries of [e0, e1) into a page-locked buffer at off[e], on the staging threads (below 8 MiB: on the calling thread)
+static void parallel_stage(uint8_t *dst, const void *const *src, const size_t *src_len, const uint64_t *off, size_t e0, size_t e1, unsigned threads) {
+    parallel_copy(e1 - e0, threads, 8u << 20, [=](size_t i) { return CopyJob{dst + off[e0 + i], (const uint8_t *)src[e0 + i], src_len[e0 + i]}; });
+}
 // no entries, or zstd's single_frame option (an entry's segments form ONE frame): one H2D of the entries, the device path, one D2H of the archive, handed
 // to the sink in pieces of at most 16 MiB
 static int solid_one_shot(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
@@ -197,21 +232,18 @@ static int solid_one_shot(pna_gpu_ctx *c, int algo, int level, size_t n, const c
     for (size_t i = 0; i < n; i++) { off[i] = pos; len[i] = src_len[i]; pos = (pos + src_len[i] + 15) & ~(uint64_t)15; }
     off[n] = pos;
     const size_t cap = pna_gpu_solid_archive_enc_bound(algo, n, names, len.data(), cipher);
-    if (c->stage_in.ensure(pos + 8192) || c->stage_out.ensure(cap + 64) || c->hp_in[0].ensure(pos + 64) || c->hp_out[0].ensure(cap + 64))
-        return fail(c, PNA_E_NOMEM, "staging allocation failed");
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    parallel_stage((uint8_t *)c->hp_in[0].p, src, src_len, off.data(), 0, n, std::min(8u, std::max(1u, hw / 2)));
+    int rc = Reserve{c}.add(c->stage_in, pos + 8192).add(c->stage_out, cap + 64).add(c->hp_in[0], pos + 64).add(c->hp_out[0], cap + 64).done();
+    if (rc) return rc;
+    parallel_stage((uint8_t *)c->hp_in[0].p, src, src_len, off.data(), 0, n, staging_threads(c));
     if (pos) HIPCHK(c, hipMemcpyAsync(c->stage_in.p, c->hp_in[0].p, pos, hipMemcpyHostToDevice, c->stream));
     uint64_t total = 0;
-    int rc = pna_gpu_create_solid_archive_enc_device(c, algo, level, n, names, c->stage_in.p, off.data(), len.data(), cipher, c->stage_out.p, cap + 64, &total, nullptr);
+    rc = pna_gpu_create_solid_archive_enc_device(c, algo, level, n, names, c->stage_in.p, off.data(), len.data(), cipher, c->stage_out.p, cap + 64, &total, nullptr);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->hp_out[0].p, c->stage_out.p, total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint64_t p = 0; p < total; p += (16u << 20)) {
-        const size_t k = (size_t)std::min<uint64_t>(16u << 20, total - p);
-        if (sink(user, (const uint8_t *)c->hp_out[0].p + p, k) != 0) return fail(c, PNA_E_SINK, "sink failed");
-    }
-    return PNA_OK;
+    for (uint64_t p = 0; p < total && rc == PNA_OK; p += (16u << 20))
+        rc = sink_put(c, sink, user, (const uint8_t *)c->hp_out[0].p + p, (size_t)std::min<uint64_t>(16u << 20, total - p));
+    return rc;
 }
 static bool solid_windowed(const pna_gpu_ctx *c, int algo, size_t n) {
     return n && c->tun.solid_win_mib > 0 && (algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_ZSTD && !c->tun.single_frame));
@@ -298,35 +330,259 @@ static bool entries_all_lent(pna_gpu_ctx *c, const void *const *src, const size_
     return true;
 }
 
-static void parallel_stage(uint8_t *dst, const void *const *src, const size_t *src_len, const uint64_t *off, size_t e0, size_t e1, unsigned threads) {
-    uint64_t total = 0;
-    for (size_t e = e0; e < e1; e++) total += src_len[e];
-    if (threads <= 1 || total < (8u << 20)) { for (size_t e = e0; e < e1; e++) if (src_len[e]) memcpy(dst + off[e], src[e], src_len[e]); return; }
-    std::vector<std::thread> th;
-    const uint64_t per = (total + threads - 1) / threads;
-    size_t e = e0;
-    for (unsigned t = 0; t < threads && e < e1; t++) {
-        size_t b = e; uint64_t acc = 0;
-        while (e < e1 && (acc < per || t + 1 == threads)) acc += src_len[e++];
-        th.emplace_back([=]() { for (size_t i = b; i < e; i++) if (src_len[i]) memcpy(dst + off[i], src[i], src_len[i]); });
+namespace {
+// ---- pna_gpu_create_archive_host in stages.  CreateCall: what the stages share; CreatePlan: the sub-batches and the per-entry arrays they are cut over
+struct CreateCall {
+    pna_gpu_ctx *c; int algo; size_t n; const char *const *names; const void *const *src; const size_t *src_len;
+    const pna_gpu_cipher *cipher; const uint8_t *ivs; const pna_gpu_entry_meta *meta; uint32_t part_flags, max_chunk; pna_sink_fn sink; void *user;
+    std::chrono::steady_clock::time_point t_entry, t0;          // PNA_TRACE: the call's start, the pipeline's start
+    void trace(const char *what, size_t k) const {
+        if (c->tun.trace) fprintf(stderr, "[pna create] %8.3f ms  %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what, k);
     }
-    for (auto &x : th) x.join();
+};
+struct Sub { size_t e0, e1; uint64_t in_bytes, out_cap; };
+struct CreatePlan {
+    std::vector<Sub> subs; uint64_t *off, *len64, *ecap, *eoff;   // staging offsets, lengths, capacity terms, archive offsets of the entries (the context's arrays)
+    uint64_t in_total = 0; bool all_lent = false;                // (then no page-locked staging of the library's own is needed, and no staging copy)
+    uint64_t out_len[2] = {0, 0}, out_total = 0;                 // archive bytes in the two output slots, bytes handed to the sink
+};
+constexpr int NS = 4;                                            // input slots (page-locked staging + device buffer)
+// ---- the stager: sub-batch i into slot i % NS as soon as sub-batch i - NS has left the device.  It owns its thread: the destructor stops and joins it, so no
+// exit of the pipeline leaves it running (what it has issued on cp_in by then is the caller's to wait for).
+struct Stager {
+    const CreateCall &k; const CreatePlan &p;
+    std::mutex mu; std::condition_variable cv;
+    size_t staged = 0, freed = 0; int rc = PNA_OK; bool stop = false;      // sub-batches staged (copies issued) / sub-batches whose kernels are done
+    const unsigned threads;
+    std::thread th;
+    Stager(const CreateCall &call, const CreatePlan &plan) : k(call), p(plan), threads(staging_threads(call.c)), th([this] { run(); }) {}
+    ~Stager() { { std::lock_guard<std::mutex> lk(mu); stop = true; cv.notify_all(); } th.join(); }
+    int wait_staged(size_t i) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return staged > i; }); return rc; }
+    void release(size_t i) { std::lock_guard<std::mutex> lk(mu); freed = i + 1; cv.notify_all(); }        // sub-batch i's kernels are done: its input slot is free
+  private:
+    void give_up(int r) { std::lock_guard<std::mutex> lk(mu); rc = r; staged = p.subs.size(); cv.notify_all(); }
+    // every entry lies in page-locked memory the library lent out (pna_gpu_host_alloc): no staging copy, the copy engine reads the host's
+    // buffers themselves -- runs of entries that are contiguous there and here (16-byte stride) travel as ONE copy
+    int lend_subbatch(const Sub &sb, uint8_t *db) const {
+        const uint64_t *off = p.off;
+        for (size_t g0 = sb.e0, g1; g0 < sb.e1; g0 = g1) {
+            g1 = g0 + 1;
+            while (g1 < sb.e1 && (const uint8_t *)k.src[g1] == (const uint8_t *)k.src[g0] + (off[g1] - off[g0])) g1++;
+            const uint64_t bytes = (g1 < sb.e1 ? off[g1] : off[g1 - 1] + k.src_len[g1 - 1]) - off[g0];
+            const uint64_t nb = std::min<uint64_t>(bytes, (const uint8_t *)k.src[g1 - 1] + k.src_len[g1 - 1] - (const uint8_t *)k.src[g0]);
+            if (nb && hipMemcpyAsync(db + off[g0], k.src[g0], nb, hipMemcpyHostToDevice, k.c->cp_in) != hipSuccess) return PNA_E_HIP;
+        }
+        return PNA_OK;
+    }
+    // entries in pageable memory: groups of ~128 MiB into the slot's page-locked buffer on the staging threads, each group's H2D copy right behind it
+    int stage_subbatch(const Sub &sb, uint8_t *hb, uint8_t *db) const {
+        for (size_t g0 = sb.e0, g1; g0 < sb.e1; g0 = g1) {
+            uint64_t acc = 0;
+            for (g1 = g0; g1 < sb.e1 && acc < (128ull << 20);) acc += k.src_len[g1++];
+            parallel_stage(hb, k.src, k.src_len, p.off, g0, g1, threads);
+            const uint64_t b0 = p.off[g0], b1 = g1 < sb.e1 ? p.off[g1] : sb.in_bytes;
+            if (b1 > b0 && hipMemcpyAsync(db + b0, hb + b0, b1 - b0, hipMemcpyHostToDevice, k.c->cp_in) != hipSuccess) return PNA_E_HIP;
+        }
+        return PNA_OK;
+    }
+    void run() {
+        pna_gpu_ctx *c = k.c;
+        try {
+            if (hipSetDevice(c->device) != hipSuccess) { give_up(PNA_E_HIP); return; }
+            for (size_t i = 0; i < p.subs.size(); i++) {
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return stop || i < freed + NS; });
+                    if (stop) return;
+                }
+                const int sl = (int)(i % NS);
+                int r = p.all_lent ? lend_subbatch(p.subs[i], (uint8_t *)c->dp_in[sl].p) : stage_subbatch(p.subs[i], (uint8_t *)c->hp_in[sl].p, (uint8_t *)c->dp_in[sl].p);
+                if (r == PNA_OK && hipEventRecord(c->ev_in[sl], c->cp_in) != hipSuccess) r = PNA_E_HIP;
+                k.trace("staged + H2D issued", i);
+                if (r != PNA_OK) { give_up(r); return; }
+                std::lock_guard<std::mutex> lk(mu);
+                staged = i + 1; cv.notify_all();
+            }
+        } catch (...) { give_up(PNA_E_NOMEM); }
+    }
+};
+}
+// ---- check and resolve: arguments, metadata, algorithm, level, IVs; the device, the copy streams
+static int create_check(CreateCall &k, int level, std::vector<uint8_t> &own_ivs) {
+    pna_gpu_ctx *c = k.c;
+    { int rcm = check_meta(c, k.meta, k.n); if (rcm) return rcm; }
+    if (!c || !k.sink || (k.n && (!k.names || !k.src || !k.src_len))) return fail(c, PNA_E_INVAL, "null argument");
+    if (!encode_algo_ok(c, k.algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    set_call_level(c, k.algo, level);
+    if (k.cipher && k.cipher->encryption == PNA_ENC_NONE) k.cipher = nullptr;
+    if (k.cipher) { int rc0 = resolve_ivs(c, k.cipher, k.n, own_ivs, &k.ivs); if (rc0) return rc0; }
+    HIPCHK(c, hipSetDevice(c->device));
+    return ensure_copy_lanes(c);
+}
+// ---- capacity terms: every entry's share of its sub-batch's output capacity (name length, worst-case payload, chunk framing): on the host-loop threads -- for
+// 10^5 .. 10^6 small entries this loop, on one thread, was 8 .. 40 ms in front of the pipeline (a third of the end-to-end time of 10^6 x 4 KiB)
+static void capacity_terms(const CreateCall &k, CreatePlan &p) {
+    pna_gpu_ctx *c = k.c; const size_t n = k.n;
+    // (the context keeps these arrays between calls: 10^6 entries are 24 MB, and fresh memory costs a page fault per 4 KiB -- milliseconds in front of the pipeline)
+    if (c->pl_off.size() < n + 1) { c->pl_off.resize(n + 1); c->pl_len.resize(n + 1); c->pl_cap.resize(n + 1); }
+    if (c->pl_eoff.size() < n + 1) c->pl_eoff.resize(n + 1);
+    p.off = c->pl_off.data(); p.len64 = c->pl_len.data(); p.ecap = c->pl_cap.data(); p.eoff = c->pl_eoff.data();
+    const unsigned plan_nt = host_loop_threads(n);
+    std::vector<std::pair<uint64_t, uint64_t>> psum(plan_nt, {0, 0});         // (bytes, longest entry) per thread
+    par_ranges(n, plan_nt, [&](unsigned t, size_t a, size_t b) {
+        uint64_t tot = 0, mx = 0;
+        for (size_t i = a; i < b; i++) {
+            const uint64_t l = k.src_len[i], wb = pna_gpu_bound(k.algo, (size_t)l);
+            tot += l; mx = std::max(mx, l);
+            uint64_t cap = (k.cipher ? frame_entry_prefix_enc_bound(k.names[i], k.cipher->phsf) + 16 : frame_entry_prefix_bound(k.names[i])) + meta_len(k.meta, i) + wb + 16;
+            if (k.cipher && k.cipher->cipher_mode == PNA_MODE_GCM) cap += 16 * (wb / gcm_seg_size(k.cipher));   // a tag per full stream segment
+            // a CRC + a header per further FDAT chunk once max_chunk_size cuts the payload (the term of pna_gpu_archive_chunked_bound: without it data
+            // that does not compress overran the sub-batch's device buffer by 12 bytes per chunk -- PNA_E_DSTSIZE for a 2 MiB random entry at mcs = 1000)
+            cap += 12 * (uint64_t)((wb + 64 + 16 * (l >> 12)) / chunk_limit(k.max_chunk) + 1);
+            p.ecap[i] = cap;
+        }
+        psum[t] = {tot, mx};
+    });
+    uint64_t longest = 0;
+    for (auto &q : psum) { p.in_total += q.first; longest = std::max(longest, q.second); }
+    plan_call_longest(c, longest);
+}
+// ---- Sub-batches.  What bounds this path is the host link in the H2D direction (page-locked memory -> HBM: 56.8 GB/s on the MI355X boxes;
+// experiments/link_duplex.hip, profiles/r03_c_link_duplex.txt) -- the kernels take a sixth of that time, the archive bytes going back a third of the
+// volume and the link is full duplex.  So the pipeline is built around ONE rule: the H2D copy engine never waits.
+//   * a stager thread runs ahead through all sub-batches over a ring of four input slots (page-locked staging + device buffer): it copies
+//     the entries of a sub-batch into the slot's page-locked buffer (several threads, groups of ~128 MiB) and issues each group's H2D copy
+//     right behind it; it blocks only while all four slots are in use (a slot is free again when its sub-batch's kernels are done);
+//   * the main thread takes the sub-batches in order: kernels on the context's stream, then the archive bytes of the sub-batch travel to
+//     the host next to the following sub-batch's kernels and copies -- by a small copy KERNEL that stores into the page-locked buffer
+//     (d2h_wgs workgroups: ~30 GB/s, which leaves the H2D engine its full rate; the runtime's own D2H copy ran as a blit kernel at 51 GB/s
+//     and took 30 % off the H2D copies next to it) --, and are handed to the sink one sub-batch later;
+//   * sub-batch sizes grow from 64 MiB to `sub_mib` (default 256 MiB) at the start: the first kernels start after 2 ms instead of 20, and
+//     what is left to do when the last input byte has arrived is the work of one sub-batch.  256 MiB is the smallest size whose kernels
+//     (1.2 ms of fixed costs + 1 ms per 85 MiB) keep up with its H2D copy (1 ms per 53 MiB); shrinking sizes at the end only makes the
+//     kernels fall behind the copies (measured, LAB_LOG.md).
+static void cut_subbatches(const CreateCall &k, CreatePlan &p) {
+    pna_gpu_ctx *c = k.c;
+    const uint64_t SUBMAX = (uint64_t)c->tun.sub_mib << 20, SUBMIN = std::min<uint64_t>(64ull << 20, SUBMAX);
+    uint64_t target = SUBMIN;
+    for (size_t e = 0; e < k.n;) {
+        const uint64_t want = std::min(target, SUBMAX);
+        Sub sb{e, e, 0, 64}; uint64_t pos = 0; size_t blocks = 0;
+        while (sb.e1 < k.n) {
+            const size_t i = sb.e1; const uint64_t l = k.src_len[i];
+            const size_t nb = plan_blocks(c, l);
+            if (i > sb.e0 && (pos + l > want || blocks + nb > c->max_blocks)) break;
+            p.off[i] = pos; p.len64[i] = l; pos = (pos + l + 15) & ~(uint64_t)15; blocks += nb;
+            sb.out_cap += p.ecap[i];
+            sb.e1++;
+        }
+        sb.in_bytes = pos; p.subs.push_back(sb); e = sb.e1;
+        target = std::min(SUBMAX, target * 2);
+    }
+}
+// ---- slots sized once for the largest sub-batch (allocation of page-locked memory is slow: not inside the pipeline)
+static int reserve_create_slots(const CreateCall &k, const CreatePlan &p) {
+    pna_gpu_ctx *c = k.c;
+    uint64_t max_in = 0, max_out = 0;
+    for (const Sub &sb : p.subs) { max_in = std::max(max_in, sb.in_bytes); max_out = std::max(max_out, sb.out_cap); }
+    const size_t ns_in = std::min<size_t>(NS, p.subs.size()), ns_out = std::min<size_t>(2, p.subs.size());
+    return Reserve{c}.add(c->hp_in, p.all_lent ? 0 : ns_in, max_in + 8192).add(c->dp_in, ns_in, max_in + 8192).add(c->dp_out, ns_out, max_out + 64).add(c->hp_out, ns_out, max_out + 64).done();
+}
+// sub-batch `so`'s archive bytes from its device slot to its page-locked one on cp_out: by k_link_copy (option d2h_wgs) or the runtime's copy
+static int copy_out(const CreateCall &k, const CreatePlan &p, int so, uint8_t *(&dev_view)[2]) {
+    pna_gpu_ctx *c = k.c;
+    const uint32_t d2h_wgs = (uint32_t)c->tun.d2h_wgs;
+    bool ok = true;
+    if (d2h_wgs && !dev_view[so]) ok = hipHostGetDevicePointer((void **)&dev_view[so], c->hp_out[so].p, 0) == hipSuccess;
+    if (ok && d2h_wgs) { launch_link_copy((const uint8_t *)c->dp_out[so].p, dev_view[so], p.out_len[so], d2h_wgs, c->cp_out); ok = hipGetLastError() == hipSuccess; }
+    else if (ok) ok = hipMemcpyAsync(c->hp_out[so].p, c->dp_out[so].p, p.out_len[so], hipMemcpyDeviceToHost, c->cp_out) == hipSuccess;
+    if (!ok || hipEventRecord(c->ev_out[so], c->cp_out) != hipSuccess) return fail(c, PNA_E_HIP, "D2H copy failed");
+    return PNA_OK;
+}
+// the archive bytes in output slot `so` (their copy has been waited for) -> sink
+static int hand_over(const CreateCall &k, CreatePlan &p, int so) {
+    const int rc = sink_put(k.c, k.sink, k.user, k.c->hp_out[so].p, p.out_len[so]);
+    p.out_total += p.out_len[so];
+    return rc;
+}
+// ---- the drain loop: the sub-batches in order -- kernels on the context's stream, the archive bytes on their way to the host (copy_out), the sub-batch
+// before handed to the sink.  An error exit leaves copies and kernels in flight: the caller stops the stager, then waits for the device.
+static int drain_subbatches(const CreateCall &k, CreatePlan &p, Stager &stager) {
+    pna_gpu_ctx *c = k.c;
+    const FrameJob fj{k.names, 0, k.cipher, k.ivs, k.meta, k.max_chunk, false};
+    const CallTotalScope call_total(c, p.len64, k.n);                                               // (the block size follows the archive, not its sub-batches)
+    uint8_t *dev_view[2] = {nullptr, nullptr};                   // device views of the page-locked output slots (the copy kernel's destination)
+    for (size_t i = 0; i < p.subs.size(); i++) {
+        const Sub &sb = p.subs[i]; const int sl = (int)(i % NS), so = (int)(i & 1);
+        if (const int r = stager.wait_staged(i)) return fail(c, r, "staging / H2D copy failed");
+        if (hipEventSynchronize(c->ev_in[sl]) != hipSuccess) return fail(c, PNA_E_HIP, "H2D copy failed");
+        k.trace("H2D done, kernels start", i);
+        int rc = run_subbatch(c, k.algo, (const uint8_t *)c->dp_in[sl].p, p.off, p.len64, sb.e0, sb.e1, (uint8_t *)c->dp_out[so].p, sb.out_cap + 64, 0, p.eoff, c->stream, true, &fj);
+        stager.release(i);                                       // (run_subbatch has waited for its kernels: the input slot is free)
+        k.trace("kernels done", i);
+        if (rc == PNA_OK) { p.out_len[so] = p.eoff[sb.e1]; rc = copy_out(k, p, so, dev_view); }
+        if (rc == PNA_OK && i > 0) {                             // archive bytes of the previous sub-batch -> sink
+            if (hipEventSynchronize(c->ev_out[so ^ 1]) != hipSuccess) return fail(c, PNA_E_HIP, "D2H copy failed");
+            rc = hand_over(k, p, so ^ 1);
+        }
+        if (rc) return rc;
+    }
+    return PNA_OK;
+}
+// ---- finish: the last sub-batch, the tail, the call's totals.  Its copy has been waited for when the sink is called: nothing is in flight at these exits
+static int create_finish(const CreateCall &k, CreatePlan &p, const std::vector<uint8_t> &tail) {
+    pna_gpu_ctx *c = k.c;
+    int rc = PNA_OK;
+    if (!p.subs.empty()) {
+        const int so = (int)((p.subs.size() - 1) & 1);
+        HIPCHK(c, hipEventSynchronize(c->ev_out[so]));
+        if ((rc = hand_over(k, p, so))) return rc;
+    }
+    if ((rc = sink_put(c, k.sink, k.user, tail.data(), tail.size()))) return rc;
+    p.out_total += tail.size();
+    k.trace("all bytes handed to the sink", 0);
+    c->timing.in_bytes = p.in_total; c->timing.out_bytes = p.out_total;
+    return PNA_OK;
+}
+static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                    const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                    const pna_gpu_entry_meta *meta, uint32_t part_flags, pna_sink_fn sink, void *user, uint32_t max_chunk) {
+    using clk = std::chrono::steady_clock;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    CreateCall k{c, algo, n, names, src, src_len, cipher, nullptr, meta, part_flags, max_chunk, sink, user, clk::now(), {}};
+    std::vector<uint8_t> own_ivs;
+    int rc = create_check(k, level, own_ivs); if (rc) return rc;
+    c->timing = pna_gpu_timing{};
+    std::vector<uint8_t> head, tail;
+    if (part_flags & PNA_PART_HEAD) frame_archive_head(head, 0);
+    if (part_flags & PNA_PART_TAIL) frame_archive_tail(tail);
+    if ((rc = sink_put(c, sink, user, head.data(), head.size()))) return rc;
+    CreatePlan p;
+    p.out_total = head.size();
+    capacity_terms(k, p);
+    const auto t_caps = clk::now();
+    cut_subbatches(k, p);
+    const auto t_cut = clk::now();
+    p.all_lent = entries_all_lent(c, src, src_len, n);
+    if ((rc = reserve_create_slots(k, p))) return rc;
+    k.t0 = clk::now();
+    if (c->tun.trace) fprintf(stderr, "[pna create] planning took %.3f ms (capacity terms at %.3f, sub-batches cut at %.3f)\n", ms(k.t_entry, k.t0), ms(k.t_entry, t_caps), ms(k.t_entry, t_cut));
+    k.trace("planned, slots ready; sub-batches:", p.subs.size());
+    { Stager stager(k, p); rc = drain_subbatches(k, p, stager); }                             // (the stager is stopped and joined behind this line)
+    k.trace("loop done", 0);
+    if (rc != PNA_OK) { (void)hipDeviceSynchronize(); return rc; }                            // (nothing of this call is in flight when the error is returned)
+    return create_finish(k, p, tail);
 }
 
 extern "C" int pna_gpu_create_archive_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                            const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
     return pna_gpu_create_archive_enc_host(c, algo, level, n, names, src, src_len, nullptr, sink, user);
 }
-
 extern "C" int pna_gpu_create_archive_enc_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
                                                pna_sink_fn sink, void *user) {
     return pna_gpu_create_archive_meta_host(c, algo, level, n, names, src, src_len, cipher, nullptr, sink, user);
 }
-
-static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
-                                    const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
-                                    const pna_gpu_entry_meta *meta, uint32_t part_flags, pna_sink_fn sink, void *user, uint32_t max_chunk);
 extern "C" int pna_gpu_create_archive_meta_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                 const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
                                                 const pna_gpu_entry_meta *meta, pna_sink_fn sink, void *user) {
@@ -376,7 +632,7 @@ extern "C" int pna_gpu_create_archive_multi_host(pna_gpu_ctx *const *ctxs, size_
     // Every range runs the bounded pipeline on a thread of its own; range 0 hands its pieces to the caller's sink as they come, the ranges behind it keep
     // theirs in memory until every range before them has finished (the sink sees the archive in index order, on the calling thread only).  An exception
     // inside a worker (allocation) is that range's PNA_E_NOMEM, not a terminate; the first failing range's code is returned and its message copied to
-    // ctxs[0] (what pna_gpu_last_error of the first context reports).
+    // ctxs[0] (what pna_gpu_last_error of the first context reports).  Every exit lies behind the join of the range threads.
     struct Part { std::vector<uint8_t> buf; int rc = PNA_OK; bool done = false; };
     std::vector<Part> parts(n_ctx);
     // every range picks the block size of the WHOLE call (pna_ctx.h CallTotalScope): the archive equals pna_gpu_create_archive_host's on one context
@@ -395,308 +651,118 @@ extern "C" int pna_gpu_create_archive_multi_host(pna_gpu_ctx *const *ctxs, size_
             std::lock_guard<std::mutex> lk(mu);
             parts[r].rc = rc; parts[r].done = true; cv.notify_all();
         });
-    int rc0;
-    try { rc0 = pna_gpu_create_archive_part_host(ctxs[0], algo, level, lo[1] - lo[0], names + lo[0], src + lo[0], src_len + lo[0], PNA_PART_HEAD, sink, user); }
-    catch (...) { rc0 = fail(ctxs[0], PNA_E_NOMEM, "out of memory"); }
-    int rc = rc0;
+    int rc;
+    try { rc = pna_gpu_create_archive_part_host(ctxs[0], algo, level, lo[1] - lo[0], names + lo[0], src + lo[0], src_len + lo[0], PNA_PART_HEAD, sink, user); }
+    catch (...) { rc = fail(ctxs[0], PNA_E_NOMEM, "out of memory"); }
     for (size_t r = 1; r < n_ctx; r++) {
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return parts[r].done; }); }
         if (rc == PNA_OK && parts[r].rc != PNA_OK) { rc = parts[r].rc; const std::string msg = std::string("range ") + std::to_string(r) + ": " + pna_gpu_last_error(ctxs[r]); (void)fail(ctxs[0], rc, msg.c_str()); }
-        if (rc == PNA_OK && !parts[r].buf.empty() && sink(user, parts[r].buf.data(), parts[r].buf.size()) != 0) rc = fail(ctxs[0], PNA_E_SINK, "sink failed");
+        if (rc == PNA_OK) rc = sink_put(ctxs[0], sink, user, parts[r].buf.data(), parts[r].buf.size());
         std::vector<uint8_t>().swap(parts[r].buf);                // handed on (or abandoned): the memory goes back at once
     }
     for (auto &t : th) t.join();
     return rc;
 }
-static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
-                                    const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
-                                    const pna_gpu_entry_meta *meta, uint32_t part_flags, pna_sink_fn sink, void *user, uint32_t max_chunk) {
-    const auto t_entry = std::chrono::steady_clock::now();
-    { int rcm = check_meta(c, meta, n); if (rcm) return rcm; }
-    if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
-    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
-    set_call_level(c, algo, level);
-    if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
-    std::vector<uint8_t> own_ivs;
-    const uint8_t *ivs = nullptr;
-    if (cipher) { int rc0 = resolve_ivs(c, cipher, n, own_ivs, &ivs); if (rc0) return rc0; }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->cp_in) {
-        HIPCHK(c, hipStreamCreate(&c->cp_in)); HIPCHK(c, hipStreamCreate(&c->cp_out));
-        for (auto &e : c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : c->ev_out) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    c->timing = pna_gpu_timing{};
-    std::vector<uint8_t> head, tail;
-    if (part_flags & PNA_PART_HEAD) frame_archive_head(head, 0);
-    if (part_flags & PNA_PART_TAIL) frame_archive_tail(tail);
-    if (!head.empty() && sink(user, head.data(), head.size()) != 0) return fail(c, PNA_E_SINK, "sink failed");
-    // Sub-batches.  What bounds this path is the host link in the H2D direction (page-locked memory -> HBM: 56.8 GB/s on the MI355X boxes;
-    // experiments/link_duplex.hip, profiles/r03_c_link_duplex.txt) -- the kernels take a sixth of that time, the archive bytes going back a third of the
-    // volume and the link is full duplex.  So the pipeline is built around ONE rule: the H2D copy engine never waits.
-    //   * a stager thread runs ahead through all sub-batches over a ring of four input slots (page-locked staging + device buffer): it copies
-    //     the entries of a sub-batch into the slot's page-locked buffer (several threads, groups of ~128 MiB) and issues each group's H2D copy
-    //     right behind it; it blocks only while all four slots are in use (a slot is free again when its sub-batch's kernels are done);
-    //   * the main thread takes the sub-batches in order: kernels on the context's stream, then the archive bytes of the sub-batch travel to
-    //     the host next to the following sub-batch's kernels and copies -- by a small copy KERNEL that stores into the page-locked buffer
-    //     (d2h_wgs workgroups: ~30 GB/s, which leaves the H2D engine its full rate; the runtime's own D2H copy ran as a blit kernel at 51 GB/s
-    //     and took 30 % off the H2D copies next to it) --, and are handed to the sink one sub-batch later;
-    //   * sub-batch sizes grow from 64 MiB to `sub_mib` (default 256 MiB) at the start: the first kernels start after 2 ms instead of 20, and
-    //     what is left to do when the last input byte has arrived is the work of one sub-batch.  256 MiB is the smallest size whose kernels
-    //     (1.2 ms of fixed costs + 1 ms per 85 MiB) keep up with its H2D copy (1 ms per 53 MiB); shrinking sizes at the end only makes the
-    //     kernels fall behind the copies (measured, LAB_LOG.md).
-    const uint64_t SUBMAX = (uint64_t)c->tun.sub_mib << 20, SUBMIN = std::min<uint64_t>(64ull << 20, SUBMAX);
-    struct Sub { size_t e0, e1; uint64_t in_bytes, out_cap; };
-    std::vector<Sub> subs;
-    // (the context keeps these arrays between calls: 10^6 entries are 24 MB, and fresh memory costs a page fault per 4 KiB -- milliseconds in front of the pipeline)
-    if (c->pl_off.size() < n + 1) { c->pl_off.resize(n + 1); c->pl_len.resize(n + 1); c->pl_cap.resize(n + 1); }
-    uint64_t *off = c->pl_off.data(), *len64 = c->pl_len.data(), *ecap = c->pl_cap.data();
-    uint64_t in_total = 0, longest = 0;
-    // every entry's share of its sub-batch's output capacity (name length, worst-case payload, chunk framing): on the host-loop threads -- for 10^5 .. 10^6 small
-    // entries this loop, on one thread, was 8 .. 40 ms in front of the pipeline (a third of the end-to-end time of 10^6 x 4 KiB)
-    const unsigned plan_nt = host_loop_threads(n);
-    std::vector<std::pair<uint64_t, uint64_t>> psum(plan_nt, {0, 0});         // (bytes, longest entry) per thread
-    par_ranges(n, plan_nt, [&](unsigned t, size_t a, size_t b) {
-        uint64_t tot = 0, mx = 0;
-        for (size_t i = a; i < b; i++) {
-            const uint64_t l = src_len[i], wb = pna_gpu_bound(algo, (size_t)l);
-            tot += l; mx = std::max(mx, l);
-            uint64_t cap = (cipher ? frame_entry_prefix_enc_bound(names[i], cipher->phsf) + 16 : frame_entry_prefix_bound(names[i])) + meta_len(meta, i) + wb + 16;
-            if (cipher && cipher->cipher_mode == PNA_MODE_GCM) cap += 16 * (wb / gcm_seg_size(cipher));   // a tag per full stream segment
-            // a CRC + a header per further FDAT chunk once max_chunk_size cuts the payload (the term of pna_gpu_archive_chunked_bound: without it data
-            // that does not compress overran the sub-batch's device buffer by 12 bytes per chunk -- PNA_E_DSTSIZE for a 2 MiB random entry at mcs = 1000)
-            cap += 12 * (uint64_t)((wb + 64 + 16 * (l >> 12)) / chunk_limit(max_chunk) + 1);
-            ecap[i] = cap;
-        }
-        psum[t] = {tot, mx};
-    });
-    for (auto &q : psum) { in_total += q.first; longest = std::max(longest, q.second); }
-    plan_call_longest(c, longest);
-    const auto t_caps = std::chrono::steady_clock::now();
-    {
-        uint64_t target = SUBMIN;
-        for (size_t e = 0; e < n;) {
-            const uint64_t want = std::min(target, SUBMAX);
-            Sub sb{e, e, 0, 64}; uint64_t pos = 0; size_t blocks = 0;
-            while (sb.e1 < n) {
-                const size_t i = sb.e1; const uint64_t l = src_len[i];
-                const size_t nb = plan_blocks(c, l);
-                if (i > sb.e0 && (pos + l > want || blocks + nb > c->max_blocks)) break;
-                off[i] = pos; len64[i] = l; pos = (pos + l + 15) & ~(uint64_t)15; blocks += nb;
-                sb.out_cap += ecap[i];
-                sb.e1++;
-            }
-            sb.in_bytes = pos; subs.push_back(sb); e = sb.e1;
-            target = std::min(SUBMAX, target * 2);
-        }
-    }
-    const auto t_cut = std::chrono::steady_clock::now();
-    const bool all_lent = entries_all_lent(c, src, src_len, n);                     // (then no page-locked staging of the library's own is needed, and no staging copy)
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    unsigned threads = std::min(8u, std::max(1u, hw / 2));
-    if (c->tun.stage_threads) threads = (unsigned)c->tun.stage_threads;
-    FrameJob fj{names, 0, cipher, ivs, meta, max_chunk, false};
-    if (c->pl_eoff.size() < n + 1) c->pl_eoff.resize(n + 1);
-    uint64_t *eoff = c->pl_eoff.data();
-    uint64_t out_len[2] = {0, 0}, out_total = head.size();
-    constexpr int NS = 4;
-    {   // slots sized once for the largest sub-batch (allocation of page-locked memory is slow: not inside the pipeline)
-        uint64_t max_in = 0, max_out = 0;
-        for (const Sub &sb : subs) { max_in = std::max(max_in, sb.in_bytes); max_out = std::max(max_out, sb.out_cap); }
-        for (int s = 0; s < NS && s < (int)subs.size(); s++)
-            if ((!all_lent && c->hp_in[s].ensure(max_in + 8192)) || c->dp_in[s].ensure(max_in + 8192)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
-        for (int s = 0; s < 2 && s < (int)subs.size(); s++)
-            if (c->dp_out[s].ensure(max_out + 64) || c->hp_out[s].ensure(max_out + 64)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
-    }
-    int rc = PNA_OK;
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto trace = [&](const char *what, size_t k) { if (c->tun.trace) fprintf(stderr, "[pna create] %8.3f ms  %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(), what, k); };
-    if (c->tun.trace) fprintf(stderr, "[pna create] planning took %.3f ms (capacity terms at %.3f, sub-batches cut at %.3f)\n", std::chrono::duration<double, std::milli>(tr0 - t_entry).count(),
-                              std::chrono::duration<double, std::milli>(t_caps - t_entry).count(), std::chrono::duration<double, std::milli>(t_cut - t_entry).count());
-    trace("planned, slots ready; sub-batches:", subs.size());
-    // the stager: sub-batch k into slot k % NS as soon as sub-batch k - NS has left the device
-    std::mutex mu; std::condition_variable cv;
-    size_t staged = 0, freed = 0; int stager_rc = PNA_OK; bool stop = false;      // sub-batches staged (copies issued) / sub-batches whose kernels are done
-    const int dev_id = c->device;
-    hipStream_t cp_in = c->cp_in;
-    std::thread stager([&]() {
-        try {
-            if (hipSetDevice(dev_id) != hipSuccess) { std::lock_guard<std::mutex> lk(mu); stager_rc = PNA_E_HIP; staged = subs.size(); cv.notify_all(); return; }
-            for (size_t k = 0; k < subs.size(); k++) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return stop || k < freed + NS; });
-                    if (stop) return;
-                }
-                const Sub &nx = subs[k]; const int sl = (int)(k % NS);
-                uint8_t *hb = (uint8_t *)c->hp_in[sl].p, *db = (uint8_t *)c->dp_in[sl].p;
-                int r = PNA_OK;
-                size_t g0 = nx.e0;
-                if (all_lent) {
-                    // every entry lies in page-locked memory the library lent out (pna_gpu_host_alloc): no staging copy, the copy engine reads the host's
-                    // buffers themselves -- runs of entries that are contiguous there and here (16-byte stride) travel as ONE copy
-                    while (g0 < nx.e1 && r == PNA_OK) {
-                        size_t g1 = g0 + 1;
-                        while (g1 < nx.e1 && (const uint8_t *)src[g1] == (const uint8_t *)src[g0] + (off[g1] - off[g0])) g1++;
-                        const uint64_t bytes = (g1 < nx.e1 ? off[g1] : off[g1 - 1] + src_len[g1 - 1]) - off[g0];
-                        const uint64_t k = std::min<uint64_t>(bytes, (const uint8_t *)src[g1 - 1] + src_len[g1 - 1] - (const uint8_t *)src[g0]);
-                        if (k && hipMemcpyAsync(db + off[g0], src[g0], k, hipMemcpyHostToDevice, cp_in) != hipSuccess) r = PNA_E_HIP;
-                        g0 = g1;
-                    }
-                }
-                while (g0 < nx.e1 && r == PNA_OK) {
-                    size_t g1 = g0; uint64_t acc = 0;
-                    while (g1 < nx.e1 && acc < (128ull << 20)) acc += src_len[g1++];
-                    parallel_stage(hb, src, src_len, off, g0, g1, threads);
-                    const uint64_t b0 = off[g0], b1 = g1 < nx.e1 ? off[g1] : nx.in_bytes;
-                    if (b1 > b0 && hipMemcpyAsync(db + b0, hb + b0, b1 - b0, hipMemcpyHostToDevice, cp_in) != hipSuccess) r = PNA_E_HIP;
-                    g0 = g1;
-                }
-                if (r == PNA_OK && hipEventRecord(c->ev_in[sl], cp_in) != hipSuccess) r = PNA_E_HIP;
-                trace("staged + H2D issued", k);
-                std::lock_guard<std::mutex> lk(mu);
-                if (r != PNA_OK) { stager_rc = r; staged = subs.size(); cv.notify_all(); return; }
-                staged = k + 1; cv.notify_all();
-            }
-        } catch (...) { std::lock_guard<std::mutex> lk(mu); stager_rc = PNA_E_NOMEM; staged = subs.size(); cv.notify_all(); }
-    });
-    const CallTotalScope call_total(c, len64, n);                                                   // (the block size follows the archive, not its sub-batches)
-    uint8_t *hp_out_dev[2] = {nullptr, nullptr};                 // device views of the page-locked output slots (the copy kernel's destination)
-    const uint32_t d2h_wgs = (uint32_t)c->tun.d2h_wgs;
-    for (size_t k = 0; k < subs.size() && rc == PNA_OK; k++) {
-        const Sub &sb = subs[k]; const int sl = (int)(k % NS), so = (int)(k & 1);
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return staged > k; });
-            if (stager_rc != PNA_OK) { rc = fail(c, stager_rc, "staging / H2D copy failed"); break; }
-        }
-        if (hipEventSynchronize(c->ev_in[sl]) != hipSuccess) { rc = fail(c, PNA_E_HIP, "H2D copy failed"); break; }
-        trace("H2D done, kernels start", k);
-        rc = run_subbatch(c, algo, (const uint8_t *)c->dp_in[sl].p, off, len64, sb.e0, sb.e1, (uint8_t *)c->dp_out[so].p,
-                          sb.out_cap + 64, 0, eoff, c->stream, true, &fj);
-        { std::lock_guard<std::mutex> lk(mu); freed = k + 1; cv.notify_all(); }       // (run_subbatch has waited for its kernels: the input slot is free)
-        trace("kernels done", k);
-        if (rc == PNA_OK) {
-            out_len[so] = eoff[sb.e1];
-            bool ok = true;
-            if (d2h_wgs && !hp_out_dev[so]) ok = hipHostGetDevicePointer((void **)&hp_out_dev[so], c->hp_out[so].p, 0) == hipSuccess;
-            if (ok && d2h_wgs) { launch_link_copy((const uint8_t *)c->dp_out[so].p, hp_out_dev[so], out_len[so], d2h_wgs, c->cp_out); ok = hipGetLastError() == hipSuccess; }
-            else if (ok) ok = hipMemcpyAsync(c->hp_out[so].p, c->dp_out[so].p, out_len[so], hipMemcpyDeviceToHost, c->cp_out) == hipSuccess;
-            if (!ok || hipEventRecord(c->ev_out[so], c->cp_out) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
-        }
-        if (rc == PNA_OK && k > 0) {                             // archive bytes of the previous sub-batch -> sink
-            if (hipEventSynchronize(c->ev_out[so ^ 1]) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
-            else if (out_len[so ^ 1] && sink(user, c->hp_out[so ^ 1].p, out_len[so ^ 1]) != 0) rc = fail(c, PNA_E_SINK, "sink failed");
-            out_total += out_len[so ^ 1];
-        }
-    }
-    { std::lock_guard<std::mutex> lk(mu); stop = true; cv.notify_all(); }
-    stager.join();
-    trace("loop done", 0);
-    if (rc != PNA_OK) { (void)hipDeviceSynchronize(); return rc; }
-    if (!subs.empty()) {
-        const int so = (int)((subs.size() - 1) & 1);
-        HIPCHK(c, hipEventSynchronize(c->ev_out[so]));
-        if (out_len[so] && sink(user, c->hp_out[so].p, out_len[so]) != 0) return fail(c, PNA_E_SINK, "sink failed");
-        out_total += out_len[so];
-    }
-    if (!tail.empty() && sink(user, tail.data(), tail.size()) != 0) return fail(c, PNA_E_SINK, "sink failed");
-    out_total += tail.size();
-    trace("all bytes handed to the sink", 0);
-    c->timing.in_bytes = in_total; c->timing.out_bytes = out_total;
-    return PNA_OK;
-}
 
-
-extern "C" int pna_gpu_compress_batch(pna_gpu_ctx *c, int algo, int level, size_t n, const void *const *src,
-                                      const size_t *src_len, void *const *dst, const size_t *dst_cap, size_t *dst_len) {
-    if (!c || (n && (!src || !src_len || !dst || !dst_cap || !dst_len))) return fail(c, PNA_E_INVAL, "null argument");
-    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented");
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> off(n + 1), len(n), doff(n + 1), obase(n + 1);       // obase: running sum of the entries' bounds
-    uint64_t pos = 0, bound = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (dst_cap[i] < pna_gpu_bound(algo, src_len[i])) return fail(c, PNA_E_DSTSIZE, "dst_cap below pna_gpu_bound");
-        off[i] = pos; len[i] = src_len[i]; pos = (pos + src_len[i] + 15) & ~(uint64_t)15;
-        obase[i] = bound; bound += pna_gpu_bound(algo, src_len[i]);
-    }
-    off[n] = pos; obase[n] = bound;
-    const CallTotalScope call_total(c, src_len, n);              // (the pieces below pick the block size of the whole call: the bytes equal pna_gpu_compress_batch_device's)
-    // Inputs are staged into page-locked memory by several threads and copied H2D, outputs copied D2H and scattered by several threads
-    // (per-entry copies from pageable memory ran at ~1 GiB/s).  A large batch goes through in PIECES of >= 256 MiB (a round of the CUs:
-    // the kernels' fixed latencies stay amortised): piece k + 1 is staged and copied while piece k is on the device, piece k - 1's results
-    // travel back meanwhile -- 512 x 1 MiB: 27.5 -> see profiles/ (PNA_BATCH_PIECE_MIB; 0 = one piece).
-    const uint64_t piece_bytes = c->tun.batch_piece_mib <= 0 ? ~0ull >> 1 : (uint64_t)c->tun.batch_piece_mib << 20;
+namespace {
+// ---- pna_gpu_compress_batch in stages.  Inputs are staged into page-locked memory by several threads and copied H2D, outputs copied D2H and scattered by
+// several threads (per-entry copies from pageable memory ran at ~1 GiB/s).  A large batch goes through in PIECES of >= 256 MiB (a round of the CUs:
+// the kernels' fixed latencies stay amortised): piece k + 1 is staged and copied while piece k is on the device, piece k - 1's results
+// travel back meanwhile -- 512 x 1 MiB: 27.5 -> see profiles/ (PNA_BATCH_PIECE_MIB; 0 = one piece).
+struct BatchPlan {
+    std::vector<uint64_t> off, len, obase, pbase;                // staging offsets, lengths, running sum of the entries' bounds; where piece k's output starts in stage_out (256-byte aligned)
     std::vector<size_t> pe{0};                                   // piece k = entries [pe[k], pe[k + 1])
-    for (size_t i = 0; i < n;) {
-        size_t j = i; uint64_t acc = 0;
-        while (j < n && (j == i || acc + src_len[j] <= piece_bytes)) acc += src_len[j++];
-        pe.push_back(j); i = j;
-    }
-    if (pe.size() > 2 && off[n] - off[pe[pe.size() - 2]] < piece_bytes / 2) pe.erase(pe.end() - 2);   // a short last piece joins its neighbour
-    const size_t K = pe.size() - 1;
-    uint64_t max_in = 0, max_out = 0;
-    std::vector<uint64_t> pbase(K + 1, 0);                       // where piece k's output starts in stage_out (256-byte aligned)
-    for (size_t k = 0; k < K; k++) {
-        max_in = std::max(max_in, off[pe[k + 1]] - off[pe[k]]); max_out = std::max(max_out, obase[pe[k + 1]] - obase[pe[k]]);
-        pbase[k + 1] = (pbase[k] + (obase[pe[k + 1]] - obase[pe[k]]) + 64 + 255) & ~(uint64_t)255;
-    }
-    if (c->stage_in.ensure(pos + 8192) || c->stage_out.ensure(pbase[K] + 64)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
-    for (int sl = 0; sl < (K > 1 ? 2 : 1); sl++) if (c->hp_in[sl].ensure(max_in + 64) || c->hp_out[sl].ensure(max_out + 64)) return fail(c, PNA_E_NOMEM, "staging allocation failed");
-    if (K > 1 && !c->cp_in) {
-        HIPCHK(c, hipStreamCreate(&c->cp_in)); HIPCHK(c, hipStreamCreate(&c->cp_out));
-        for (auto &e : c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : c->ev_out) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned threads = std::min(8u, std::max(1u, hw / 2));
-    hipStream_t s_in = K > 1 ? c->cp_in : c->stream, s_out = K > 1 ? c->cp_out : c->stream;
-    auto stage = [&](size_t k) -> int {                          // entries of piece k -> pinned slot -> their place in stage_in
+    uint64_t max_in = 0, max_out = 0; size_t K = 0;
+};
+struct BatchRun {
+    pna_gpu_ctx *c; int algo, level; const void *const *src; const size_t *src_len; void *const *dst; size_t *dst_len;
+    const BatchPlan &p; const unsigned threads; const bool lanes;                     // lanes: several pieces -- copies on cp_in / cp_out, slots guarded by events
+    std::vector<uint64_t> doff, ptotal; pna_gpu_timing tsum{};   // output offsets of the entries (running, all pieces), compressed bytes per piece
+    hipStream_t s_in() const { return lanes ? c->cp_in : c->stream; }
+    hipStream_t s_out() const { return lanes ? c->cp_out : c->stream; }
+    int stage(size_t k) {                                        // entries of piece k -> pinned slot -> their place in stage_in
         const int sl = (int)(k & 1);
-        const uint64_t b0 = off[pe[k]], nb = off[pe[k + 1]] - b0;
-        std::vector<uint64_t> rel(pe[k + 1] - pe[k] + 1);
-        for (size_t i = pe[k]; i <= pe[k + 1]; i++) rel[i - pe[k]] = off[i] - b0;
-        parallel_stage((uint8_t *)c->hp_in[sl].p, src + pe[k], src_len + pe[k], rel.data(), 0, pe[k + 1] - pe[k], threads);
-        if (nb) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->stage_in.p + b0, c->hp_in[sl].p, nb, hipMemcpyHostToDevice, s_in));
-        if (K > 1) HIPCHK(c, hipEventRecord(c->ev_in[sl], s_in));
+        const size_t e0 = p.pe[k], e1 = p.pe[k + 1];
+        const uint64_t b0 = p.off[e0], nb = p.off[e1] - b0;
+        uint8_t *hb = (uint8_t *)c->hp_in[sl].p;
+        parallel_copy(e1 - e0, threads, 8u << 20, [&](size_t i) { return CopyJob{hb + (p.off[e0 + i] - b0), (const uint8_t *)src[e0 + i], src_len[e0 + i]}; });
+        if (nb) HIPCHK(c, hipMemcpyAsync((uint8_t *)c->stage_in.p + b0, hb, nb, hipMemcpyHostToDevice, s_in()));
+        if (lanes) HIPCHK(c, hipEventRecord(c->ev_in[sl], s_in()));
         return PNA_OK;
-    };
-    std::vector<uint64_t> ptotal(K);
-    auto scatter = [&](size_t k) -> int {                        // piece k's compressed entries: pinned slot -> the caller's buffers
+    }
+    int compress(size_t k) {                                     // the device call on piece k, its compressed entries on their way to the pinned slot
         const int sl = (int)(k & 1);
-        if (K > 1) HIPCHK(c, hipEventSynchronize(c->ev_out[sl])); else HIPCHK(c, hipStreamSynchronize(c->stream));
-        const uint8_t *hb = (const uint8_t *)c->hp_out[sl].p;
-        const size_t e0 = pe[k], e1 = pe[k + 1];
-        const unsigned T = ptotal[k] < (8u << 20) ? 1u : threads;
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < T; t++)
-            th.emplace_back([=, &doff]() { for (size_t i = e0 + t; i < e1; i += T) if (dst_len[i]) memcpy(dst[i], hb + (doff[i] - doff[e0]), dst_len[i]); });
-        for (auto &x : th) x.join();
-        return PNA_OK;
-    };
-    pna_gpu_timing tsum{};
-    int rc = K ? stage(0) : PNA_OK;
-    if (rc) return rc;
-    doff[0] = 0;
-    for (size_t k = 0; k < K; k++) {
-        const int sl = (int)(k & 1);
-        if (k + 1 < K && (rc = stage(k + 1))) return rc;         // (its slot's previous copy, piece k - 1, was waited for by that piece's kernels)
-        if (K > 1) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[sl], 0));
-        const size_t e0 = pe[k], nk = pe[k + 1] - e0;
+        if (lanes) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[sl], 0));
+        const size_t e0 = p.pe[k], nk = p.pe[k + 1] - e0;
         std::vector<uint64_t> d(nk + 1);
-        uint8_t *ob = (uint8_t *)c->stage_out.p + pbase[k];
-        rc = pna_gpu_compress_batch_device(c, algo, level, nk, c->stage_in.p, off.data() + e0, len.data() + e0, ob, obase[pe[k + 1]] - obase[e0] + 64, d.data(), nullptr);
+        uint8_t *ob = (uint8_t *)c->stage_out.p + p.pbase[k];
+        const int rc = pna_gpu_compress_batch_device(c, algo, level, nk, c->stage_in.p, p.off.data() + e0, p.len.data() + e0, ob, p.obase[p.pe[k + 1]] - p.obase[e0] + 64, d.data(), nullptr);
         if (rc) return rc;
         { const pna_gpu_timing &t = c->timing; tsum.ms_lz += t.ms_lz; tsum.ms_stats += t.ms_stats; tsum.ms_lit += t.ms_lit; tsum.ms_seq += t.ms_seq; tsum.ms_pack += t.ms_pack;
           tsum.in_bytes += t.in_bytes; tsum.out_bytes += t.out_bytes; tsum.n_segments += t.n_segments; tsum.n_blocks += t.n_blocks; tsum.ms_lz_match += t.ms_lz_match; tsum.lz_match_launches += t.lz_match_launches; }
         for (size_t i = 0; i < nk; i++) { doff[e0 + i + 1] = doff[e0] + d[i + 1]; dst_len[e0 + i] = (size_t)(d[i + 1] - d[i]); }
         ptotal[k] = d[nk];
-        if (ptotal[k]) HIPCHK(c, hipMemcpyAsync(c->hp_out[sl].p, ob, ptotal[k], hipMemcpyDeviceToHost, s_out));   // (the kernels are done: compress_batch_device returns synchronised)
-        if (K > 1) HIPCHK(c, hipEventRecord(c->ev_out[sl], s_out));
-        if (k >= 1 && (rc = scatter(k - 1))) return rc;
+        if (ptotal[k]) HIPCHK(c, hipMemcpyAsync(c->hp_out[sl].p, ob, ptotal[k], hipMemcpyDeviceToHost, s_out()));   // (the kernels are done: compress_batch_device returns synchronised)
+        if (lanes) HIPCHK(c, hipEventRecord(c->ev_out[sl], s_out()));
+        return PNA_OK;
     }
-    if (K && (rc = scatter(K - 1))) return rc;
-    c->timing = tsum;
+    int scatter(size_t k) {                                      // piece k's compressed entries: pinned slot -> the caller's buffers (below 8 MiB: on the calling thread)
+        const int sl = (int)(k & 1);
+        if (lanes) HIPCHK(c, hipEventSynchronize(c->ev_out[sl])); else HIPCHK(c, hipStreamSynchronize(c->stream));
+        const uint8_t *hb = (const uint8_t *)c->hp_out[sl].p;
+        const size_t e0 = p.pe[k], e1 = p.pe[k + 1];
+        parallel_copy(e1 - e0, threads, 8u << 20, [&](size_t i) { return CopyJob{(uint8_t *)dst[e0 + i], hb + (doff[e0 + i] - doff[e0]), dst_len[e0 + i]}; });
+        return PNA_OK;
+    }
+    // an error exit: the copies issued so far read or write the pinned slots, which the next call on the context reuses -- wait for the streams they are on
+    int drain(int rc) { (void)hipStreamSynchronize(s_in()); (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(s_out()); return rc; }
+};
+}
+// ---- the piece cut
+static BatchPlan cut_pieces(const pna_gpu_ctx *c, int algo, size_t n, const size_t *src_len) {
+    BatchPlan p;
+    p.off.resize(n + 1); p.len.resize(n); p.obase.resize(n + 1);
+    uint64_t pos = 0, bound = 0;
+    for (size_t i = 0; i < n; i++) {
+        p.off[i] = pos; p.len[i] = src_len[i]; pos = (pos + src_len[i] + 15) & ~(uint64_t)15;
+        p.obase[i] = bound; bound += pna_gpu_bound(algo, src_len[i]);
+    }
+    p.off[n] = pos; p.obase[n] = bound;
+    const uint64_t piece_bytes = c->tun.batch_piece_mib <= 0 ? ~0ull >> 1 : (uint64_t)c->tun.batch_piece_mib << 20;
+    for (size_t i = 0; i < n;) {
+        size_t j = i; uint64_t acc = 0;
+        while (j < n && (j == i || acc + src_len[j] <= piece_bytes)) acc += src_len[j++];
+        p.pe.push_back(j); i = j;
+    }
+    if (p.pe.size() > 2 && p.off[n] - p.off[p.pe[p.pe.size() - 2]] < piece_bytes / 2) p.pe.erase(p.pe.end() - 2);   // a short last piece joins its neighbour
+    p.K = p.pe.size() - 1;
+    p.pbase.assign(p.K + 1, 0);
+    for (size_t k = 0; k < p.K; k++) {
+        p.max_in = std::max(p.max_in, p.off[p.pe[k + 1]] - p.off[p.pe[k]]); p.max_out = std::max(p.max_out, p.obase[p.pe[k + 1]] - p.obase[p.pe[k]]);
+        p.pbase[k + 1] = (p.pbase[k] + (p.obase[p.pe[k + 1]] - p.obase[p.pe[k]]) + 64 + 255) & ~(uint64_t)255;
+    }
+    return p;
+}
+extern "C" int pna_gpu_compress_batch(pna_gpu_ctx *c, int algo, int level, size_t n, const void *const *src,
+                                      const size_t *src_len, void *const *dst, const size_t *dst_cap, size_t *dst_len) {
+    if (!c || (n && (!src || !src_len || !dst || !dst_cap || !dst_len))) return fail(c, PNA_E_INVAL, "null argument");
+    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (size_t i = 0; i < n; i++) if (dst_cap[i] < pna_gpu_bound(algo, src_len[i])) return fail(c, PNA_E_DSTSIZE, "dst_cap below pna_gpu_bound");
+    const CallTotalScope call_total(c, src_len, n);              // (the pieces below pick the block size of the whole call: the bytes equal pna_gpu_compress_batch_device's)
+    const BatchPlan p = cut_pieces(c, algo, n, src_len);
+    const size_t K = p.K, slots = K > 1 ? 2 : 1;
+    int rc = Reserve{c}.add(c->stage_in, p.off[n] + 8192).add(c->stage_out, p.pbase[K] + 64).add(c->hp_in, slots, p.max_in + 64).add(c->hp_out, slots, p.max_out + 64).done();
+    if (rc) return rc;
+    if (K > 1 && (rc = ensure_copy_lanes(c))) return rc;
+    BatchRun r{c, algo, level, src, src_len, dst, dst_len, p, staging_threads(c), K > 1, std::vector<uint64_t>(n + 1), std::vector<uint64_t>(K)};
+    if (K && (rc = r.stage(0))) return r.drain(rc);
+    for (size_t k = 0; k < K; k++) {
+        if (k + 1 < K && (rc = r.stage(k + 1))) return r.drain(rc);          // (its slot's previous copy, piece k - 1, was waited for by that piece's kernels)
+        if ((rc = r.compress(k))) return r.drain(rc);
+        if (k >= 1 && (rc = r.scatter(k - 1))) return r.drain(rc);
+    }
+    if (K && (rc = r.scatter(K - 1))) return r.drain(rc);
+    c->timing = r.tsum;
     return PNA_OK;
 }
-

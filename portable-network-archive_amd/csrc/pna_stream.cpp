@@ -8,17 +8,11 @@
 // (W::write is never called from a foreign thread).  While a batch runs, the finishes that arrive pile up and form the next,
 // larger batch -- no timer needed under load (PNA_STREAM_LINGER_US adds an optional wait for stragglers).
 // one large copy on several threads (a pageable stream of GiBs, e.g. pna_gpu_compress_solid over a whole solid archive)
-static void big_memcpy(uint8_t *dst, const uint8_t *src, size_t n) {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned T = n < (64u << 20) ? 1u : std::min(8u, std::max(1u, hw / 2));
-    if (T == 1) { memcpy(dst, src, n); return; }
-    std::vector<std::thread> th;
+// -- from 64 MiB, in one page-aligned share per staging thread
+static void big_memcpy(const pna_gpu_ctx *c, uint8_t *dst, const uint8_t *src, size_t n) {
+    const unsigned T = staging_threads(c);
     const size_t per = ((n + T - 1) / T + 4095) & ~(size_t)4095;
-    for (unsigned t = 0; t < T; t++) {
-        const size_t a = std::min(n, (size_t)t * per), b = std::min(n, a + per);
-        if (b > a) th.emplace_back([=]() { memcpy(dst + a, src + a, b - a); });
-    }
-    for (auto &x : th) x.join();
+    parallel_copy(T, T, 64u << 20, [=](size_t t) { const size_t a = std::min(n, t * per), b = std::min(n, a + per); return CopyJob{dst + a, src + a, b - a}; });
 }
 constexpr size_t S_SLAB = 1u << 20, S_ARENA = 64u << 20, S_MAX_SLABS = 256;   // a stream beyond 256 MiB continues in pageable memory
 struct pna_gpu_stream {
@@ -135,7 +129,7 @@ static void stream_run_batch(pna_gpu_ctx *c, const std::vector<pna_gpu_stream *>
                 uint8_t *d = (uint8_t *)c->st_in[slot].p + g.in_base + g.off[k];
                 if (x->pageable) {
                     if (!x->buf.empty()) {
-                        big_memcpy((uint8_t *)c->hp_in[0].p + ppos, x->buf.data(), x->buf.size());
+                        big_memcpy(c, (uint8_t *)c->hp_in[0].p + ppos, x->buf.data(), x->buf.size());
                         if (hipMemcpyAsync(d, (uint8_t *)c->hp_in[0].p + ppos, x->buf.size(), hipMemcpyHostToDevice, c->s_h2d) != hipSuccess) rc0 = set_err(PNA_E_HIP, "H2D copy failed");
                         ppos += (x->buf.size() + 15) & ~(size_t)15;
                     }

@@ -442,6 +442,140 @@ static void test_extract_matrix() {
     pna_gpu_shutdown(c);
 }
 
+// ---- the host create pipelines' other branches: compress_batch in pieces, zero-staging slots, the multi-context form, and a sink that fails
+struct Entries {                                                 // n entries cut from one generated buffer (16-byte stride), with names
+    Bytes buf; std::vector<std::string> nm; std::vector<const char *> names; std::vector<const void *> src; std::vector<size_t> len;
+    Entries(const std::vector<size_t> &lens, uint32_t seed) {
+        size_t at = 0; std::vector<size_t> off;
+        for (size_t l : lens) { off.push_back(at); at = (at + l + 15) & ~(size_t)15; }
+        buf = text(at + 16, seed);
+        for (size_t i = 0; i < lens.size(); i++) { nm.push_back("e/" + std::to_string(i)); src.push_back(buf.data() + off[i]); len.push_back(lens[i]); }
+        for (auto &s : nm) names.push_back(s.c_str());
+    }
+    size_t n() const { return len.size(); }
+    bool same(const std::vector<std::pair<std::string, Bytes>> &ents) const {
+        if (ents.size() != n()) return false;
+        for (size_t i = 0; i < n(); i++) if (ents[i].first != nm[i] || ents[i].second != Bytes((const uint8_t *)src[i], (const uint8_t *)src[i] + len[i])) return false;
+        return true;
+    }
+};
+static pna_gpu_ctx *fresh_ctx(long sub_mib, long solid_win_mib) {
+    pna_gpu_ctx *c = nullptr;
+    CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK && c);
+    if (c) CHECK(pna_gpu_set_option(c, "sub_mib", sub_mib) == PNA_OK && pna_gpu_set_option(c, "solid_win_mib", solid_win_mib) == PNA_OK && pna_gpu_set_option(c, "latency_max_mib", 0) == PNA_OK);
+    return c;
+}
+// entries of a solid archive written by the (stubbed) zstd path: the SDAT bodies are frames of raw blocks around the stored inner records
+static bool read_back_solid(const Bytes &arc, std::vector<std::pair<std::string, Bytes>> &ents) {
+    std::vector<Chunk> ch; if (!walk(arc, ch)) return false;
+    Bytes pay, inner(8, 0);                                      // (walk skips a signature)
+    for (const Chunk &c : ch) if (!strcmp(c.ty, "SDAT")) pay.insert(pay.end(), arc.begin() + c.off, arc.begin() + c.off + c.len);
+    if (!unraw(pay.data(), pay.size(), inner)) return false;
+    std::vector<Chunk> ic; if (!walk(inner, ic)) return false;
+    for (const Chunk &c : ic) {
+        if (!strcmp(c.ty, "FHED")) ents.emplace_back(std::string((const char *)&inner[c.off + 6], c.len - 6), Bytes());
+        else if (!strcmp(c.ty, "FDAT") && !ents.empty()) ents.back().second.insert(ents.back().second.end(), inner.begin() + c.off, inner.begin() + c.off + c.len);
+    }
+    return true;
+}
+static void test_batch_in_pieces() {
+    pna_gpu_ctx *c = fresh_ctx(16, 1);
+    if (!c) return;
+    const Entries e({700000, 420000, 0, 900000, 650000, 800000, 512345}, 4100);   // 1 MiB pieces: {0}, {1, 2}, {3}, {4}, {5, 6} -- the short last piece joined its neighbour
+    const size_t n = e.n();
+    std::vector<Bytes> out[2]; std::vector<size_t> dl[2];
+    for (int k = 0; k < 2; k++) {
+        CHECK(pna_gpu_set_option(c, "batch_piece_mib", k == 0 ? 0 : 1) == PNA_OK);
+        out[k].resize(n); dl[k].resize(n);
+        std::vector<void *> dst(n); std::vector<size_t> cap(n);
+        for (size_t i = 0; i < n; i++) { out[k][i].resize(pna_gpu_bound(PNA_ALGO_ZSTD, e.len[i])); dst[i] = out[k][i].data(); cap[i] = out[k][i].size(); }
+        CHECK(pna_gpu_compress_batch(c, PNA_ALGO_ZSTD, 3, n, e.src.data(), e.len.data(), dst.data(), cap.data(), dl[k].data()) == PNA_OK);
+        for (size_t i = 0; i < n; i++) { out[k][i].resize(dl[k][i]); Bytes d; CHECK(unraw(out[k][i].data(), dl[k][i], d) && d == Bytes((const uint8_t *)e.src[i], (const uint8_t *)e.src[i] + e.len[i])); }
+    }
+    CHECK(out[0] == out[1]);
+    pna_gpu_shutdown(c);
+}
+static void test_zero_staging_slots() {
+    pna_gpu_ctx *c = fresh_ctx(16, 1);
+    if (!c) return;
+    std::vector<size_t> lens;
+    for (size_t i = 0; i < 30; i++) lens.push_back(i == 7 ? 0 : 1200000 + 33333 * i);           // ~50 MiB: four sub-batches of 16 MiB
+    const Entries e(lens, 4200);
+    void *slot = nullptr;
+    CHECK(pna_gpu_host_alloc(c, e.buf.size() + 4096 * e.n(), &slot) == PNA_OK && slot);
+    if (!slot) { pna_gpu_shutdown(c); return; }
+    // inside the lent buffer: the first ten entries adjacent at 16-byte stride as in `e`, the others with a gap of 4 KiB in front of each
+    std::vector<const void *> lent(e.n());
+    for (size_t i = 0; i < e.n(); i++) {
+        uint8_t *p = (uint8_t *)slot + ((const uint8_t *)e.src[i] - e.buf.data()) + (i < 10 ? 0 : 4096 * (i - 9));
+        if (e.len[i]) memcpy(p, e.src[i], e.len[i]);
+        lent[i] = p;
+    }
+    std::vector<const void *> mixed = lent; mixed[12] = e.src[12];                              // one entry elsewhere: the call is staged
+    Bytes arc[3];
+    const std::vector<const void *> *srcs[3] = {&lent, &mixed, &e.src};
+    for (int k = 0; k < 3; k++) {
+        CHECK(pna_gpu_create_archive_host(c, PNA_ALGO_ZSTD, 3, e.n(), e.names.data(), srcs[k]->data(), e.len.data(), vec_sink, &arc[k]) == PNA_OK);
+        std::vector<std::pair<std::string, Bytes>> ents;
+        CHECK(read_back(arc[k], ents) && e.same(ents));
+    }
+    CHECK(arc[0] == arc[2] && arc[1] == arc[2]);
+    int foreign = 0;
+    CHECK(pna_gpu_host_free(c, &foreign) == PNA_E_INVAL);
+    CHECK(pna_gpu_host_free(c, slot) == PNA_OK);
+    pna_gpu_shutdown(c);
+}
+static void test_multi_context() {
+    pna_gpu_ctx *cs[3] = {fresh_ctx(16, 1), fresh_ctx(16, 1), fresh_ctx(16, 1)};
+    if (!cs[0] || !cs[1] || !cs[2]) return;
+    const Entries many({300000, 0, 1500000, 70000, 900000, 1 << 20, 5000}, 4300), two({800000, 600000}, 4301), one({700000}, 4302);
+    struct { const Entries *e; size_t n_ctx; } cases[] = {{&many, 2}, {&many, 3}, {&two, 3}, {&one, 2}};   // (the last two: a range without entries)
+    for (auto &k : cases) {
+        const Entries &e = *k.e;
+        Bytes single, multi;
+        CHECK(pna_gpu_create_archive_host(cs[0], PNA_ALGO_ZSTD, 3, e.n(), e.names.data(), e.src.data(), e.len.data(), vec_sink, &single) == PNA_OK);
+        CHECK(pna_gpu_create_archive_multi_host(cs, k.n_ctx, PNA_ALGO_ZSTD, 3, e.n(), e.names.data(), e.src.data(), e.len.data(), vec_sink, &multi) == PNA_OK);
+        std::vector<std::pair<std::string, Bytes>> ents;
+        CHECK(read_back(multi, ents) && e.same(ents));
+        CHECK(multi == single);
+    }
+    for (pna_gpu_ctx *c : cs) pna_gpu_shutdown(c);
+}
+// A sink that fails on its k-th call: the entry point returns PNA_E_SINK (with every thread of the pipeline stopped and joined: the sanitizers watch), and
+// the same context then writes the archive a fresh context writes.
+struct FailSink { Bytes out; size_t calls = 0, fail_at = 0; };
+static int fail_sink(void *u, const void *b, size_t n) { FailSink *f = (FailSink *)u; if (++f->calls == f->fail_at) return 1; return vec_sink(&f->out, b, n); }
+static void failing_sink_case(const char *what, const std::function<int(pna_gpu_ctx *const *, FailSink &)> &create, const Entries &e, bool solid, size_t min_calls) {
+    pna_gpu_ctx *fresh[2] = {fresh_ctx(16, 1), fresh_ctx(16, 1)}, *used[2] = {fresh_ctx(16, 1), fresh_ctx(16, 1)};
+    if (!fresh[0] || !fresh[1] || !used[0] || !used[1]) return;
+    FailSink good;
+    CHECK(create(fresh, good) == PNA_OK);
+    std::vector<std::pair<std::string, Bytes>> ents;
+    CHECK((solid ? read_back_solid(good.out, ents) : read_back(good.out, ents)) && e.same(ents));
+    printf("failing sink %-18s %zu sink calls\n", what, good.calls);
+    CHECK(good.calls >= min_calls);
+    for (size_t at : {(size_t)1, good.calls / 2 + 1, good.calls}) {                            // the head, a piece in the middle, the tail
+        FailSink bad; bad.fail_at = at;
+        CHECK(create(used, bad) == PNA_E_SINK);
+        CHECK(std::string(pna_gpu_last_error(used[0])) == "sink failed");
+        FailSink again;
+        CHECK(create(used, again) == PNA_OK);
+        CHECK(again.out == good.out);
+    }
+    for (pna_gpu_ctx *c : fresh) pna_gpu_shutdown(c);
+    for (pna_gpu_ctx *c : used) pna_gpu_shutdown(c);
+}
+static void test_failing_sink() {
+    const Entries big(std::vector<size_t>(56, 1310720), 4400);                                  // 70 MiB: five sub-batches of 16 MiB
+    failing_sink_case("create", [&](pna_gpu_ctx *const *cs, FailSink &s) {
+        return pna_gpu_create_archive_host(cs[0], PNA_ALGO_ZSTD, 3, big.n(), big.names.data(), big.src.data(), big.len.data(), fail_sink, &s); }, big, false, 6);
+    const Entries small({900000, 0, 1 << 20, 1400000, 12345, 850000}, 4401);                    // ~4 MiB: windows of 1 MiB
+    failing_sink_case("solid", [&](pna_gpu_ctx *const *cs, FailSink &s) {
+        return pna_gpu_create_solid_archive_host(cs[0], PNA_ALGO_ZSTD, 3, small.n(), small.names.data(), small.src.data(), small.len.data(), fail_sink, &s); }, small, true, 6);
+    failing_sink_case("multi-context", [&](pna_gpu_ctx *const *cs, FailSink &s) {              // (range 0 owns the head and the middle call, the last range the tail)
+        return pna_gpu_create_archive_multi_host(cs, 2, PNA_ALGO_ZSTD, 3, small.n(), small.names.data(), small.src.data(), small.len.data(), fail_sink, &s); }, small, false, 3);
+}
+
 int main() {
     pna_gpu_ctx *c = nullptr;
     CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK);
@@ -451,6 +585,10 @@ int main() {
     test_batch(c);
     test_streams(c);
     test_pipeline_and_append(c);
+    test_batch_in_pieces();
+    test_zero_staging_slots();
+    test_multi_context();
+    test_failing_sink();
     test_framing_matrix();
     test_extract_matrix();
     pna_gpu_shutdown(c);

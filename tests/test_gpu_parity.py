@@ -796,6 +796,58 @@ def test_host_pipeline_many_sub_batches(gpu_ctx, pna, pf, codec):
     assert dst[:total].cpu().numpy().tobytes() == arc
 
 
+def test_host_pipelines_after_a_failing_sink(gpu_ctx, pna):
+    """A sink that fails on its third call -- behind the head and one piece, with the stager thread (or the next window's assembly) ahead and copies
+    in flight: pna_gpu_create_archive_host over five sub-batches and pna_gpu_create_solid_archive_host over six windows return PNA_E_SINK with
+    everything of the call stopped and drained, and the same context then writes the archive of the device entry point, byte for byte."""
+    import ctypes
+    import torch
+    n, L = 48, 3 << 19
+    src = torch.empty(n * L + 8192, dtype=torch.uint8, device="cuda")
+    gpu_ctx.corpus_fill_device(0, 310, n, L, L, src.data_ptr())
+    host = src[:n * L].cpu().numpy()
+    ents = [host[i * L:(i + 1) * L].tobytes() for i in range(n)]
+    names = [f"q/{i:03d}" for i in range(n)]
+    lib = pna.load_library()
+
+    def host_create(entry_point, k, fail_at):
+        out, calls = bytearray(), [0]
+
+        def _sink(_u, buf, size):
+            calls[0] += 1
+            if calls[0] == fail_at:
+                return 1
+            out.extend((ctypes.c_char * size).from_address(buf))
+            return 0
+        a_names = (ctypes.c_char_p * k)(*[s.encode() for s in names[:k]])
+        a_src = (ctypes.c_void_p * k)(*[ctypes.cast(ctypes.c_char_p(e), ctypes.c_void_p) for e in ents[:k]])
+        a_len = (ctypes.c_size_t * k)(*[L] * k)
+        gpu_ctx._check(entry_point(gpu_ctx._h, pna.ALGO_ZSTD, pna.LEVEL_DEFAULT, k, a_names, a_src, a_len, pna.SINK_FN(_sink), None))
+        return bytes(out)
+
+    def device_create(k, solid):
+        offs = [i * L for i in range(k)]                        # (L is a multiple of 16)
+        cap = (pna.solid_archive_bound if solid else pna.archive_bound)(pna.ALGO_ZSTD, names[:k], [L] * k)
+        dst = torch.empty(cap, dtype=torch.uint8, device="cuda")
+        if solid:
+            total = gpu_ctx.create_solid_archive_device(names[:k], src.data_ptr(), offs, [L] * k, dst.data_ptr(), cap, algo=pna.ALGO_ZSTD)
+        else:
+            total, _ = gpu_ctx.create_archive_device(names[:k], src.data_ptr(), offs, [L] * k, dst.data_ptr(), cap)
+        return dst[:total].cpu().numpy().tobytes()
+
+    try:
+        gpu_ctx.set_option("sub_mib", 16)
+        gpu_ctx.set_option("solid_win_mib", 1)
+        for entry_point, k, solid in ((lib.pna_gpu_create_archive_host, n, False), (lib.pna_gpu_create_solid_archive_host, 4, True)):
+            with pytest.raises(pna.PnaGpuError) as err:
+                host_create(entry_point, k, 3)
+            assert err.value.code == pna.E_SINK
+            assert host_create(entry_point, k, 0) == device_create(k, solid)
+    finally:
+        gpu_ctx.set_option("sub_mib", 1024)
+        gpu_ctx.set_option("solid_win_mib", 256)
+
+
 def test_many_short_matches_bit_exact(gpu_ctx, pna, codec):
     """Adversarial for the per-block sequence capacity and for the merge of the waves' parses: 7-byte words from a small
     vocabulary (back-to-back minimum-length matches, ends that fall 1-2 bytes behind the running end)."""
