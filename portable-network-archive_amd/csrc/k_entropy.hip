@@ -605,13 +605,73 @@ void k_stats(const SegDesc *__restrict__ segs, const uint64_t *__restrict__ seqs
 }
 
 // ------------------------------------------------------------------ k_lit
-// One workgroup per block, one wave per Huffman stream.  Both passes read the literals with coalesced 16-byte loads
-// (lane i <- granule base+i): pass 1 sums the code lengths of each stream, pass 2 walks each stream from its END in
-// rounds of 64 granules (later symbols sit at lower bit positions), places the lanes' 16-symbol pieces with a wave
-// suffix scan, ORs them into a per-wave LDS staging buffer (64-bit LDS atomics) and flushes completed qwords to the
-// zeroed body with coalesced 64-bit atomic ORs (neighbouring streams share their boundary qwords).
+// One workgroup per block, one wave per Huffman stream.  The literals are read with coalesced 16-byte loads (lane i <- granule base+i).  A stream is
+// walked from its END in rounds of 64 granules (later symbols sit at lower bit positions): the lanes' 16-symbol pieces are placed with a wave suffix
+// scan and ORed into a per-wave LDS staging buffer (64-bit LDS atomics), whose completed qwords are flushed coalesced.
+// One pass (the form of every block whose regions fit its litc slot, lit_regions): wave k codes stream k into region k of the slot -- a region has one
+// writer, so the flushes are plain stores into memory nobody zeroed, the sizes are known when the streams are done, and k_write puts the four pieces end to
+// end behind the jump table.  The RLE test rides in the same read.
+// Two passes (large nlit under long codes: 11 bits a symbol against the slot's 8 a byte): pass 1 sums the code lengths of each stream, pass 2 codes the
+// streams where they belong in the zeroed body with coalesced 64-bit atomic ORs (neighbouring streams share their boundary qwords).
 constexpr uint32_t LIT_THREADS = 256;
 constexpr uint32_t LIT_STAGE_Q = 184;            // qwords of staging per wave: 64 lanes x 176 bits + carry
+
+// Symbols [a, e) of the block (a < e), coded by one wave through its zeroed staging buffer `st`; out64's qword 0 holds bit 0 of the bit address `pos`.
+// SHARED: out64 is the zeroed body that the four waves OR into; otherwise the wave's own region, and `same` takes the RLE test (every symbol == b0).
+// Writes the closing 1-bit and returns the stream's bits without it.
+template <bool SHARED>
+__device__ __forceinline__ uint32_t lit_code_stream(const uint4 *__restrict__ bl16, const uint32_t *code, unsigned long long *st, unsigned long long *out64,
+                                                    uint32_t a, uint32_t e, uint32_t pos, uint32_t lane, uint32_t b0, int &same) {
+    const uint32_t gfirst = a >> 4, gend = (e + 15) >> 4, pos0 = pos;
+    uint32_t qfl = pos >> 6;                                       // st[0] holds qword qfl of out64
+    const uint32_t nround = (gend - gfirst + 63) / 64;
+    for (uint32_t r = 0; r < nround; r++) {
+        const int32_t gi = (int32_t)gend - 64 * (int32_t)(r + 1) + (int32_t)lane;
+        const bool act = gi >= (int32_t)gfirst;
+        unsigned long long gv[4] = {0, 0, 0, 0}; uint32_t gl[4] = {0, 0, 0, 0};
+        if (act) {
+            const uint4 v = bl16[gi];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w}, base = (uint32_t)gi << 4;
+#pragma unroll
+            for (int k = 15; k >= 0; k--) {                        // later symbols first (lower bit positions)
+                const uint32_t i = base + (uint32_t)k;
+                if (i >= a && i < e) {
+                    const uint32_t sym = (w[k >> 2] >> (8 * (k & 3))) & 0xFF, cv = code[sym];
+                    const int grp = 3 - (k >> 2);
+                    gv[grp] |= (unsigned long long)(cv & 0xFFFF) << gl[grp]; gl[grp] += cv >> 16;
+                    if (!SHARED) same &= (sym == b0);
+                }
+            }
+        }
+        const uint32_t ltot = gl[0] + gl[1] + gl[2] + gl[3];
+        uint32_t sc = ltot;                                        // inclusive prefix over lanes
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { uint32_t t = (uint32_t)__shfl_up((int)sc, d); if (lane >= (uint32_t)d) sc += t; }
+        const uint32_t rtot = (uint32_t)__shfl((int)sc, 63);
+        uint32_t p = pos + (rtot - sc) - (qfl << 6);               // staging bit of this lane's first group (lane 63 lowest)
+#pragma unroll
+        for (int grp = 0; grp < 4; grp++) {
+            if (gl[grp]) {
+                const uint32_t qi = p >> 6, sh = p & 63;
+                atomicOr(&st[qi], gv[grp] << sh);
+                if (sh + gl[grp] > 64) atomicOr(&st[qi + 1], gv[grp] >> (64 - sh));
+                p += gl[grp];
+            }
+        }
+        pos += rtot;
+        // flush completed qwords, keep the partial one at st[0]
+        const uint32_t nq = (pos >> 6) - qfl;
+        const unsigned long long part = st[nq];
+        for (uint32_t j = lane; j < nq; j += 64) { const unsigned long long x = st[j]; if (SHARED) { if (x) atomicOr(&out64[qfl + j], x); } else out64[qfl + j] = x; }
+        for (uint32_t j = lane; j <= nq; j += 64) st[j] = (j == 0) ? part : 0ull;
+        qfl += nq;
+    }
+    // closing 1-bit, then flush what is left (at most two qwords; the last one as it stands: nothing behind the stream's end is read)
+    if (lane == 0) atomicOr(&st[(pos - (qfl << 6)) >> 6], 1ull << ((pos - (qfl << 6)) & 63));
+    const uint32_t nq = ((pos + 1 - (qfl << 6)) + 63) >> 6;
+    for (uint32_t j = lane; j < nq; j += 64) { const unsigned long long x = st[j]; if (SHARED) { if (x) atomicOr(&out64[qfl + j], x); } else out64[qfl + j] = x; }
+    return pos - pos0;
+}
 
 __global__ __launch_bounds__(LIT_THREADS)
 void k_lit(const SegDesc *__restrict__ segs, const uint32_t *__restrict__ blk_seg, const uint8_t *__restrict__ lits,
@@ -625,7 +685,8 @@ void k_lit(const SegDesc *__restrict__ segs, const uint32_t *__restrict__ blk_se
     const uint32_t nlit = blk[g].nlit;
     const uint8_t *bl = lits + ((size_t)g << blk_log);
     const uint4 *bl16 = (const uint4 *)bl;
-    unsigned long long *out64 = (unsigned long long *)(litc + ((size_t)g << blk_log));
+    uint8_t *slot = litc + ((size_t)g << blk_log);
+    unsigned long long *out64 = (unsigned long long *)slot;
     if (!(flags & F_HUF) || nlit < 64) { if (tid == 0) { blk[g].lit_body = 0; blk[g].lit_rle = 0; } return; }
     if (!T->huf_ok) {
         // no Huffman code for this segment: only the RLE test is left (coalesced)
@@ -647,9 +708,26 @@ void k_lit(const SegDesc *__restrict__ segs, const uint32_t *__restrict__ blk_se
     if (wave < nstreams) m = (nstreams == 4 && wave == 3) ? nlit - 3 * segsz : segsz;
     const uint32_t e = a + m;
     const uint32_t gfirst = a >> 4, gend = m ? (e + 15) >> 4 : gfirst;
-    // ---- pass 1: bits of the stream, and the RLE test (all literals equal) in the same read: the waves' ranges cover every literal
+    const uint32_t b0 = bl[0];
+    unsigned long long *st = stage[wave];
+    uint32_t roff[4];
+    if (lit_regions(nlit, T->maxbits, roff) <= (1u << blk_log)) {
+        // ---- one pass: stream `wave` into its region; the waves' ranges cover every literal, so the RLE test (all literals equal) is complete
+        for (uint32_t i = lane; i < LIT_STAGE_Q; i += 64) st[i] = 0;
+        __builtin_amdgcn_wave_barrier();
+        int same = 1;
+        if (wave < nstreams) sbits[wave] = lit_code_stream<false>(bl16, code, st, (unsigned long long *)(slot + roff[wave]), a, e, 0, lane, b0, same);
+        same = __syncthreads_and(same);
+        if (tid == 0) {
+            uint32_t sz[4] = {0, 0, 0, 0}, body = nstreams == 4 ? 6u : 0u;
+            for (uint32_t k = 0; k < nstreams; k++) { sz[k] = (sbits[k] >> 3) + 1; body += sz[k]; }
+            blk[g].lit_rle = same ? 1u : 0u; blk[g].lit_body = same ? 0u : body;   // (body >= nlit: Huffman cannot win, k_plan picks raw literals)
+            blk[g].adler_a = nstreams == 4 ? sz[0] | (sz[1] << 16) : 0u; blk[g].adler_b = sz[2] | (sz[3] << 16);   // one stream: the body as it stands (region 0)
+        }
+        return;
+    }
+    // ---- pass 1: bits of the stream, and the RLE test in the same read
     {
-        const uint32_t b0 = bl[0];
         uint32_t bits = 0; int same = 1;
         for (uint32_t gi = gfirst + lane; gi < gend; gi += 64) {
             const uint4 v = bl16[gi];
@@ -669,63 +747,14 @@ void k_lit(const SegDesc *__restrict__ segs, const uint32_t *__restrict__ blk_se
     // stream byte sizes and offsets
     uint32_t sz[4], off[4], body = nstreams == 4 ? 6u : 0u;
     for (uint32_t k = 0; k < 4; k++) { sz[k] = k < nstreams ? (sbits[k] >> 3) + 1 : 0; off[k] = body; body += sz[k]; }
-    if (tid == 0) { blk[g].lit_body = body; blk[g].lit_rle = 0; }
+    if (tid == 0) { blk[g].lit_body = body; blk[g].lit_rle = 0; blk[g].adler_a = 0; blk[g].adler_b = 0; }
     if (body >= nlit || body > (1u << blk_log)) return;                   // Huffman cannot win: k_plan picks raw literals
     for (uint32_t i = tid; i < (body + 7) / 8; i += LIT_THREADS) out64[i] = 0;
-    for (uint32_t i = lane; i < LIT_STAGE_Q; i += 64) stage[wave][i] = 0;
+    for (uint32_t i = lane; i < LIT_STAGE_Q; i += 64) st[i] = 0;
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    if (wave < nstreams) {
-        unsigned long long *st = stage[wave];
-        uint32_t pos = off[wave] * 8;                              // next free bit of the body (global bit address)
-        uint32_t qfl = pos >> 6;                                   // st[0] holds body qword qfl
-        const uint32_t nround = (gend - gfirst + 63) / 64;
-        for (uint32_t r = 0; r < nround; r++) {
-            const int32_t gi = (int32_t)gend - 64 * (int32_t)(r + 1) + (int32_t)lane;
-            const bool act = gi >= (int32_t)gfirst;
-            unsigned long long gv[4] = {0, 0, 0, 0}; uint32_t gl[4] = {0, 0, 0, 0};
-            if (act) {
-                const uint4 v = bl16[gi];
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w}, base = (uint32_t)gi << 4;
-#pragma unroll
-                for (int k = 15; k >= 0; k--) {                    // later symbols first (lower bit positions)
-                    const uint32_t i = base + (uint32_t)k;
-                    if (i >= a && i < e) {
-                        const uint32_t cv = code[(w[k >> 2] >> (8 * (k & 3))) & 0xFF];
-                        const int grp = 3 - (k >> 2);
-                        gv[grp] |= (unsigned long long)(cv & 0xFFFF) << gl[grp]; gl[grp] += cv >> 16;
-                    }
-                }
-            }
-            const uint32_t ltot = gl[0] + gl[1] + gl[2] + gl[3];
-            uint32_t sc = ltot;                                    // inclusive prefix over lanes
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { uint32_t t = (uint32_t)__shfl_up((int)sc, d); if (lane >= (uint32_t)d) sc += t; }
-            const uint32_t rtot = (uint32_t)__shfl((int)sc, 63);
-            uint32_t p = pos + (rtot - sc) - (qfl << 6);           // staging bit of this lane's first group (lane 63 lowest)
-#pragma unroll
-            for (int grp = 0; grp < 4; grp++) {
-                if (gl[grp]) {
-                    const uint32_t qi = p >> 6, sh = p & 63;
-                    atomicOr(&st[qi], gv[grp] << sh);
-                    if (sh + gl[grp] > 64) atomicOr(&st[qi + 1], gv[grp] >> (64 - sh));
-                    p += gl[grp];
-                }
-            }
-            pos += rtot;
-            // flush completed qwords, keep the partial one at st[0]
-            const uint32_t nq = (pos >> 6) - qfl;
-            const unsigned long long part = st[nq];
-            for (uint32_t j = lane; j < nq; j += 64) { const unsigned long long x = st[j]; if (x) atomicOr(&out64[qfl + j], x); }
-            for (uint32_t j = lane; j <= nq; j += 64) st[j] = (j == 0) ? part : 0ull;
-            qfl += nq;
-        }
-        // closing 1-bit, then flush what is left (at most two qwords)
-        if (lane == 0) atomicOr(&st[(pos - (qfl << 6)) >> 6], 1ull << ((pos - (qfl << 6)) & 63));
-        pos += 1;
-        const uint32_t nq = ((pos - (qfl << 6)) + 63) >> 6;
-        for (uint32_t j = lane; j < nq; j += 64) { const unsigned long long x = st[j]; if (x) atomicOr(&out64[qfl + j], x); }
-    }
+    int unused = 1;
+    if (wave < nstreams) lit_code_stream<true>(bl16, code, st, out64, a, e, off[wave] * 8, lane, b0, unused);
     if (tid == 0 && nstreams == 4) atomicOr(&out64[0], (unsigned long long)sz[0] | ((unsigned long long)sz[1] << 16) | ((unsigned long long)sz[2] << 32));
 }
 
@@ -1220,7 +1249,16 @@ void k_write(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, 
             for (uint32_t i = 0; i < lh; i++) out[i] = (uint8_t)(h >> (8 * i));
         }
         copy_bytes(out + lh, T->tree, ts, tid, NT);
-        copy_bytes(out + lh + ts, litc + ((size_t)g << sd.blk_log), hs, tid, NT);
+        const uint8_t *slot = litc + ((size_t)g << sd.blk_log);
+        if (bi.adler_a) {
+            // k_lit's one-pass form: the jump table, then the four streams from their regions, end to end
+            const uint32_t sz[4] = {bi.adler_a & 0xFFFF, bi.adler_a >> 16, bi.adler_b & 0xFFFF, bi.adler_b >> 16};
+            uint32_t roff[4], o = lh + ts + 6;
+            lit_regions(nlit, T->maxbits, roff);
+            if (tid < 6) out[lh + ts + tid] = (uint8_t)(sz[tid >> 1] >> (8 * (tid & 1)));
+            for (uint32_t k = 0; k < 4; k++) { copy_bytes(out + o, slot + roff[k], sz[k], tid, NT); o += sz[k]; }
+        } else
+            copy_bytes(out + lh + ts, slot, hs, tid, NT);
         pos = lh + ts + hs;
     } else {
         uint32_t h = raw_lit_hdr(nlit);

@@ -130,7 +130,23 @@ struct BlkInfo {
     uint32_t pad;
     uint64_t out_off;      // offset of the block header in the batch output buffer
     uint32_t adler_a, adler_b;   // deflate: Adler-32 halves of this block's input started from adler = 1
+                                 // zstd: the four Huffman streams' byte sizes, sz0 | sz1 << 16 and sz2 | sz3 << 16 (a stream is at most 11 bits for each of 32 Ki symbols,
+                                 // below 64 KiB), when k_lit coded them into regions of their own (lit_regions); 0: the body stands whole at the start of the litc slot
 };
+
+// zstd, k_lit's one-pass form: stream k of a block is coded into region k of the block's litc slot, so that no stream's size is needed before it is coded;
+// k_write puts the pieces end to end.  A region holds its stream at the segment's longest code, the closing bit and a last qword stored whole --
+// ceil(m_k * maxbits / 8) + 9 bytes -- and starts at a multiple of 16.  Returns the bytes the regions take: a block whose slot is smaller takes the two-pass form.
+__host__ __device__ inline uint32_t lit_regions(uint32_t nlit, uint32_t maxbits, uint32_t off[4]) {
+    const uint32_t ns = nlit >= 256 ? 4u : 1u, segsz = ns == 4 ? (nlit + 3) / 4 : nlit;
+    uint32_t o = 0;
+    for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t m = k >= ns ? 0u : (ns == 4 && k == 3) ? nlit - 3 * segsz : segsz;
+        off[k] = o;
+        if (k < ns) o += ((m * maxbits + 7) / 8 + 9 + 15) & ~15u;
+    }
+    return o;
+}
 
 // deflate: per-segment Huffman tables (k_dstats output)
 struct DeflTables {
