@@ -1,6 +1,6 @@
 // k_lz.hip -- LZ77 match finding + greedy parse for gfx950 (CDNA4), one 1024-thread workgroup per segment: the ONE-kernel form of the LZ stage
-// (short runs, PNA_F_LZ_FUSED, fallback without workspace) and, as MODE 1 / 2, its two halves as kernels.  The default for large batches is the
-// split form in k_lz_split.hip (k_lzm + k_lzp); shared pieces live in lz_common.h.
+// and, as MODE 1 / 2, its two halves as kernels.  The default is the split form in k_lz_split.hip (k_lzm + k_lzp); shared pieces and the instance
+// ladder live in lz_common.h.  Which form a run takes is decided on the host, in one place: lz_stage (pna_lz.cpp).
 //
 // Replaces the match finder inside the third-party encoder the reference drives at
 // lib/src/compress.rs:32-41 (CompressionWriter::write -> ZstdEncoder::write).  Integer/byte work, no MFMA.
@@ -35,11 +35,9 @@
 
 namespace pna {
 
-void launch_lz_split(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                     uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg);   // k_lz_split.hip
+void launch_lz_split(const LzLaunch &L);              // k_lz_split.hip
+void launch_lz_small(const LzLaunch &L, bool w3);     // k_lz_split.hip
 void lzp_read_stamps(unsigned long long *out);
-void launch_lz_small(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                     uint32_t flags, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, const LzParseGrid *pg, bool w3);   // k_lz_split.hip
 
 // diagnostic build only (STAMP = true): lane 0 of every wave accumulates s_memtime deltas per phase (sums over the 16 waves)
 __device__ unsigned long long g_lz_stamps[8];
@@ -49,7 +47,7 @@ __device__ unsigned long long g_lz_stamps[8];
 // CT: the launch fills the deflate chunk table (a template parameter so that the zstd instance carries none of that code).
 // STRONG: the parameter set of the high levels (third adoption round over 7 back bytes, two-step lazy deferral) as an instance of its own,
 // so that the default instance carries none of its loads and branches (as run-time switches they cost it 3.3 %).
-// MODE: 0 = the whole stage in one kernel; 1 / 2 = its two halves as kernels of their own (launch_lz_split): 1 = look-up, match and
+// MODE: 0 = the whole stage in one kernel; 1 / 2 = its two halves as kernels of their own (LzForm::SplitWaveParse): 1 = look-up, match and
 // inserts only -- one word per position (length | offset << 6, after adoption) goes to `pbuf` --, 2 = parse, merge and emission from those
 // words (no window, no table: 192 bytes of LDS, two workgroups per CU).  Same code, same results: the halves only meet in `pbuf`.
 template <bool STAMP, int G, bool CT, int STRONG, int MODE, uint32_t WLOG, bool TAB3 = false>   // TAB3: the packed table (lz_common.h); STRONG: 0 / 1 / 2 as in k_lzm (2: a fourth adoption round over eight positions, 15 back bytes)
@@ -621,9 +619,9 @@ void k_lz(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, uin
     if (STAMP && lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&g_lz_stamps[k], st_acc[k]);
 }
 
-template <int G, bool CT, int STRONG, uint32_t WLOG, bool TAB3 = false>
-static void launch_lz_g(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                        uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg) {
+// One launch of the instance (G, CT, STRONG, WLOG, TAB3), in the form the host names (LzLaunch::form; pna_lz.cpp decides it)
+template <int G, bool CT, int STRONG, uint32_t WLOG, bool TAB3>
+static void launch_lz_g(const LzLaunch &L) {
     static constexpr uint32_t LT = LzGeo<WLOG, TAB3>::L_TOTAL;
     static const hipError_t attr_set = [] {                    // once per process, thread-safe (contexts may be created on several threads)
         (void)hipFuncSetAttribute((const void *)k_lz<false, G, CT, STRONG, 0, WLOG, TAB3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LT);
@@ -631,44 +629,28 @@ static void launch_lz_g(const uint8_t *src, const SegDesc *segs, uint32_t nseg, 
         return hipFuncSetAttribute((const void *)k_lz<true, G, CT, STRONG, 0, WLOG, TAB3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LT);
     }();
     (void)attr_set;
-    if (pbuf) {
-        if (flags & FLAG_SPLIT_WAVEPARSE) {
-            if ((flags >> FLAG_MT_SHIFT) & 7u) launch_lz_split(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, nullptr, nullptr, nullptr);   // (option mtile: only k_lzm has sub-tiles -- here with words of four bytes, for the parse kernel below)
-            else
-            hipLaunchKernelGGL((k_lz<false, G, CT, STRONG, 1, WLOG, TAB3>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, seqs, lits, blk, ctab, flags, max_off, max_len, pbuf, blk0);
-            if (flags & FLAG_HAS_SMALL) launch_lz_small(src, segs, nseg, seqs, lits, blk, ctab, flags, max_len, st, pbuf, blk0, nullptr, false);   // (match kernel only; this form's words take four bytes)
-            if (ev_match) (void)hipEventRecord(ev_match, st);
-            hipLaunchKernelGGL((k_lz<false, G, CT, STRONG, 2, WLOG, TAB3>), dim3(nseg), dim3(LZ_THREADS), 4 * LZ_WAVES + 8 * LZ_WAVES, st, src, segs, seqs, lits, blk, ctab, flags, max_off, max_len, pbuf, blk0);
-            return;
-        }
-        launch_lz_split(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);   // k_lzm + k_lzp (k_lz_split.hip)
+    auto go = [&](decltype(&k_lz<false, G, CT, STRONG, 0, WLOG, TAB3>) k, uint32_t lds) {
+        hipLaunchKernelGGL(k, dim3(L.nseg), dim3(LZ_THREADS), lds, L.st, L.src, L.segs, L.seqs, L.lits, L.blk, L.ctab, L.flags, L.max_off, L.max_len, L.pbuf, L.blk0);
+    };
+    switch (L.form) {
+    case LzForm::OneKernel:
+        go((L.flags & FLAG_STAMP) ? k_lz<true, G, CT, STRONG, 0, WLOG, TAB3> : k_lz<false, G, CT, STRONG, 0, WLOG, TAB3>, LT);
+        break;
+    case LzForm::SplitWaveParse: {
+        LzLaunch m = L; m.form = LzForm::MatchOnly; m.ev_match = nullptr; m.gtab = nullptr;     // the match kernels alone, words of four bytes for the parse below
+        if ((L.flags >> FLAG_MT_SHIFT) & 7u) launch_lz_split(m);                                // (option mtile: only k_lzm has sub-tiles)
+        else go(k_lz<false, G, CT, STRONG, 1, WLOG, TAB3>, LT);
+        if (L.flags & FLAG_HAS_SMALL) launch_lz_small(m, false);
+        if (L.ev_match) (void)hipEventRecord(L.ev_match, L.st);
+        go(k_lz<false, G, CT, STRONG, 2, WLOG, TAB3>, 4 * LZ_WAVES + 8 * LZ_WAVES);
+        break;
     }
-    else if (flags & FLAG_STAMP) hipLaunchKernelGGL((k_lz<true, G, CT, STRONG, 0, WLOG, TAB3>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, seqs, lits, blk, ctab, flags, max_off, max_len, pbuf, blk0);
-    else hipLaunchKernelGGL((k_lz<false, G, CT, STRONG, 0, WLOG, TAB3>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, seqs, lits, blk, ctab, flags, max_off, max_len, pbuf, blk0);
+    default: launch_lz_split(L);                               // Split, MatchOnly: k_lzm + k_lzp (k_lz_split.hip)
+    }
 }
 // zstd launches (no chunk table) run LZ_G_ZSTD positions per lane and tile, deflate launches LZ_G_DEFLATE (k_dblock walks the 2 KiB chunks of the table)
-// pbuf != nullptr: the split form (two kernels; pbuf holds one word per position of the launch's blocks, blk0 = the first of them;
-// ev_match, if given, is recorded between the two)
-void launch_lz(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-               uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg) {
-    const bool strong = (flags & F_STRONG) && (flags & F_ADOPT), strong2 = strong && (flags & FLAG_STRONG2);
-    if (ctab) { if (strong) launch_lz_g<LZ_G_DEFLATE, true, true, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-                else launch_lz_g<LZ_G_DEFLATE, true, false, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
-    else if ((flags & FLAG_TAB3) && (flags & FLAG_W16)) {
-           if (strong2) launch_lz_g<LZ_G_ZSTD, false, 2, 14, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-           else if (strong) launch_lz_g<LZ_G_ZSTD, false, true, 14, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-           else launch_lz_g<LZ_G_ZSTD, false, false, 14, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
-    else if ((flags & FLAG_TAB3) && (flags & FLAG_W32)) {
-           if (strong) launch_lz_g<LZ_G_ZSTD, false, true, 15, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-           else launch_lz_g<LZ_G_ZSTD, false, false, 15, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
-    else if (flags & FLAG_W16) {
-           if (strong) launch_lz_g<LZ_G_ZSTD, false, true, 14>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-           else launch_lz_g<LZ_G_ZSTD, false, false, 14>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
-    else if (flags & FLAG_W32) {
-           if (strong) launch_lz_g<LZ_G_ZSTD, false, true, 15>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-           else launch_lz_g<LZ_G_ZSTD, false, false, 15>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
-    else { if (strong) launch_lz_g<LZ_G_ZSTD, false, true, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-           else launch_lz_g<LZ_G_ZSTD, false, false, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
+void launch_lz(const LzLaunch &L) {
+    lz_instance(L.flags, L.ctab != nullptr, [&](auto I) { using T = decltype(I); launch_lz_g<T::CT ? LZ_G_DEFLATE : LZ_G_ZSTD, T::CT, T::STRONG, T::WLOG, T::TAB3>(L); });
 }
 
 // diagnostic: read and clear the phase stamps (cycles summed over workgroups); a -DLZP_PROF build hands out k_lzp's instead

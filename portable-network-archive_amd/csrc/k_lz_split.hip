@@ -3,7 +3,8 @@
 //   k_lzp: greedy parse, merge, emission of sequences and literals with one LANE per parse region
 // Replaces, together, the match finder + parser inside the third-party encoder the reference drives at lib/src/compress.rs:32-41
 // (CompressionWriter::write -> ZstdEncoder::write / ZlibEncoder::write).  Same results as k_lz (k_lz.hip), which stays as the one-kernel
-// form for short runs; DESIGN.md section 5 "Round 2, second half" has the measurements.  Integer / byte work, no MFMA.
+// form; which one a run takes is decided in lz_stage (pna_lz.cpp), the launchers at the end of this file do as the launch descriptor says.
+// DESIGN.md section 5 "Round 2, second half" has the measurements.  Integer / byte work, no MFMA.
 #include <type_traits>
 #include "lz_common.h"
 
@@ -1059,76 +1060,63 @@ void k_lzp(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, co
     }
 }
 
-template <bool CT, int STRONG, uint32_t GLOG, uint32_t WLOG, bool FARP = !CT, bool TAB3 = false, bool SUBTILE = false>
-static void launch_split_g(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                           uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg) {
+// the short segments of a launch, which k_lzm and k_lz skip: k_lzms, one launch per tier the launch holds
+template <int STRONG, bool W3>
+static void launch_lzms(const LzLaunch &L) {
+    if (L.flags & FLAG_TIER1) hipLaunchKernelGGL((k_lzms<STRONG, W3>), dim3(L.nseg), dim3(64), lzms_lds(SMALL_SEG), L.st, L.src, L.segs, L.flags, L.pbuf, L.blk0, 0u, SMALL_SEG);
+    if (L.flags & FLAG_TIER2) { const uint32_t mx = 8192u + 4096u * ((L.flags >> FLAG_T2_SHIFT) & 3u);
+                                hipLaunchKernelGGL((k_lzms<STRONG, W3>), dim3(L.nseg), dim3(64), lzms_lds(mx), L.st, L.src, L.segs, L.flags, L.pbuf, L.blk0, SMALL_SEG, mx); }
+}
+// the parse kernel over the grid's blocks, one wave each; its lazy depth by the flags
+template <bool CT, bool W3>
+static void launch_lzp(const LzLaunch &L, uint32_t flags) {
+    auto go = [&](decltype(&k_lzp<CT, 1, W3>) k) {
+        hipLaunchKernelGGL(k, dim3(L.pg.nb), dim3(LZP_THREADS), 0, L.st, L.src, L.pg.segs_all, L.pg.blk_seg, L.seqs, L.lits, L.blk, L.ctab, flags, L.max_len, L.pbuf, L.blk0, L.pg.hist);
+    };
+    go((flags & FLAG_LAZY3) ? k_lzp<CT, 3, W3> : (flags & FLAG_LAZY2) ? k_lzp<CT, 2, W3> : k_lzp<CT, 1, W3>);
+}
+template <bool CT, int STRONG, uint32_t GLOG, uint32_t WLOG, bool FARP, bool TAB3, bool SUBTILE>
+static void launch_split_g(const LzLaunch &L) {
     constexpr uint32_t LT = GLOG ? LzGeo<WLOG>::L_TABLE : LzGeo<WLOG, TAB3>::L_TOTAL;
     static const hipError_t attr_set = hipFuncSetAttribute((const void *)k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3, SUBTILE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LzGeo<WLOG, TAB3>::L_TOTAL);   // once per process, thread-safe
     (void)attr_set;
     constexpr bool W3 = GLOG == 0;
-    if (!(flags & FLAG_ALL_SMALL)) hipLaunchKernelGGL((k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3, SUBTILE>), dim3(nseg), dim3(LZ_THREADS), LT, st, src, segs, flags, max_off, pbuf, blk0, gtab);
-    if (SUBTILE && (flags & FLAG_SPLIT_WAVEPARSE)) return;     // (sub-tiles in front of the wave-per-region parse: the caller launches the short segments' kernel -- words of four bytes -- and the parse)
-    if (flags & FLAG_TIER1) hipLaunchKernelGGL((k_lzms<STRONG, W3>), dim3(nseg), dim3(64), lzms_lds(SMALL_SEG), st, src, segs, flags, pbuf, blk0, 0u, SMALL_SEG);     // the short segments, which k_lzm skipped
-    if (flags & FLAG_TIER2) { const uint32_t mx = 8192u + 4096u * ((flags >> FLAG_T2_SHIFT) & 3u);
-                              hipLaunchKernelGGL((k_lzms<STRONG, W3>), dim3(nseg), dim3(64), lzms_lds(mx), st, src, segs, flags, pbuf, blk0, SMALL_SEG, mx); }
-    if (ev_match) (void)hipEventRecord(ev_match, st);
-    if (!pg || pg->nb == 0) return;                            // (no grid: the caller wants the match kernel alone; a run of empty entries has segments and no blocks)
-    if (flags & FLAG_LAZY3) hipLaunchKernelGGL((k_lzp<CT, 3, W3>), dim3(pg->nb), dim3(LZP_THREADS), 0, st, src, pg->segs_all, pg->blk_seg, seqs, lits, blk, ctab, flags, max_len, pbuf, blk0, pg->hist);
-    else if (flags & FLAG_LAZY2) hipLaunchKernelGGL((k_lzp<CT, 2, W3>), dim3(pg->nb), dim3(LZP_THREADS), 0, st, src, pg->segs_all, pg->blk_seg, seqs, lits, blk, ctab, flags, max_len, pbuf, blk0, pg->hist);
-    else hipLaunchKernelGGL((k_lzp<CT, 1, W3>), dim3(pg->nb), dim3(LZP_THREADS), 0, st, src, pg->segs_all, pg->blk_seg, seqs, lits, blk, ctab, flags, max_len, pbuf, blk0, pg->hist);
+    if (!(L.flags & FLAG_ALL_SMALL)) hipLaunchKernelGGL((k_lzm<CT, STRONG, GLOG, WLOG, FARP, TAB3, SUBTILE>), dim3(L.nseg), dim3(LZ_THREADS), LT, L.st, L.src, L.segs, L.flags, L.max_off, L.pbuf, L.blk0, GLOG ? L.gtab : nullptr);
+    if (SUBTILE && (L.flags & FLAG_SPLIT_WAVEPARSE)) return;     // (sub-tiles in front of the wave-per-region parse: the caller launches the short segments' kernel -- words of four bytes -- and the parse)
+    launch_lzms<STRONG, W3>(L);
+    if (L.ev_match) (void)hipEventRecord(L.ev_match, L.st);
+    if (L.form == LzForm::MatchOnly || L.pg.nb == 0) return;   // (a run of empty entries has segments and no blocks)
+    launch_lzp<CT, W3>(L, L.flags);
 }
-// match kernel + parse kernel over `nseg` segments; pbuf holds one word per position of the launch's blocks, blk0 = the first of them; ctab != nullptr:
-// a deflate launch (chunk table, look-back inside the LDS window); ev_match, if given, is recorded between the two kernels
-// gtab != nullptr (zstd, strong set): the match kernel's hash tables in global memory, nseg << GTAB_LOG words
-void launch_lz_split(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                     uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg) {
-    const bool strong = (flags & F_STRONG) && (flags & F_ADOPT), strong2 = strong && (flags & FLAG_STRONG2);     // (FLAG_STRONG2: only with the global table or the packed 16 KiB geometry)
-    const bool mt = !gtab && ((flags >> FLAG_MT_SHIFT) & 7u) != 0;           // option mtile: the instances with sub-tiles (every set with the table in LDS)
-#define LSG(CT_, ST_, WLOG_, FARP_, TAB3_) do { \
-        if (mt) launch_split_g<CT_, ST_, 0, WLOG_, FARP_, TAB3_, true>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); \
-        else launch_split_g<CT_, ST_, 0, WLOG_, FARP_, TAB3_>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, nullptr, pg); } while (0)
-    if (ctab) { if (strong) LSG(true, true, 16, false, false);
-                else LSG(true, false, 16, false, false); }
-    else if (strong && gtab) { if (strong2) launch_split_g<false, 2, GTAB_LOG, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg);
-                               else launch_split_g<false, true, GTAB_LOG, 16>(src, segs, nseg, seqs, lits, blk, ctab, flags, max_off, max_len, st, pbuf, blk0, ev_match, gtab, pg); }
-    else if ((flags & FLAG_TAB3) && (flags & FLAG_W16)) {
-           if (strong2) LSG(false, 2, 14, true, true);
-           else if (strong) LSG(false, true, 14, true, true);
-           else LSG(false, false, 14, true, true); }
-    else if ((flags & FLAG_TAB3) && (flags & FLAG_W32)) {
-           if (strong) LSG(false, true, 15, true, true);
-           else LSG(false, false, 15, true, true); }
-    else if (flags & FLAG_W16) {
-           if (strong) LSG(false, true, 14, true, false);
-           else LSG(false, false, 14, true, false); }
-    else if (flags & FLAG_W32) {
-           if (strong) LSG(false, true, 15, true, false);
-           else LSG(false, false, 15, true, false); }
-    else { if (strong) LSG(false, true, 16, true, false);
-           else if (max_off <= NEAR_OFF) LSG(false, false, 16, false, false);
-           else LSG(false, false, 16, true, false); }
-#undef LSG
+// Split / MatchOnly: match kernel (+ parse kernel) over L.nseg segments; pbuf holds one word per position of the launch's blocks.  To the shared ladder this adds
+// what is k_lzm's own: the tables in global memory (gtab; zstd, strong sets), FARP from max_off, the instances with sub-tiles (option mtile; table in LDS)
+void launch_lz_split(const LzLaunch &L) {
+    const bool strong = (L.flags & F_STRONG) && (L.flags & F_ADOPT);
+    if (!L.ctab && strong && L.gtab) {
+        if (L.flags & FLAG_STRONG2) launch_split_g<false, 2, GTAB_LOG, 16, true, false, false>(L); else launch_split_g<false, 1, GTAB_LOG, 16, true, false, false>(L);
+        return;
+    }
+    const bool mt = !L.gtab && ((L.flags >> FLAG_MT_SHIFT) & 7u) != 0;
+    lz_instance(L.flags, L.ctab != nullptr, [&](auto I) {
+        using T = decltype(I);
+        auto go = [&](auto farp) {
+            constexpr bool FARP = decltype(farp)::value;
+            if (mt) launch_split_g<T::CT, T::STRONG, 0, T::WLOG, FARP, T::TAB3, true>(L); else launch_split_g<T::CT, T::STRONG, 0, T::WLOG, FARP, T::TAB3, false>(L);
+        };
+        if constexpr (T::CT) go(std::false_type{});                                      // deflate: the look-back lies in the LDS window
+        else if constexpr (T::STRONG == 0 && T::WLOG == 16) { if (L.max_off <= NEAR_OFF) go(std::false_type{}); else go(std::true_type{}); }
+        else go(std::true_type{});
+    });
 }
-// The short segments of a launch that took the one-kernel form (which skips them: FLAG_HAS_SMALL): k_lzms + the parse kernel over their blocks only.  w3: words of
-// three bytes (the caller's choice: every launch but the zstd levels with the table in global memory takes them, as in the split form).
-void launch_lz_small(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                     uint32_t flags, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, const LzParseGrid *pg, bool w3) {
-    const bool strong = (flags & F_STRONG) && (flags & F_ADOPT), strong2 = strong && (flags & FLAG_STRONG2);
-#define LZMS(ST_, W3_) do { \
-        if (flags & FLAG_TIER1) hipLaunchKernelGGL((k_lzms<ST_, W3_>), dim3(nseg), dim3(64), lzms_lds(SMALL_SEG), st, src, segs, flags, pbuf, blk0, 0u, SMALL_SEG); \
-        if (flags & FLAG_TIER2) { const uint32_t mx = 8192u + 4096u * ((flags >> FLAG_T2_SHIFT) & 3u); \
-                                  hipLaunchKernelGGL((k_lzms<ST_, W3_>), dim3(nseg), dim3(64), lzms_lds(mx), st, src, segs, flags, pbuf, blk0, SMALL_SEG, mx); } } while (0)
-    if (strong2) { if (w3) LZMS(2, true); else LZMS(2, false); }
-    else if (strong) { if (w3) LZMS(true, true); else LZMS(true, false); }
-    else { if (w3) LZMS(false, true); else LZMS(false, false); }
-#undef LZMS
-    if (!pg || pg->nb == 0) return;
-    const uint32_t pf = flags | FLAG_SMALL_ONLY;
-#define LZP_SMALL(CT_, LZD_) do { if (w3) hipLaunchKernelGGL((k_lzp<CT_, LZD_, true>), dim3(pg->nb), dim3(LZP_THREADS), 0, st, src, pg->segs_all, pg->blk_seg, seqs, lits, blk, ctab, pf, max_len, pbuf, blk0, pg->hist); \
-                                  else hipLaunchKernelGGL((k_lzp<CT_, LZD_, false>), dim3(pg->nb), dim3(LZP_THREADS), 0, st, src, pg->segs_all, pg->blk_seg, seqs, lits, blk, ctab, pf, max_len, pbuf, blk0, pg->hist); } while (0)
-    if (ctab) { if (flags & FLAG_LAZY3) LZP_SMALL(true, 3); else if (flags & FLAG_LAZY2) LZP_SMALL(true, 2); else LZP_SMALL(true, 1); }
-    else { if (flags & FLAG_LAZY3) LZP_SMALL(false, 3); else if (flags & FLAG_LAZY2) LZP_SMALL(false, 2); else LZP_SMALL(false, 1); }
-#undef LZP_SMALL
+// Small: the short segments of a launch that took the one-kernel form (which skips them: FLAG_HAS_SMALL) -- k_lzms + the parse kernel over their blocks only; MatchOnly: k_lzms
+// alone.  w3: words of three bytes (every launch but the wave-per-region parse's, whose words take four)
+void launch_lz_small(const LzLaunch &L, bool w3) {
+    lz_instance(L.flags, L.ctab != nullptr, [&](auto I) {
+        using T = decltype(I);
+        if (w3) launch_lzms<T::STRONG, true>(L); else launch_lzms<T::STRONG, false>(L);
+        if (L.form == LzForm::MatchOnly || L.pg.nb == 0) return;
+        if (w3) launch_lzp<T::CT, true>(L, L.flags | FLAG_SMALL_ONLY); else launch_lzp<T::CT, false>(L, L.flags | FLAG_SMALL_ONLY);
+    });
 }
 uint32_t lz_gtab_log() { return GTAB_LOG; }
 void lzp_read_stamps(unsigned long long *out) {

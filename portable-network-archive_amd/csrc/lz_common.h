@@ -1,6 +1,6 @@
-// lz_common.h -- what the kernels of the LZ stage share: LDS layout of the match finder (window + hash table), flags, cross-lane helpers,
-// the wave-cooperative match extension.  k_lz.hip: the one-kernel form and its two halves as kernels; k_lz_split.hip: k_lzm + k_lzp, the
-// default split form.
+// lz_common.h -- what the kernels of the LZ stage share: LDS layout of the match finder (window + hash table), the instance ladder of their launchers,
+// cross-lane helpers, the wave-cooperative match extension.  k_lz.hip: the one-kernel form and its two halves as kernels; k_lz_split.hip: k_lzm, k_lzms,
+// k_lzp.  The launch flags and the launch descriptor (LzLaunch) are in pna_dev.h; which form a run takes is decided in pna_lz.cpp alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pna_dev.h"
@@ -58,8 +58,20 @@ __device__ __forceinline__ void t3_max(uint64_t *p, uint64_t v) { (void)__hip_at
 struct WPub  { uint32_t cnt; uint32_t gl; };   // cnt = nsel | nlit << 16; gl = (local literal index of the LAST match + 1) | (same for the FIRST match) << 16, 0 = no match
 static_assert(sizeof(WPub) == 8, "LDS record size");
 
-constexpr uint32_t FLAG_SPLIT_WAVEPARSE = 0x1000u;   // split form: the parse half as k_lz<MODE = 2> (a wave per region) instead of k_lzp (testing)
-constexpr uint32_t FLAG_STAMP = 0x100u, FLAG_FORCE_SERIAL = 0x200u;   // 0x200: always take the serial form of the end scan (testing)
+// The instance ladder: which (CT, STRONG, WLOG, TAB3) a launch's flag word and chunk table select, written once for launch_lz, launch_lz_split and
+// launch_lz_small.  f is called with ONE of these thirteen LzInst types, so a launcher instantiates its kernels for them and for nothing else.
+//   CT: a deflate launch (chunk table; 64 KiB window).  STRONG: 0 / 1 = F_STRONG with F_ADOPT / 2 = + FLAG_STRONG2 (packed 16 KiB geometry only).
+//   WLOG: 16, or FLAG_W32 -> 15, FLAG_W16 -> 14.  TAB3: the packed table (FLAG_TAB3 with either of the two).
+template <bool CT_, int STRONG_, uint32_t WLOG_, bool TAB3_> struct LzInst { static constexpr bool CT = CT_, TAB3 = TAB3_; static constexpr int STRONG = STRONG_; static constexpr uint32_t WLOG = WLOG_; };
+template <class F> inline void lz_instance(uint32_t flags, bool ctab, F &&f) {
+    const bool strong = (flags & F_STRONG) && (flags & F_ADOPT), strong2 = strong && (flags & FLAG_STRONG2), t3 = (flags & FLAG_TAB3) != 0;
+    if (ctab) { if (strong) f(LzInst<true, 1, 16, false>{}); else f(LzInst<true, 0, 16, false>{}); }
+    else if (t3 && (flags & FLAG_W16)) { if (strong2) f(LzInst<false, 2, 14, true>{}); else if (strong) f(LzInst<false, 1, 14, true>{}); else f(LzInst<false, 0, 14, true>{}); }
+    else if (t3 && (flags & FLAG_W32)) { if (strong) f(LzInst<false, 1, 15, true>{}); else f(LzInst<false, 0, 15, true>{}); }
+    else if (flags & FLAG_W16) { if (strong) f(LzInst<false, 1, 14, false>{}); else f(LzInst<false, 0, 14, false>{}); }
+    else if (flags & FLAG_W32) { if (strong) f(LzInst<false, 1, 15, false>{}); else f(LzInst<false, 0, 15, false>{}); }
+    else { if (strong) f(LzInst<false, 1, 16, false>{}); else f(LzInst<false, 0, 16, false>{}); }
+}
 static_assert(CAP1 >= 16 && CAP1 % 16 == 0 && CAP1 <= 32 && BACK_CAP == 3 && MIN_MATCH > 3, "the match step compares 16 bytes at a time, the next 16 only where all before matched");
 static_assert(GROUPS_PER_WAVE == 2 && TILE == 2048, "TILE / GROUPS_PER_WAVE describe the G = 2 (deflate) form; k_lz itself is generic in G");
 

@@ -28,10 +28,8 @@
 struct XzScan; struct XzBlock;     // xz_core.h
 struct KdfArgonJob; struct KdfPbkdf2Job;     // kdf_core.h
 namespace pna {
-void launch_lz_small(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-                     uint32_t flags, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, const LzParseGrid *pg, bool w3);
-void launch_lz(const uint8_t *src, const SegDesc *segs, uint32_t nseg, uint64_t *seqs, uint8_t *lits, BlkInfo *blk, uint4 *ctab,
-               uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, uint32_t *pbuf, uint32_t blk0, hipEvent_t ev_match, uint32_t *gtab, const LzParseGrid *pg);
+void launch_lz(const LzLaunch &L);                    // k_lz.hip: every form but Small (pna_dev.h LzLaunch)
+void launch_lz_small(const LzLaunch &L, bool w3);     // k_lz_split.hip: the short segments behind a one-kernel launch; w3: words of three bytes
 uint32_t lz_gtab_log();
 void launch_deflate_stage1(const uint8_t *src, const SegDesc *segs, uint32_t nseg, const uint32_t *blk_seg, uint32_t nblk,
                            const uint64_t *seqs, const uint8_t *lits, BlkInfo *blk, const uint4 *ctab, DeflTables *tabs, uint8_t *outc,
@@ -266,6 +264,16 @@ struct Tuning {
 };
 struct TuningName { const char *name, *env; long Tuning::*field; long lo, hi; };
 
+// The LZ stage's parameter set of one call: what its level and the options choose (lz_level_set), the source of every launch's flag word (lz_launch_flags)
+struct LzSet {
+    uint32_t bits = 0;                 // of call_flags, what the launch word takes over: the level set and the diagnostics the LZ kernels know (INIT_TO_LAUNCH)
+    bool lazy2 = false, lazy3 = false; // lazy deferral over two / three positions (FLAG_LAZY2, FLAG_LAZY3)
+    bool gtab = false;                 // the max set: the match kernel's table in global memory -- always the split form, words of four bytes
+    bool w32 = false, w16 = false;     // the match finder's LDS geometry: the 32 KiB window, of these the 16 KiB one (FLAG_W32 / FLAG_W16)
+    bool tab3 = false, far1 = false;   // ... its table packed (FLAG_TAB3), far candidates in one compacted round (FLAG_FAR1)
+    bool strong2 = false;              // the high / max sets' fourth adoption round and 15 back bytes (FLAG_STRONG2)
+    uint32_t max_off = 0, max_len = 0; // the longest look-back and match of the codec and the set
+};
 struct pna_gpu_stream;
 struct pna_gpu_ctx {
     Tuning tun;
@@ -278,16 +286,11 @@ struct pna_gpu_ctx {
     int device = 0;
     uint32_t flags = 0;
     uint32_t call_flags = 0;                        // flags of the current call: the level picks the parse (level_flags)
-    bool call_lazy3 = false;
-    bool call_lazy2 = false;                         // two-step lazy deferral (FLAG_LAZY2 of the LZ kernels)
+    LzSet lz;                                       // ... and the LZ stage's parameter set (lz_level_set, pna_lz.cpp)
     uint32_t n_cus = 256;                           // compute units of the device (hipDeviceProp_t::multiProcessorCount): a full round of one-workgroup-per-CU kernels
     bool call_xz = false;                           // the current call writes xz: LZ blocks of at most 64 KiB (one LZMA2 chunk each), matches of at most 273 bytes
     bool call_stored = false;                       // deflate level 0: stored blocks only (Compression::none())
-    bool call_strong2 = false;                      // ... the high / max sets' fourth adoption round and 15 back bytes (FLAG_STRONG2: zstd 4 .. 22 on the packed 16 KiB geometry or the global table)
-    uint32_t *lzp_hist = nullptr; bool lzp_hist_all = false;   // the current sub-batch: the counters the parse kernel adds the sequence codes to (null: none), and whether EVERY segment's parse did
-    bool call_tab3 = false;                         // ... its table packed (lz_common.h TAB3)
-    bool call_w16 = false;                          // ... the 16 KiB window (zstd 6..9)
-    bool call_gtab = false, call_w32 = false;       // ... and where the match finder's table lies / its LDS geometry (set_call_level)
+    bool lzp_hist_all = false;                      // the current sub-batch: the parse kernel has added EVERY segment's sequence codes to the segments' counters (lz_run)
     std::vector<hipEvent_t> lzm_ev; size_t lzm_used = 0;   // event pairs around the match kernel launches of the current sub-batch (timed calls)
     std::vector<uint8_t> lzm_nl;                            // launches inside each pair (2 where a run's last segments go in units)
     hipStream_t stream = nullptr;
@@ -429,6 +432,19 @@ struct GcmCallKeys { uint8_t kc[32], phsf_hash[32]; };
 inline uint32_t gcm_seg_size(const pna_gpu_cipher *ci) { return ci->gcm_segment_size ? ci->gcm_segment_size : (1u << 20); }
 
 void set_call_level(pna_gpu_ctx *c, int algo, int level);
+// The plan of a sub-batch (plan_subbatch, pna_host.cpp): its geometry, its forms, and the host's copy of the tables it uploaded
+struct SubPlan {
+    uint32_t blk_log = PNA_BLK_LOG, unit_log = 20, nseg = 0, nblk = 0, nunits = 0;
+    uint64_t max_len = 0;                    // the longest entry (a window of a solid stream: the whole stream)
+    bool latency = false, unit_mode = false, single_block = false, hist_on = false, seq_hist = false, any_empty = false;
+    uint32_t small_fl = 0;                   // launch flags of the short segments' geometry (k_lzms)
+    bool wave_blk = false;                   // many small entries: deflate's stage 1 runs a wave per segment, the write kernels a wave per block
+    uint32_t frame_max_payload = 0;          // an upper bound of every payload when the entries are small and plain (k_frame's wave-per-entry form; 0: none)
+    const SegDesc *segs = nullptr; const uint32_t *entry_first_seg = nullptr;
+};
+// pna_lz.cpp -- the host side of the LZ stage: the level's parameter set (algo: zstd or deflate; xz: zstd's with LZMA's match cap), and the stage over one sub-batch
+LzSet lz_level_set(const pna_gpu_ctx *c, int algo, int level, bool xz);
+int lz_run(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const SubPlan &p, hipStream_t st, bool timed);
 // what the compress entry points take: zstd, deflate and -- with option xz_encode, on the batch and the non-solid archive entry points -- xz
 inline bool encode_algo_ok(const pna_gpu_ctx *c, int algo) {
     return algo == PNA_ALGO_ZSTD || algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_XZ && c && c->tun.xz_encode != 0 && launch_xzenc_stage && launch_xzenc_write);

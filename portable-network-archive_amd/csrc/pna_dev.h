@@ -3,6 +3,7 @@
 // Normative algorithm: DESIGN.md §"Encoder specification".  The same rules are restated independently in plain C
 // under oracle/ (test infrastructure); tests require the two to agree byte for byte.
 #pragma once
+#include <hip/hip_runtime.h>      // (LzLaunch: uint4, hipStream_t, hipEvent_t)
 #include <stdint.h>
 #include <stddef.h>
 #include "aes_core.h"
@@ -44,13 +45,45 @@ constexpr uint32_t LOOKAHEAD  = 1024;
 constexpr uint32_t WIN_BYTES  = 65536;      // circular look-back window in LDS
 constexpr uint32_t SEQ_CAP    = PNA_BLK_LOG == 17 ? 22528 : ((BLK_SIZE / MIN_MATCH + BLK_SIZE / 256 + 256 + 255) & ~255u);      // sequences per block: (BLK_SIZE - 3 * 1024) / MIN_MATCH + one front-cut match (>= 3 bytes) per wave region, rounded up to 256
 
-constexpr uint32_t F_HUF = 1, F_FSE = 2, F_LAZY = 4, F_REP = 8;
-constexpr uint32_t FLAG_LAZY2 = 0x400u;   // launch flag of the LZ kernels (with F_LAZY): two-step lazy deferral -- a start also waits for a match at q + 2 that is longer by two or more
-constexpr uint32_t FLAG_LAZY3 = 0x800u;   // (with FLAG_LAZY2) three-step deferral: ... and for a match at q + 3 that is longer by three or more
-constexpr uint32_t FLAG_W16 = 0x4000u;   // ... the 16 KiB-window geometry (36 800 table slots)
-constexpr uint32_t FLAG_LEN36 = 0x8000u;  // adopted lengths clamped to 36: what the 3-byte words of the split form keep (5 bits: 0 or length - 5) next to 19 bits of offset
-constexpr uint32_t MAX_OFF_W3 = (1u << 19) - 1;   // ... so the look-back of the sets with an LDS table ends there (the estimator: 2.7761 -> 2.7759; 2^18: 2.7678)
-constexpr uint32_t FLAG_TAB3 = 0x10000u;  // (with FLAG_W32 / FLAG_W16, even inserts) the packed table: three 21-bit entries per 64-bit LDS word, 49 062 / 55 206 slots (lz_common.h)
+// ---- The launch flags of the LZ kernels (k_lz, k_lzm, k_lzms, k_lzp): ONE 32-bit word per launch, built by lz_launch_flags (pna_lz.cpp).  In bit order:
+constexpr uint32_t F_HUF = 0x1, F_FSE = 0x2;              // (the entropy stage's: Huffman literals, FSE sequences -- the LZ kernels ignore them)
+constexpr uint32_t F_LAZY = 0x4;                          // lazy deferral: a start waits for a longer match at the next position
+constexpr uint32_t F_REP = 0x8;                           // repeat-offset codes (not produced by this build)
+constexpr uint32_t F_FAR = 0x10;                          // look-back beyond the LDS window
+constexpr uint32_t F_ADOPT = 0x20;                        // backward adoption
+constexpr uint32_t F_INS2 = 0x40;                         // only even positions enter the table
+constexpr uint32_t F_STRONG = 0x80;                       // third adoption round (7 back bytes) + two-step lazy
+constexpr uint32_t FLAG_STAMP = 0x100u;                   // the one-kernel form's instance with phase stamps (diagnostics)
+constexpr uint32_t FLAG_FORCE_SERIAL = 0x200u;            // always take the serial form of the end scan (testing)
+constexpr uint32_t FLAG_LAZY2 = 0x400u;                   // (with F_LAZY) two-step lazy deferral -- a start also waits for a match at q + 2 that is longer by two or more
+constexpr uint32_t FLAG_LAZY3 = 0x800u;                   // (with FLAG_LAZY2) three-step deferral: ... and for a match at q + 3 that is longer by three or more
+constexpr uint32_t FLAG_SPLIT_WAVEPARSE = 0x1000u;        // split form: the parse half as k_lz<MODE = 2> (a wave per region) instead of k_lzp (testing)
+constexpr uint32_t FLAG_W32 = 0x2000u;                    // the 32 KiB-window geometry (zstd only; lz_common.h LzGeo)
+constexpr uint32_t FLAG_W16 = 0x4000u;                    // ... the 16 KiB-window geometry (36 800 table slots)
+constexpr uint32_t FLAG_LEN36 = 0x8000u;                  // adopted lengths clamped to 36: what the 3-byte words of the split form keep (5 bits: 0 or length - 5) next to 19 bits of offset
+constexpr uint32_t FLAG_TAB3 = 0x10000u;                  // (with FLAG_W32 / FLAG_W16, even inserts) the packed table: three 21-bit entries per 64-bit LDS word, 49 062 / 55 206 slots (lz_common.h)
+constexpr uint32_t FLAG_HAS_SMALL = 0x20000u;             // the launch may hold short segments (at most MID_SEG bytes) -- k_lzms takes them, the other match kernels skip them
+constexpr uint32_t FLAG_SMALL_ONLY = 0x40000u;            // (k_lzp) parse the blocks of short segments only: the pass behind a one-kernel launch, which skipped them
+constexpr uint32_t FLAG_ALL_SMALL = 0x80000u;             // every segment of the launch is short (or empty): the large geometry's kernels are not launched at all
+constexpr uint32_t FLAG_TIER1 = 0x100000u, FLAG_TIER2 = 0x200000u;   // (with FLAG_HAS_SMALL) the launch holds segments of the first / second tier: which of k_lzms's two forms to launch
+constexpr uint32_t FLAG_T2_SHIFT = 22;                    // two bits: the second tier's longest segment is at most 8 / 12 / 16 KiB (0, 1, 2)
+constexpr uint32_t FLAG_FAR1 = 0x1000000u;                // (with FLAG_TAB3 + FLAG_W32) at most 63 far candidates per wave of 256 positions are verified -- ONE compacted round of k_lzm --, the rest dropped (oracle: far_slots, far_from)
+constexpr uint32_t FLAG_STRONG2 = 0x2000000u;             // (with F_STRONG; the packed 16 KiB geometry or the table in global memory: zstd 4 .. 22) a fourth adoption round over eight positions, first, and up to 15 back bytes (oracle: rounds 0x2148, back_cap 15; usable candidates lie at position 16 or beyond)
+constexpr uint32_t FLAG_MT_SHIFT = 28;                    // three bits, k_lzm (option mtile): 0 = look-ups and inserts alternate per tile; k + 1: per sub-tile of 256 << k positions (k = 0 .. 3) inside it
+constexpr uint32_t LZ_LAUNCH_BITS[] = {F_HUF, F_FSE, F_LAZY, F_REP, F_FAR, F_ADOPT, F_INS2, F_STRONG, FLAG_STAMP, FLAG_FORCE_SERIAL, FLAG_LAZY2, FLAG_LAZY3, FLAG_SPLIT_WAVEPARSE, FLAG_W32, FLAG_W16,
+                                       FLAG_LEN36, FLAG_TAB3, FLAG_HAS_SMALL, FLAG_SMALL_ONLY, FLAG_ALL_SMALL, FLAG_TIER1, FLAG_TIER2, 3u << FLAG_T2_SHIFT, FLAG_FAR1, FLAG_STRONG2, 7u << FLAG_MT_SHIFT};
+constexpr bool lz_launch_bits_disjoint() { uint32_t all = 0; for (uint32_t b : LZ_LAUNCH_BITS) { if (all & b) return false; all |= b; } return true; }
+static_assert(lz_launch_bits_disjoint(), "the launch flags of the LZ kernels are pairwise disjoint");
+// The word pna_gpu_init takes (pna_gpu_ctx::flags, call_flags) is ANOTHER namespace that shares the low bits with the launch word and collides with it above them:
+//   PNA_F_LZ_WAVEPARSE (0x4000) is FLAG_W16's bit, PNA_F_LZ_FUSED (0x8000) FLAG_LEN36's, and the init diagnostics 0x1000 / 0x2000 -- which choose the SEQUENCE
+//   coder of the entropy stage -- are FLAG_SPLIT_WAVEPARSE's and FLAG_W32's.  So the init word never travels to a launch as it is: these masks separate the two.
+constexpr uint32_t INIT_LEVEL_SET = 0xFFu;                                    // the level set (F_HUF .. F_STRONG): the same bits in both words
+constexpr uint32_t INIT_DIAG = 0x3F00u;                                       // diagnostics, taken only without PNA_F_DEFAULT; four of its bits mean something:
+constexpr uint32_t INIT_DIAG_STAMP = FLAG_STAMP, INIT_DIAG_SERIAL = FLAG_FORCE_SERIAL;   //   phase stamps / the serial end scan of k_lz: the same bits in the launch word
+constexpr uint32_t INIT_DIAG_SEQ_ONE = 0x1000u, INIT_DIAG_SEQ_TWO = 0x2000u;  //   the one-kernel / the two-phase sequence coder (k_entropy.hip): NOT launch flags of the LZ kernels
+constexpr uint32_t INIT_LZ_FORM = 0x4000u | 0x8000u;                          // PNA_F_LZ_WAVEPARSE | PNA_F_LZ_FUSED: the form of the LZ stage, read by lz_stage (pna_lz.cpp) only
+constexpr uint32_t INIT_TO_LAUNCH = INIT_LEVEL_SET | INIT_DIAG_STAMP | INIT_DIAG_SERIAL;   // what of the init word a zstd launch takes over (deflate: without the bits it has no use for)
+constexpr uint32_t MAX_OFF_W3 = (1u << 19) - 1;   // the look-back of the sets with an LDS table ends where the 3-byte words' 19 bits of offset do (the estimator: 2.7761 -> 2.7759; 2^18: 2.7678)
 // SHORT segments (at most SMALL_SEG bytes: less than one tile of the match finder, whose positions do not see each other's inserts -- such a segment would never
 // find a match) run the SMALL geometry: one wave per segment (k_lzms, k_lz_split.hip), a table of SMALL_SLOTS 32-bit entries, look-ups and inserts alternating per
 // 256 positions; the parse is the common one.  oracle/zstd_model.h: small_seg, small_slots, small_tile.
@@ -59,16 +92,6 @@ constexpr uint32_t SMALL_SEG = 4096, SMALL_SLOTS = 2048;
 // entries 1.93 -> 2.12, 16 KiB 2.14 -> 2.24; above 16 KiB the large table wins).  Same table size (4 096 slots were + 1 % of ratio for half the waves per CU); the tiers
 // differ in the LDS their window takes, which a launch sizes by its longest segment of the tier (FLAG_T2_SHIFT: 8, 12 or 16 KiB).  oracle: mid_seg, mid_slots.
 constexpr uint32_t MID_SEG = 16384, MID_SLOTS = SMALL_SLOTS;
-constexpr uint32_t FLAG_T2_SHIFT = 22;          // two bits: the second tier's longest segment is at most 8 / 12 / 16 KiB (0, 1, 2)
-constexpr uint32_t FLAG_HAS_SMALL = 0x20000u;   // launch flag of the LZ kernels: the launch may hold short segments (at most MID_SEG bytes) -- k_lzms takes them, the other match kernels skip them
-constexpr uint32_t FLAG_SMALL_ONLY = 0x40000u;  // (k_lzp) parse the blocks of short segments only: the pass behind a one-kernel launch, which skipped them
-constexpr uint32_t FLAG_TIER1 = 0x100000u, FLAG_TIER2 = 0x200000u;   // (with FLAG_HAS_SMALL) the launch holds segments of the first / second tier: which of k_lzms's two forms to launch
-constexpr uint32_t FLAG_ALL_SMALL = 0x80000u;   // every segment of the launch is short (or empty): the large geometry's kernels are not launched at all
-constexpr uint32_t FLAG_FAR1 = 0x1000000u;   // (with FLAG_TAB3 + FLAG_W32) at most 63 far candidates per wave of 256 positions are verified -- ONE compacted round of k_lzm --, the rest dropped (oracle: far_slots, far_from)
-constexpr uint32_t FLAG_STRONG2 = 0x2000000u; // (with F_STRONG; the packed 16 KiB geometry or the table in global memory: zstd 4 .. 22) a fourth adoption round over eight positions, first, and up to 15 back bytes (oracle: rounds 0x2148, back_cap 15; usable candidates lie at position 16 or beyond)
-constexpr uint32_t FLAG_MT_SHIFT = 28;          // three bits, launch flag of k_lzm (option mtile): 0 = look-ups and inserts alternate per tile; k + 1: per sub-tile of 256 << k positions (k = 0 .. 3) inside it
-constexpr uint32_t FLAG_W32 = 0x2000u;   // launch flag of the LZ kernels: the 32 KiB-window geometry (zstd only; lz_common.h LzGeo)
-constexpr uint32_t F_FAR = 0x10, F_ADOPT = 0x20, F_INS2 = 0x40, F_STRONG = 0x80;   // look-back beyond the LDS window; backward adoption; only even positions enter the table; third adoption round (7 back bytes) + two-step lazy
 
 // packed sequence: off(20) | ml(18) << 20 | ll(18) << 38
 __host__ __device__ inline uint64_t seq_pack(uint32_t ll, uint32_t ml, uint32_t off) {
@@ -94,6 +117,26 @@ struct SegDesc {
 // block -> segment map, and the launch's blocks [blk0, blk0 + nb)
 struct LzParseGrid { const SegDesc *segs_all; const uint32_t *blk_seg; uint32_t nb;
                      uint32_t *hist = nullptr; };    // hist (round 5; zstd, large batches): the segments' histogram counters (448 words each: k_entropy.hip HIST_WORDS) -- the parse kernel adds every block's sequence codes to words 256 .. 447 of its segment, so that k_stats reads the literals only
+// One launch of the LZ stage, as the host hands it to the launch layer (launch_lz, launch_lz_small: k_lz.hip, k_lz_split.hip).  The host builds it once per
+// sub-batch (lz_run, pna_lz.cpp) and adjusts it per run: form, segs / nseg, blk0, pbuf / gtab, the event, the grid's nb.
+struct BlkInfo;
+enum class LzForm : uint8_t {
+    OneKernel,        // k_lz<MODE 0>: match and parse in one kernel, no workspace; skips the short segments (FLAG_HAS_SMALL)
+    Split,            // k_lzm (+ k_lzms for the short segments) -> one word per position in pbuf -> k_lzp over the grid's blocks
+    SplitWaveParse,   // the same with k_lz<MODE 1> / <MODE 2> as the halves (testing; with sub-tiles k_lzm as the first)
+    MatchOnly,        // the match kernels of Split alone: the parse follows in a later launch over the same pbuf
+    Small,            // launch_lz_small: k_lzms + k_lzp over the short segments' blocks, behind a one-kernel launch
+};
+struct LzLaunch {
+    LzForm form;
+    const uint8_t *src; const SegDesc *segs; uint32_t nseg;      // segs: segments, or units (pieces of segments)
+    uint64_t *seqs; uint8_t *lits; BlkInfo *blk;
+    uint4 *ctab;                                                 // deflate: the chunk table (null: a zstd / xz launch)
+    uint32_t *pbuf, *gtab;                                       // the words workspace (blk0 = the first block it holds); the match kernel's tables in global memory (null: in LDS)
+    uint32_t blk0, flags, max_off, max_len;
+    hipStream_t st; hipEvent_t ev_match;                         // ev_match, if given, is recorded between the match and the parse kernels
+    LzParseGrid pg;                                              // Split, SplitWaveParse, Small
+};
 constexpr uint32_t BLK_LOG_MIN = 13;   // smallest block of the latency mode (bounds: pna_gpu_bound)
 static_assert(sizeof(SegDesc) == 40, "SegDesc layout");
 // deflate, one zlib stream compressed in runs of whole segments (k_dfold): the run does not start the stream (no zlib header; the Adler-32 carry holds

@@ -1,5 +1,5 @@
-// pna_host.cpp -- context, options, level sets and the ENCODE core of libpna_gpu.so (plans, the LZ / entropy / framing launches of one sub-batch, the
-// device-resident entry points); the host pipelines, the read side and the streaming facade live in pna_pipeline.cpp, pna_extract.cpp, pna_decode.cpp and
+// pna_host.cpp -- context, options, level sets and the ENCODE core of libpna_gpu.so (plans, the entropy / framing launches of one sub-batch, the
+// device-resident entry points); the LZ stage's host side lives in pna_lz.cpp, the host pipelines, the read side and the streaming facade live in pna_pipeline.cpp, pna_extract.cpp, pna_decode.cpp and
 // pna_stream.cpp, what they share in pna_ctx.h.
 #include "pna_ctx.h"
 #include "xz_enc_core.h"
@@ -33,12 +33,6 @@ extern "C" const char *pna_gpu_strerror(int code) {
 extern "C" const char *pna_gpu_last_error(const pna_gpu_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 static bool mtile_ok(long v) { return v == 0 || v == 256 || v == 512 || v == 1024 || v == 2048; }
-// option mtile as the launch flag of k_lzm (FLAG_MT_SHIFT): only where the match finder's table lies in LDS
-static uint32_t mtile_flag(const pna_gpu_ctx *c, bool gt) {
-    uint32_t k = 0;
-    for (long v = c->tun.mtile; v >= 256; v >>= 1) k++;
-    return gt ? 0u : k << FLAG_MT_SHIFT;
-}
 extern "C" int pna_gpu_init(pna_gpu_ctx **out, int device_id, uint32_t flags) {
     if (!out) return PNA_E_INVAL;
     *out = nullptr;
@@ -49,13 +43,13 @@ extern "C" int pna_gpu_init(pna_gpu_ctx **out, int device_id, uint32_t flags) {
     pna_gpu_ctx *c = new pna_gpu_ctx();
     c->device = device_id;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->n_cus = (uint32_t)cus; }
-    c->flags = (flags & PNA_F_DEFAULT) ? (F_HUF | F_FSE | F_LAZY | F_FAR | F_ADOPT | F_INS2) : (flags & 0xFF);
+    c->flags = (flags & PNA_F_DEFAULT) ? (F_HUF | F_FSE | F_LAZY | F_FAR | F_ADOPT | F_INS2) : (flags & INIT_LEVEL_SET);
     c->flags &= ~F_REP;                    // repeat-offset codes are not produced by this build
     for (const TuningName &t : TUNING_NAMES)
         if (const char *e = getenv(t.env)) { const long v = atol(e); if (v >= t.lo && v <= t.hi && (t.field != &Tuning::mtile || mtile_ok(v))) c->tun.*(t.field) = v; }
     if (const char *pm = getenv("PNA_STREAM_POOL_MIB")) c->pool_cap = (size_t)std::min<unsigned long>(strtoul(pm, nullptr, 10), 1ul << 20) << 20;
     if (const char *lg = getenv("PNA_STREAM_LINGER_US")) c->comb_linger_us = (uint32_t)std::min<unsigned long>(strtoul(lg, nullptr, 10), 100000ul);
-    if (!(flags & PNA_F_DEFAULT)) c->flags |= flags & 0x3F00u;  // diagnostics: 0x100 phase stamps, 0x200 force the serial fallback in k_lz, 0x1000 / 0x2000 force the one-kernel / two-phase sequence coder
+    if (!(flags & PNA_F_DEFAULT)) c->flags |= flags & INIT_DIAG;  // diagnostics (pna_dev.h): phase stamps, the serial fallback in k_lz, the one-kernel / two-phase sequence coder
     c->flags |= flags & (PNA_F_LZ_FUSED | PNA_F_LZ_WAVEPARSE);  // the form of the LZ stage: honoured next to PNA_F_DEFAULT as well
     c->call_flags = c->flags;
     if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return PNA_E_NODEVICE; }
@@ -168,9 +162,7 @@ extern "C" int pna_gpu_clamp_level(int algo, int level) {
 //   default   zstd 0, 3                      + a third adoption round (matches move back by up to 7 positions): ratio at the reference's default level (round 4)
 //   high      zstd 4..9,      deflate 9      the default set on the 16 KiB-window geometry (more table slots, more candidates verified in HBM / L2) + a fourth adoption round over eight positions, 15 back bytes; deflate: + third round
 //   max       zstd 10..22                    + the match kernel's hash table in global memory: 2^19 slots per segment instead of what LDS holds
-// zstd light / default run the match finder's 32 KiB-window geometry, high the 16 KiB one (lz_common.h LzGeo), both with the PACKED table (three 21-bit
-// entries per 64-bit LDS word: 49 062 / 55 206 slots; option tab3 = 0: 32-bit entries, 32 704 / 36 800); the others and deflate the 64 KiB geometry (24 512).
-constexpr int HIGH_FROM = 4;        // the first zstd level of the high set
+// (the match finder's geometry per set: lz_level_set, pna_lz.cpp)
 static uint32_t level_flags(const pna_gpu_ctx *c, int algo, int level) {
     const int lv = pna_gpu_clamp_level(algo, level);
     const bool fast = algo == PNA_ALGO_DEFLATE ? lv <= 3 : (lv < 0 || lv == 1);
@@ -187,15 +179,8 @@ void set_call_level(pna_gpu_ctx *c, int algo, int level) {
     c->call_xz = algo == PNA_ALGO_XZ;
     if (c->call_xz) { level = XZ_LZ_LEVEL[pna_gpu_clamp_level(PNA_ALGO_XZ, level)]; algo = PNA_ALGO_ZSTD; }
     c->call_flags = level_flags(c, algo, level);
-    const bool zstd = algo != PNA_ALGO_DEFLATE;
-    c->call_gtab = zstd && pna_gpu_clamp_level(algo, level) >= 10 && (c->call_flags & F_STRONG) && (c->call_flags & F_ADOPT) && c->tun.strong_gtab != 0;
-    c->call_w32 = zstd && !c->call_gtab && (c->call_flags & F_FAR) && (c->call_flags & F_LAZY) && c->tun.win32k != 0;
-    c->call_w16 = c->call_w32 && (c->tun.win32k >= 2 || pna_gpu_clamp_level(algo, level) >= HIGH_FROM);   // the high set's geometry (round 4: chosen by the level, no longer by F_STRONG; round 5: from level 4 on -- libzstd 1.5.7's own 4 / 5 give 2.863 / 2.906 on the corpus, the default set 2.850, the high set 2.884)
-    c->call_stored = !zstd && pna_gpu_clamp_level(algo, level) == 0;
-    c->call_tab3 = c->call_w32 && (c->call_flags & F_INS2) && (c->call_flags & F_ADOPT) && c->tun.tab3 != 0;
-    c->call_strong2 = zstd && pna_gpu_clamp_level(algo, level) >= HIGH_FROM && (c->call_flags & F_STRONG) && (c->call_flags & F_ADOPT) && c->tun.strong2 != 0 && (c->call_gtab || (c->call_tab3 && c->call_w16));
-    c->call_lazy2 = (c->call_flags & F_LAZY) && (c->tun.lazy2 != 0 || (c->call_flags & F_STRONG));   // every lazy set defers over two positions (the high sets always did)
-    c->call_lazy3 = c->call_lazy2 && c->tun.lazy2 >= 2;                                               // ... and over three (option lazy2 = 2, the default)
+    c->call_stored = algo == PNA_ALGO_DEFLATE && pna_gpu_clamp_level(algo, level) == 0;
+    c->lz = lz_level_set(c, algo, level, c->call_xz);
 }
 
 // blocks an entry of `len` bytes takes in the per-block workspace (sub-batches are cut by block count); a forced block size counts as such
@@ -304,132 +289,6 @@ static void splice_meta(std::vector<uint8_t> &pre, const pna_gpu_entry_meta *m, 
     pre.swap(out);
 }
 
-// The LZ stage over segments [s0, s1) of a sub-batch.  Runs of more than 1 024 segments take the split form -- match kernel (k_lzm) + parse
-// kernel (k_lzp) per run of at most `split_blocks` blocks, which meet in c->pbuf (4 bytes per input byte of the run; one run at a time on the
-// stream, so runs share it) --, shorter ones and PNA_F_LZ_FUSED / PNA_LZ_SPLIT=0 the one-kernel form (k_lz<MODE 0>, no pbuf);
-// PNA_F_LZ_WAVEPARSE / PNA_LZ_SPLIT=2: the split form as k_lz<MODE 1> + k_lz<MODE 2> (testing).  All forms give the same bytes.  If pbuf
-// cannot be had, the run is halved down to 1 024 blocks, then fused.
-// The end of a run of segments from `a` on: the first segment before s1 whose blocks no longer fit `run_blocks` blocks from a's first one (block bases grow
-// with the index: a binary search -- 10^6 small entries made the linear walk a millisecond)
-static uint32_t run_end(const SegDesc *segs, uint32_t nseg_all, uint32_t nblk, uint32_t a, uint32_t s1, uint32_t bps, uint32_t run_blocks) {
-    uint32_t b = a + 1, hi = s1;
-    while (b < hi) { const uint32_t mid = b + (hi - b) / 2; if ((mid < nseg_all ? segs[mid].blk_base : nblk) - segs[a].blk_base + bps <= run_blocks) b = mid + 1; else hi = mid; }
-    return b;
-}
-// The SHORT segments among [s0, s1) behind a launch of the one-kernel form, which skips them (pna_dev.h SMALL_SEG): k_lzms + the parse kernel over their blocks, through
-// the words workspace, in runs of blocks as the split form's
-static int lz_small_pass(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, uint32_t nseg_all, uint32_t s0, uint32_t s1, uint32_t nblk, uint4 *ctab,
-                         uint32_t flags, uint32_t max_len, hipStream_t st) {
-    uint32_t run_blocks = (uint32_t)std::min<uint64_t>((uint64_t)c->tun.lz_split_blocks << (PNA_BLK_LOG - segs[s0].blk_log), 1u << 30);
-    const uint32_t bps = 1u << (20 - segs[s0].blk_log);
-    for (uint32_t a = s0; a < s1;) {
-        const uint32_t b0 = segs[a].blk_base;
-        const uint32_t b = run_end(segs, nseg_all, nblk, a, s1, bps, run_blocks);
-        const uint32_t b1 = b < nseg_all ? segs[b].blk_base : nblk;
-        if (c->pbuf.ensure(((size_t)std::max<uint32_t>(b1 - b0, 1) << segs[a].blk_log) * 4)) {
-            (void)hipGetLastError();
-            if (run_blocks > 1024 && b - a > 1) { run_blocks /= 2; continue; }
-            return fail(c, PNA_E_NOMEM, "no room for the short segments' words");
-        }
-        const LzParseGrid pg{c->d_segs, c->d_blk_seg, b1 - b0};
-        launch_lz_small(d_src, c->d_segs + a, b - a, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, ctab, flags, max_len, st, (uint32_t *)c->pbuf.p, b0, &pg,
-                        (flags & FLAG_LEN36) != 0);
-        a = b;
-    }
-    return PNA_OK;
-}
-
-static int lz_stage(pna_gpu_ctx *c, const uint8_t *d_src, const SegDesc *segs, uint32_t nseg_all, uint32_t s0, uint32_t s1, uint32_t nblk, uint4 *ctab,
-                    uint32_t flags, uint32_t max_off, uint32_t max_len, hipStream_t st, bool timed) {
-    const int env_split = (int)c->tun.lz_split;
-    // (the option counts blocks of 128 KiB: a run is that many BYTES of input whatever the batch's block size)
-    const uint32_t env_blocks = (uint32_t)std::min<uint64_t>((uint64_t)c->tun.lz_split_blocks << (PNA_BLK_LOG - segs[s0].blk_log), 1u << 30);
-    const uint32_t bps = 1u << (20 - segs[s0].blk_log);          // blocks of a full segment
-    // zstd levels 10 .. 22 (the strong set): the match kernel's hash tables lie in global memory (2^19 slots per segment instead of the 24 512 LDS
-    // holds; k_lz_split.hip) -- only k_lzm has that form, so those levels always take the split form, whatever the run's length
-    const bool gt = !ctab && c->call_gtab;
-    // option mtile: only k_lzm has sub-tiles, so every run with a segment of the large geometry takes the split form -- whatever lz_split, lz_split_min or PNA_F_LZ_FUSED say --,
-    // in whole segments (no tail units: their pre-warm replays tiles), and a words workspace that cannot be had is an error: the one-kernel form would write other bytes
-    const uint32_t mt = (flags & FLAG_ALL_SMALL) ? 0u : mtile_flag(c, gt);
-    flags |= mt;
-    const bool fused = !gt && !mt && ((c->call_flags & PNA_F_LZ_FUSED) || env_split == 0 || (flags & 0x100u));   // (0x100: the phase stamps live in the fused kernel)
-    const bool waveparse = !gt && ((c->call_flags & PNA_F_LZ_WAVEPARSE) || env_split == 2);
-    uint32_t split_blocks = env_blocks;
-    if (s1 > s0) {
-        // several runs: of about equal size (whole rounds of 256 one-MiB segments) instead of full ones and a short tail -- a tail under the
-        // split form's threshold would fall back to the slower one-kernel form (5 000 segments: 2 560 + 2 440 instead of 4 096 + 904)
-        const uint32_t total = (s1 < nseg_all ? segs[s1].blk_base : nblk) - segs[s0].blk_base;
-        const uint32_t nruns = (total + split_blocks - 1) / split_blocks;
-        if (nruns > 1) {
-            const uint32_t round = c->n_cus * bps, even = ((total + nruns - 1) / nruns + round - 1) / round * round;
-            if (even < split_blocks) split_blocks = even;
-        }
-    }
-    const uint32_t s1_all = s1; bool fused_tail = false;
-    // The split form at every size: its parse kernel runs one wave per BLOCK (a block's parse depends on nothing outside the block), so a short run no
-    // longer waits for one wave's walk over a whole segment (N x 1 MiB, one-kernel / split: 32: 2.3 / 1.6 ms, 256: 2.4 / 1.8, 1 024: 9.3 / 6.3,
-    // 2 048: 18.6 / 12.3; scripts/lz_forms.py).  The one-kernel form remains for PNA_F_LZ_FUSED, for a workspace that cannot be allocated and for the
-    // units of the latency mode; lz_split_min restores a threshold.
-    const uint32_t min_segs = (gt || mt) ? 0u : (uint32_t)c->tun.lz_split_min;
-    for (uint32_t a = s0; a < s1 && !fused;) {
-        const uint32_t b0 = segs[a].blk_base;
-        const uint32_t b = run_end(segs, nseg_all, nblk, a, s1, bps, split_blocks);
-        const uint32_t b1 = b < nseg_all ? segs[b].blk_base : nblk;
-        if (b - a < min_segs && !waveparse) { s0 = a; s1 = b; fused_tail = b < s1_all; break; }
-        if ((c->tun.lz_pbuf_fail && !gt) /* testing: as if the allocation failed */ || c->pbuf.ensure(((size_t)std::max<uint32_t>(b1 - b0, 1) << segs[a].blk_log) * 4) ||
-            (gt && c->gtab.ensure((size_t)(b - a) << (lz_gtab_log() + 2)))) {
-            (void)hipGetLastError();                                   // (the failed allocation's sticky code)
-            if (split_blocks > 1024 && b - a > 1) { split_blocks /= 2; continue; }                    // (for this call only: the next one tries the full run again)
-            if (gt) return fail(c, PNA_E_NOMEM, "no room for the strong level set's hash tables");    // (the one-kernel form has LDS tables: other bytes)
-            if (mt) return fail(c, PNA_E_NOMEM, "mtile: no room for the words workspace (the one-kernel form has no sub-tiles)");
-            s0 = a; break;                                             // no room for the words: the rest goes through the fused kernel
-        }
-        hipEvent_t e1 = nullptr;
-        if (timed) {
-            while (c->lzm_ev.size() < c->lzm_used + 2) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreate(&e)); c->lzm_ev.push_back(e); }
-            HIPCHK(c, hipEventRecord(c->lzm_ev[c->lzm_used], st)); e1 = c->lzm_ev[c->lzm_used + 1]; c->lzm_used += 2; c->lzm_nl.push_back(1);
-        }
-        LzParseGrid pg{c->d_segs, c->d_blk_seg, b1 - b0};                  // the parse kernel: one wave per block of the run
-        pg.hist = c->lzp_hist;                                            // (the sequence codes' counters, where the entropy stage takes them from the parse kernel)
-        if (waveparse) c->lzp_hist_all = false;
-        // The match kernel runs one workgroup per segment and CU, all of equal length: a run of 3 334 segments is 13 full rounds of the 256 CUs and a 14th for
-        // 6 of them.  The segments behind the last full round are therefore cut into UNITS of one block each (table pre-warmed: the same words, SS4a), a launch
-        // of their own behind the full rounds: R x 8 short workgroups instead of R long ones next to 256 - R idle CUs.
-        uint32_t R = (!gt && !mt && !waveparse && c->tun.tail_units && b - a >= 2 * c->n_cus) ? (b - a) % c->n_cus : 0;     // (n_cus: the device's compute units, 256 on an MI355X)
-        if (R > 3 * c->n_cus / 8 || (flags & FLAG_ALL_SMALL)) R = 0;
-        if (R) {
-            const uint32_t bl = segs[a].blk_log, bs = 1u << bl;
-            size_t nu = 0;
-            for (uint32_t sgi = b - R; sgi < b; sgi++) nu += std::max<uint32_t>(1, (segs[sgi].len + bs - 1) >> bl);
-            constexpr size_t TAIL_CAP = 16 * 96 * 128;                 // (allocated once at this size: a buffer that grew would move under the launches already queued)
-            if (c->tail_used + nu > TAIL_CAP || c->h_tail.ensure(TAIL_CAP * sizeof(SegDesc)) || c->d_tail.ensure(TAIL_CAP * sizeof(SegDesc))) R = 0;
-            else {
-                SegDesc *hu = (SegDesc *)c->h_tail.p + c->tail_used; SegDesc *du = (SegDesc *)c->d_tail.p + c->tail_used;
-                size_t k = 0;
-                for (uint32_t sgi = b - R; sgi < b; sgi++)
-                    for (uint32_t u = 0; u < std::max<uint32_t>(segs[sgi].len, 1); u += bs) { SegDesc us = segs[sgi]; us.u0 = u; us.u1 = std::min<uint32_t>(segs[sgi].len, u + bs); hu[k++] = us; }
-                HIPCHK(c, hipMemcpyAsync(du, hu, nu * sizeof(SegDesc), hipMemcpyHostToDevice, st));
-                launch_lz(d_src, c->d_segs + a, b - a - R, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, ctab, flags, max_off, max_len, st,
-                          (uint32_t *)c->pbuf.p, b0, nullptr, nullptr, nullptr);                        // the full rounds: match kernel only
-                launch_lz(d_src, du, (uint32_t)nu, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, ctab, flags, max_off, max_len, st,
-                          (uint32_t *)c->pbuf.p, b0, e1, nullptr, &pg);                                 // the rest in units, then the parse kernel over the whole run
-                c->tail_used += nu;
-                if (timed) c->lzm_nl.back() = 2;                               // (the pair of events spans both launches of the match kernel)
-            }
-        }
-        if (!R)
-        launch_lz(d_src, c->d_segs + a, b - a, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, ctab, flags | (waveparse ? 0x1000u : 0u), max_off, max_len, st,
-                  (uint32_t *)c->pbuf.p, b0, e1, gt ? (uint32_t *)c->gtab.p : nullptr, &pg);
-        a = b;
-        if (a >= s1) return PNA_OK;
-    }
-    c->lzp_hist_all = false;                                           // (the one-kernel form: its parse counts nothing)
-    if (!(flags & FLAG_ALL_SMALL)) launch_lz(d_src, c->d_segs + s0, s1 - s0, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, ctab, flags, max_off, max_len, st, nullptr, 0, nullptr, nullptr, nullptr);
-    if (flags & FLAG_HAS_SMALL) { const int rc = lz_small_pass(c, d_src, segs, nseg_all, s0, s1, nblk, ctab, flags, max_len, st); if (rc) return rc; }   // (the one-kernel form skips the short segments)
-    if (fused_tail) return lz_stage(c, d_src, segs, nseg_all, s1, s1_all, nblk, ctab, flags, max_off, max_len, st, timed);   // (a short run in the middle: only with tiny PNA_LZ_SPLIT_BLOCKS)
-    return PNA_OK;
-}
-
 // stage times of a finished sub-batch from its events (the stream has been waited for)
 static int collect_timing(pna_gpu_ctx *c, bool defl, uint32_t nseg, uint32_t nblk, bool with_cipher) {
     float ms[6] = {0, 0, 0, 0, 0, 0}, msf = 0;
@@ -465,16 +324,6 @@ struct HostMarks {
     void mark(const char *what) { if (on) marks.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
     void print(size_t ne) const { if (on && !marks.empty()) { fprintf(stderr, "[pna sub-batch] %zu entries, host:", ne); for (auto &m : marks) fprintf(stderr, "  %s %.2f", m.first, m.second); fprintf(stderr, " ms\n"); } }
 };
-// The plan of a sub-batch (plan_subbatch): its geometry, its forms, and the host's copy of the tables it uploaded
-struct SubPlan {
-    uint32_t blk_log = PNA_BLK_LOG, unit_log = 20, nseg = 0, nblk = 0, nunits = 0;
-    uint64_t max_len = 0;                    // the longest entry (a window of a solid stream: the whole stream)
-    bool latency = false, unit_mode = false, single_block = false, hist_on = false, seq_hist = false, any_empty = false;
-    uint32_t small_fl = 0;                   // launch flags of the short segments' geometry (k_lzms)
-    bool wave_blk = false;                   // many small entries: deflate's stage 1 runs a wave per segment, the write kernels a wave per block
-    uint32_t frame_max_payload = 0;          // an upper bound of every payload when the entries are small and plain (k_frame's wave-per-entry form; 0: none)
-    const SegDesc *segs = nullptr; const uint32_t *entry_first_seg = nullptr;
-};
 // LATENCY MODE: a small batch -- the CompressionWriter seam with a handful of writers in flight, one entry of
 // `pna_gpu_compress_batch` -- has fewer segments than the chip has CUs, and its time is the length of the per-segment and per-block serial
 // chains (one workgroup walks a segment's 256 tiles; one lane codes a block's sequences).  Such a batch is cut finer: blocks of 8 .. 64 KiB
@@ -482,14 +331,14 @@ struct SubPlan {
 // everything before it (lz_prewarm), which gives the very matches of the segment-long walk.  Both follow from the batch's size alone
 // (and pna_gpu_set_option), are reported by pna_gpu_last_timing, and are parameters of the oracle's model.
 static void plan_geometry(const pna_gpu_ctx *c, int algo, uint64_t in_total, uint64_t nseg_est, SubPlan &p) {
-    const bool latency = c->tun.latency_max_mib > 0 && in_total <= ((uint64_t)c->tun.latency_max_mib << 20) && nseg_est <= 1024 && !(c->call_flags & 0x100u);
+    const bool latency = c->tun.latency_max_mib > 0 && in_total <= ((uint64_t)c->tun.latency_max_mib << 20) && nseg_est <= 1024 && !(c->call_flags & INIT_DIAG_STAMP);
     uint32_t blk_log = blk_log_for_longest(c, p.max_len), unit_log = 20;
     if (algo == PNA_ALGO_XZ) {
         // xz: an LZ block is an LZMA2 chunk, 64 KiB at most (a shorter longest entry: the power of two that holds it), and a chunk is one wave's serial chain.  In
         // latency mode the blocks are zstd's there -- 16 KiB up to 32 MiB of input, 32 KiB beyond --, a quarter or half of the chain for a model that starts anew
         // more often.  Whole segments always: the LZ stage's units are not used, the coder behind it is what an xz call waits for.
         if (latency && blk_log == 16 && !c->tun.blk_log) blk_log = std::max<uint64_t>(in_total, c->call_total) <= (32ull << 20) ? 14u : 15u;
-    } else if (blk_log == PNA_BLK_LOG && algo != PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & 0x100u) && !(latency && in_total <= (64ull << 20))) {
+    } else if (blk_log == PNA_BLK_LOG && algo != PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & INIT_DIAG_STAMP) && !(latency && in_total <= (64ull << 20))) {
         // deflate beyond 64 MiB of input: whole segments, and 64 KiB blocks up to 384 MiB of the call's input (96 / 192 / 256 MiB: 1.78 / 2.19 / 2.52 -> 1.66 / 1.99 / 2.20 ms;
         // ratio 2.540 -> 2.536: every dynamic block repeats the code description, so the blocks stay larger than zstd's)
         if (std::max<uint64_t>(in_total, c->call_total) <= (384ull << 20)) blk_log = 16;
@@ -501,7 +350,7 @@ static void plan_geometry(const pna_gpu_ctx *c, int algo, uint64_t in_total, uin
         // units: about one per CU (256), never smaller than a block
         unit_log = blk_log;
         while (unit_log < 20 && (in_total >> unit_log) > 384) unit_log++;
-    } else if (blk_log == PNA_BLK_LOG && algo == PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & 0x100u)) {       // (latency_max_mib = 0: 128 KiB blocks whatever the batch)
+    } else if (blk_log == PNA_BLK_LOG && algo == PNA_ALGO_ZSTD && c->tun.latency_max_mib > 0 && !(c->call_flags & INIT_DIAG_STAMP)) {       // (latency_max_mib = 0: 128 KiB blocks whatever the batch)
         // zstd, measured again on the round's final kernels (LAB_LOG.md 4.10: one device batch of n x 1 MiB): what a batch below ~1 GiB costs is its blocks' chains, so
         // the blocks stay small well beyond the latency mode -- 16 KiB up to 32 MiB of input, 32 KiB up to 384 MiB, 64 KiB up to 1 GiB (256 MiB: 3.3 -> 2.5 ms, 512: 5.2 -> 4.6;
         // ratio 2.847 -> 2.844 / 2.846), the call's whole input deciding where a large call is cut into sub-batches --, and UNITS pay only while they fit ONE round of
@@ -515,7 +364,7 @@ static void plan_geometry(const pna_gpu_ctx *c, int algo, uint64_t in_total, uin
     }
     if (c->tun.unit_log) unit_log = (uint32_t)std::max<long>(c->tun.unit_log, blk_log);
     // option mtile: whole segments -- a unit's pre-warm (lz_prewarm / lz_prewarm3) replays a tile's inserts as ONE contest, which is not what sub-tiles leave in the table
-    if (c->tun.mtile && !(algo == PNA_ALGO_ZSTD && c->call_gtab)) unit_log = 20;
+    if (c->tun.mtile && !(algo == PNA_ALGO_ZSTD && c->lz.gtab)) unit_log = 20;
     if (unit_log < blk_log) unit_log = blk_log;
     p.latency = latency; p.blk_log = blk_log; p.unit_log = unit_log;
 }
@@ -605,12 +454,12 @@ static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
     const bool unit_mode = unit_log < 20 && nunits > 0;
     c->last_blk_log = blk_log; c->last_units = unit_mode ? nunits : 0;
     // zstd entropy stage, two forms: statistics per block (k_hist) + tables + three-lane state chains (k_seqa) + token-parallel packing (k_seqb) while
-    // the chain waves fit the chip's SIMDs (<= 40 960 blocks); beyond, statistics per segment inside k_stats and the one-kernel coder k_seq.  Flags
-    // 0x1000 / 0x2000 and option hist_by_block force one.
+    // the chain waves fit the chip's SIMDs (<= 40 960 blocks); beyond, statistics per segment inside k_stats and the one-kernel coder k_seq.  The init
+    // diagnostics INIT_DIAG_SEQ_ONE / INIT_DIAG_SEQ_TWO and option hist_by_block force one.
     // (batches whose segments hold one block each -- entries of at most a block --: statistics per segment and the sequence coder with a lane per segment)
     const bool single_block = max_len <= bsz;
-    const bool hist_on = algo == PNA_ALGO_ZSTD && !(c->call_flags & 0x1000u) && !single_block &&
-                         ((c->call_flags & 0x2000u) || (c->tun.hist_by_block < 0 ? nblk <= 40960u : c->tun.hist_by_block != 0));
+    const bool hist_on = algo == PNA_ALGO_ZSTD && !(c->call_flags & INIT_DIAG_SEQ_ONE) && !single_block &&
+                         ((c->call_flags & INIT_DIAG_SEQ_TWO) || (c->tun.hist_by_block < 0 ? nblk <= 40960u : c->tun.hist_by_block != 0));
     // round 5: large zstd batches behind the split LZ stage -- the parse kernel counts the sequence codes per block into the segments' counters, k_stats walks the literals only
     const bool seq_hist = algo == PNA_ALGO_ZSTD && !hist_on && !single_block && c->tun.seq_hist != 0;
     const size_t o_hist = ((size_t)(nblk + 1) * sizeof(BlkInfo) + 15) & ~(size_t)15, blk_bytes = o_hist + ((hist_on || seq_hist) ? (size_t)nseg * 448 * 4 : 0);
@@ -644,24 +493,10 @@ static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
 // compressed size and offset in c->seg_size / c->seg_off.
 static int compress_subbatch(const SubBatch &sb, const SubPlan &p) {
     pna_gpu_ctx *c = sb.c; const uint8_t *d_src = sb.d_src; const hipStream_t st = sb.st; const bool timed = sb.timed;
-    const uint32_t nseg = p.nseg, nblk = p.nblk, nunits = p.nunits, blk_log = p.blk_log;
-    c->lzm_used = 0; c->lzm_nl.clear();
-    c->lzp_hist = nullptr; c->lzp_hist_all = false;
+    const uint32_t nseg = p.nseg, nblk = p.nblk, blk_log = p.blk_log;
+    const bool defl = sb.algo == PNA_ALGO_DEFLATE;
     if (timed) HIPCHK(c, hipEventRecord(c->ev[0], st));
-    if (sb.algo == PNA_ALGO_DEFLATE) {
-        const uint32_t dfl = (c->call_flags & (F_LAZY | F_ADOPT | F_INS2 | F_STRONG | 0x300u)) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | FLAG_LEN36 | p.small_fl;
-        if (c->call_stored) { }                                // deflate level 0 = Compression::none(): stored blocks only, no match finder, no codes
-        else if (p.unit_mode) {
-            if (!(dfl & FLAG_ALL_SMALL)) launch_lz(d_src, c->d_units, nunits, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (uint4 *)c->ctab.p, dfl, 32768u, 258u, st, nullptr, 0, nullptr, nullptr, nullptr);
-            if (dfl & FLAG_HAS_SMALL) { const int rc = lz_small_pass(c, d_src, p.segs, nseg, 0, nseg, nblk, (uint4 *)c->ctab.p, dfl, 258u, st); if (rc) return rc; }
-        }
-        else { const int rc = lz_stage(c, d_src, p.segs, nseg, 0, nseg, nblk, (uint4 *)c->ctab.p, dfl, 32768u, 258u, st, timed); if (rc) return rc; }
-        if (timed) HIPCHK(c, hipEventRecord(c->ev[1], st));
-        launch_deflate_stage1(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const uint64_t *)c->seqs.p,
-                              (const uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (const uint4 *)c->ctab.p, (DeflTables *)c->tabs.p, (uint8_t *)c->litc.p,
-                              (uint64_t *)c->seg_size.p, (uint64_t *)c->seg_off.p, st, timed ? &c->ev[2] : nullptr, c->call_flags, c->call_stored,
-                              /* a wave per segment: many small entries */ p.wave_blk);
-    } else {
+    if (!defl) {
         // zstd (and xz, whose LZ stage is zstd's with matches of at most 273 bytes): everything stays on `st` -- a hand-over to the auxiliary stream and back costs ~45 us of idle device, a tenth of a small batch --, except the
         // literal coder of large batches, which runs on the auxiliary stream next to the sequence coder (option lit_beside_seq)
         if (!c->aux) {
@@ -673,24 +508,16 @@ static int compress_subbatch(const SubBatch &sb, const SubPlan &p) {
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         }
         HIPCHK(c, hipEventRecord(c->ev_lz[0], st));
+    }
+    { const int rc = lz_run(c, sb.algo, d_src, p, st, timed); if (rc) return rc; }       // the LZ stage, every codec and form (pna_lz.cpp)
+    if (defl) {
+        if (timed) HIPCHK(c, hipEventRecord(c->ev[1], st));
+        launch_deflate_stage1(d_src, c->d_segs, nseg, c->d_blk_seg, nblk, (const uint64_t *)c->seqs.p,
+                              (const uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, (const uint4 *)c->ctab.p, (DeflTables *)c->tabs.p, (uint8_t *)c->litc.p,
+                              (uint64_t *)c->seg_size.p, (uint64_t *)c->seg_off.p, st, timed ? &c->ev[2] : nullptr, c->call_flags, c->call_stored,
+                              /* a wave per segment: many small entries */ p.wave_blk);
+    } else {
         const bool xz = sb.algo == PNA_ALGO_XZ;
-        const uint32_t zlen = xz ? (uint32_t)XZE_MAX_LEN : 0xFFFFFFFFu;
-        const uint32_t zfl = (c->call_flags & 0x3FFu) | (c->call_w32 ? (c->call_w16 ? FLAG_W16 : FLAG_W32) : 0u) | (c->call_lazy2 ? FLAG_LAZY2 : 0u) | (c->call_lazy3 ? FLAG_LAZY3 : 0u) | (c->call_gtab ? 0u : FLAG_LEN36) | (c->call_tab3 ? FLAG_TAB3 : 0u) | ((c->call_tab3 && !c->call_w16 && c->tun.far1) ? FLAG_FAR1 : 0u) | (c->call_strong2 ? FLAG_STRONG2 : 0u) | p.small_fl;
-        const uint32_t zmax = (c->call_flags & F_FAR) ? (c->call_gtab ? MAX_OFF : MAX_OFF_W3) : NEAR_OFF;   // (3-byte words keep 19 bits of offset)
-        if (p.unit_mode) {
-            // (one launch over all units; the strong set: split form over the units, tables in global memory)
-            const bool gt = c->call_gtab;
-            const LzParseGrid pgu{c->d_segs, c->d_blk_seg, nblk};
-            if (gt && (c->pbuf.ensure(((size_t)nblk << blk_log) * 4) || c->gtab.ensure((size_t)nunits << (lz_gtab_log() + 2)))) return fail(c, PNA_E_NOMEM, "no room for the strong level set's hash tables");
-            if (gt || !(zfl & FLAG_ALL_SMALL))
-            launch_lz(d_src, c->d_units, nunits, (uint64_t *)c->seqs.p, (uint8_t *)c->lits.p, (BlkInfo *)c->blk.p, nullptr, zfl,
-                      zmax, zlen, st, gt ? (uint32_t *)c->pbuf.p : nullptr, 0, nullptr, gt ? (uint32_t *)c->gtab.p : nullptr, gt ? &pgu : nullptr);
-            if (!gt && (zfl & FLAG_HAS_SMALL)) { const int rc = lz_small_pass(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, zlen, st); if (rc) return rc; }   // (the split form above takes them itself)
-        }
-        else {
-            c->lzp_hist = p.seq_hist ? c->d_hist : nullptr; c->lzp_hist_all = c->lzp_hist != nullptr;
-            const int rc = lz_stage(c, d_src, p.segs, nseg, 0, nseg, nblk, nullptr, zfl, zmax, zlen, st, timed); if (rc) return rc;
-        }
         HIPCHK(c, hipEventRecord(c->ev_lz[1], st));
         HIPCHK(c, hipEventRecord(c->ev_en[0], st));
         if (xz) {

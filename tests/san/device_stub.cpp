@@ -1,11 +1,13 @@
 // tests/san/device_stub.cpp -- TEST INFRASTRUCTURE: the launch layer of libpna_gpu.so on the CPU for the sanitizer builds.
 // The zstd write path is stubbed with a trivially valid encoder (every segment = one frame of RAW blocks; the empty entry = the
-// reference's 9-byte frame), the framing kernels (prefix + CRC-32 + FEND, the pieces' raw CRC registers, the CRC patches, the read side's CRC check)
+// reference's 9-byte frame), deflate with stored blocks, the LZ launches with a recorder of what was asked of them, the framing kernels (prefix + CRC-32 + FEND, the pieces' raw CRC registers, the CRC patches, the read side's CRC check)
 // are restated bytewise, the cipher kernels by keyed hashes that fold in everything the host hands them (CBC decryption: the exact inverse of the
 // stub's encryption); everything else aborts: the sanitizer
 // driver exercises the HOST code around the kernels, not the codecs (those are checked against the oracle on the GPU).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <algorithm>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "pna_dev.h"                                             // (with aes_core.h: the host code's key schedule, aes256_expand)
@@ -14,12 +16,33 @@
 namespace pna {
 [[noreturn]] static void nostub(const char *what) { fprintf(stderr, "device_stub: %s is not stubbed\n", what); abort(); }
 
-void launch_lz(const uint8_t *, const SegDesc *, uint32_t, uint64_t *, uint8_t *, BlkInfo *, uint4 *, uint32_t, uint32_t, uint32_t, hipStream_t, uint32_t *, uint32_t, hipEvent_t, uint32_t *, const LzParseGrid *) {}
-void launch_lz_small(const uint8_t *, const SegDesc *, uint32_t, uint64_t *, uint8_t *, BlkInfo *, uint4 *, uint32_t, uint32_t, hipStream_t, uint32_t *, uint32_t, const LzParseGrid *, bool) {}
+// The LZ launches leave one text row each while a recorder is open (lz_rows_begin .. lz_rows_take: san_driver's launch matrix): what was asked of the launch
+// layer, without pointer values.  "Device" memory is host memory here, so the first and the last descriptor are read through the pointer.
+static std::mutex g_rows_mu; static std::string g_rows; static bool g_rows_on = false;
+void lz_rows_begin() { std::lock_guard<std::mutex> lk(g_rows_mu); g_rows.clear(); g_rows_on = true; }
+std::string lz_rows_take() { std::lock_guard<std::mutex> lk(g_rows_mu); g_rows_on = false; return std::move(g_rows); }
+static void lz_row(const char *entry, const LzLaunch &L, int w3) {
+    std::lock_guard<std::mutex> lk(g_rows_mu);
+    if (!g_rows_on) return;
+    static const char *const forms[] = {"one-kernel", "split", "split+waveparse", "match-only", "small"};
+    const bool small = L.form == LzForm::Small, grid = L.form == LzForm::Split || L.form == LzForm::SplitWaveParse || small;
+    char b[512]; int n = snprintf(b, sizeof b, "%s %s nseg=%u", entry, forms[(int)L.form], L.nseg);
+    for (const SegDesc *sd : {L.segs, L.segs + (L.nseg ? L.nseg - 1 : 0)})
+        if (L.nseg) n += snprintf(b + n, sizeof b - n, " {%llu,%u,%u,%u,%u,%u}", (unsigned long long)sd->src_off, sd->len, sd->blk_base, sd->blk_log, sd->u0, sd->u1);
+    snprintf(b + n, sizeof b - n, " flags=%08x max_off=%ld max_len=%u blk0=%u ctab=%d pbuf=%d gtab=%d ev=%d nb=%ld hist=%d w3=%d\n", L.flags, small ? -1l : (long)L.max_off, L.max_len, L.blk0,
+             L.ctab != nullptr, L.pbuf != nullptr, L.gtab != nullptr, L.ev_match != nullptr, grid ? (long)L.pg.nb : -1l, grid && L.pg.hist, w3);
+    g_rows += b;
+}
+void launch_lz(const LzLaunch &L) { lz_row("launch_lz", L, -1); }
+void launch_lz_small(const LzLaunch &L, bool w3) { lz_row("launch_lz_small", L, w3); }
 void launch_default_tables(hipStream_t) {}
 uint32_t lz_gtab_log() { return 19; }
+// (the row: whether the entropy stage was told that the parse kernel has counted every segment's sequence codes -- the LZ stage decides that)
 void launch_entropy_chunk(const SegDesc *, uint32_t, uint32_t, const uint32_t *, uint32_t, uint32_t, const uint64_t *, const uint8_t *, BlkInfo *, SegTables *,
-                          uint8_t *, uint8_t *, uint32_t *, uint32_t, uint32_t, uint32_t *, hipStream_t, hipEvent_t *, hipStream_t, hipEvent_t, hipEvent_t, bool, const uint32_t *) {}
+                          uint8_t *, uint8_t *, uint32_t *, uint32_t, uint32_t, uint32_t *hist, hipStream_t, hipEvent_t *, hipStream_t, hipEvent_t, hipEvent_t, bool, const uint32_t *seq_hist) {
+    std::lock_guard<std::mutex> lk(g_rows_mu);
+    if (g_rows_on) g_rows += std::string("launch_entropy_chunk hist=") + (hist ? "1" : "0") + " seq_hist=" + (seq_hist ? "1" : "0") + "\n";
+}
 static uint64_t seg_bytes(const SegDesc &sd) {
     if (sd.len == 0) return 9;
     return 6 + 3ull * seg_nblk(sd) + sd.len;
@@ -87,10 +110,29 @@ void launch_link_gather(const void *segs, uint32_t nseg, uint32_t, hipStream_t) 
 }
 void lz_read_stamps(unsigned long long *out) { memset(out, 0, 8 * sizeof *out); }
 
-void launch_deflate_stage1(const uint8_t *, const SegDesc *, uint32_t, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, BlkInfo *, const uint4 *, DeflTables *,
-                           uint8_t *, uint64_t *, uint64_t *, hipStream_t, hipEvent_t *, uint32_t, bool, bool) { nostub("deflate"); }
-void launch_deflate_write(const uint8_t *, const SegDesc *, const uint32_t *, uint32_t, const BlkInfo *, const uint64_t *, const uint64_t *, const uint8_t *, const uint32_t *,
-                          uint32_t, uint8_t *, hipStream_t, bool, bool) { nostub("deflate"); }
+// deflate as stored blocks, so that a deflate call completes (the launch matrix looks at the LZ launches in front of these, not at the bytes): the zlib header in front of an
+// entry's first segment, every segment as stored blocks of at most 65 535 bytes (an empty one: one empty block), BFINAL and four trailer bytes (zeros: no Adler-32) on the entry's last
+static uint64_t stored_bytes(const SegDesc &sd) { return (sd.first & 1 ? 2 : 0) + 5ull * std::max<uint32_t>(1, (sd.len + 65534) / 65535) + sd.len + (sd.first & 2 ? 4 : 0); }
+void launch_deflate_stage1(const uint8_t *, const SegDesc *segs, uint32_t nseg, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, BlkInfo *, const uint4 *, DeflTables *,
+                           uint8_t *, uint64_t *seg_size, uint64_t *seg_off, hipStream_t, hipEvent_t *, uint32_t, bool, bool) {
+    uint64_t pos = 0;
+    for (uint32_t s = 0; s < nseg; s++) { seg_size[s] = stored_bytes(segs[s]); seg_off[s] = pos; pos += seg_size[s]; }
+    seg_off[nseg] = pos;
+}
+void launch_deflate_write(const uint8_t *src, const SegDesc *segs, const uint32_t *, uint32_t, const BlkInfo *, const uint64_t *seg_off, const uint64_t *, const uint8_t *, const uint32_t *entry_seg,
+                          uint32_t nentry, uint8_t *dst, hipStream_t, bool, bool) {
+    for (uint32_t s = 0; s < entry_seg[nentry]; s++) {
+        const SegDesc &sd = segs[s];
+        uint8_t *o = dst + seg_off[s];
+        if (sd.first & 1) { *o++ = 0x78; *o++ = 0x01; }
+        for (uint32_t b0 = 0; b0 == 0 || b0 < sd.len; b0 += 65535) {
+            const uint32_t bl = std::min<uint32_t>(sd.len - b0, 65535);
+            const uint8_t h[5] = {(uint8_t)((sd.first & 2) && b0 + bl == sd.len), (uint8_t)bl, (uint8_t)(bl >> 8), (uint8_t)~bl, (uint8_t)(~bl >> 8)};
+            memcpy(o, h, 5); memcpy(o + 5, src + sd.src_off + b0, bl); o += 5 + bl;
+        }
+        if (sd.first & 2) memset(o, 0, 4);
+    }
+}
 // The read side's CRC check (k_frame in verify mode) over whole chunks: verify[0] counts mismatches, verify[1] keeps the lowest failing descriptor index
 void launch_frame_verify(const FrameDesc *fd, uint32_t n, const CrcTabs *, const uint8_t *buf, uint64_t, const char ty[4], uint32_t *verify, hipStream_t, uint32_t) {
     for (uint32_t i = 0; i < n; i++) {

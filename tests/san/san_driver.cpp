@@ -576,7 +576,171 @@ static void test_failing_sink() {
         return pna_gpu_create_archive_multi_host(cs, 2, PNA_ALGO_ZSTD, 3, small.n(), small.names.data(), small.src.data(), small.len.data(), fail_sink, &s); }, small, false, 3);
 }
 
+// LZ launch matrix: what the host asks of the LZ stage's launch layer -- which form, over which segments or units, with which flag word, in which order -- for
+// every branch of the stage's driver (pna_lz.cpp).  The device stub records one text row per launch; each case goes through pna_gpu_compress_batch_device on a
+// context of its own and compares the CRC-32 of its rows (and of the error text of a failing call), the return code and pna_gpu_timing's lz_match_launches and
+// lz_units with the values recorded when the matrix was written.  On a mismatch the rows are printed.
+namespace pna { void lz_rows_begin(); std::string lz_rows_take(); }
+struct LzOpt { const char *name; long v; };
+struct LzCase { const char *what; uint32_t init; int algo, level; const std::vector<size_t> *lens; std::vector<LzOpt> opts; int rc; uint64_t launches; uint32_t units, crc; };
+static void test_lz_launch_matrix() {
+    const size_t K = 1024, M = K * K;
+    std::vector<size_t> lat(2, 300 * K), seg(3, M + 1), mix{0, 100, 5000, 12000, 20000}, small{0, 100, 5000, 12000}, empty(3, 0), tail(600, 20 * K), tail700(700, 16400),
+                        runs{0, M, M, 0, 0, M}, many(4200, 1), latmix{300 * K, 100, 300 * K, 5000};
+    many.push_back(20 * K);
+    const uint32_t D = PNA_F_DEFAULT; const int Z = PNA_ALGO_ZSTD, F = PNA_ALGO_DEFLATE;
+    const LzOpt L0{"latency_max_mib", 0};
+    const LzCase cases[] = {
+        // latency mode: one launch over the units (zstd: the one-kernel form; the max set: the split form over the units), the short segments behind it
+        {"units z3", D, Z, 3, &lat, {}, 0, 0, 38, 0x8d7c6783u},
+        {"units z3 unit_log=14", D, Z, 3, &lat, {{"unit_log", 14}}, 0, 0, 38, 0x8d7c6783u},
+        {"units z1", D, Z, 1, &lat, {}, 0, 0, 38, 0x2a8d6f3au},
+        {"units z6", D, Z, 6, &lat, {}, 0, 0, 38, 0xd85a5819u},
+        {"units z10 (global table)", D, Z, 10, &lat, {}, 0, 0, 38, 0x68b41dfau},
+        {"units z19 strong_gtab=0", D, Z, 19, &lat, {{"strong_gtab", 0}}, 0, 0, 38, 0xd85a5819u},
+        {"units d6", D, F, 6, &lat, {}, 0, 0, 38, 0x96e5f7b8u},
+        {"units d1", D, F, 1, &lat, {}, 0, 0, 38, 0x21107ad3u},
+        {"units d9 unit_log=14", D, F, 9, &lat, {{"unit_log", 14}}, 0, 0, 38, 0x3bdb3dcdu},
+        {"units mix z3", D, Z, 3, &mix, {}, 0, 1, 0, 0x04be8ce0u},
+        {"units mix z10", D, Z, 10, &mix, {}, 0, 1, 0, 0x9ddce176u},
+        {"units mix d6", D, F, 6, &mix, {}, 0, 1, 0, 0x377df913u},
+        {"units small z3 (all small)", D, Z, 3, &small, {}, 0, 1, 0, 0x9d54a23au},
+        {"units small d6 (all small)", D, F, 6, &small, {}, 0, 1, 0, 0xff93768cu},
+        {"units mtile=512 z3 (whole segments)", D, Z, 3, &lat, {{"mtile", 512}}, 0, 1, 0, 0x79f4e351u},
+        {"units + short z3", D, Z, 3, &latmix, {}, 0, 0, 40, 0xbfe6c8fcu},
+        {"units + short z10", D, Z, 10, &latmix, {}, 0, 0, 40, 0x0fb8713cu},
+        {"units + short d6", D, F, 6, &latmix, {}, 0, 0, 40, 0x14943babu},
+        {"units + short z3 small_geometry=0", D, Z, 3, &latmix, {{"small_geometry", 0}}, 0, 0, 40, 0x3c2d7301u},
+        {"stored d0", D, F, 0, &lat, {}, 0, 0, 38, 0x00000000u},
+        // whole segments: the split form, the level sets and their options
+        {"segments z1", D, Z, 1, &seg, {L0}, 0, 1, 0, 0xadb0a290u},
+        {"segments z3", D, Z, 3, &seg, {L0}, 0, 1, 0, 0x4a58e198u},
+        {"segments z6", D, Z, 6, &seg, {L0}, 0, 1, 0, 0x1f7ede02u},
+        {"segments z10", D, Z, 10, &seg, {L0}, 0, 1, 0, 0x5bdf0640u},
+        {"segments z19", D, Z, 19, &seg, {L0}, 0, 1, 0, 0x5bdf0640u},
+        {"segments d1", D, F, 1, &seg, {L0}, 0, 1, 0, 0x93506727u},
+        {"segments d6", D, F, 6, &seg, {L0}, 0, 1, 0, 0x24a5ea4cu},
+        {"segments d9", D, F, 9, &seg, {L0}, 0, 1, 0, 0x899b2039u},
+        {"segments z3 win32k=0", D, Z, 3, &seg, {L0, {"win32k", 0}}, 0, 1, 0, 0x83e2cdbeu},
+        {"segments z3 win32k=2", D, Z, 3, &seg, {L0, {"win32k", 2}}, 0, 1, 0, 0x24ea343eu},
+        {"segments z3 tab3=0", D, Z, 3, &seg, {L0, {"tab3", 0}}, 0, 1, 0, 0x35763509u},
+        {"segments z6 tab3=0", D, Z, 6, &seg, {L0, {"tab3", 0}}, 0, 1, 0, 0x460e95b1u},
+        {"segments z6 strong2=0", D, Z, 6, &seg, {L0, {"strong2", 0}}, 0, 1, 0, 0x24ea343eu},
+        {"segments z10 strong2=0", D, Z, 10, &seg, {L0, {"strong2", 0}}, 0, 1, 0, 0x748bee2du},
+        {"segments z10 strong_gtab=0", D, Z, 10, &seg, {L0, {"strong_gtab", 0}}, 0, 1, 0, 0x1f7ede02u},
+        {"segments z3 far1=0", D, Z, 3, &seg, {L0, {"far1", 0}}, 0, 1, 0, 0x57929486u},
+        {"segments z3 lazy2=0", D, Z, 3, &seg, {L0, {"lazy2", 0}}, 0, 1, 0, 0x716dc5b0u},
+        {"segments z3 lazy2=1", D, Z, 3, &seg, {L0, {"lazy2", 1}}, 0, 1, 0, 0x716dc5b0u},
+        {"segments z1 lazy2=0", D, Z, 1, &seg, {L0, {"lazy2", 0}}, 0, 1, 0, 0x394b967cu},
+        {"segments d6 lazy2=1", D, F, 6, &seg, {L0, {"lazy2", 1}}, 0, 1, 0, 0x9702d8a3u},
+        // the forms: options, init flags, a workspace that cannot be had, mtile
+        {"segments z3 lz_split=0", D, Z, 3, &seg, {L0, {"lz_split", 0}}, 0, 0, 0, 0xb3c2509cu},
+        {"segments z3 lz_split=2", D, Z, 3, &seg, {L0, {"lz_split", 2}}, 0, 1, 0, 0xac692a45u},
+        {"segments d6 lz_split=0", D, F, 6, &seg, {L0, {"lz_split", 0}}, 0, 0, 0, 0xc81cb6d0u},
+        {"segments d6 lz_split=2", D, F, 6, &seg, {L0, {"lz_split", 2}}, 0, 1, 0, 0xf7c29d9fu},
+        {"segments z10 lz_split=0 (stays split)", D, Z, 10, &seg, {L0, {"lz_split", 0}}, 0, 1, 0, 0x5bdf0640u},
+        {"segments z10 lz_split=2 (stays k_lzp)", D, Z, 10, &seg, {L0, {"lz_split", 2}}, 0, 1, 0, 0x5bdf0640u},
+        {"segments z3 FUSED", D | PNA_F_LZ_FUSED, Z, 3, &seg, {L0}, 0, 0, 0, 0xb3c2509cu},
+        {"segments z3 WAVEPARSE", D | PNA_F_LZ_WAVEPARSE, Z, 3, &seg, {L0}, 0, 1, 0, 0xac692a45u},
+        {"segments d6 FUSED", D | PNA_F_LZ_FUSED, F, 6, &seg, {L0}, 0, 0, 0, 0xc81cb6d0u},
+        {"segments z3 FUSED + WAVEPARSE", D | PNA_F_LZ_FUSED | PNA_F_LZ_WAVEPARSE, Z, 3, &seg, {L0}, 0, 0, 0, 0xb3c2509cu},
+        {"segments z3 stamps (0x100)", 0x177u, Z, 3, &seg, {L0}, 0, 0, 0, 0xe78da8b3u},
+        {"segments z3 serial end scan (0x200)", 0x277u, Z, 3, &seg, {L0}, 0, 1, 0, 0x7cf3ab50u},
+        {"segments d6 stamps + serial (0x300)", 0x377u, F, 6, &seg, {L0}, 0, 0, 0, 0xcd969fbbu},
+        // (the init diagnostics 0x1000 / 0x2000 choose the sequence coder: they are not the launch flags of the same value)
+        {"segments z1 init 0x1000 (no wave parse)", 0x1077u, Z, 1, &seg, {L0}, 0, 1, 0, 0x00444131u},
+        {"segments z1 init 0x2000 (no 32 KiB window)", 0x2077u, Z, 1, &seg, {L0}, 0, 1, 0, 0xadb0a290u},
+        {"segments d6 init 0x3000", 0x3077u, F, 6, &seg, {L0}, 0, 1, 0, 0x24a5ea4cu},
+        // the parse kernel counts the sequence codes (seq_hist) where the entropy stage runs per segment; not behind the wave parse or the one-kernel form
+        {"segments z3 hist_by_block=0", D, Z, 3, &seg, {L0, {"hist_by_block", 0}}, 0, 1, 0, 0xe7ac0239u},
+        {"segments z3 hist_by_block=0 lz_split=2", D, Z, 3, &seg, {L0, {"hist_by_block", 0}, {"lz_split", 2}}, 0, 1, 0, 0x1886f8a5u},
+        {"segments z3 hist_by_block=0 lz_split=0", D, Z, 3, &seg, {L0, {"hist_by_block", 0}, {"lz_split", 0}}, 0, 0, 0, 0x6e548919u},
+        {"runs 2-1-3 z3 hist_by_block=0 lz_split_min=2", D, Z, 3, &runs, {L0, {"hist_by_block", 0}, {"lz_split_blocks", 8}, {"lz_split_min", 2}}, 0, 2, 0, 0x03df9a7du},
+        {"units z3 hist_by_block=0", D, Z, 3, &lat, {{"hist_by_block", 0}}, 0, 0, 38, 0x50eabe06u},
+        {"segments z3 lz_pbuf_fail", D, Z, 3, &seg, {L0, {"lz_pbuf_fail", 1}}, 0, 0, 0, 0xb3c2509cu},
+        {"segments d6 lz_pbuf_fail", D, F, 6, &seg, {L0, {"lz_pbuf_fail", 1}}, 0, 0, 0, 0xc81cb6d0u},
+        {"segments z10 lz_pbuf_fail (ignored)", D, Z, 10, &seg, {L0, {"lz_pbuf_fail", 1}}, 0, 1, 0, 0x5bdf0640u},
+        {"segments z3 mtile=512", D, Z, 3, &seg, {L0, {"mtile", 512}}, 0, 1, 0, 0x650c09f5u},
+        {"segments d6 mtile=2048", D, F, 6, &seg, {L0, {"mtile", 2048}}, 0, 1, 0, 0xfec2115fu},
+        {"segments z10 mtile=512 (ignored)", D, Z, 10, &seg, {L0, {"mtile", 512}}, 0, 1, 0, 0x5bdf0640u},
+        {"segments z3 mtile=512 FUSED (stays split)", D | PNA_F_LZ_FUSED, Z, 3, &seg, {L0, {"mtile", 512}}, 0, 1, 0, 0x650c09f5u},
+        {"segments z3 mtile=512 lz_split=2", D, Z, 3, &seg, {L0, {"mtile", 512}, {"lz_split", 2}}, 0, 1, 0, 0x833dc228u},
+        {"segments z3 mtile=512 lz_pbuf_fail", D, Z, 3, &seg, {L0, {"mtile", 512}, {"lz_pbuf_fail", 1}}, -3, 0, 0, 0x5a63b6b8u},
+        // short segments next to a large one, alone, and none at all
+        {"mix z3", D, Z, 3, &mix, {L0}, 0, 1, 0, 0x04be8ce0u},
+        {"mix z6 lz_split=0", D, Z, 6, &mix, {L0, {"lz_split", 0}}, 0, 0, 0, 0xfb992f2cu},
+        {"mix z3 lz_split=2", D, Z, 3, &mix, {L0, {"lz_split", 2}}, 0, 1, 0, 0x386efab7u},
+        {"mix z3 lz_pbuf_fail", D, Z, 3, &mix, {L0, {"lz_pbuf_fail", 1}}, 0, 0, 0, 0x0f3df5aau},
+        {"mix d6", D, F, 6, &mix, {L0}, 0, 1, 0, 0x377df913u},
+        {"mix d9 lz_split=0", D, F, 9, &mix, {L0, {"lz_split", 0}}, 0, 0, 0, 0xd96a837du},
+        {"mix z3 small_geometry=0", D, Z, 3, &mix, {L0, {"small_geometry", 0}}, 0, 1, 0, 0x80084eb4u},
+        {"mix z3 mtile=512 lz_split=2", D, Z, 3, &mix, {L0, {"mtile", 512}, {"lz_split", 2}}, 0, 1, 0, 0x03fa108bu},
+        {"small z3 (all small)", D, Z, 3, &small, {L0}, 0, 1, 0, 0x9d54a23au},
+        {"small z3 lz_split=0", D, Z, 3, &small, {L0, {"lz_split", 0}}, 0, 0, 0, 0xf0aaad46u},
+        {"small z3 lz_split=2", D, Z, 3, &small, {L0, {"lz_split", 2}}, 0, 1, 0, 0x01939e2fu},
+        {"small z10", D, Z, 10, &small, {L0}, 0, 1, 0, 0xd4f836feu},
+        {"small d6 mtile=512 (no sub-tiles)", D, F, 6, &small, {L0, {"mtile", 512}}, 0, 1, 0, 0xff93768cu},
+        {"small z3 small_geometry=0", D, Z, 3, &small, {L0, {"small_geometry", 0}}, 0, 1, 0, 0xb9e51c78u},
+        {"empty z3", D, Z, 3, &empty, {L0}, 0, 1, 0, 0xce1d5adau},
+        {"empty z3 latency mode", D, Z, 3, &empty, {}, 0, 1, 0, 0xce1d5adau},
+        {"empty d6 lz_split=0", D, F, 6, &empty, {L0, {"lz_split", 0}}, 0, 0, 0, 0x70b210beu},
+        // the tail units: 600 mod 256 = 88 segments behind the last full round; 700 mod 256 = 188 is too many
+        {"tail z3", D, Z, 3, &tail, {L0}, 0, 2, 0, 0x696f87ccu},
+        {"tail z3 tail_units=0", D, Z, 3, &tail, {L0, {"tail_units", 0}}, 0, 1, 0, 0xabee78c0u},
+        {"tail d6", D, F, 6, &tail, {L0}, 0, 2, 0, 0xc54b4c59u},
+        {"tail z10 (global table: none)", D, Z, 10, &tail, {L0}, 0, 1, 0, 0x8061be88u},
+        {"tail z3 lz_split=2 (none)", D, Z, 3, &tail, {L0, {"lz_split", 2}}, 0, 1, 0, 0x0e6e6718u},
+        {"tail z3 mtile=512 (none)", D, Z, 3, &tail, {L0, {"mtile", 512}}, 0, 1, 0, 0x98c231cdu},
+        {"tail z3 700 segments (none)", D, Z, 3, &tail700, {L0}, 0, 1, 0, 0xd38a31fdu},
+        {"tail z3 lz_pbuf_fail (halved, then one kernel)", D, Z, 3, &tail, {L0, {"lz_pbuf_fail", 1}}, 0, 0, 0, 0xb867de41u},
+        // several runs: one segment each; runs of 2, 1 and 3 segments with the short one in the middle taking the one-kernel form; runs evened to whole rounds
+        {"runs z3 lz_split_blocks=8", D, Z, 3, &seg, {L0, {"lz_split_blocks", 8}}, 0, 6, 0, 0x3535d4c8u},
+        {"runs d6 lz_split_blocks=8", D, F, 6, &seg, {L0, {"lz_split_blocks", 8}}, 0, 6, 0, 0x9afbf01eu},
+        {"runs z3 lz_split_blocks=8 lz_split=0", D, Z, 3, &seg, {L0, {"lz_split_blocks", 8}, {"lz_split", 0}}, 0, 0, 0, 0x7e8683c7u},
+        {"runs 2-1-3 z3 lz_split_blocks=8", D, Z, 3, &runs, {L0, {"lz_split_blocks", 8}}, 0, 3, 0, 0x5057be18u},
+        {"runs 2-1-3 z3 lz_split_min=2", D, Z, 3, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 2}}, 0, 2, 0, 0x1f3f0102u},
+        {"runs 2-1-3 d6 lz_split_min=2", D, F, 6, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 2}}, 0, 2, 0, 0x4303da9eu},
+        {"runs 2-1-3 z3 lz_split_min=3", D, Z, 3, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 3}}, 0, 1, 0, 0xc3579f81u},
+        {"runs 2-1-3 z3 lz_split_min=4 (all one kernel)", D, Z, 3, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 4}}, 0, 0, 0, 0x40702774u},
+        {"runs 2-1-3 z10 lz_split_min=2 (ignored)", D, Z, 10, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 2}}, 0, 3, 0, 0xad972255u},
+        {"runs 2-1-3 z3 lz_split_min=2 lz_split=2 (ignored)", D, Z, 3, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 2}, {"lz_split", 2}}, 0, 3, 0, 0x33e8d264u},
+        {"runs 2-1-3 z3 lz_split_min=2 lz_pbuf_fail", D, Z, 3, &runs, {L0, {"lz_split_blocks", 8}, {"lz_split_min", 2}, {"lz_pbuf_fail", 1}}, 0, 0, 0, 0x682fe307u},
+        {"runs evened z3 lz_split_blocks=2100", D, Z, 3, &many, {L0, {"blk_log", 17}, {"lz_split_blocks", 2100}}, 0, 3, 0, 0x35bfe524u},
+        {"runs evened d6 lz_split_blocks=2100 lz_pbuf_fail", D, F, 6, &many, {L0, {"blk_log", 17}, {"lz_split_blocks", 2100}, {"lz_pbuf_fail", 1}}, 0, 0, 0, 0x15b58b66u},
+        {"runs evened z3 lz_split_blocks=2100 small pass", D, Z, 3, &many, {L0, {"blk_log", 17}, {"lz_split_blocks", 2100}, {"lz_split", 0}}, 0, 0, 0, 0xec85229au},
+    };
+    const bool record = getenv("PNA_SAN_RECORD_LZ") != nullptr;         // print the table's last four columns instead of comparing (how the values were recorded)
+    for (const LzCase &k : cases) {
+        pna_gpu_ctx *c = nullptr;
+        CHECK(pna_gpu_init(&c, 0, k.init) == PNA_OK);
+        if (!c) return;
+        for (const LzOpt &o : k.opts) CHECK(pna_gpu_set_option(c, o.name, o.v) == PNA_OK);
+        const size_t n = k.lens->size();
+        std::vector<uint64_t> off(n), len(n), doff(n + 1); uint64_t at = 0; size_t cap = 4096;
+        for (size_t i = 0; i < n; i++) { off[i] = at; len[i] = (*k.lens)[i]; at = (at + len[i] + 15) & ~(uint64_t)15; cap += pna_gpu_bound(k.algo, (*k.lens)[i]); }
+        const Bytes src = text(at + 64, 9000); Bytes dst(cap);
+        pna::lz_rows_begin();
+        const int rc = pna_gpu_compress_batch_device(c, k.algo, k.level, n, src.data(), off.data(), len.data(), dst.data(), cap, doff.data(), nullptr);
+        std::string rows = pna::lz_rows_take();
+        if (rc) rows += std::string("error: ") + pna_gpu_last_error(c) + "\n";
+        pna_gpu_timing t; CHECK(pna_gpu_last_timing(c, &t) == PNA_OK);
+        const uint32_t crc = pna_crc32(0, rows.data(), rows.size());
+        if (record) printf("LZREC \"%s\" %d, %llu, %u, 0x%08xu\n", k.what, rc, (unsigned long long)t.lz_match_launches, t.lz_units, crc);
+        else {
+            printf("lz launches %-52s rc %d match launches %llu units %u crc %08x\n", k.what, rc, (unsigned long long)t.lz_match_launches, t.lz_units, crc);
+            if (rc != k.rc || t.lz_match_launches != k.launches || t.lz_units != k.units || crc != k.crc) {
+                fprintf(stderr, "lz launches %s: rc %d launches %llu units %u crc %08x (recorded %d %llu %u %08x); the rows:\n%s", k.what, rc, (unsigned long long)t.lz_match_launches,
+                        t.lz_units, crc, k.rc, (unsigned long long)k.launches, k.units, k.crc, rows.c_str());
+                g_fail++;
+            }
+        }
+        if (record) fputs(rows.c_str(), stdout);
+        pna_gpu_shutdown(c);
+    }
+}
+
 int main() {
+    if (getenv("PNA_SAN_RECORD_LZ")) { test_lz_launch_matrix(); return 0; }
     pna_gpu_ctx *c = nullptr;
     CHECK(pna_gpu_init(&c, 0, PNA_F_DEFAULT) == PNA_OK);
     if (!c) return 2;
@@ -591,6 +755,7 @@ int main() {
     test_failing_sink();
     test_framing_matrix();
     test_extract_matrix();
+    test_lz_launch_matrix();
     pna_gpu_shutdown(c);
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("san_driver: all checks passed\n");
