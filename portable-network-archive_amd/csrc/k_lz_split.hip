@@ -15,8 +15,9 @@ namespace pna {
 // k_lzm -- the match half of the split form: look-up, match, backward adoption and the tile's inserts, as in k_lz<MODE 1>, but with
 // FOUR CONSECUTIVE POSITIONS PER LANE (lane i of wave w: positions t0 + 256 w + 4 i + j, j = 0..3) instead of one position per lane and
 // group.  Nothing in this half needs a ballot over a group's positions, and with consecutive positions
-//   * the 36 + 4 bytes around a lane's positions are ten aligned dwords, loaded once; the 8 / 16 / 32 bytes at position j are
-//     v_alignbyte with a constant (j = 0: the registers themselves) -- k_lz loads and aligns them per position;
+//   * the 36 + 4 bytes around a lane's positions are ten aligned dwords, loaded once; the hash's bytes at position j are
+//     v_alignbyte with a constant (j = 0: the registers themselves); the default set's match step compares a candidate with the
+//     dwords as they are, shifted to the lane's alignment instead of the position's (near_match) -- k_lz loads and aligns them per position;
 //   * the right neighbours of the adoption rounds sit in the same lane, except across the lane border (DPP row_shl: a row of
 //     16 lanes is a group of 64 positions, and the zero fill at the row's end is the rule "adoption stops at the group border");
 //     the offset moves along with every adoption instead of one ds_bpermute at the end;
@@ -28,12 +29,15 @@ namespace pna {
 // moves one value per position (one DPP, one select) instead of key and offset: taking over the match of position q + s is + (s << 26) - (s << 3), and
 // "strictly longer" is a compare against the own key with everything below the length set.
 // STRONG = 2 (the high and max zstd sets, round 5: a fourth adoption round over EIGHT positions and up to 15 back bytes): the back count takes four bits, << 2 (PKB).
+// Nothing reads the bits below the back count (0 .. 2 with PKB = 3): near_match and its far_match leave what their count of leading zero BITS has there (back7_field).
 constexpr uint32_t PK_LEN = 26, PK_OFF = 6, PK_LOW = (1u << PK_LEN) - 1;
 __host__ __device__ constexpr uint32_t pkb_of(int strong) { return strong == 2 ? 2u : 3u; }
-__device__ __forceinline__ uint32_t pk_make(uint32_t l, uint32_t off, uint32_t bkf) { return (l << PK_LEN) | ((off << PK_OFF) | bkf); }   // bkf: back << PKB
+__device__ __forceinline__ uint32_t pk_make(uint32_t l, uint32_t off, uint32_t bkf) { return (l << PK_LEN) + ((off << PK_OFF) | bkf); }   // bkf: back << PKB.  (+, not |: offset and back stay below 2^26, and the sum is v_lshl_or + v_lshl_add wherever the key is made -- as an OR of three the compiler chose between that and two shifts + v_or3 from build to build)
 template <uint32_t S, uint32_t PKB = 3>
 __device__ __forceinline__ uint32_t pk_adopt(uint32_t P, uint32_t Pn) {            // Pn: the key of position q + S
     constexpr uint32_t BM = PKB == 2 ? 0x3Cu : 0x38u;
+    static_assert((BM & ((1u << PKB) - 1)) == 0 && ((S << PKB) & ((1u << PKB) - 1)) == 0 && (PK_LOW >> PK_OFF) != 0 && PKB < PK_OFF,
+                  "adoption neither tests nor changes the key's bits below the back count: back7_field leaves a count's bit part there");
     const uint32_t T = Pn + ((S << PK_LEN) - (S << PKB));
     const bool a = (Pn & (BM & ~((S - 1) << PKB))) != 0 && T > (P | PK_LOW);        // back >= S (S = 1, 2, 4, 8: a test of the upper back bits)
     return a ? T : P;
@@ -48,6 +52,14 @@ __device__ __forceinline__ uint32_t back15_field(uint32_t x1, uint32_t x2, uint3
     asm("v_min3_u32 %0, %1, %2, %3" : "=v"(n) : "v"(f2), "v"(f3), "v"(f4));
     asm("v_min_u32 %0, %1, %2" : "=v"(m) : "v"(f1), "v"(n));
     return (m >> 1) & 0x3Cu;
+}
+// back << 3 for up to 7 back bytes, WITH THE COUNT'S BIT PART BELOW IT (at most 56: the lowest byte of x2 differs): the bits 0 .. 2 of a key with PKB = 3 are nobody's -- pk_adopt
+// tests and moves the bits 3 .. 5 and compares above PK_LOW, the words take length and offset --, so they are not cleared.  x1, x2 = position XOR candidate of the two dwords before them, nearest first, the lowest byte of x2 (the eighth back, never counted) forced
+// to differ by the caller: the leading zero bits of the 64 as the minimum of two counts -- v_ffbh_u32 yields 0xFFFFFFFF for x1 == 0, the saturating add keeps it there --,
+// their byte part.  (As `x1 ? clz(x1) & 24 : 32 + (clz(x2) & 24)`: an OR, two masks, a compare and a select more per position.)
+__device__ __forceinline__ uint32_t back7_field(uint32_t x1, uint32_t x2) {
+    const uint32_t f1 = ffbh_hw(x1), f2 = __builtin_elementwise_add_sat(ffbh_hw(x2), 32u);
+    return f1 < f2 ? f1 : f2;
 }
 // GLOG != 0: the hash table of this workgroup lies in GLOBAL memory, 1 << GLOG slots (gtab + blockIdx.x << GLOG): the zstd levels 10 .. 22.  What a
 // 1 MiB segment's match finder can remember is what sets the ratio on text (24 512 slots in LDS 2.70, 2^19 slots 2.96), and LDS
@@ -88,7 +100,7 @@ __device__ __forceinline__ void far_pull(const bool (&farj)[4], const uint32_t (
     }
 }
 // the match step of position q against those bytes: the packed key (pk_make) with the offset so, exactly as for a candidate inside the window
-template <int STRONG, uint32_t WB>
+template <int STRONG, uint32_t WB, bool B7>   // B7: the seven back bytes by back7_field (the instances that run near_match)
 __device__ __forceinline__ uint32_t far_match(const uint32_t *win32, uint32_t q, uint32_t so, v4u fa, uint32_t fb, v4u fd, uint32_t fc, v2u fe, bool edge, uint32_t blk_end) {
     // the position's bytes q - 8 .. q + 36 from ONE base address (the dword that holds q - 8; what lies behind the window's end is its mirror):
     // pq[0] = q - 8 .., pq[1] = q - 4 .., pq[2 ..] = q ..
@@ -107,7 +119,8 @@ __device__ __forceinline__ uint32_t far_match(const uint32_t *win32, uint32_t q,
     if (edge) { const uint32_t lim = blk_end - q; l = l < lim ? l : lim; }
     const uint32_t xk = EW(0) ^ fa.x;
     uint32_t bk3 = (uint32_t)__builtin_clz(xk | 0xFFu) & 24u;                      // back << 3
-    if (STRONG == 1 && xk == 0) bk3 = 32u + ((uint32_t)__builtin_clz((__builtin_amdgcn_alignbit(E[0], pq[0], shq) ^ fc) | 0xFFu) & 24u);
+    if (STRONG == 1 && !B7 && xk == 0) bk3 = 32u + ((uint32_t)__builtin_clz((__builtin_amdgcn_alignbit(E[0], pq[0], shq) ^ fc) | 0xFFu) & 24u);
+    if (STRONG == 1 && B7) bk3 = back7_field(xk, (__builtin_amdgcn_alignbit(E[0], pq[0], shq) ^ fc) | 0xFFu);   // (and bits below it)
     if (STRONG == 2) {
         lds_cu32 *pe = lds_word(L_WIN + ((q - 16) & (WB - 4)));                      // the dwords of q - 16 and q - 12 (pq[0] holds q - 8)
         const uint32_t e0 = pe[0], e1 = pe[1], p0 = pq[0];
@@ -115,6 +128,58 @@ __device__ __forceinline__ uint32_t far_match(const uint32_t *win32, uint32_t q,
     }
 #undef EW
     return STRONG ? (l >= MIN_MATCH ? pk_make(l, so, bk3) : 0u) : pk_make(l >= MIN_MATCH ? l : 0u, so, bk3);
+}
+// first_diff16 from byte j of x0 on and counted from there: min(16, first differing byte) - j (the shift and the constants of the saturating adds carry the - j)
+__device__ __forceinline__ uint32_t first_diff16_from(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t j) {
+    const uint32_t b = 8u * j;
+    const uint32_t f0 = ffbl_hw(x0 >> b), f1 = __builtin_elementwise_add_sat(ffbl_hw(x1), 32u - b), f2 = __builtin_elementwise_add_sat(ffbl_hw(x2), 64u - b),
+                   f3 = __builtin_elementwise_add_sat(ffbl_hw(x3), 96u - b);
+    uint32_t n, m;
+    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(n) : "v"(f2), "v"(f3), "s"(128u - b));
+    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(m) : "v"(f0), "v"(f1), "v"(n));
+    return m >> 3;
+}
+// ---- near_match: the match step of a candidate inside the window, IN THE LANE'S OWN ALIGNMENT -- position q = q0 + j of a lane against c = q - o.  The form of k_lzm's
+// instances of the default set (the packed table with STRONG = 1, LANE_ALIGNED in the kernel); every other instance and k_lzms keep the step that aligns the candidate to c
+// and shifts the position's dwords by j, which they were measured or left with (LAB_LOG.md 6.3).
+// q0 is a multiple of 4 and the lane holds its bytes as aligned dwords (D[k] = bytes q0 + 4 k .. + 3, Dm1 / Dm2 the dwords before q0), so only the candidate's side is
+// funnel-shifted -- to a = q0 - o, not to c --, and ONE XOR stream serves the position: with A[k] = bytes a + 4 k .. + 3 and X[k] = D[k] ^ A[k], byte x of X is zero
+// exactly where S[q0 + x] == S[a + x], that is where S[q + (x - j)] == S[c + (x - j)].  Hence
+//   length  = min(CAP1, F - j), F = the first x >= j whose byte of X differs: first_diff16_from on X[0 .. 3], the second 16 bytes X[4 .. 7] where those found nothing, and
+//             for j > 0 the low j bytes of X[8] where those found nothing either (stream bytes 32 .. 31 + j; the position's are in D[8]);
+//   clamp   = the block's end, on the length as in the other form;
+//   back    = the equal bytes below x = j, read downwards: the four before q are alignbyte(X[0], X[-1], j), the four before them alignbyte(X[-1], X[-2], j) (back7_field).
+// The second 16 bytes are a wave-uniform branch and the ninth dword a branch inside it, as in the other form, but the second half's four LDS dwords are requested together
+// with the first half's: on text some lane of nearly every wave and position takes the branch, and its LDS round trip behind the first half's costs more than the reads.
+// ab: LDS byte address of the dword that holds a - 8 (the reads reach ab + 44, behind the window's end its mirror), sha: 8 (a & 3) or anything congruent modulo 32.
+// A candidate lies at 8 or beyond, so a - 8 is >= - 3: the base is then the window's last dword, the segment's first bytes come from the mirror, and what lies in front of
+// them is read, never used.
+__device__ __forceinline__ uint32_t near_match(uint32_t ab, uint32_t sha, const uint32_t (&D)[9], uint32_t Dm1, uint32_t Dm2, uint32_t j, uint32_t o, uint32_t q, bool edge, uint32_t blk_end) {
+    // pc[0] = a - 8 .., pc[1] = a - 4 .., pc[2 .. 6] the first 16 (+ 4) bytes, pc[6 .. 10] the second, pc[11] with pc[10] the j after them
+    lds_cu32 *pc = lds_word(ab);
+    const uint32_t dm = pc[1], d0 = pc[2], d1 = pc[3], d2 = pc[4], d3 = pc[5], d4 = pc[6];
+    uint32_t f1 = pc[7], f2 = pc[8], f3 = pc[9], f4 = pc[10];                       // the second half's dwords, requested WITH the first's
+    const uint32_t x0 = D[0] ^ __builtin_amdgcn_alignbit(d1, d0, sha), x1 = D[1] ^ __builtin_amdgcn_alignbit(d2, d1, sha);
+    const uint32_t x2 = D[2] ^ __builtin_amdgcn_alignbit(d3, d2, sha), x3 = D[3] ^ __builtin_amdgcn_alignbit(d4, d3, sha);
+    const uint32_t xm1 = Dm1 ^ __builtin_amdgcn_alignbit(d0, dm, sha), xm2 = Dm2 ^ __builtin_amdgcn_alignbit(dm, pc[0], sha);
+    uint32_t l = first_diff16_from(x0, x1, x2, x3, j);
+    asm volatile("" : "+v"(f1), "+v"(f2), "+v"(f3), "+v"(f4));                      // (keeps the four reads in front of the branch: the compiler sinks them into it otherwise)
+    if (l == 16u - j) {
+        const uint32_t y0 = D[4] ^ __builtin_amdgcn_alignbit(f1, d4, sha), y1 = D[5] ^ __builtin_amdgcn_alignbit(f2, f1, sha);
+        const uint32_t y2 = D[6] ^ __builtin_amdgcn_alignbit(f3, f2, sha), y3 = D[7] ^ __builtin_amdgcn_alignbit(f4, f3, sha);
+        l += first_diff16(y0, y1, y2, y3);
+        if (j != 0 && l == CAP1 - j) {                                              // the last j bytes of the 32 lie in the ninth dword
+            const uint32_t t = ffbl_hw(D[8] ^ __builtin_amdgcn_alignbit(pc[11], f4, sha)) >> 3;     // (no difference at all: 0x1FFFFFFF)
+            l += t < j ? t : j;
+        }
+    }
+    if (edge) { const uint32_t lim = blk_end - q; l = l < lim ? l : lim; }
+    const uint32_t xk = j ? __builtin_amdgcn_alignbyte(x0, xm1, j) : xm1;          // position XOR candidate of the 4 bytes before them (q - 1 in the top byte)
+    // (the eighth byte back is never counted: byte j of X[-2], forced to differ BEFORE the shift, where the OR joins the XOR in one v_bitop3)
+    const uint32_t xf = xm2 | (0xFFu << (8u * j));
+    const uint32_t bk3 = back7_field(xk, j ? __builtin_amdgcn_alignbyte(xm1, xf, j) : xf);          // back << 3 and bits below it
+    // (a length below MIN_MATCH drops the whole key -- 0 + 1 + 2 + 4 adopted bytes would be a match)
+    return l >= MIN_MATCH ? pk_make(l, o, bk3) : 0u;
 }
 
 // the inserts of a lane's four positions (k_lzm): behind the tile's look-ups, with sub-tiles behind the sub-tile's
@@ -142,6 +207,7 @@ __global__ __launch_bounds__(LZ_THREADS)
 void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, uint32_t flags, uint32_t max_off, uint32_t *__restrict__ pbuf, uint32_t blk0,
            uint32_t *__restrict__ gtab) {
     constexpr uint32_t RW = 256, TILE_G = RW * LZ_WAVES, PKB = pkb_of(STRONG), MIN_C = STRONG == 2 ? 16u : 8u;   // MIN_C: a usable candidate lies at this position or beyond (its back bytes exist)
+    constexpr bool LANE_ALIGNED = TAB3 && STRONG == 1;     // the default set's instances: the match step in the lane's alignment (near_match)
     constexpr bool FAR = !DEFL && FARP;                     // deflate offsets (<= 32 KiB) never leave the LDS window; FARP = false: a zstd launch whose look-back ends with the window (the fast set)
     using GEO = LzGeo<WLOG, TAB3>;                          // (lz_common.h) these names hide the 64 KiB geometry's constants of pna_dev.h
     constexpr uint32_t WIN_BYTES = GEO::WIN, HASH_ENTRIES = GEO::ENTRIES, L_TABLE = GEO::L_TABLE, NW3 = GEO::WORDS3;
@@ -155,7 +221,7 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
     static_assert(WIN_BYTES >= TILE_G + LA + NEAR + 8 + 200 && (!DEFL || NEAR >= 32768), "window: look-back (+ 8 back bytes) + this tile + look-ahead");
     static_assert(!TAB3 || (GLOG == 0 && !DEFL && FAR), "the packed table: zstd sets with the table in LDS and far candidates");
     static_assert(!SUBTILE || GLOG == 0, "sub-tiles: the table in LDS (a workgroup barrier orders its inserts and look-ups)");
-    static_assert(LZ_G_ZSTD == 4 && LZ_G_DEFLATE == 4 && WIN_MIRROR >= 40, "k_lzm: four positions per lane, 36 bytes read behind a lane's first position");
+    static_assert(LZ_G_ZSTD == 4 && LZ_G_DEFLATE == 4 && WIN_MIRROR >= 48, "k_lzm: four positions per lane; near_match reads the dwords base .. base + 44, the other form of the match step base .. base + 40");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint32_t *win32 = (uint32_t *)(lds + L_WIN);
     uint32_t *table = GLOG ? gtab + ((size_t)blockIdx.x << GLOG) : (uint32_t *)(lds + L_TABLE);
@@ -320,7 +386,9 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
             for (int j = 0; j < 4; j++) {
                 const uint32_t o = off[j], q = q0 + j;
                 uint32_t Pj = 0;
-                if (nearj[j]) {
+                if constexpr (LANE_ALIGNED) {
+                    if (nearj[j]) Pj = near_match(L_WIN + ((q0 - 8 - o) & (WIN_BYTES - 4)), (q0 - 8 - o) << 3, D, Dm1, Dm2, (uint32_t)j, o, q, edge, blk_end);   // a - 8, a = q0 - o
+                } else if (nearj[j]) {
                     uint32_t l, bk3;
                     // the candidate's bytes c - 8 .. c + 36 from ONE base address (the dword of c - 8; the mirror behind the window's end covers the base + 44):
                     // pc[0] = c - 8 .., pc[1] = c - 4 .., pc[2 .. 6] the first 16 (+ 4) bytes, pc[6 .. 10] the second
@@ -362,7 +430,7 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
             if (FAR && npair) {
                 {
                     uint32_t Kf = 0;
-                    if (slot0) Kf = far_match<STRONG, WIN_BYTES>(win32, sq, so, ffa, ffb, ffd, ffc, ffe, edge, blk_end);
+                    if (slot0) Kf = far_match<STRONG, WIN_BYTES, LANE_ALIGNED>(win32, sq, so, ffa, ffb, ffd, ffc, ffe, edge, blk_end);
                     far_pull(farj, idx, 0u, Kf, P);
                 }
                 if (!(flags & FLAG_FAR1))                                               // (uniform; FLAG_FAR1, the default and light sets since round 5: the pairs beyond the first 63 are dropped -- - 0.16 % of ratio, - 6 % of the kernel's time)
@@ -372,7 +440,7 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
                     if (lane < 63u && lane < npair - r0) {
                         v4u ga, gd; uint32_t gb, gc; v2u ge;
                         far_load<true, STRONG>(seg, sq2 - so2, ga, gb, gd, gc, ge);
-                        Kf = far_match<STRONG, WIN_BYTES>(win32, sq2, so2, ga, gb, gd, gc, ge, edge, blk_end);
+                        Kf = far_match<STRONG, WIN_BYTES, LANE_ALIGNED>(win32, sq2, so2, ga, gb, gd, gc, ge, edge, blk_end);
                     }
                     far_pull(farj, idx, r0, Kf, P);
                 }
@@ -422,7 +490,7 @@ void k_lzm(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, ui
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         const uint32_t l = P[j] >> PK_LEN, lc = l < 5u ? 5u : (l > 36u ? 36u : l);   // (v_med3_u32: lengths below MIN_MATCH are strays of the adoption, nobody's match)
-                        ww[j] = (lc - 5u) | ((P[j] >> (PK_OFF - 5)) & (0xFFFFFu << 5));
+                        ww[j] = (lc - 5u) | ((P[j] >> (PK_OFF - 5)) & (0xFFFFFu << 5));         // (the offset's bits alone: nothing below PK_OFF reaches a word)
                     }
                     W12 *o = (W12 *)(pb8 + 3 * (size_t)q0);                              // (q0 is a multiple of 4: the 12 bytes are dword-aligned)
                     __builtin_nontemporal_store(__builtin_amdgcn_perm(ww[1], ww[0], 0x04020100u), &o->x);   // bytes 0 1 2 of word 0, byte 0 of word 1

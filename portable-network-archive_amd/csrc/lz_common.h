@@ -14,7 +14,7 @@ constexpr uint32_t TAG_BITS = 11, TAG_MASK = (1u << TAG_BITS) - 1;
 
 // LDS layout (byte offsets into the dynamic shared array)
 constexpr uint32_t L_WIN    = 0;
-constexpr uint32_t WIN_MIRROR = 48;                        // the window's first 48 bytes again behind its end: unaligned reads never wrap (k_lz reads 16 past a position, k_lzm 36 past a lane's first)
+constexpr uint32_t WIN_MIRROR = 48;                        // the window's first 48 bytes again behind its end: reads never wrap (k_lz reads 16 past a position; k_lzm's match step reads the twelve dwords base .. base + 44 from the dword of a - 8, a = q0 - o up to 3 below the candidate, and for a - 8 < 0 -- a candidate at 8 .. 10 -- the base is the window's last dword and the segment's first bytes come from here)
 // Two geometries share the CU's 160 KiB (WLOG = log2 of the window): 64 KiB window + 24 512-slot table (deflate, whose 32 KiB look-back must lie in
 // the window; the zstd sets without far candidates, whose look-back IS the window), and 32 KiB window + 32 704-slot table (the zstd sets with far
 // candidates: a third more slots are worth +1.6 % of ratio on text, and what the window no longer holds -- candidates more than NEAR bytes back -- is
