@@ -682,19 +682,26 @@ void k_lzms(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, u
 // k_lzp -- the parse half of the split form with one LANE per parse region.  What a whole wave does in k_lz with scalar loops on
 // ballot masks (an SALU instruction takes an issue slot like a vector one), sixteen lanes do here with vector arithmetic for the
 // sixteen regions of a tile at once.  One wave (= one workgroup: no barriers, 8.4 KiB of LDS) per segment; per tile of 4 096 positions:
-//   1. the tile's words (k_lzm's output), 4 consecutive positions per lane and 16-byte load -> their lengths, a byte each, to LDS;
+//   1. the tile's words (k_lzm's output), 4 consecutive positions per lane and load, all sixteen regions' loads in one round -> their lengths, a byte each, to LDS;
 //      then one lane per GROUP of 64 positions: start / cap masks of the group from its 64 length bytes, four at a time inside a
 //      register (byte-wise compares by carry-free subtraction, the four results gathered into a nibble by one multiplication)
 //   2. lanes 0..15: greedy walk over the region's eight half-groups on 32-bit masks (length of a chosen start from LDS; a capped
 //      match is extended by the whole wave, the lengths are kept in LDS), merge across the regions = across the lanes (serial
 //      form of the scan, DPP row scans for the counts), selection / literal masks, one record per group to LDS
-//   3. one lane per group again: the group's sequences (offsets from the words in memory, four requested at a time)
+//   3. one lane per group again: the group's sequences (offsets from the words in memory, eight requested at a time)
 //   4. the literals, 4 consecutive positions per lane (their input bytes were requested from memory before step 3): the lane's
 //      literal bytes are packed by v_perm (selector from a 16-entry table) and stored behind the literals of the positions before it.
 // Same results as k_lz<MODE = 2> (and so as the fused kernel): tests/test_gpu_parity.py runs all three.
 constexpr uint32_t LZP_THREADS = 64;
+constexpr uint32_t LZP_TURN = 8;                        // step 3: starts of a group whose words are requested together
+// names a turn's words as read and written HERE, in one statement: the loads into them are waited for at this point, once, and nothing that uses them moves
+// in front of it (near_match pins its LDS reads the same way)
+__device__ __forceinline__ void pin_regs(uint32_t (&a)[LZP_TURN]) {
+    static_assert(LZP_TURN == 8, "pin_regs: one operand per word of a turn");
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
+}
 template <bool CT, int LZD, bool W3>   // W3: the words take three bytes (k_lzm); LZD: how many positions ahead a start looks before it is taken (lazy deferral: 1, 2 or 3; without F_LAZY none)
-__global__ __launch_bounds__(LZP_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5)))   // (88 registers: 5 waves per SIMD; asked for 6 / 7 the allocator spills 4 / 9 registers and the kernel is no faster / 2 % slower)
+__global__ __launch_bounds__(LZP_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5)))   // (96 registers: 5 waves per SIMD; asked for 6 / 7 the allocator spills 4 / 9 registers and the kernel is no faster / 2 % slower)
 void k_lzp(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, const uint32_t *__restrict__ blk_seg, uint64_t *__restrict__ seqs, uint8_t *__restrict__ lits,
            BlkInfo *__restrict__ blk, uint4 *__restrict__ ctab, uint32_t flags, uint32_t max_len, const uint32_t *__restrict__ pbuf, uint32_t blk0, uint32_t *__restrict__ hist) {
     constexpr uint32_t RW = 256, TG = 4096;
@@ -764,13 +771,19 @@ void k_lzp(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, co
         {
             const uint4 *pt = (const uint4 *)(pb + t0);
             const W12 *pt3 = (const W12 *)(pb8 + 3 * (size_t)t0);
-            for (uint32_t wq = 0; wq < 4 && wq * 1024 < npos; wq++) {                   // four regions at a time: their loads go out together
-                uint4 v[4]; W12 v3[4];
+            // ONE load round per tile: the sixteen regions' loads go out together and are waited for one after the other (vmcnt 15 .. 0) -- in rounds of four they were four
+            // dependent round trips for addresses that are all known here.  A partial tile's loads go out all the same (see above: inside pbuf; what they bring is masked
+            // below).  The four-byte words take two rounds of eight, 32 registers in flight instead of 64; the second is skipped where the tile ends before it.
+            constexpr uint32_t NR = W3 ? 16u : 8u;
 #pragma unroll
-                for (uint32_t i = 0; i < 4; i++) { if (W3) v3[i] = pt3[(wq * 4 + i) * 64 + lane]; else v[i] = pt[(wq * 4 + i) * 64 + lane]; }
+            for (uint32_t r0 = 0; r0 < 16; r0 += NR) {
+                if (r0 * RW >= npos) continue;                                          // (uniform)
+                uint4 v[NR]; W12 v3[NR];
 #pragma unroll
-                for (uint32_t i = 0; i < 4; i++) {
-                    const uint32_t p = (wq * 4 + i) * RW + lane * 4;
+                for (uint32_t i = 0; i < NR; i++) { if (W3) v3[i] = pt3[(r0 + i) * 64 + lane]; else v[i] = pt[(r0 + i) * 64 + lane]; }
+#pragma unroll
+                for (uint32_t i = 0; i < NR; i++) {
+                    const uint32_t p = (r0 + i) * RW + lane * 4;
                     uint32_t d;
                     if (W3) {
                         // the four 5-bit fields (bytes 0, 3, 6, 9 of the lane's 12) as bytes; length = field + 5 where the field is not 0
@@ -1046,17 +1059,22 @@ void k_lzp(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, co
             const uint32_t cut_b2 = rc.z & 0xFFu, cut_l2 = rc.z >> 8;
             bool first = true;
             const uint32_t pg0 = t0 + lane * 64;
-            while (rem) {
-                // four starts at a time: their words (the offsets) are requested together
-                uint32_t sq[4], pw[4];
+            // LZP_TURN starts at a time: their words (the offsets) are requested TOGETHER and waited for once, in front of the turn's first store.  The loads are
+            // unconditional -- a slot without a start reads its group's first word, inside the tile's words --: a load under `rem ? .. : 0` is a load under a branch,
+            // which the compiler waits for inside the branch, three dependent round trips a turn.  Eight, not four: text has 4.1 chosen starts per group, and the
+            // turns a wave takes are those of its busiest group -- at four that was two turns on most tiles, at eight it is one (LAB_LOG.md 6.4).
+            // do .. while: every lane takes the first turn, so its wait -- for loads younger than lw[]'s, on a counter that is in order -- stands on every path to
+            // step 4, where no store of this tile is outstanding yet.  Behind `while (rem)`, which a wave without a start skips, the compiler had to wait for lw[]
+            // at its first use in each chunk of literals, and could only wait for everything: the sequence and literal stores' acknowledgements included.
+            do {
+                uint32_t sq[LZP_TURN], pw[LZP_TURN];
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    sq[u] = rem ? ctz64(rem) : 64u;
-                    pw[u] = rem ? word_at(pg0 + sq[u]) : 0u;
-                    rem &= rem - 1;                                                 // (0 stays 0)
-                }
+                for (int u = 0; u < (int)LZP_TURN; u++) { sq[u] = rem ? ctz64(rem) : 64u; rem &= rem - 1; }   // (0 stays 0)
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
+                for (int u = 0; u < (int)LZP_TURN; u++) pw[u] = word_at(pg0 + (sq[u] & 63u));
+                pin_regs(pw);
+#pragma unroll
+                for (int u = 0; u < (int)LZP_TURN; u++) {
                     const uint32_t s = sq[u];
                     if (s < 64) {
                         uint32_t ml = pw[u] & 63u, of = pw[u] >> 6;
@@ -1075,7 +1093,7 @@ void k_lzp(const uint8_t *__restrict__ src, const SegDesc *__restrict__ segs, co
                         idx++; prev = lq; first = false;
                     }
                 }
-            }
+            } while (rem);                                                          // (a group with more than LZP_TURN starts)
         }
         if (hist && t1 == blk_end) {                            // (uniform) the block's counters go to its segment's
             __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory");
