@@ -34,6 +34,14 @@ int  pna_archive_add_file(pna_archive *a, const char *name, int compression, int
                           const void *payload, size_t payload_len, uint32_t max_chunk_size);
 /* Directory entry: FHED(kind 1, store) FEND, no fSIZ/FDAT (lib/src/entry/builder/dir.rs:52-54). */
 int  pna_archive_add_dir(pna_archive *a, const char *name);
+/* The whole record of an entry that is not a file, as raw chunk bytes: kind 1 directory (FHED FEND), 2 symbolic link, 3 hard link
+ * (FHED FDAT* FEND: the target stored, never encrypted -- new_link, lib/src/entry/builder.rs:341-349 -- and cut into chunks of at most
+ * max_chunk_size bytes, 0 = u32::MAX).  No fSIZ (builder.rs:630-632).  `extra` and `facets` are chunks the caller has already framed;
+ * they follow FHED in that order (NormalEntry::write_chunks_to, lib/src/entry.rs:895-911).  The name is sanitised like a file's.
+ * Returns the number of bytes written to dst (cap checked), the required size when dst is NULL, or 0 for a kind outside 1 .. 3 and a
+ * link without a target.  pna_archive_add_dir and the pna_gpu_create_*_tree_* entry points write exactly these bytes. */
+size_t pna_archive_entry_record_bytes(int kind, const char *name, const void *extra, size_t extra_len, const void *facets, size_t facets_len,
+                                      const void *target, size_t target_len, uint32_t max_chunk_size, void *dst, size_t cap);
 /* Solid entry from an already compressed stream: SHED SDAT* SEND; each piece becomes one SDAT chunk. */
 int  pna_archive_add_solid(pna_archive *a, int compression, const void *const *pieces, const size_t *piece_len, size_t n_pieces);
 /* Serialise one inner STORE entry (FHED fSIZ FDAT FEND as raw chunk bytes) -- what SolidArchive::add_entry feeds

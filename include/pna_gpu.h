@@ -288,6 +288,53 @@ int  pna_gpu_create_archive_chunked_device(pna_gpu_ctx *ctx, int algo, int level
 int  pna_gpu_create_archive_chunked_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
                                          const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
                                          const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, uint32_t part_flags, pna_sink_fn sink, void *user);
+/* ENTRY KINDS: `pna create some/tree` in ONE call.  create_entry (cli/src/command/core.rs:915-977) has four arms and writes them in walk order: a hard link
+ * (HardLinkEntryBuilder::new, core.rs:938-943), a symbolic link (SymlinkEntryBuilder::new, core.rs:945-955), a directory (DirEntryBuilder, EntryHeader::for_dir; kept by
+ * default, --keep-dir) and files, everything else.  The pna_gpu_create_*_tree_* entry points take the arms as kind[i] next to entry i; they are their counterparts'
+ * parameter lists plus `kinds` (and cipher, meta and max_chunk_size where the counterpart has none).
+ *   directory   FHED(kind 1, compression 0, encryption 0, cipher_mode 0) | extra[i] | facets[i] | FEND -- no fSIZ, no PHSF, no FDAT: what pna_archive_add_dir writes.
+ *   links       FHED(kind 2 / 3, 0, 0, 0) | extra[i] | facets[i] | FDAT(target)* | FEND.  No fSIZ: only DataKind::FILE records one (lib/src/entry/builder.rs:630-632).
+ *               The target is STORED and NOT ENCRYPTED even when the call has a cipher: new_link takes WriteOptions::store() (builder.rs:341-349), which is what
+ *               core.rs:938,948 call; max_chunk_size cuts it as FlattenWriter cuts any stream (lib/src/util/io.rs:60-77).
+ *   names       sanitised exactly as file names are.  The host still does read_link and gathers the metadata facets; it passes them in `link` and `meta`.
+ * For an entry that is not a file src_len[i] must be 0 (PNA_E_INVAL otherwise) and its source pointer / offset is ignored; an unknown kind, an empty link target and
+ * link == NULL with a link kind present are PNA_E_INVAL (pna_gpu_entry_kinds_check: the same checks without a context).  kinds == NULL or kinds->kind == NULL: the
+ * counterpart's bytes, byte for byte.  entry_off[i] is filled for every entry.  cipher->ivs stays indexed by entry i: the slots of entries that are not files are
+ * unused (nothing of them reaches the archive; no cipher unit or stream key is made for such an entry).  In a solid stream the same records stand between the file records -- every inner entry
+ * there is a stored record already; the solid tree forms also place the files' meta chunks and cut the files' data at max_chunk_size.  Such an entry has no
+ * segment: a sub-batch of directories and links alone launches no codec, write or framing kernel (its records travel in one copy).
+ * Not covered: pna_gpu_create_archive_multi_host, pna_gpu_append_archive_host (append is reachable through part_flags) and the pna_gpu_stream_entry_* writer. */
+#define PNA_KIND_FILE 0         /* == DataKind::to_byte() */
+#define PNA_KIND_DIRECTORY 1
+#define PNA_KIND_SYMLINK 2
+#define PNA_KIND_HARDLINK 3
+typedef struct {
+    const uint8_t *kind;            /* n bytes; NULL: all files */
+    const void *const *link;        /* HOST memory: target bytes of entry i (kinds 2, 3), else ignored */
+    const size_t *link_len;
+} pna_gpu_entry_kinds;
+int  pna_gpu_entry_kinds_check(size_t n, const uint64_t *src_len, const pna_gpu_entry_kinds *kinds);
+/* pna_gpu_archive_chunked_bound + the meta blobs' lengths + the links' targets and their chunk framing */
+size_t pna_gpu_archive_tree_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_cipher *cipher,
+                                  const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds);
+int  pna_gpu_create_archive_tree_device(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
+                                        const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                                        const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds,
+                                        void *d_dst, size_t dst_cap, uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream);
+int  pna_gpu_create_archive_tree_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
+                                      const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                      const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds, uint32_t part_flags, pna_sink_fn sink, void *user);
+/* The solid forms (pna_gpu_create_solid_archive_enc_device / _host below, and pna_gpu_solid_archive_enc_bound). */
+size_t pna_gpu_solid_archive_tree_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_cipher *cipher,
+                                        const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds);
+int  pna_gpu_create_solid_archive_tree_device(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
+                                              const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                                              const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds,
+                                              void *d_dst, size_t dst_cap, uint64_t *archive_len, void *hip_stream);
+int  pna_gpu_create_solid_archive_tree_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
+                                            const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                            const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds,
+                                            pna_sink_fn sink, void *user);
 /* pna_gpu_create_archive_host (bounded in-flight window from host memory) with the cipher stage. */
 int  pna_gpu_create_archive_enc_host(pna_gpu_ctx *ctx, int algo, int level, size_t n, const char *const *names,
                                      const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,

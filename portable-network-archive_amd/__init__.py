@@ -79,6 +79,53 @@ class MetaStruct(ctypes.Structure):
                 ("facets", ctypes.POINTER(ctypes.c_void_p)), ("facets_len", ctypes.POINTER(ctypes.c_size_t))]
 
 
+KIND_FILE, KIND_DIRECTORY, KIND_SYMLINK, KIND_HARDLINK = 0, 1, 2, 3      # DataKind::to_byte(): the kinds of the create_archive_tree* entry points
+
+
+class KindsStruct(ctypes.Structure):
+    """pna_gpu_entry_kinds (include/pna_gpu.h)."""
+    _fields_ = [("kind", ctypes.POINTER(ctypes.c_uint8)), ("link", ctypes.POINTER(ctypes.c_void_p)), ("link_len", ctypes.POINTER(ctypes.c_size_t))]
+
+
+def _kinds_struct(n: int, kinds, links):
+    """(KindsStruct or None, what must stay alive): kinds None = all files; links None = the struct's link arrays stay NULL."""
+    if kinds is None:
+        return None, []
+    ks = KindsStruct()
+    a_kind = (ctypes.c_uint8 * max(n, 1))(*[int(k) for k in kinds])
+    keep = [a_kind]
+    ks.kind = ctypes.cast(a_kind, ctypes.POINTER(ctypes.c_uint8))
+    if links is not None:
+        bb = [bytes(b) if b is not None else b"" for b in links]
+        arr = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) if b else None for b in bb])
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in bb])
+        keep += [bb, arr, lens]
+        ks.link = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
+        ks.link_len = ctypes.cast(lens, ctypes.POINTER(ctypes.c_size_t))
+    return ks, keep
+
+
+def _meta_struct(n: int, extra, facets):
+    """(MetaStruct or None, what must stay alive) from per-entry blobs of framed chunks (None: no such blobs)."""
+    if extra is None and facets is None:
+        return None, []
+    ms = MetaStruct()
+    keep = []
+    for field, blobs in (("extra", extra), ("facets", facets)):
+        if blobs is None:
+            continue
+        bb = [bytes(b) if b is not None else b"" for b in blobs]
+        arr = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) if b else None for b in bb])
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in bb])
+        keep += [bb, arr, lens]
+        setattr(ms, field, ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)))
+        setattr(ms, field + "_len", ctypes.cast(lens, ctypes.POINTER(ctypes.c_size_t)))
+    return ms, keep
+
+
+_TREE_BOUND_ARGS = [ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+
+
 class Cipher:
     """What WriteCipher carries (lib/src/entry/write.rs:54-57): algorithm, mode, the derived key, the PHSF string; plus the
     per-entry IVs (None = drawn by the library like random::random_vec)."""
@@ -211,6 +258,9 @@ EXPORTS = [
     "pna_gpu_extract_select_host", "pna_extract_plan_runs", "pna_gpu_debug_extract_stats", "pna_gpu_debug_pick_device",
     # key derivation on the device (include/pna_gpu.h)
     "pna_gpu_kdf_batch", "pna_phsf_parse", "pna_gpu_debug_kdf_stats",
+    # entry kinds: directories, symbolic links, hard links in the create calls (include/pna_gpu.h, include/pna_archive.h)
+    "pna_gpu_entry_kinds_check", "pna_gpu_archive_tree_bound", "pna_gpu_create_archive_tree_device", "pna_gpu_create_archive_tree_host",
+    "pna_gpu_solid_archive_tree_bound", "pna_gpu_create_solid_archive_tree_device", "pna_gpu_create_solid_archive_tree_host", "pna_archive_entry_record_bytes",
 ]
 
 
@@ -633,6 +683,34 @@ class Context:
                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
         self._check(f(self._h, algo, level, n, a_names, ctypes.c_void_p(d_src), a_off, a_len, ctypes.byref(cs) if cs is not None else None, None,
                       max_chunk_size, ctypes.c_void_p(d_dst), dst_cap, a_out, ctypes.byref(total), part, None))
+        return total.value, list(a_out)
+
+    def create_archive_tree_device(self, names: Sequence[str], d_src: int, src_off: Sequence[int], src_len: Sequence[int], d_dst: int, dst_cap: int,
+                                   kinds=None, links=None, algo: int = ALGO_ZSTD, level: int = LEVEL_DEFAULT, cipher: Optional[Cipher] = None,
+                                   facets=None, extra=None, max_chunk_size: int = 0, solid: bool = False, part: int = PART_HEAD | PART_TAIL):
+        """pna_gpu_create_archive_tree_device / pna_gpu_create_solid_archive_tree_device: the archive in HBM with directories (KIND_DIRECTORY), symbolic
+        links and hard links (KIND_SYMLINK, KIND_HARDLINK: links[i] = the target's bytes) between the files, in the order given.  An entry that is not a
+        file has src_len[i] == 0.  Returns (archive_len, entry_off); entry_off is None for a solid archive."""
+        n = len(src_len)
+        a_names = (ctypes.c_char_p * max(n, 1))(*[s.encode() for s in names])
+        a_off = (ctypes.c_uint64 * (n + 1))(*(list(src_off)[:n] + [0]))
+        a_len = (ctypes.c_uint64 * max(n, 1))(*src_len)
+        a_out = (ctypes.c_uint64 * (n + 1))()
+        total = ctypes.c_uint64()
+        cs = cipher.struct(1 if solid else n) if cipher is not None else None
+        ks, _keep_k = _kinds_struct(n, kinds, links)
+        ms, _keep_m = _meta_struct(n, extra, facets)
+        vp = ctypes.c_void_p
+        ref = lambda x: ctypes.byref(x) if x is not None else None
+        if solid:
+            f = self._L.pna_gpu_create_solid_archive_tree_device
+            f.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_size_t, vp, vp]
+            self._check(f(self._h, algo, level, n, a_names, vp(d_src), a_off, a_len, ref(cs), ref(ms), max_chunk_size, ref(ks), vp(d_dst), dst_cap, ctypes.byref(total), None))
+            return total.value, None
+        f = self._L.pna_gpu_create_archive_tree_device
+        f.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_uint32, vp]
+        self._check(f(self._h, algo, level, n, a_names, vp(d_src), a_off, a_len, ref(cs), ref(ms), max_chunk_size, ref(ks), vp(d_dst), dst_cap, a_out,
+                      ctypes.byref(total), part, None))
         return total.value, list(a_out)
 
     def set_option(self, name: str, value: int) -> None:
@@ -1520,4 +1598,95 @@ def create_archive_multi(ctxs: Sequence[Context], names: Sequence[str], entries:
     rc = L.pna_gpu_create_archive_multi_host(a_ctx, len(ctxs), algo, level, n, a_names, a_src, a_len, cb, None)
     if rc:
         raise PnaGpuError(rc, L.pna_gpu_last_error(ctxs[0]._h).decode() or L.pna_gpu_strerror(rc).decode())
+    return bytes(out)
+
+
+def entry_record_bytes(kind: int, name: str, target: bytes = b"", extra: bytes = b"", facets: bytes = b"", max_chunk_size: int = 0) -> bytes:
+    """pna_archive_entry_record_bytes: the whole record of a directory (KIND_DIRECTORY), symbolic link or hard link as raw chunk bytes --
+    FHED | extra | facets | FDAT(target)* | FEND.  Raises ValueError for what the library refuses (a file's kind, a link without a target)."""
+    L = load_library()
+    f = L.pna_archive_entry_record_bytes
+    f.restype = ctypes.c_size_t
+    f.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                  ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+    args = (kind, name.encode(), bytes(extra) or None, len(extra), bytes(facets) or None, len(facets), bytes(target) or None, len(target), max_chunk_size)
+    need = f(*args, None, 0)
+    if need == 0:
+        raise ValueError("not a record this library writes: kind %d, target of %d bytes" % (kind, len(target)))
+    buf = ctypes.create_string_buffer(need)
+    got = f(*args, buf, need)
+    return buf.raw[:got]
+
+
+def entry_kinds_check(src_len: Sequence[int], kinds, links) -> int:
+    """pna_gpu_entry_kinds_check: PNA_OK, or E_INVAL for an unknown kind, a non-file with source bytes, a link without a target.  Needs no device."""
+    n = len(src_len)
+    ks, _keep = _kinds_struct(n, kinds, links)
+    a_len = (ctypes.c_uint64 * max(n, 1))(*src_len)
+    f = load_library().pna_gpu_entry_kinds_check
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    return f(n, a_len, ctypes.byref(ks) if ks is not None else None)
+
+
+def _tree_bound(fn_name: str, algo: int, names, src_len, kinds, links, cipher, facets, extra, max_chunk_size: int) -> int:
+    n = len(src_len)
+    a_names = (ctypes.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    a_len = (ctypes.c_uint64 * max(n, 1))(*src_len)
+    cs = cipher.struct(0) if cipher is not None else None
+    ks, _keep_k = _kinds_struct(n, kinds, links)
+    ms, _keep_m = _meta_struct(n, extra, facets)
+    f = getattr(load_library(), fn_name)
+    f.restype = ctypes.c_size_t
+    f.argtypes = _TREE_BOUND_ARGS
+    ref = lambda x: ctypes.byref(x) if x is not None else None
+    return f(algo, n, a_names, a_len, ref(cs), ref(ms), max_chunk_size, ref(ks))
+
+
+def archive_tree_bound(algo: int, names: Sequence[str], src_len: Sequence[int], kinds=None, links=None, cipher: Optional[Cipher] = None,
+                       facets=None, extra=None, max_chunk_size: int = 0) -> int:
+    """pna_gpu_archive_tree_bound: the destination capacity of Context.create_archive_tree_device."""
+    return _tree_bound("pna_gpu_archive_tree_bound", algo, names, src_len, kinds, links, cipher, facets, extra, max_chunk_size)
+
+
+def solid_archive_tree_bound(algo: int, names: Sequence[str], src_len: Sequence[int], kinds=None, links=None, cipher: Optional[Cipher] = None,
+                             facets=None, extra=None, max_chunk_size: int = 0) -> int:
+    """pna_gpu_solid_archive_tree_bound: ... of Context.create_archive_tree_device(solid=True)."""
+    return _tree_bound("pna_gpu_solid_archive_tree_bound", algo, names, src_len, kinds, links, cipher, facets, extra, max_chunk_size)
+
+
+def create_archive_tree(ctx: Context, names: Sequence[str], entries: Sequence[bytes], kinds=None, links=None, algo: int = ALGO_ZSTD,
+                        level: int = LEVEL_DEFAULT, cipher: Optional[Cipher] = None, facets=None, extra=None, max_chunk_size: int = 0,
+                        solid: bool = False, part: int = PART_HEAD | PART_TAIL) -> bytes:
+    """`pna create some/tree` in one call (pna_gpu_create_archive_tree_host; solid: pna_gpu_create_solid_archive_tree_host): create_entry's four arms
+    (cli/src/command/core.rs:915-977) as kinds[i] -- KIND_FILE: entries[i] is the file; KIND_DIRECTORY: a record without data; KIND_SYMLINK /
+    KIND_HARDLINK: links[i] is the target (stored, never encrypted).  entries[i] of an entry that is not a file must be empty.  facets / extra: framed
+    chunks per entry, as in create_archive_with_metadata.  kinds None: create_archive_chunked's bytes."""
+    L = load_library()
+    n = len(entries)
+    out = bytearray()
+
+    def _sink(_u, buf, k):
+        out.extend((ctypes.c_char * k).from_address(buf))
+        return 0
+    cb = SINK_FN(_sink)
+    bufs = [e if isinstance(e, bytes) else bytes(e) for e in entries]
+    a_names = (ctypes.c_char_p * max(n, 1))(*[s.encode() for s in names])
+    a_src = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+    a_len = (ctypes.c_size_t * max(n, 1))(*[len(e) for e in bufs])
+    cs = cipher.struct(1 if solid else n) if cipher is not None else None
+    ks, _keep_k = _kinds_struct(n, kinds, links)
+    ms, _keep_m = _meta_struct(n, extra, facets)
+    vp = ctypes.c_void_p
+    ref = lambda x: ctypes.byref(x) if x is not None else None
+    if solid:
+        f = L.pna_gpu_create_solid_archive_tree_host
+        f.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, SINK_FN, vp]
+        rc = f(ctx._h, algo, level, n, a_names, a_src, a_len, ref(cs), ref(ms), max_chunk_size, ref(ks), cb, None)
+    else:
+        f = L.pna_gpu_create_archive_tree_host
+        f.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32, SINK_FN, vp]
+        rc = f(ctx._h, algo, level, n, a_names, a_src, a_len, ref(cs), ref(ms), max_chunk_size, ref(ks), part, cb, None)
+    if rc:
+        raise PnaGpuError(rc, L.pna_gpu_last_error(ctx._h).decode() or L.pna_gpu_strerror(rc).decode())
     return bytes(out)

@@ -680,6 +680,7 @@ __global__ void k_dfinal(const SegDesc *__restrict__ segs, const uint32_t *__res
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nentry) return;
     const uint32_t s0 = entry_seg[e], s1 = entry_seg[e + 1];
+    if (s1 <= s0) return;                                    // an entry without a stream (not a file: the tree entry points)
     uint8_t *o = dst + seg_off[s0];
     if (segs[s0].len == 0) {
         if (stored_only) { const uint8_t z[11] = {0x78, 0x01, 0x01, 0x00, 0x00, 0xFF, 0xFF, 0x00, 0x00, 0x00, 0x01}; for (int i = 0; i < 11; i++) o[i] = z[i]; return; }

@@ -377,7 +377,8 @@ void k_layout_a(const FrameDesc *__restrict__ fd, const uint32_t *__restrict__ e
     __shared__ uint64_t part[2][1024];
     const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
     uint64_t s = 0;
-    if (i < nentry) s = (uint64_t)fd[i].prefix_len + (seg_off[entry_seg[i + 1]] - seg_off[entry_seg[i]]) + 16;
+    // (a record without a data chunk -- pad bit 0: an entry that is not a file, its whole record in the prefix blob -- takes its prefix_len bytes and nothing else)
+    if (i < nentry) { const FrameDesc d = fd[i]; s = (d.pad & 1) ? (uint64_t)d.prefix_len : (uint64_t)d.prefix_len + (seg_off[entry_seg[i + 1]] - seg_off[entry_seg[i]]) + 16; }
     uint64_t tot;
     const uint64_t incl = wg_scan_1024(s, part, &tot);
     if (i < nentry) ent_off[i] = incl - s;
@@ -394,11 +395,14 @@ void k_layout_c(FrameDesc *__restrict__ fd, uint8_t *__restrict__ blob, const ui
         const uint32_t s0 = entry_seg[i], s1 = entry_seg[i + 1];
         const uint64_t base = seg_off[s0], plen = seg_off[s1] - base;
         FrameDesc d = fd[i];
-        d.arc_off = pos; d.payload_len = (uint32_t)plen;
+        const bool record = (d.pad & 1) != 0;                                       // no data chunk: no length field to fill in, no segments (s0 == s1)
+        d.arc_off = pos; d.payload_len = record ? 0u : (uint32_t)plen;
         fd[i] = d;
-        uint8_t *lenf = blob + d.prefix_off + d.prefix_len - 8;                     // the FDAT chunk's length, big-endian
-        lenf[0] = (uint8_t)(plen >> 24); lenf[1] = (uint8_t)(plen >> 16); lenf[2] = (uint8_t)(plen >> 8); lenf[3] = (uint8_t)plen;
-        for (uint32_t sg = s0; sg < s1; sg++) segdst[sg] = pos + d.prefix_len + (seg_off[sg] - base);
+        if (!record) {
+            uint8_t *lenf = blob + d.prefix_off + d.prefix_len - 8;                 // the FDAT chunk's length, big-endian
+            lenf[0] = (uint8_t)(plen >> 24); lenf[1] = (uint8_t)(plen >> 16); lenf[2] = (uint8_t)(plen >> 8); lenf[3] = (uint8_t)plen;
+            for (uint32_t sg = s0; sg < s1; sg++) segdst[sg] = pos + d.prefix_len + (seg_off[sg] - base);
+        }
         ent_off[i] = pos;
     }
     if (i == 0) { const uint64_t end = out_base + wg_off[nwg]; segdst[nseg] = end; ent_off[nentry] = end; *total = end - out_base; }

@@ -203,6 +203,21 @@ void frame_solid_head_enc(std::vector<uint8_t> &o, int compression, int encrypti
     put_chunk(o, "SDAT", prefix, prefix_len);                       // CTR: the IV; GCM STREAM: the stream header
 }
 void frame_solid_tail(std::vector<uint8_t> &o) { put_chunk(o, "SEND", nullptr, 0); }
+// The whole record of an entry that is not a file -- kind 1 directory (DirEntryBuilder, EntryHeader::for_dir), 2 symbolic link, 3 hard link
+// (SymlinkEntryBuilder::new / HardLinkEntryBuilder::new, cli/src/command/core.rs:938-955; for_symlink / for_hard_link, lib/src/entry/header.rs:65-78: compression 0,
+// encryption 0, cipher_mode 0): FHED | extra | facets | FDAT* | FEND (NormalEntry::write_chunks_to, lib/src/entry.rs:895-911).  No fSIZ: only DataKind::FILE records one
+// (lib/src/entry/builder.rs:630-632).  A link's target is stored and never encrypted (new_link takes WriteOptions::store(), builder.rs:341-349) and is cut into FDAT
+// chunks as FlattenWriter cuts any stream (lib/src/util/io.rs:60-77); a directory has no data chunk.  `extra` / `facets`: chunks the caller has already framed.
+void frame_nonfile_record(std::vector<uint8_t> &o, int kind, const char *name, const void *extra, size_t extra_len, const void *facets, size_t facets_len,
+                          const void *target, size_t target_len, uint32_t max_chunk) {
+    std::vector<uint8_t> h = fhed(kind, 0, 0, 0, sanitize(name));
+    put_chunk(o, "FHED", h.data(), h.size());
+    if (extra_len) o.insert(o.end(), (const uint8_t *)extra, (const uint8_t *)extra + extra_len);
+    if (facets_len) o.insert(o.end(), (const uint8_t *)facets, (const uint8_t *)facets + facets_len);
+    const size_t mx = max_chunk ? max_chunk : 0xFFFFFFFFull;
+    if (kind != 1) for (size_t p = 0; p < target_len; p += mx) put_chunk(o, "FDAT", (const uint8_t *)target + p, std::min(mx, target_len - p));
+    put_chunk(o, "FEND", nullptr, 0);
+}
 size_t frame_entry_prefix_bound(const char *name) { return 12 + 6 + (name ? strlen(name) : 0) + 12 + 16 + 8; }
 uint32_t frame_fend_crc() { return pna_crc32(0, "FEND", 4); }
 } // namespace pna
@@ -231,9 +246,21 @@ extern "C" int pna_archive_add_file(pna_archive *a, const char *name, int compre
 
 extern "C" int pna_archive_add_dir(pna_archive *a, const char *name) {
     if (!a) return PNA_E_INVAL;
-    std::vector<uint8_t> h = fhed(1, 0, 0, 0, sanitize(name));                            // lib/src/entry/header.rs:44-52,65-67
-    a->chunk("FHED", h.data(), h.size());
-    return a->chunk("FEND", nullptr, 0);
+    std::vector<uint8_t> rec;
+    frame_nonfile_record(rec, 1, name, nullptr, 0, nullptr, 0, nullptr, 0, 0);              // lib/src/entry/header.rs:44-52,65-67
+    return a->emit(rec.data(), rec.size());
+}
+
+extern "C" size_t pna_archive_entry_record_bytes(int kind, const char *name, const void *extra, size_t extra_len, const void *facets, size_t facets_len,
+                                                 const void *target, size_t target_len, uint32_t max_chunk_size, void *dst, size_t cap) {
+    if (kind < 1 || kind > 3 || (extra_len && !extra) || (facets_len && !facets)) return 0;
+    if (kind != 1 && (!target || !target_len)) return 0;          // a link without a target
+    std::vector<uint8_t> rec;
+    frame_nonfile_record(rec, kind, name, extra, extra_len, facets, facets_len, target, target_len, max_chunk_size);
+    if (!dst) return rec.size();
+    if (cap < rec.size()) return 0;
+    memcpy(dst, rec.data(), rec.size());
+    return rec.size();
 }
 
 extern "C" int pna_archive_add_solid(pna_archive *a, int compression, const void *const *pieces, const size_t *piece_len, size_t n) {

@@ -153,6 +153,8 @@ void frame_inner_entry_empty(std::vector<uint8_t> &o, const char *name);
 void frame_solid_head(std::vector<uint8_t> &o, int compression);
 void frame_solid_head_enc(std::vector<uint8_t> &o, int compression, int encryption, int cipher_mode, const char *phsf, const uint8_t *prefix, size_t prefix_len);
 void frame_solid_tail(std::vector<uint8_t> &o);
+void frame_nonfile_record(std::vector<uint8_t> &o, int kind, const char *name, const void *extra, size_t extra_len, const void *facets, size_t facets_len,
+                          const void *target, size_t target_len, uint32_t max_chunk);
 void frame_archive_head(std::vector<uint8_t> &o, uint32_t archive_number);
 void frame_archive_tail(std::vector<uint8_t> &o);
 void frame_entry_prefix(std::vector<uint8_t> &o, const char *name, int compression, uint64_t raw_size, uint32_t payload_len);
@@ -395,13 +397,19 @@ inline int fail(pna_gpu_ctx *c, int code, const char *what, hipError_t e = hipSu
 // ---- what the translation units of the host code share (defined in pna_host.cpp unless noted)
 constexpr uint64_t CTR_UNIT = 256u << 10;                    // bytes of one CTR work unit (one workgroup)
 struct PlaceDescH { uint64_t src_off, dst_off; uint32_t len, pad; };   // = PlaceDesc of k_frame.hip (k_place / k_gather)
+// The entries of a call that are not files (pna_gpu_entry_kinds: directories, symbolic links, hard links): their finished records (frame_nonfile_record),
+// built once per call.  Entry e's record is blob[off[e] .. off[e + 1]); a file's is empty, so `len(e) != 0` is "entry e is not a file".
+struct EntryRecords { std::vector<uint8_t> blob; std::vector<uint64_t> off; size_t count = 0;
+                      uint64_t len(size_t e) const { return off[e + 1] - off[e]; } const uint8_t *at(size_t e) const { return blob.data() + off[e]; } };
 struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cipher = nullptr; const uint8_t *ivs = nullptr; const pna_gpu_entry_meta *meta = nullptr;
                   uint32_t max_chunk = 0; bool want_offsets = true;      // FDAT chunks of at most this many bytes (FlattenWriter::max_chunk_size; 0 = the reference's default u32::MAX)
                   // a solid stream compressed in windows (pna_gpu_create_solid_archive_host): the sub-batch is one window of a stream of stream_len bytes and
                   // is planned as the whole stream; deflate: DRUN_* flags of the window's place in the stream, the stream's Adler-32 carry in device memory
                   uint64_t stream_len = 0; uint32_t run = 0; uint32_t *adler_carry = nullptr;
                   // ... with a cipher: where the window stands in the cipher stream, updated by layout_solid (SolidCipherRun)
-                  struct SolidCipherRun *crun = nullptr; };
+                  struct SolidCipherRun *crun = nullptr;
+                  // the tree entry points: the call's non-file records (NULL: every entry is a file).  Such an entry has no segments, no cipher unit, no IV drawn
+                  const EntryRecords *recs = nullptr; };
 // The cipher state of a solid stream compressed in windows.  CTR: `pos`, the stream offset of the window's first compressed byte (the keystream
 // continues).  GCM STREAM: segments are cut from the whole compressed stream -- `seg`, the counter of the next segment; `carry` (carry_len bytes,
 // 1 .. G once the stream has begun, in device memory) the tail of the output before that is not yet known to be a non-final segment, placed in
@@ -568,6 +576,15 @@ uint64_t chunk_limit(uint32_t max_chunk);
 size_t meta_len(const pna_gpu_entry_meta *m, size_t e);
 bool meta_blob_ok(const uint8_t *p, size_t n);
 int  check_meta(pna_gpu_ctx *c, const pna_gpu_entry_meta *meta, size_t n);
+// the checks of pna_gpu_entry_kinds_check, then every non-file's record into `out` (kinds == NULL or kinds->kind == NULL: `out` stays empty -- all files)
+int  build_entry_records(pna_gpu_ctx *c, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_entry_kinds *kinds,
+                         const pna_gpu_entry_meta *meta, uint32_t max_chunk, EntryRecords &out);
+// FHED | fSIZ | rest  ->  FHED | extra | fSIZ | facets | rest: entry e's metadata chunks where NormalEntry::write_chunks_to puts them
+void splice_meta(std::vector<uint8_t> &pre, const pna_gpu_entry_meta *m, size_t e);
+// pna_gpu_create_solid_archive_enc_device and its tree form (meta, max_chunk, kinds: NULL / 0 for the former)
+int  create_solid_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                              const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk, const pna_gpu_entry_kinds *kinds,
+                              void *d_dst, size_t dst_cap, uint64_t *archive_len, void *hip_stream);
 int  run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
                   size_t e0, size_t e1, uint8_t *d_dst, size_t dst_cap, uint64_t out_base, uint64_t *dst_off,
                   hipStream_t st, bool timed, const FrameJob *fj = nullptr);

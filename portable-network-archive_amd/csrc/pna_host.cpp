@@ -278,7 +278,7 @@ bool meta_blob_ok(const uint8_t *p, size_t n) {
     return true;
 }
 // prefix = FHED | fSIZ | rest  ->  FHED | extra | fSIZ | facets | rest   (NormalEntry::write_chunks_to, lib/src/entry.rs:895-911)
-static void splice_meta(std::vector<uint8_t> &pre, const pna_gpu_entry_meta *m, size_t e) {
+void splice_meta(std::vector<uint8_t> &pre, const pna_gpu_entry_meta *m, size_t e) {
     if (!meta_len(m, e)) return;
     const size_t c0 = 12 + (size_t)rd_be32(pre.data()), c1 = 12 + (size_t)rd_be32(pre.data() + c0);
     std::vector<uint8_t> out(pre.begin(), pre.begin() + c0);
@@ -377,9 +377,12 @@ static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
     const unsigned host_nt = host_loop_threads(ne_all);
     struct PlanPart { uint64_t in_total = 0, nseg_est = 0, max_len = 0, n_short = 0, n_mid = 0, max_mid = 0; uint32_t sg = 0, bk = 0, un = 0; bool misaligned = false, any_empty = false; };
     std::vector<PlanPart> pp(host_nt);
+    // an entry that is not a file (FrameJob::recs) is no frame at all: no segment, no block, its source offset unread -- an EMPTY FILE is one empty frame (any_empty)
+    const EntryRecords *recs = fj ? fj->recs : nullptr;
     par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
         PlanPart q;
         for (size_t e = e0 + a; e < e0 + b; e++) {
+            if (recs && recs->len(e)) continue;
             const uint64_t len = src_len[e];
             q.in_total += len; q.nseg_est += len ? (len + SEG_SIZE - 1) / SEG_SIZE : 1; q.max_len = std::max<uint64_t>(q.max_len, len);
             q.misaligned |= (src_off[e] & 15) != 0; q.any_empty |= len == 0;
@@ -409,7 +412,7 @@ static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
         uint32_t sg = 0, bk = 0, un = 0;
         for (size_t e = e0 + a; e < e0 + b; e++) {
             const uint64_t len = src_len[e];
-            if (len == 0) { sg++; continue; }
+            if (len == 0) { if (!(recs && recs->len(e))) sg++; continue; }
             const uint64_t full = len >> 20, rest = len & (SEG_SIZE - 1);
             sg += (uint32_t)(full + (rest ? 1 : 0));
             bk += (uint32_t)((full << (20 - blk_log)) + ((rest + bsz - 1) >> blk_log));
@@ -438,6 +441,7 @@ static int plan_subbatch(const SubBatch &sb, HostMarks &hm, SubPlan &p) {
         for (size_t e = e0 + a; e < e0 + b; e++) {
             entry_first_seg[e - e0] = sg;
             const uint64_t len = src_len[e], off = src_off[e];
+            if (recs && recs->len(e)) continue;
             if (len == 0) { segs[sg++] = SegDesc{off, 0, bk, (uint32_t)e, 3, 0, 0, blk_log, 0}; continue; }
             for (uint64_t q = 0; q < len; q += SEG_SIZE) {
                 const uint32_t sl = (uint32_t)std::min<uint64_t>(SEG_SIZE, len - q);
@@ -611,9 +615,14 @@ static int frame_prefixes(const SubBatch &sb, const SubPlan &p, SubLayout &L) {
     struct FramePart { size_t bound = 0, extra = 0; uint64_t need = 0; bool over = false; };
     std::vector<FramePart> fp(host_nt);
     const uint64_t CHb = chunk_limit(fj->max_chunk);
+    // an entry that is not a file: its finished record is its prefix and all of it -- a descriptor "without a data chunk" (FrameDesc::pad bit 0), which k_frame copies
+    // and leaves alone: no data CRC, no FEND (the record has both); no stream key, no cipher unit
+    const EntryRecords *recs = fj->recs;
+    auto record_desc = [&](size_t e, size_t at) { const size_t rl = (size_t)recs->len(e); memcpy(L.blob + at, recs->at(e), rl); return FrameDesc{0, 0, (uint32_t)at, (uint32_t)rl, 1u}; };
     par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
         FramePart q;
         for (size_t e = e0 + a; e < e0 + b; e++) {
+            if (recs && recs->len(e)) { q.bound += (size_t)recs->len(e); q.need += recs->len(e); continue; }
             const size_t pb = (fj->cipher ? frame_entry_prefix_enc_bound(fj->names[e], fj->cipher->phsf) : frame_entry_prefix_bound(fj->names[e])) + meta_len(fj->meta, e);
             const uint64_t wb = pna_gpu_bound(algo, (size_t)src_len[e]);
             q.bound += pb; q.extra += (size_t)((wb + 64 + 16 * (src_len[e] >> 12)) / CHb); q.need += pb + wb + 16; q.over |= wb > CHb;
@@ -635,7 +644,7 @@ static int frame_prefixes(const SubBatch &sb, const SubPlan &p, SubLayout &L) {
         for (unsigned t = 0; t < nt; t++)
             th.emplace_back([&, t]() {
                 for (size_t e = e0 + t; e < e1; e += nt)
-                    gcm_entry_material(fj->cipher, keys, fj->ivs + 39 * e, gcm_seg, fj->names[e], algo, L.gmat[e - e0]);
+                    if (!(recs && recs->len(e))) gcm_entry_material(fj->cipher, keys, fj->ivs + 39 * e, gcm_seg, fj->names[e], algo, L.gmat[e - e0]);
             });
         for (auto &x : th) x.join();
     }
@@ -645,6 +654,7 @@ static int frame_prefixes(const SubBatch &sb, const SubPlan &p, SubLayout &L) {
         par_ranges(ne_all, host_nt, [&](unsigned t, size_t a, size_t b) {
             size_t at = fp[t].bound;
             for (size_t i = a; i < b; i++) {
+                if (recs && recs->len(e0 + i)) { fds[i] = record_desc(e0 + i, at); at += fds[i].prefix_len; continue; }
                 const size_t pl = frame_entry_prefix_into(blob + at, fj->names[e0 + i], algo, src_len[e0 + i]);
                 fds[i] = FrameDesc{0, 0, (uint32_t)at, (uint32_t)pl, 0};
                 at += pl;
@@ -655,6 +665,7 @@ static int frame_prefixes(const SubBatch &sb, const SubPlan &p, SubLayout &L) {
     }
     std::vector<uint8_t> tmp;
     for (size_t e = e0; e < e1; e++) {
+        if (recs && recs->len(e)) { fds[e - e0] = record_desc(e, L.blob_len); L.blob_len += fds[e - e0].prefix_len; continue; }
         tmp.clear();
         if (gcm) frame_entry_prefix_enc(tmp, fj->names[e], algo, src_len[e], fj->cipher->encryption, PNA_MODE_GCM, fj->cipher->phsf, L.gmat[e - e0].header, 75);
         else if (fj->cipher) frame_entry_prefix_enc(tmp, fj->names[e], algo, src_len[e], fj->cipher->encryption, fj->cipher->cipher_mode, fj->cipher->phsf, fj->ivs + 16 * e, 16);
@@ -735,6 +746,7 @@ static int layout_entries(const SubBatch &sb, const SubPlan &p, const uint64_t *
         const uint32_t s0 = p.entry_first_seg[e - e0], s1 = p.entry_first_seg[e - e0 + 1];
         const FrameDesc f0 = L.fds[e - e0];                // prefix of the entry: FHED | fSIZ | ... | first FDAT header
         sb.dst_off[e] = pos;
+        if (f0.pad & 1) { FrameDesc u = f0; u.arc_off = pos; units.push_back(u); pos += f0.prefix_len; continue; }   // not a file: its prefix_len bytes and nothing else
         const uint64_t p0 = pos + f0.prefix_len;           // where the payload starts
         uint64_t plen = seg_off[s1] - seg_off[s0];         // the entry's compressed stream, then what the cipher makes of it
         for (uint32_t sg = s0; sg < s1; sg++) L.segdst[sg] = p0 + (seg_off[sg] - seg_off[s0]);
@@ -857,6 +869,17 @@ static int cipher_stage(const SubBatch &sb, const SubLayout &L) {
     if (gcm) launch_gcm_tag((const GcmEntry *)c->ci_gcm.p, (uint32_t)L.gents.size(), sb.d_dst, st);
     return cipher_mark(c, 1, st);
 }
+// A sub-batch without a single file (the tree entry points: a run of directories and links): no segment, so no LZ, entropy, write or framing launch --
+// the finished records, which lie back to back in the call's blob, go to their place in one copy
+static int records_subbatch(const SubBatch &sb) {
+    pna_gpu_ctx *c = sb.c; const EntryRecords &r = *sb.fj->recs;
+    const uint64_t b0 = r.off[sb.e0], bytes = r.off[sb.e1] - b0;
+    if (sb.out_base + bytes + 16 > sb.dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
+    for (size_t e = sb.e0; e <= sb.e1; e++) sb.dst_off[e] = sb.out_base + (r.off[e] - b0);
+    if (bytes) HIPCHK(c, hipMemcpyAsync(sb.d_dst + sb.out_base, r.blob.data() + b0, bytes, hipMemcpyHostToDevice, sb.st));
+    HIPCHK(c, hipStreamSynchronize(sb.st));
+    return PNA_OK;
+}
 // One sub-batch: entries [e0, e1) -> segments -> kernels; output appended at d_dst + out_base.
 int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
                  size_t e0, size_t e1, uint8_t *d_dst, size_t dst_cap, uint64_t out_base, uint64_t *dst_off,
@@ -865,6 +888,7 @@ int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t 
     HostMarks hm{c->tun.trace != 0};
     SubPlan p;
     int rc = plan_subbatch(sb, hm, p);
+    if (rc == PNA_OK && p.nseg == 0 && fj && fj->recs) return records_subbatch(sb);
     if (rc || p.nseg == 0) return rc;
     hm.mark("plan queued");
     rc = compress_subbatch(sb, p); if (rc) return rc;
@@ -1015,12 +1039,46 @@ int check_meta(pna_gpu_ctx *c, const pna_gpu_entry_meta *meta, size_t n) {
     return PNA_OK;
 }
 
+// The entry kinds of a tree call (pna_gpu_entry_kinds; create_entry's four arms, cli/src/command/core.rs:915-977): every kind known, a non-file without source
+// bytes, a link with a target.  Needs no context.
+extern "C" int pna_gpu_entry_kinds_check(size_t n, const uint64_t *src_len, const pna_gpu_entry_kinds *kinds) {
+    if (!kinds || !kinds->kind) return PNA_OK;
+    if (n && !src_len) return PNA_E_INVAL;
+    for (size_t e = 0; e < n; e++) {
+        const uint8_t k = kinds->kind[e];
+        if (k == PNA_KIND_FILE) continue;
+        if (k > PNA_KIND_HARDLINK || src_len[e] != 0) return PNA_E_INVAL;
+        if (k != PNA_KIND_DIRECTORY && (!kinds->link || !kinds->link_len || !kinds->link[e] || !kinds->link_len[e])) return PNA_E_INVAL;
+    }
+    return PNA_OK;
+}
+int build_entry_records(pna_gpu_ctx *c, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_entry_kinds *kinds,
+                        const pna_gpu_entry_meta *meta, uint32_t max_chunk, EntryRecords &out) {
+    out = EntryRecords{};
+    if (!kinds || !kinds->kind) return PNA_OK;
+    if (pna_gpu_entry_kinds_check(n, src_len, kinds)) return fail(c, PNA_E_INVAL, "entry kinds: an unknown kind, a non-file with source bytes, or a link without a target");
+    out.off.resize(n + 1);
+    for (size_t e = 0; e < n; e++) {
+        out.off[e] = out.blob.size();
+        const int k = kinds->kind[e];
+        if (k == PNA_KIND_FILE) continue;
+        const bool ex = meta && meta->extra && meta->extra_len && meta->extra_len[e], fa = meta && meta->facets && meta->facets_len && meta->facets_len[e];
+        frame_nonfile_record(out.blob, k, names[e], ex ? meta->extra[e] : nullptr, ex ? meta->extra_len[e] : 0, fa ? meta->facets[e] : nullptr, fa ? meta->facets_len[e] : 0,
+                             k == PNA_KIND_DIRECTORY ? nullptr : kinds->link[e], k == PNA_KIND_DIRECTORY ? 0 : kinds->link_len[e], max_chunk);
+        if (out.blob.size() - out.off[e] > 0x7FFFFFFFull) return fail(c, PNA_E_INVAL, "a link's record exceeds 2 GiB");
+        out.count++;
+    }
+    out.off[n] = out.blob.size();
+    if (!out.count) out = EntryRecords{};                      // every entry a file: the counterpart's path
+    return PNA_OK;
+}
+
 // ... and with per-entry metadata: chunks the host has already framed (timestamps, permissions, owner, xattr: try_for_each_metadata_facet,
 // lib/src/entry.rs:124-180; user-defined extra chunks) are placed where NormalEntry::write_chunks_to puts them.
 int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                       const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
                                       const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk, void *d_dst, size_t dst_cap,
-                                      uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream);
+                                      uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream, const pna_gpu_entry_kinds *kinds = nullptr);
 extern "C" int pna_gpu_create_archive_meta_device(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                   const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
                                                   const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, void *d_dst, size_t dst_cap,
@@ -1042,9 +1100,12 @@ extern "C" size_t pna_gpu_archive_chunked_bound(int algo, size_t n, const char *
 int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                       const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
                                       const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk, void *d_dst, size_t dst_cap,
-                                      uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream) {
+                                      uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream, const pna_gpu_entry_kinds *kinds) {
     { int rcm = check_meta(c, meta, n); if (rcm) return rcm; }
-    if (!c || !archive_len || (n && (!names || !src_off || !src_len || !d_src)) || !d_dst) return fail(c, PNA_E_INVAL, "null argument");
+    if (!c || !archive_len || (n && (!names || !src_off || !src_len)) || !d_dst) return fail(c, PNA_E_INVAL, "null argument");
+    EntryRecords recs;                                          // the tree form: the records of the entries that are not files
+    { int rck = build_entry_records(c, n, names, src_len, kinds, meta, max_chunk, recs); if (rck) return rck; }
+    if (!d_src && recs.count < n) return fail(c, PNA_E_INVAL, "null argument");
     if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     if ((uintptr_t)d_dst & 15) return fail(c, PNA_E_INVAL, "archive buffer must be 16-byte aligned");
     if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
@@ -1075,6 +1136,7 @@ int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, co
     }
     const CallTotalScope call_total(c, in_total);                                                // (the block size follows the call, not its sub-batches)
     FrameJob fj{names, 0, cipher, ivs, meta, max_chunk, entry_off != nullptr};
+    if (recs.count) fj.recs = &recs;
     size_t e = 0;
     plan_call_longest(c, longest);
     const bool one_block_each = longest <= ((uint64_t)1 << c->plan_log);
@@ -1112,15 +1174,57 @@ int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, co
 //   2. that stream is compressed as ONE entry (independent 1 MiB frames / zlib blocks inside the kernels),
 //   3. every segment's output becomes one SDAT chunk between SHED and SEND.
 
-extern "C" size_t pna_gpu_solid_archive_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len) {
-    uint64_t plain = 0;
-    for (size_t i = 0; i < n; i++) plain += frame_entry_prefix_bound(names ? names[i] : nullptr) + src_len[i] + 16;
+// the bound of a solid archive whose inner stream holds `plain` bytes, then what a cipher adds to it
+static size_t solid_bound_of(int algo, uint64_t plain) {
     const uint64_t segs = (plain + SEG_SIZE - 1) / SEG_SIZE + 1;
     return 28 + 17 + pna_gpu_bound(algo, (size_t)plain) + 12 * segs + 12 + 12 + 64;
 }
+static uint64_t solid_plain_bound(size_t n, const char *const *names, const uint64_t *src_len) {
+    uint64_t plain = 0;
+    for (size_t i = 0; i < n; i++) plain += frame_entry_prefix_bound(names ? names[i] : nullptr) + src_len[i] + 16;
+    return plain;
+}
+extern "C" size_t pna_gpu_solid_archive_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len) {
+    return solid_bound_of(algo, solid_plain_bound(n, names, src_len));
+}
 
+static size_t solid_enc_bound_of(size_t b, const pna_gpu_cipher *cipher);
 extern "C" size_t pna_gpu_solid_archive_enc_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_cipher *cipher) {
-    size_t b = pna_gpu_solid_archive_bound(algo, n, names, src_len);
+    return solid_enc_bound_of(pna_gpu_solid_archive_bound(algo, n, names, src_len), cipher);
+}
+// What the entries that are not files, the metadata chunks and the chunk cut add to a bound whose per-entry terms treat every entry as a file (those
+// terms cover FHED and FEND): the blobs, a link's target, a chunk frame per FDAT chunk of it
+static size_t tree_bound_terms(size_t n, const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds) {
+    size_t b = 0; const uint64_t CH = chunk_limit(max_chunk_size);
+    for (size_t i = 0; i < n; i++) {
+        b += meta_len(meta, i);
+        if (kinds && kinds->kind && kinds->kind[i] != PNA_KIND_FILE && kinds->kind[i] != PNA_KIND_DIRECTORY && kinds->link_len) b += kinds->link_len[i] + 12 * (size_t)(kinds->link_len[i] / CH + 1);
+    }
+    return b;
+}
+extern "C" size_t pna_gpu_archive_tree_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_cipher *cipher,
+                                             const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds) {
+    return pna_gpu_archive_chunked_bound(algo, n, names, src_len, cipher, max_chunk_size) + tree_bound_terms(n, meta, max_chunk_size, kinds);
+}
+extern "C" size_t pna_gpu_solid_archive_tree_bound(int algo, size_t n, const char *const *names, const uint64_t *src_len, const pna_gpu_cipher *cipher,
+                                                   const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds) {
+    uint64_t plain = solid_plain_bound(n, names, src_len) + tree_bound_terms(n, meta, max_chunk_size, kinds);
+    if (max_chunk_size) for (size_t i = 0; i < n; i++) plain += 12 * (src_len[i] / chunk_limit(max_chunk_size) + 1);      // a file's further FDAT chunks
+    return solid_enc_bound_of(solid_bound_of(algo, plain), cipher);
+}
+extern "C" int pna_gpu_create_archive_tree_device(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                                  const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                                                  const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds,
+                                                  void *d_dst, size_t dst_cap, uint64_t *entry_off, uint64_t *archive_len, uint32_t part_flags, void *hip_stream) {
+    return create_archive_device_impl(c, algo, level, n, names, d_src, src_off, src_len, cipher, meta, max_chunk_size, d_dst, dst_cap, entry_off, archive_len, part_flags, hip_stream, kinds);
+}
+extern "C" int pna_gpu_create_solid_archive_tree_device(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                                        const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                                                        const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds,
+                                                        void *d_dst, size_t dst_cap, uint64_t *archive_len, void *hip_stream) {
+    return create_solid_device_impl(c, algo, level, n, names, d_src, src_off, src_len, cipher, meta, max_chunk_size, kinds, d_dst, dst_cap, archive_len, hip_stream);
+}
+static size_t solid_enc_bound_of(size_t b, const pna_gpu_cipher *cipher) {
     if (!cipher || cipher->encryption == PNA_ENC_NONE) return b;
     b += 12 + (cipher->phsf ? strlen(cipher->phsf) : 0) + 12 + 75 + 64;          // PHSF chunk, the chunk of the IV / stream header
     if (cipher->cipher_mode == PNA_MODE_GCM) {
@@ -1143,49 +1247,83 @@ extern "C" int pna_gpu_create_solid_archive_enc_device(pna_gpu_ctx *c, int algo,
                                                        const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
                                                        const pna_gpu_cipher *cipher, void *d_dst, size_t dst_cap, uint64_t *archive_len,
                                                        void *hip_stream) {
+    return create_solid_device_impl(c, algo, level, n, names, d_src, src_off, src_len, cipher, nullptr, 0, nullptr, d_dst, dst_cap, archive_len, hip_stream);
+}
+// (the tree form: inner entries that are not files are finished records between the file records -- blob spans, "without a data chunk" for k_frame --, files carry
+// their metadata chunks and are cut into FDAT chunks of max_chunk bytes: every inner entry of a solid stream is a stored record)
+int create_solid_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                             const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                             const pna_gpu_cipher *cipher, const pna_gpu_entry_meta *meta, uint32_t max_chunk, const pna_gpu_entry_kinds *kinds,
+                             void *d_dst, size_t dst_cap, uint64_t *archive_len, void *hip_stream) {
+    { int rcm = check_meta(c, meta, n); if (rcm) return rcm; }
     if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
     std::vector<uint8_t> own_ivs;
     const uint8_t *ivs = nullptr;
     if (cipher) { int rc0 = resolve_ivs(c, cipher, 1, own_ivs, &ivs); if (rc0) return rc0; }
     if (cipher && cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
-    if (!c || !archive_len || (n && (!names || !src_off || !src_len || !d_src)) || !d_dst) return fail(c, PNA_E_INVAL, "null argument");
+    if (!c || !archive_len || (n && (!names || !src_off || !src_len)) || !d_dst) return fail(c, PNA_E_INVAL, "null argument");
+    EntryRecords recs;
+    { int rck = build_entry_records(c, n, names, src_len, kinds, meta, max_chunk, recs); if (rck) return rck; }
+    if (!d_src && recs.count < n) return fail(c, PNA_E_INVAL, "null argument");
     if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
     if ((uintptr_t)d_dst & 15) return fail(c, PNA_E_INVAL, "archive buffer must be 16-byte aligned");
     set_call_level(c, algo, level);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     // ---- 1. layout of the serialised inner entries (all sizes are known up front)
-    std::vector<FrameDesc> fds(n); std::vector<uint8_t> blob; std::vector<PlaceDescH> places;
-    uint64_t pos = 0, max_inner = 0;
-    for (size_t i = 0; i < n; i++) max_inner = std::max<uint64_t>(max_inner, src_len[i]);
-    const uint32_t solid_max_inner = max_inner <= 16380 ? (uint32_t)std::max<uint64_t>(max_inner, 1) : 0u;      // (stored inner entries: the FDAT payload is the entry; small ones take k_frame's wave-per-entry form)
+    std::vector<FrameDesc> fds; std::vector<uint8_t> blob, tmp; std::vector<PlaceDescH> places;
+    fds.reserve(n);
+    // (without max_chunk an inner entry is ONE data chunk, below 2 GiB; with it, FlattenWriter's chunks -- lib/src/util/io.rs:60-77 --, a descriptor each)
+    const uint64_t CH = max_chunk ? chunk_limit(max_chunk) : 0x7FFF0000ull;
+    const bool cut = max_chunk != 0;
+    uint64_t pos = 0, max_piece = 0;
+    for (size_t i = 0; i < n; i++) if (!(recs.count && recs.len(i))) max_piece = std::max<uint64_t>(max_piece, std::min<uint64_t>(src_len[i], CH));
+    const uint32_t solid_max_inner = max_piece <= 16380 ? (uint32_t)std::max<uint64_t>(max_piece, 1) : 0u;      // (stored inner entries: the FDAT payload is the entry; small ones take k_frame's wave-per-entry form)
     for (size_t i = 0; i < n; i++) {
-        if (src_off[i] & 15) return fail(c, PNA_E_INVAL, "entry offset not 16-byte aligned");
-        if (src_len[i] >= 0x7FFF0000ull) return fail(c, PNA_E_INVAL, "inner entry too large for one FDAT chunk");
         const size_t po = blob.size();
+        if (recs.count && recs.len(i)) {
+            blob.insert(blob.end(), recs.at(i), recs.at(i) + recs.len(i));
+            fds.push_back(FrameDesc{pos, 0, (uint32_t)po, (uint32_t)recs.len(i), 1});
+            pos += recs.len(i);
+            continue;
+        }
+        if (src_off[i] & 15) return fail(c, PNA_E_INVAL, "entry offset not 16-byte aligned");
+        if (!cut && src_len[i] >= CH) return fail(c, PNA_E_INVAL, "inner entry too large for one FDAT chunk");
         if (src_len[i] == 0) {
-            frame_inner_entry_empty(blob, names[i]);
-            fds[i] = FrameDesc{pos, 0, (uint32_t)po, (uint32_t)(blob.size() - po), 1};
+            if (!meta_len(meta, i)) frame_inner_entry_empty(blob, names[i]);
+            else { tmp.clear(); frame_inner_entry_empty(tmp, names[i]); splice_meta(tmp, meta, i); blob.insert(blob.end(), tmp.begin(), tmp.end()); }
+            fds.push_back(FrameDesc{pos, 0, (uint32_t)po, (uint32_t)(blob.size() - po), 1});
             pos += blob.size() - po;
             continue;
         }
-        frame_entry_prefix(blob, names[i], PNA_ALGO_STORE, src_len[i], (uint32_t)src_len[i]);
-        const uint32_t pl = (uint32_t)(blob.size() - po);
-        fds[i] = FrameDesc{pos, (uint32_t)src_len[i], (uint32_t)po, pl, 0};
-        for (uint64_t k = 0; k < src_len[i]; k += SEG_SIZE)
-            places.push_back(PlaceDescH{src_off[i] + k, pos + pl + k, (uint32_t)std::min<uint64_t>(SEG_SIZE, src_len[i] - k), 0});
-        pos += pl + src_len[i] + 16;
+        for (uint64_t o = 0; o < src_len[i]; o += CH) {
+            const uint64_t cl = std::min<uint64_t>(CH, src_len[i] - o);
+            const bool last = o + cl == src_len[i];
+            const size_t pk = blob.size();
+            if (o == 0 && !meta_len(meta, i)) frame_entry_prefix(blob, names[i], PNA_ALGO_STORE, src_len[i], (uint32_t)cl);
+            else if (o == 0) { tmp.clear(); frame_entry_prefix(tmp, names[i], PNA_ALGO_STORE, src_len[i], (uint32_t)cl); splice_meta(tmp, meta, i); blob.insert(blob.end(), tmp.begin(), tmp.end()); }
+            else { const uint8_t h[8] = {(uint8_t)(cl >> 24), (uint8_t)(cl >> 16), (uint8_t)(cl >> 8), (uint8_t)cl, 'F', 'D', 'A', 'T'}; blob.insert(blob.end(), h, h + 8); }
+            const uint32_t pl = (uint32_t)(blob.size() - pk);
+            fds.push_back(FrameDesc{pos, (uint32_t)cl, (uint32_t)pk, pl, last ? 0u : 2u});
+            for (uint64_t k = 0; k < cl; k += SEG_SIZE)
+                places.push_back(PlaceDescH{src_off[i] + o + k, pos + pl + k, (uint32_t)std::min<uint64_t>(SEG_SIZE, cl - k), 0});
+            pos += pl + cl + (last ? 16 : 4);
+        }
     }
+    if (blob.size() > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "the inner entries' framing exceeds 4 GiB");
+    const size_t nfd = fds.size();
     const uint64_t plain_len = pos;
-    if (c->solid_plain.ensure(plain_len + 8192) || c->solid_desc.ensure(n * sizeof(FrameDesc) + 16) || c->solid_blob.ensure(blob.size() + 16) ||
+    if (c->solid_plain.ensure(plain_len + 8192) || c->solid_desc.ensure(nfd * sizeof(FrameDesc) + 16) || c->solid_blob.ensure(blob.size() + 16) ||
         c->solid_place.ensure(places.size() * sizeof(PlaceDescH) + 16)) return fail(c, PNA_E_NOMEM, "solid workspace");
     int rc = ensure_crc(c); if (rc) return rc;
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->solid_desc.p, fds.data(), n * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->solid_desc.p, fds.data(), nfd * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(c->solid_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
         if (!places.empty()) HIPCHK(c, hipMemcpyAsync(c->solid_place.p, places.data(), places.size() * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
-        launch_place(c->solid_place.p, (uint32_t)places.size(), (const uint8_t *)d_src, (uint8_t *)c->solid_plain.p, st);
-        launch_frame((const FrameDesc *)c->solid_desc.p, (uint32_t)n, (const uint8_t *)c->solid_blob.p, (const CrcTabs *)c->crc_tabs.p,
+        // (chunks cut by max_chunk start at any byte of their entry: k_gather takes any alignment on both sides, k_place wants 16-byte aligned sources)
+        if (cut) launch_gather(c->solid_place.p, (uint32_t)places.size(), (const uint8_t *)d_src, (uint8_t *)c->solid_plain.p, st);
+        else launch_place(c->solid_place.p, (uint32_t)places.size(), (const uint8_t *)d_src, (uint8_t *)c->solid_plain.p, st);
+        launch_frame((const FrameDesc *)c->solid_desc.p, (uint32_t)nfd, (const uint8_t *)c->solid_blob.p, (const CrcTabs *)c->crc_tabs.p,
                      (uint8_t *)c->solid_plain.p, (uint64_t)c->solid_plain.cap & ~(uint64_t)15, frame_fend_crc(), "FDAT", true, st, solid_max_inner);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(st));                     // the host vectors above are read by the async copies

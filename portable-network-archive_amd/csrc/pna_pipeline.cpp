@@ -76,22 +76,29 @@ struct SolidAssembler {
 };
 }
 // ---- the stream's layout
-static SolidLayout solid_layout(size_t n, const char *const *names, const size_t *src_len) {
+// (the tree form: `recs` holds the finished records of the inner entries that are not files -- blob spans like any framing bytes, which a window edge may cut
+// anywhere --, `meta` the files' metadata chunks, max_chunk FlattenWriter's cut of their data)
+static SolidLayout solid_layout(size_t n, const char *const *names, const size_t *src_len, const EntryRecords *recs = nullptr, const pna_gpu_entry_meta *meta = nullptr, uint32_t max_chunk = 0) {
     SolidLayout L;
     std::vector<uint8_t> &blob = L.blob;
-    const uint64_t CH = 0xFFFFFFFBull;
+    std::vector<uint8_t> tmp;
+    const uint64_t CH = chunk_limit(max_chunk);
     uint64_t pos = 0;
     uint8_t fend[12] = {0, 0, 0, 0, 'F', 'E', 'N', 'D', 0, 0, 0, 0};
     { const uint32_t fc = frame_fend_crc(); fend[8] = (uint8_t)(fc >> 24); fend[9] = (uint8_t)(fc >> 16); fend[10] = (uint8_t)(fc >> 8); fend[11] = (uint8_t)fc; }
     auto lit = [&](size_t from) { const uint64_t l = blob.size() - from; L.spans.push_back(SolidSpan{pos, l, 0u, 0u, (uint64_t)from, 0}); pos += l; };
     for (size_t i = 0; i < n && L.chunks.size() <= 0x7FFFFFF0u; i++) {                         // (more chunks than that: refused by the caller)
         const size_t b0 = blob.size();
-        if (src_len[i] == 0) { frame_inner_entry_empty(blob, names[i]); lit(b0); continue; }
+        if (recs && recs->len(i)) { blob.insert(blob.end(), recs->at(i), recs->at(i) + recs->len(i)); lit(b0); continue; }
+        const bool with_meta = meta_len(meta, i) != 0;
+        if (src_len[i] == 0 && !with_meta) { frame_inner_entry_empty(blob, names[i]); lit(b0); continue; }
+        if (src_len[i] == 0) { tmp.clear(); frame_inner_entry_empty(tmp, names[i]); splice_meta(tmp, meta, i); blob.insert(blob.end(), tmp.begin(), tmp.end()); lit(b0); continue; }
         const uint64_t len = src_len[i];
         for (uint64_t o = 0; o < len; o += CH) {
             const uint64_t cl = std::min<uint64_t>(CH, len - o);
             const size_t b1 = blob.size();
-            if (o == 0) frame_entry_prefix(blob, names[i], PNA_ALGO_STORE, len, (uint32_t)cl);
+            if (o == 0 && !with_meta) frame_entry_prefix(blob, names[i], PNA_ALGO_STORE, len, (uint32_t)cl);
+            else if (o == 0) { tmp.clear(); frame_entry_prefix(tmp, names[i], PNA_ALGO_STORE, len, (uint32_t)cl); splice_meta(tmp, meta, i); blob.insert(blob.end(), tmp.begin(), tmp.end()); }
             else { const uint8_t h[8] = {(uint8_t)(cl >> 24), (uint8_t)(cl >> 16), (uint8_t)(cl >> 8), (uint8_t)cl, 'F', 'D', 'A', 'T'}; blob.insert(blob.end(), h, h + 8); }
             lit(b1);
             const uint32_t ci = (uint32_t)L.chunks.size();
@@ -185,10 +192,12 @@ static int solid_window_compress(SolidRun &r, uint64_t k, const SolidWin &w, Sol
     if (next.t.joinable()) next.t.join();
     return rc ? rc : sink_put(c, r.sink, r.user, c->hp_out[k & 1].p, (size_t)offs[1]);
 }
+// the tree arguments of the solid host forms (all NULL / 0: the plain forms)
+struct SolidTree { const pna_gpu_entry_meta *meta = nullptr; uint32_t max_chunk = 0; const pna_gpu_entry_kinds *kinds = nullptr; const EntryRecords *recs = nullptr; };
 static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
-                        const pna_gpu_cipher *cipher, const uint8_t *ivs, pna_sink_fn sink, void *user) {
+                        const pna_gpu_cipher *cipher, const uint8_t *ivs, pna_sink_fn sink, void *user, const SolidTree &tree = SolidTree{}) {
     set_call_level(c, algo, level);
-    SolidRun r{c, algo, cipher, ivs, sink, user, solid_layout(n, names, src_len), {}};
+    SolidRun r{c, algo, cipher, ivs, sink, user, solid_layout(n, names, src_len, tree.recs, tree.meta, tree.max_chunk), {}};
     if (r.L.chunks.size() > 0x7FFFFFF0u) return fail(c, PNA_E_INVAL, "too many data chunks");
     // the fixed chunks around the stream (GCM: the stream header is the stream's first SDAT chunk, as in the device form)
     std::vector<uint8_t> head, tail;
@@ -226,18 +235,18 @@ static void parallel_stage(uint8_t *dst, const void *const *src, const size_t *s
 // no entries, or zstd's single_frame option (an entry's segments form ONE frame): one H2D of the entries, the device path, one D2H of the archive, handed
 // to the sink in pieces of at most 16 MiB
 static int solid_one_shot(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names, const void *const *src, const size_t *src_len,
-                          const pna_gpu_cipher *cipher, pna_sink_fn sink, void *user) {
+                          const pna_gpu_cipher *cipher, pna_sink_fn sink, void *user, const SolidTree &tree = SolidTree{}) {
     std::vector<uint64_t> off(n + 1), len(n);
     uint64_t pos = 0;
     for (size_t i = 0; i < n; i++) { off[i] = pos; len[i] = src_len[i]; pos = (pos + src_len[i] + 15) & ~(uint64_t)15; }
     off[n] = pos;
-    const size_t cap = pna_gpu_solid_archive_enc_bound(algo, n, names, len.data(), cipher);
+    const size_t cap = pna_gpu_solid_archive_tree_bound(algo, n, names, len.data(), cipher, tree.meta, tree.max_chunk, tree.kinds);
     int rc = Reserve{c}.add(c->stage_in, pos + 8192).add(c->stage_out, cap + 64).add(c->hp_in[0], pos + 64).add(c->hp_out[0], cap + 64).done();
     if (rc) return rc;
     parallel_stage((uint8_t *)c->hp_in[0].p, src, src_len, off.data(), 0, n, staging_threads(c));
     if (pos) HIPCHK(c, hipMemcpyAsync(c->stage_in.p, c->hp_in[0].p, pos, hipMemcpyHostToDevice, c->stream));
     uint64_t total = 0;
-    rc = pna_gpu_create_solid_archive_enc_device(c, algo, level, n, names, c->stage_in.p, off.data(), len.data(), cipher, c->stage_out.p, cap + 64, &total, nullptr);
+    rc = create_solid_device_impl(c, algo, level, n, names, c->stage_in.p, off.data(), len.data(), cipher, tree.meta, tree.max_chunk, tree.kinds, c->stage_out.p, cap + 64, &total, nullptr);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->hp_out[0].p, c->stage_out.p, total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -273,6 +282,31 @@ extern "C" int pna_gpu_create_solid_archive_enc_host(pna_gpu_ctx *c, int algo, i
     pna_gpu_cipher ci = *cipher; ci.ivs = ivs;                  // (IVs drawn here: the one-shot form must not draw others)
     if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, &ci, ivs, sink, user);
     return solid_one_shot(c, algo, level, n, names, src, src_len, &ci, sink, user);
+}
+
+// The tree form (pna_gpu.h "ENTRY KINDS"): directories and links stand between the file records of the inner stream
+extern "C" int pna_gpu_create_solid_archive_tree_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                                      const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                                      const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds,
+                                                      pna_sink_fn sink, void *user) {
+    { int rcm = check_meta(c, meta, n); if (rcm) return rcm; }
+    if (!c || !sink || (n && (!names || !src || !src_len))) return fail(c, PNA_E_INVAL, "null argument");
+    if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
+    EntryRecords recs;
+    { int rck = build_entry_records(c, n, names, (const uint64_t *)src_len, kinds, meta, max_chunk_size, recs); if (rck) return rck; }
+    std::vector<uint8_t> own_ivs;
+    const uint8_t *ivs = nullptr;
+    pna_gpu_cipher ci{};
+    if (cipher) {
+        int rc = resolve_ivs(c, cipher, 1, own_ivs, &ivs); if (rc) return rc;
+        if (cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
+        ci = *cipher; ci.ivs = ivs; cipher = &ci;               // (IVs drawn here: the one-shot form must not draw others)
+    }
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
+    HIPCHK(c, hipSetDevice(c->device));
+    const SolidTree tree{meta, max_chunk_size, kinds, recs.count ? &recs : nullptr};
+    if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, cipher, ivs, sink, user, tree);
+    return solid_one_shot(c, algo, level, n, names, src, src_len, cipher, sink, user, tree);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -336,6 +370,7 @@ struct CreateCall {
     pna_gpu_ctx *c; int algo; size_t n; const char *const *names; const void *const *src; const size_t *src_len;
     const pna_gpu_cipher *cipher; const uint8_t *ivs; const pna_gpu_entry_meta *meta; uint32_t part_flags, max_chunk; pna_sink_fn sink; void *user;
     std::chrono::steady_clock::time_point t_entry, t0;          // PNA_TRACE: the call's start, the pipeline's start
+    const pna_gpu_entry_kinds *kinds = nullptr; EntryRecords recs;      // the tree form: the records of the entries that are not files (built by create_check)
     void trace(const char *what, size_t k) const {
         if (c->tun.trace) fprintf(stderr, "[pna create] %8.3f ms  %s %zu\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what, k);
     }
@@ -412,6 +447,7 @@ static int create_check(CreateCall &k, int level, std::vector<uint8_t> &own_ivs)
     pna_gpu_ctx *c = k.c;
     { int rcm = check_meta(c, k.meta, k.n); if (rcm) return rcm; }
     if (!c || !k.sink || (k.n && (!k.names || !k.src || !k.src_len))) return fail(c, PNA_E_INVAL, "null argument");
+    { int rck = build_entry_records(c, k.n, k.names, (const uint64_t *)k.src_len, k.kinds, k.meta, k.max_chunk, k.recs); if (rck) return rck; }
     if (!encode_algo_ok(c, k.algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     set_call_level(c, k.algo, level);
     if (k.cipher && k.cipher->encryption == PNA_ENC_NONE) k.cipher = nullptr;
@@ -432,6 +468,7 @@ static void capacity_terms(const CreateCall &k, CreatePlan &p) {
     par_ranges(n, plan_nt, [&](unsigned t, size_t a, size_t b) {
         uint64_t tot = 0, mx = 0;
         for (size_t i = a; i < b; i++) {
+            if (k.recs.count && k.recs.len(i)) { p.ecap[i] = k.recs.len(i); continue; }       // not a file: its record and nothing else
             const uint64_t l = k.src_len[i], wb = pna_gpu_bound(k.algo, (size_t)l);
             tot += l; mx = std::max(mx, l);
             uint64_t cap = (k.cipher ? frame_entry_prefix_enc_bound(k.names[i], k.cipher->phsf) + 16 : frame_entry_prefix_bound(k.names[i])) + meta_len(k.meta, i) + wb + 16;
@@ -509,7 +546,8 @@ static int hand_over(const CreateCall &k, CreatePlan &p, int so) {
 // before handed to the sink.  An error exit leaves copies and kernels in flight: the caller stops the stager, then waits for the device.
 static int drain_subbatches(const CreateCall &k, CreatePlan &p, Stager &stager) {
     pna_gpu_ctx *c = k.c;
-    const FrameJob fj{k.names, 0, k.cipher, k.ivs, k.meta, k.max_chunk, false};
+    FrameJob fj{k.names, 0, k.cipher, k.ivs, k.meta, k.max_chunk, false};
+    if (k.recs.count) fj.recs = &k.recs;
     const CallTotalScope call_total(c, p.len64, k.n);                                               // (the block size follows the archive, not its sub-batches)
     uint8_t *dev_view[2] = {nullptr, nullptr};                   // device views of the page-locked output slots (the copy kernel's destination)
     for (size_t i = 0; i < p.subs.size(); i++) {
@@ -546,10 +584,12 @@ static int create_finish(const CreateCall &k, CreatePlan &p, const std::vector<u
 }
 static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                     const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
-                                    const pna_gpu_entry_meta *meta, uint32_t part_flags, pna_sink_fn sink, void *user, uint32_t max_chunk) {
+                                    const pna_gpu_entry_meta *meta, uint32_t part_flags, pna_sink_fn sink, void *user, uint32_t max_chunk,
+                                    const pna_gpu_entry_kinds *kinds = nullptr) {
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     CreateCall k{c, algo, n, names, src, src_len, cipher, nullptr, meta, part_flags, max_chunk, sink, user, clk::now(), {}};
+    k.kinds = kinds;
     std::vector<uint8_t> own_ivs;
     int rc = create_check(k, level, own_ivs); if (rc) return rc;
     c->timing = pna_gpu_timing{};
@@ -592,6 +632,11 @@ extern "C" int pna_gpu_create_archive_chunked_host(pna_gpu_ctx *c, int algo, int
                                                    const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
                                                    const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, uint32_t part_flags, pna_sink_fn sink, void *user) {
     return create_archive_host_impl(c, algo, level, n, names, src, src_len, cipher, meta, part_flags, sink, user, max_chunk_size);
+}
+extern "C" int pna_gpu_create_archive_tree_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
+                                                const void *const *src, const size_t *src_len, const pna_gpu_cipher *cipher,
+                                                const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds, uint32_t part_flags, pna_sink_fn sink, void *user) {
+    return create_archive_host_impl(c, algo, level, n, names, src, src_len, cipher, meta, part_flags, sink, user, max_chunk_size, kinds);
 }
 extern "C" int pna_gpu_create_archive_part_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                 const void *const *src, const size_t *src_len, uint32_t part_flags, pna_sink_fn sink, void *user) {
