@@ -180,6 +180,44 @@ int  pna_gpu_clamp_level(int algo, int level);
  *   (pna_gpu_stream_*) and pna_gpu_stream_entry_*; xz blocks smaller than a segment, other lc / lp / pb, an optimal parse: not built.
  * pna_gpu_last_timing of an xz call: ms_lz the LZ stage, ms_stats the CRC64 kernel, ms_lit the chunk coder, ms_seq sizes and offsets. */
 
+/* STORED ENTRIES ON THE DEVICE (PNA_ALGO_STORE; the reference: Compression::No, `pna create --store`, CompressionWriter's arm without an encoder).  No codec
+ * runs and the level is ignored (pna_gpu_clamp_level(PNA_ALGO_STORE, x) = 0): every payload length is known on the host, so the layout needs no device scan
+ * and no read-back, and a payload goes from the source buffer to its place in the archive in ONE pass (k_store.hip) that also leaves the CRC-32 of what it
+ * moved; k_store_fold turns those into the FDAT CRC fields and FEND.  Under a cipher the copy runs alone, the cipher stage works on the payloads where they
+ * stand and the chunk CRC is taken over the ciphertext (k_frame), as on the compressed paths.
+ *   record      FHED(kind 0, compression 0, enc, mode) | extra | fSIZ | facets | [PHSF] | [FDAT(iv or GCM stream header)] | FDAT(payload)* | FEND, byte-exact with
+ *               the reference for given IVs; the payload stream is cut at max_chunk_size as FlattenWriter cuts it.  An empty file without a cipher has NO FDAT
+ *               (FlattenWriter ignores empty writes), with CTR the IV chunk alone, with CBC the IV chunk and one padding block, with GCM STREAM the header and the
+ *               empty final segment's tag.  As for the other algos a CBC or GCM entry must fit one chunk, and the IV / stream header is one chunk whatever
+ *               max_chunk_size says.
+ *   taken by    pna_gpu_create_archive_device and its _part, _enc, _meta, _chunked and _tree forms; pna_gpu_create_archive_host and its _enc, _meta, _chunked,
+ *               _part and _tree forms; every pna_gpu_archive_*_bound (never below the bytes written).  Like every other algo a destination needs 16 bytes of room
+ *               behind the last record wherever k_frame runs -- under a cipher and, without one, in the unfused form (option "store_unfused"; the default picks it
+ *               for sub-batches whose longest chunk lies between 4 KiB and 1 MiB); only a call whose sub-batches all take the fused form gets by with a
+ *               destination of exactly the archive's size.  Size the destination with the bound functions.  pna_gpu_append_archive_host reaches the _part form
+ *               unchanged and takes PNA_ALGO_STORE with it.  AES in all three modes; Camellia under option "camellia", as elsewhere.  The device forms want
+ *               16-byte aligned src_off, as for every algo.
+ *   solid       pna_gpu_create_solid_archive_device, _enc_device and _tree_device: the serialised inner records ARE the stream -- k_store writes the inner payloads
+ *               at their places in the destination's SDAT bodies, the inner FDAT CRCs come from the fold, nothing is copied twice.  SHED(compression 0, ..) |
+ *               [PHSF] | [SDAT(iv / header)] | SDAT* | SEND, the stream cut into SDAT chunks of max_chunk_size bytes (default: one chunk up to 2^32 - 5 bytes;
+ *               GCM STREAM: one chunk per segment).  For a stream of one chunk without a cipher the bytes are pna_create_archive(.., PNA_ALGO_STORE, solid = 1, ..)'s.
+ *               The reference's own SDAT cut follows the write calls of its chunk writer and is not reproduced: as for every compressed solid stream here the
+ *               guarantee is the decoded inner stream, not the SDAT boundaries.  CTR and GCM as for the other algos, CBC stays PNA_E_UNSUPPORTED.
+ *               pna_gpu_create_solid_archive_host, _enc_host and _tree_host stream the stored stream in windows of "solid_win_mib" MiB like the compressed ones
+ *               (GCM STREAM: of whole segments): a window's bytes go out as the parts of the SDAT chunks they belong to, the CRC register of a chunk that spans
+ *               windows is chained from window to window and its CRC written with its last byte (k_crc_patch).  The bytes equal the device form's at every
+ *               window size.
+ *   not covered pna_create_archive keeps its host loop for PNA_ALGO_STORE (it needs no GPU).  pna_gpu_compress_batch[_device], pna_gpu_compress_solid, the
+ *               streaming facade (pna_gpu_stream_*), pna_gpu_stream_entry_* and pna_gpu_create_archive_multi_host answer PNA_E_UNSUPPORTED as before.
+ *   option      "store_unfused" [PNA_STORE_UNFUSED] which form payloads without a cipher take -- 0: the fused k_store + k_store_fold (one read of the payload);
+ *               1: the copy-only form and k_frame (two reads, a chunk's CRC on one workgroup); -1 (default): per sub-batch by its longest data chunk -- fused
+ *               above 1 MiB (a large entry is not CRC'd by one workgroup) and up to 4 KiB, unfused between: 10 000 x 1 MiB measured 8.6 ms unfused against
+ *               12.2 ms fused, one entry of 4 GiB 839 ms against 4.6 ms (profiles/store_rate.txt).  The bytes are the same.  Stored solid streams always
+ *               take the fused form for their inner payloads.
+ * pna_gpu_debug_store_stats: the context's latest create call with PNA_ALGO_STORE (any pointer may be NULL) -- pieces (of at most 1 MiB of one data chunk) that
+ * went through the fused k_store, pieces through its copy-only form, data chunks folded by k_store_fold, HIP-event milliseconds of the k_store launches. */
+int  pna_gpu_debug_store_stats(pna_gpu_ctx *ctx, uint64_t *pieces_fused, uint64_t *pieces_copy_only, uint64_t *chunks_folded, double *ms_k_store);
+
 /* ---- batch of independent entries: the data-parallel fan-out of spawn_entry_results()/create_entry()
  * (cli/src/command/core.rs:496-537,915-977).  Entry i becomes one independent stream in dst[i]
  * (zstd: concatenated frames; deflate: one zlib stream), exactly what FileEntryBuilder::build() hands to

@@ -19,7 +19,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PNA_GPU_LIB") or os.path.join(_HERE, "libpna_gpu.so")
 
 PNA_OK = 0
-ALGO_STORE, ALGO_DEFLATE, ALGO_ZSTD = 0, 1, 2
+ALGO_STORE, ALGO_DEFLATE, ALGO_ZSTD = 0, 1, 2                   # ALGO_STORE (Compression::No): written on the device by the archive entry points -- Context.create_archive_device,
+#   create_archive_chunked[_device], create_archive_encrypted, create_archive_with_metadata, create_archive_tree[_device] and the solid forms (store_stats tells which
+#   form of k_store ran); create_archive(None or ctx, .., algo=ALGO_STORE) keeps the host loop; compress_batch*, compress_solid, writer, write_file and create_archive_multi refuse it
 ALGO_XZ = 4                                                      # Compression::XZ: decoded everywhere; written by compress_batch* and the non-solid create_archive* on a context with set_option("xz_encode", 1)
 LEVEL_DEFAULT = -1000
 # error codes of include/pna_gpu.h
@@ -257,7 +259,7 @@ EXPORTS = [
     # extract of chosen entries, to host or device (include/pna_gpu.h)
     "pna_gpu_extract_select_host", "pna_extract_plan_runs", "pna_gpu_debug_extract_stats", "pna_gpu_debug_pick_device",
     # key derivation on the device (include/pna_gpu.h)
-    "pna_gpu_kdf_batch", "pna_phsf_parse", "pna_gpu_debug_kdf_stats",
+    "pna_gpu_kdf_batch", "pna_phsf_parse", "pna_gpu_debug_kdf_stats", "pna_gpu_debug_store_stats",
     # entry kinds: directories, symbolic links, hard links in the create calls (include/pna_gpu.h, include/pna_archive.h)
     "pna_gpu_entry_kinds_check", "pna_gpu_archive_tree_bound", "pna_gpu_create_archive_tree_device", "pna_gpu_create_archive_tree_host",
     "pna_gpu_solid_archive_tree_bound", "pna_gpu_create_solid_archive_tree_device", "pna_gpu_create_solid_archive_tree_host", "pna_archive_entry_record_bytes",
@@ -400,6 +402,8 @@ def load_library() -> ctypes.CDLL:
     L.pna_phsf_parse.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(KdfJob), ctypes.c_char_p, sz, ctypes.POINTER(sz)]
     L.pna_gpu_debug_kdf_stats.restype = ctypes.c_int
     L.pna_gpu_debug_kdf_stats.argtypes = [vp, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
+    L.pna_gpu_debug_store_stats.restype = ctypes.c_int
+    L.pna_gpu_debug_store_stats.argtypes = [vp, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
     L.pna_gpu_debug_extract_stats.restype = ctypes.c_int
     L.pna_gpu_debug_extract_stats.argtypes = [vp, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_double)]
     L.pna_gpu_debug_pick_device.restype = ctypes.c_int
@@ -1430,6 +1434,16 @@ def kdf_stats(ctx: Context):
     d, h, r, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
     ctx._check(ctx._L.pna_gpu_debug_kdf_stats(ctx._h, ctypes.byref(d), ctypes.byref(h), ctypes.byref(r), ctypes.byref(ms)))
     return d.value, h.value, r.value, ms.value
+
+
+def store_stats(ctx: Context):
+    """(pieces through the fused k_store, pieces through its copy-only form, data chunks folded by k_store_fold, k_store's HIP-event milliseconds) of the
+    context's latest create call with ALGO_STORE, solid or not (pna_gpu_debug_store_stats), summed over the call's sub-batches: stored payloads without a
+    cipher take the fused form, those under a cipher the copy-only one (their CRC is k_frame's, over the ciphertext); the inner payloads of a stored solid
+    stream always take the fused form (the cipher runs over the stream afterwards)."""
+    f, c, n, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
+    ctx._check(ctx._L.pna_gpu_debug_store_stats(ctx._h, ctypes.byref(f), ctypes.byref(c), ctypes.byref(n), ctypes.byref(ms)))
+    return f.value, c.value, n.value, ms.value
 
 
 def kdf_argon2(kind: int, password: bytes, salt: bytes, t_cost: int, m_cost_kib: int, lanes: int, key_len: int = 32) -> bytes:

@@ -57,6 +57,12 @@ void launch_frame(const FrameDesc *fd, uint32_t nentry, const uint8_t *blob, con
                   uint32_t fend_crc, const char ty[4], bool with_fend, hipStream_t st, uint32_t max_payload);
 void launch_place(const void *pd, uint32_t n, const uint8_t *src, uint8_t *dst, hipStream_t st);
 void launch_gather(const void *pd, uint32_t n, const uint8_t *src, uint8_t *dst, hipStream_t st);
+// Compression::No (k_store.hip; weak like launch_diff: the sanitizer build has no stand-ins for them, and without them PNA_ALGO_STORE stays unsupported on the
+// archive entry points).  pieces: StorePiece x n; with_crc: the fused form, states[i] = the raw CRC register of piece i; chunks: StoreChunk x n
+__attribute__((weak)) void launch_store(const void *pieces, uint32_t n, const uint8_t *src, uint8_t *dst, const CrcTabs *ct, uint32_t *states, bool with_crc, hipStream_t st);
+// (sd_ch != 0: the inner records of a stored solid stream -- StoreChunk::crc_off counts in the stream, whose position p stands at sd_base + p + sd_ovh * (p / sd_ch) of dst)
+__attribute__((weak)) void launch_store_fold(const void *chunks, uint32_t n, const uint32_t *states, const void *pieces, const char ty[4], uint32_t fend_crc, uint8_t *dst, hipStream_t st,
+                                             uint64_t sd_base = 0, uint64_t sd_ch = 0, uint64_t sd_ovh = 0);
 void launch_link_copy(const uint8_t *src, uint8_t *dst, size_t n, uint32_t wgs, hipStream_t st);
 void launch_link_gather(const void *segs, uint32_t nseg, uint32_t wgs, hipStream_t st);   // k_frame.hip: {src, dst, len} x nseg, page-locked sources
 void launch_layout(FrameDesc *fd, uint8_t *blob, const uint32_t *entry_seg, const uint64_t *seg_off, uint32_t nentry, uint32_t nseg, uint64_t out_base,
@@ -224,7 +230,7 @@ struct Tuning {
     long lz_split_min = 0;           // PNA_LZ_SPLIT_MIN: shortest run (segments) that takes the split form (0: every run; shorter ones take the one-kernel form)
     long lz_pbuf_fail = 0;           // PNA_LZ_PBUF_FAIL: testing -- behave as if the words workspace could not be allocated
     long max_chunk_size = 0;         // PNA_MAX_CHUNK_SIZE: FlattenWriter::max_chunk_size of the archive entry points without such a parameter (0 = the reference's default, u32::MAX)
-    long sub_mib = 256;              // PNA_SUB_MIB: largest sub-batch (input bytes) of the bounded host pipeline
+    long sub_mib = 256;              // PNA_SUB_MIB: largest sub-batch (input bytes) of the bounded host pipeline (1 .. 16 384; the small end is for tests)
     long stage_threads = 0;          // PNA_STAGE_THREADS: host threads that stage entries into page-locked memory (0: min(8, cores / 2))
     long extract_win_mib = 1024;     // PNA_EXTRACT_WIN_MIB: archive bytes per window of the extract driver
     long diff_slot_mib = 256;        // PNA_DIFF_SLOT_MIB: pna_gpu_diff_archive_host carries the files' bytes to the device through two page-locked slots of this many MiB (and two device slots)
@@ -262,6 +268,7 @@ struct Tuning {
     long camellia = 0;               // PNA_CAMELLIA: 1: Encryption::CAMELLIA (Camellia-256 in CTR, CBC and GCM STREAM; k_cipher.hip) is written by the entry points that take a cipher and read by extract / verify / diff / extract-select; 0 (default): PNA_E_UNSUPPORTED / PNA_VERIFY_UNSUPPORTED, as before
     long kdf_device = 0;             // PNA_KDF_DEVICE: 0 (default): the read-side drivers derive every key on the host, one PHSF string after the other; N >= 1: a window's not yet derived PHSF strings go through pna_gpu_kdf_batch (k_kdf.hip) when there are at least N of them
     long kdf_mem_mib = 0;            // PNA_KDF_MEM_MIB: the cap of pna_gpu_kdf_batch's Argon2 block memory; 0 (default): a quarter of the device's free memory at the first batch, at most 32 GiB
+    long store_unfused = -1;         // PNA_STORE_UNFUSED: stored payloads without a cipher -- 0: the fused k_store + k_store_fold (one read of the payload); 1: k_store's copy-only form and k_frame (two reads; a chunk is CRC'd by ONE workgroup); -1 (default): per sub-batch by its longest data chunk -- fused above 1 MiB and up to 4 KiB, unfused between, as measured in profiles/store_rate.txt; the bytes are the same
     long hist_by_block = -1;         // PNA_HIST_BY_BLOCK: zstd entropy stage in its per-block form (1: k_hist, k_seqa, k_seqb) or its per-segment form (0: k_stats, k_seq); -1: by batch size
 };
 struct TuningName { const char *name, *env; long Tuning::*field; long lo, hi; };
@@ -333,6 +340,10 @@ struct pna_gpu_ctx {
     DevBuf cam_tabs, ci_ckeys; bool cam_ready = false;         // ... for Camellia (option camellia): its four tables, GCM's per-segment schedules (SegKeys)
     hipEvent_t ev_ci[2] = {};
     DevBuf solid_plain, solid_desc, solid_blob, solid_place;   // serialised inner entries of a solid archive
+    // Compression::No (store_subbatch): the pieces, the framing bytes' places, the chunks and the pieces' CRC registers; the event pair around k_store; the
+    // latest call's counters (pna_gpu_debug_store_stats); option store_unfused: plain payloads take the copy-only form + k_frame
+    DevBuf st_pieces, st_lits, st_chunks, st_states; hipEvent_t st_ev[2] = {};
+    uint64_t st_fused = 0, st_copy_only = 0, st_folded = 0; double st_ms = 0;
     DevBuf solid_adler;                                        // deflate solid from host memory: the stream's Adler-32 carried from window to window
     DevBuf solid_carry;                                        // GCM solid from host memory: the tail of a window's output not yet cut into a segment
     DevBuf z_ents, z_frames, z_lit;                            // decoder descriptors, literal scratch
@@ -408,6 +419,9 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
                   uint64_t stream_len = 0; uint32_t run = 0; uint32_t *adler_carry = nullptr;
                   // ... with a cipher: where the window stands in the cipher stream, updated by layout_solid (SolidCipherRun)
                   struct SolidCipherRun *crun = nullptr;
+                  // ... stored (PNA_ALGO_STORE): where the window stands in the stream and the CRC register of the SDAT chunk that is open across the window edge,
+                  // updated by store_solid_window (SolidStoreRun); max_chunk then also cuts the stream into SDAT chunks
+                  struct SolidStoreRun *srun = nullptr;
                   // the tree entry points: the call's non-file records (NULL: every entry is a file).  Such an entry has no segments, no cipher unit, no IV drawn
                   const EntryRecords *recs = nullptr; };
 // The cipher state of a solid stream compressed in windows.  CTR: `pos`, the stream offset of the window's first compressed byte (the keystream
@@ -415,6 +429,9 @@ struct FrameJob { const char *const *names; int solid; const pna_gpu_cipher *cip
 // 1 .. G once the stream has begun, in device memory) the tail of the output before that is not yet known to be a non-final segment, placed in
 // front of the window's output; `final_win`: nothing follows the window, its last segment carries the final flag.  layout_solid advances
 // pos, seg and carry_len past the window.
+// The state of a STORED solid stream that travels in windows: `pos`, the stream position of the window's first byte; `state` / `started`: the raw CRC register of
+// the SDAT chunk that began in an earlier window and has not ended yet (chained with CRC(A || B) = x^(8|B|) CRC(A) + CRC(B), as the inner chunks are).
+struct SolidStoreRun { uint64_t pos = 0; uint32_t state = 0; bool started = false; };
 struct SolidCipherRun { uint64_t pos = 0, seg = 0, carry_len = 0; uint8_t *carry = nullptr; bool final_win = false; };
 // A block cipher's key schedule as a value (pna_cipher.cpp): which cipher (a PNA_ENC_* id) and its schedule.  cipher_ctr / cipher_cbc_enc / cipher_cbc_dec
 // turn the id into a kernel, block() into the host's block function; nobody else asks which cipher it is.
@@ -453,8 +470,10 @@ struct SubPlan {
 // pna_lz.cpp -- the host side of the LZ stage: the level's parameter set (algo: zstd or deflate; xz: zstd's with LZMA's match cap), and the stage over one sub-batch
 LzSet lz_level_set(const pna_gpu_ctx *c, int algo, int level, bool xz);
 int lz_run(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const SubPlan &p, hipStream_t st, bool timed);
-// what the compress entry points take: zstd, deflate and -- with option xz_encode, on the batch and the non-solid archive entry points -- xz
-inline bool encode_algo_ok(const pna_gpu_ctx *c, int algo) {
+// what the compress entry points take: zstd, deflate and -- with option xz_encode, on the batch and the non-solid archive entry points -- xz; `archive`: the
+// non-solid archive entry points, which write stored entries too (run_subbatch's codec-free branch)
+inline bool encode_algo_ok(const pna_gpu_ctx *c, int algo, bool archive = false) {
+    if (algo == PNA_ALGO_STORE) return archive && launch_store && launch_store_fold;
     return algo == PNA_ALGO_ZSTD || algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_XZ && c && c->tun.xz_encode != 0 && launch_xzenc_stage && launch_xzenc_write);
 }
 inline size_t plan_blocks(const pna_gpu_ctx *c, uint64_t len) {

@@ -241,6 +241,14 @@ struct DiffPiece {
     uint32_t entry, tile0;
 };
 static_assert(sizeof(DiffPiece) == 40, "DiffPiece layout");
+// k_store / k_store_fold (Compression::No on the create paths, k_store.hip).  A piece: bytes [src_off, src_off + len) of the source buffer go to
+// [dst_off, dst_off + len) of the archive buffer, len <= STORE_PIECE, any alignment on either side; it never crosses a data chunk's end.  A chunk: its
+// pieces are states[first .. first + npieces), every one STORE_PIECE bytes long but the last; len: its data bytes; crc_off: where its CRC field stands
+// (behind the data); flags bit 0: the chunk is its entry's last, FEND follows the CRC; bit 1: the pieces have the lengths of the piece list (a cut that is not the chunk's fell into it).
+constexpr uint32_t STORE_PIECE = 1u << 20;
+struct StorePiece { uint64_t src_off, dst_off; uint32_t len, pad; };
+struct StoreChunk { uint64_t crc_off, len; uint32_t first, npieces, flags, pad; };
+static_assert(sizeof(StorePiece) == 24 && sizeof(StoreChunk) == 32, "k_store descriptor layout");
 // k_pick (pna_gpu_extract_select_host's device destinations): bytes [src_off, src_off + len) of the launch's source buffer go to dst[0 .. len), any
 // alignment on either side.  A piece is PICK_TILE-byte tiles tile0, tile0 + 1, ... of the launch.
 constexpr uint32_t PICK_TILE = 16384;

@@ -7,7 +7,7 @@ static const TuningName TUNING_NAMES[] = {
     {"lz_split", "PNA_LZ_SPLIT", &Tuning::lz_split, 0, 2}, {"lz_split_blocks", "PNA_LZ_SPLIT_BLOCKS", &Tuning::lz_split_blocks, 8, 1 << 17},
     {"lz_split_min", "PNA_LZ_SPLIT_MIN", &Tuning::lz_split_min, 0, 1 << 30}, {"lz_pbuf_fail", "PNA_LZ_PBUF_FAIL", &Tuning::lz_pbuf_fail, 0, 1},
     {"max_chunk_size", "PNA_MAX_CHUNK_SIZE", &Tuning::max_chunk_size, 0, 0xFFFFFFFFl},
-    {"sub_mib", "PNA_SUB_MIB", &Tuning::sub_mib, 16, 16384}, {"stage_threads", "PNA_STAGE_THREADS", &Tuning::stage_threads, 0, 64},
+    {"sub_mib", "PNA_SUB_MIB", &Tuning::sub_mib, 1, 16384}, {"stage_threads", "PNA_STAGE_THREADS", &Tuning::stage_threads, 0, 64},
     {"extract_win_mib", "PNA_EXTRACT_WIN_MIB", &Tuning::extract_win_mib, 1, 1 << 20}, {"batch_piece_mib", "PNA_BATCH_PIECE_MIB", &Tuning::batch_piece_mib, 0, 1 << 20}, {"solid_win_mib", "PNA_SOLID_WIN_MIB", &Tuning::solid_win_mib, 1, 1 << 16}, {"diff_slot_mib", "PNA_DIFF_SLOT_MIB", &Tuning::diff_slot_mib, 1, 1 << 14},
     {"inflate_serial", "PNA_INFLATE_SERIAL", &Tuning::inflate_serial, 0, 1}, {"zdec_serial", "PNA_ZDEC_SERIAL", &Tuning::zdec_serial, 0, 1}, {"zdec_dbg", "PNA_ZDEC_DBG", &Tuning::zdec_dbg, 0, 15},
     {"blk_log", "PNA_BLK_LOG", &Tuning::blk_log, 0, PNA_BLK_LOG}, {"unit_log", "PNA_LZ_UNIT_LOG", &Tuning::unit_log, 0, 20},
@@ -15,6 +15,7 @@ static const TuningName TUNING_NAMES[] = {
     {"d2h_wgs", "PNA_D2H_WGS", &Tuning::d2h_wgs, 0, 4096}, {"trace", "PNA_TRACE", &Tuning::trace, 0, 1}, {"dev_layout", "PNA_DEV_LAYOUT", &Tuning::dev_layout, 0, 1}, {"strong_gtab", "PNA_STRONG_GTAB", &Tuning::strong_gtab, 0, 1}, {"win32k", "PNA_WIN32K", &Tuning::win32k, 0, 2}, {"tab3", "PNA_TAB3", &Tuning::tab3, 0, 1}, {"far1", "PNA_FAR1", &Tuning::far1, 0, 1}, {"seq_hist", "PNA_SEQ_HIST", &Tuning::seq_hist, 0, 1}, {"strong2", "PNA_STRONG2", &Tuning::strong2, 0, 1}, {"small_geometry", "PNA_SMALL_GEOMETRY", &Tuning::small_geometry, 0, 1}, {"mtile", "PNA_MTILE", &Tuning::mtile, 0, 2048}, {"zexec_par_min_mib", "PNA_ZEXEC_PAR_MIN_MIB", &Tuning::zexec_par_min_mib, 0, 1 << 20}, {"zexec_win_mib", "PNA_ZEXEC_WIN_MIB", &Tuning::zexec_win_mib, 1, 1024}, {"zdec_fallback_max_mib", "PNA_ZDEC_FALLBACK_MAX_MIB", &Tuning::zdec_fallback_max_mib, 0, 1 << 30}, {"stream_batch_mib", "PNA_STREAM_BATCH_MIB", &Tuning::stream_batch_mib, 1, 1 << 16}, {"stream_gather_wgs", "PNA_STREAM_GATHER_WGS", &Tuning::stream_gather_wgs, 0, 4096}, {"stream_overlap_mib", "PNA_STREAM_OVERLAP_MIB", &Tuning::stream_overlap_mib, 0, 1 << 16}, {"single_frame", "PNA_SINGLE_FRAME", &Tuning::single_frame, 0, 1}, {"lazy2", "PNA_LAZY2", &Tuning::lazy2, 0, 2}, {"tail_units", "PNA_TAIL_UNITS", &Tuning::tail_units, 0, 1}, {"lit_beside_seq", "PNA_LIT_BESIDE_SEQ", &Tuning::lit_beside_seq, 0, 1},
     {"xz_encode", "PNA_XZ_ENCODE", &Tuning::xz_encode, 0, 1}, {"camellia", "PNA_CAMELLIA", &Tuning::camellia, 0, 1},
     {"kdf_device", "PNA_KDF_DEVICE", &Tuning::kdf_device, 0, 1 << 30}, {"kdf_mem_mib", "PNA_KDF_MEM_MIB", &Tuning::kdf_mem_mib, 0, 32768},
+    {"store_unfused", "PNA_STORE_UNFUSED", &Tuning::store_unfused, -1, 1},
 };
 
 extern "C" const char *pna_gpu_strerror(int code) {
@@ -112,6 +113,8 @@ extern "C" void pna_gpu_shutdown(pna_gpu_ctx *c) {
     for (auto &e : c->df_ev_k) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->df_tev) if (e) (void)hipEventDestroy(e);
     c->xs_pieces.release();
+    for (DevBuf *b : {&c->st_pieces, &c->st_lits, &c->st_chunks, &c->st_states}) b->release();
+    for (auto &e : c->st_ev) if (e) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->xz_in, &c->xz_scan, &c->xz_blocks, &c->xz_pieces, &c->xz_acc, &c->cam_tabs, &c->ci_ckeys, &c->kdf_mem, &c->kdf_jobs, &c->kdf_seeds, &c->kdf_fin}) b->release();
     for (auto &e : c->kdf_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->xs_tev) if (e) (void)hipEventDestroy(e);
@@ -176,6 +179,7 @@ static uint32_t level_flags(const pna_gpu_ctx *c, int algo, int level) {
 // xz runs the LZ stage of a zstd level (matches capped at LZMA's 273 bytes): xz 0 the fast set, 1..3 the default set, 4..6 the high set, 7..9 the max set
 static const int XZ_LZ_LEVEL[10] = {1, 3, 3, 3, 6, 6, 6, 10, 10, 10};
 void set_call_level(pna_gpu_ctx *c, int algo, int level) {
+    if (algo == PNA_ALGO_STORE) { c->call_xz = c->call_stored = false; return; }              // no codec runs: the level means nothing (pna_gpu_clamp_level: 0)
     c->call_xz = algo == PNA_ALGO_XZ;
     if (c->call_xz) { level = XZ_LZ_LEVEL[pna_gpu_clamp_level(PNA_ALGO_XZ, level)]; algo = PNA_ALGO_ZSTD; }
     c->call_flags = level_flags(c, algo, level);
@@ -880,12 +884,224 @@ static int records_subbatch(const SubBatch &sb) {
     HIPCHK(c, hipStreamSynchronize(sb.st));
     return PNA_OK;
 }
+// Compression::No (CompressionWriter's `No` arm, lib/src/compress.rs: the bytes go through as they are): the codec-free sub-batch.  Every payload length is
+// known here, so the whole layout is the host's -- no device scan, no read-back -- and the payloads go from the source buffer straight to their places:
+//   without a cipher   k_store<true> (copy + the pieces' CRC registers) and k_store_fold (the chunks' CRC fields, FEND);
+//                      option store_unfused: k_store<false> and k_frame, the form the fused one is measured against;
+//   with a cipher      k_store<false>, the cipher stage over the payloads where they stand, k_frame over the ciphertext -- as on the compressed paths.
+// The framing bytes (records of entries that are not files, prefixes, the headers of further data chunks) travel in one blob and k_gather puts them down.
+// Record: FHED(kind 0, compression 0, enc, mode) | extra | fSIZ | facets | [PHSF] | [FDAT(iv / GCM header)] | FDAT(payload)* | FEND, the payload stream cut
+// at max_chunk_size as FlattenWriter cuts it.  An empty file without a cipher, or under CTR, has no FDAT of its own (FlattenWriter ignores empty writes);
+// CBC always writes its padding block, GCM STREAM the empty final segment's tag.  GCM segments go where they stand between their tags at once: no spread.
+// One WINDOW of a stored solid stream from host memory (pna_gpu_create_solid_archive_*_host with PNA_ALGO_STORE, pna_pipeline.cpp solid_stream): the window's bytes
+// -- serialised inner records, their CRCs already in place -- are stream positions [pos, pos + len) of a stream of fj->stream_len bytes, and go out as the pieces of
+// the SDAT chunks they belong to: SDAT chunk k holds stream bytes [k SCH, (k + 1) SCH) (SCH = chunk_limit(max_chunk); GCM STREAM: one chunk per segment -- the windows
+// are whole segments, solid_sizes sees to that, so a segment never spans two), its header goes out with its first byte, its CRC with its last.  k_store's copy-only
+// form places the bytes, the cipher runs over them where they stand (CTR: the keystream position is the stream position), k_frame's piece mode takes the raw CRC
+// register of every piece of a chunk, the host chains the registers of a chunk that spans windows (SolidStoreRun) and k_crc_patch writes the CRCs that are
+// complete.  The bytes are create_solid_store's for every window size.
+static int store_solid_window(const SubBatch &sb) {
+    pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const hipStream_t st = sb.st;
+    SolidStoreRun *sr = fj->srun;
+    if (!sr || sb.e1 - sb.e0 != 1 || !launch_store) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    const bool gcm = fj->cipher && fj->cipher->cipher_mode == PNA_MODE_GCM;
+    if (fj->cipher && fj->cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
+    const uint64_t G = gcm ? gcm_seg_size(fj->cipher) : 0, SCH = gcm ? G : chunk_limit(fj->max_chunk), plain_len = fj->stream_len;
+    const uint64_t w0 = sr->pos, w1 = w0 + sb.src_len[sb.e0], so = sb.src_off[sb.e0];
+    if (w1 > plain_len || (gcm && (w0 % G || (w1 % G && w1 != plain_len)))) return fail(c, PNA_E_INVAL, "internal: a stored window does not fit its stream");
+    const uint64_t K = (plain_len + SCH - 1) / SCH;           // SDAT chunks (= GCM segments) of the whole stream
+    std::vector<uint8_t> blob; std::vector<PlaceDescH> lits; std::vector<StorePiece> pieces; std::vector<FrameDesc> fds;
+    struct Part { uint64_t len, crc_at; bool ends; };       // a chunk's piece inside the window: its bytes (tag included), where its CRC goes if the chunk ends here
+    std::vector<Part> parts;
+    SubLayout L;
+    if (gcm) { L.gmat.resize(1); gcm_solid_material(fj->cipher, fj->ivs, PNA_ALGO_STORE, L.gmat[0]); }
+    uint64_t pos = sb.out_base;
+    sb.dst_off[sb.e0] = pos;
+    for (uint64_t k = w0 / SCH; k < K && k * SCH < w1; k++) {
+        const uint64_t cs = k * SCH, ce = std::min(cs + SCH, plain_len), a = std::max(cs, w0), b = std::min(ce, w1);
+        if (a == cs) {
+            uint8_t h[8]; put_be32(h, (uint32_t)(ce - cs + (gcm ? 16 : 0))); memcpy(h + 4, "SDAT", 4);
+            lits.push_back(PlaceDescH{blob.size(), pos, 8u, 0}); blob.insert(blob.end(), h, h + 8); pos += 8;
+        }
+        for (uint64_t o = 0; o < b - a; o += STORE_PIECE) pieces.push_back(StorePiece{so + (a - w0) + o, pos + o, (uint32_t)std::min<uint64_t>(STORE_PIECE, b - a - o), 0});
+        if (gcm) {
+            const uint32_t si = (uint32_t)(L.giv.size() / 16);
+            GcmEntry ge{pos, (uint32_t)(b - a), 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+            uint8_t iv[16];
+            gcm_segment(L.gmat[0], (uint32_t)k, k + 1 == K, ge, iv);
+            L.giv.insert(L.giv.end(), iv, iv + 16);
+            L.gkeys.push(si, L.gmat[0].key);
+            for (uint64_t o = 0; o < b - a; o += CTR_UNIT) L.cunits.push_back(CipherUnit{pos + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, b - a - o), si});
+            L.gents.push_back(ge);
+        } else if (fj->cipher)
+            for (uint64_t o = 0; o < b - a; o += CTR_UNIT) L.cunits.push_back(CipherUnit{pos + o, a + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, b - a - o), 0u});
+        const uint64_t pl = b - a + (gcm ? 16 : 0);
+        fds.push_back(FrameDesc{pos, (uint32_t)pl, 0u, 0u, 4u | (a == cs ? 0u : 8u)});
+        pos += pl;
+        parts.push_back(Part{pl, pos, b == ce});
+        if (b == ce) pos += 4;
+    }
+    if (pos + 16 > sb.dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
+    const size_t np = pieces.size(), nl = lits.size(), nf = fds.size();
+    if (c->fr_blob.ensure(blob.size() + 16) || c->st_lits.ensure(nl * sizeof(PlaceDescH) + 16) || c->st_pieces.ensure(np * sizeof(StorePiece) + 16) ||
+        c->fr_desc.ensure(nf * sizeof(FrameDesc) + 16) || c->st_states.ensure(nf * 4 + 16) || c->st_chunks.ensure(nf * sizeof(CrcPatchH) + 16))
+        return fail(c, PNA_E_NOMEM, "stored workspace");
+    int rc = ensure_crc(c); if (rc) return rc;
+    if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    if (nl) HIPCHK(c, hipMemcpyAsync(c->st_lits.p, lits.data(), nl * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
+    if (np) HIPCHK(c, hipMemcpyAsync(c->st_pieces.p, pieces.data(), np * sizeof(StorePiece), hipMemcpyHostToDevice, st));
+    if (nf) HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, fds.data(), nf * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+    launch_gather(c->st_lits.p, (uint32_t)nl, (const uint8_t *)c->fr_blob.p, sb.d_dst, st);
+    launch_store(c->st_pieces.p, (uint32_t)np, sb.d_src, sb.d_dst, (const CrcTabs *)c->crc_tabs.p, nullptr, false, st);
+    if (fj->cipher) { rc = cipher_stage(sb, L); if (rc) return rc; }
+    std::vector<uint32_t> states(nf);
+    launch_frame_pieces((const FrameDesc *)c->fr_desc.p, (uint32_t)nf, (const CrcTabs *)c->crc_tabs.p, sb.d_dst, (uint64_t)sb.dst_cap & ~(uint64_t)15, "SDAT", (uint32_t *)c->st_states.p, st);
+    HIPCHK(c, hipGetLastError());
+    if (nf) HIPCHK(c, hipMemcpyAsync(states.data(), c->st_states.p, nf * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    std::vector<CrcPatchH> patches;
+    for (size_t q = 0; q < nf; q++) {                        // (only the window's first part can continue a chunk, only its last can leave one open)
+        sr->state = sr->started ? (crc_gf2_mulmod(crc_gf2_xpow(8 * parts[q].len), sr->state) ^ states[q]) : states[q];
+        sr->started = !parts[q].ends;
+        if (parts[q].ends) patches.push_back(CrcPatchH{(int64_t)parts[q].crc_at, ~sr->state, 15u});
+    }
+    if (!patches.empty()) {
+        HIPCHK(c, hipMemcpyAsync(c->st_chunks.p, patches.data(), patches.size() * sizeof(CrcPatchH), hipMemcpyHostToDevice, st));
+        launch_crc_patch(c->st_chunks.p, (uint32_t)patches.size(), sb.d_dst, st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    sr->pos = w1;
+    sb.dst_off[sb.e1] = pos;
+    c->st_copy_only += np;
+    return PNA_OK;
+}
+static int store_subbatch(const SubBatch &sb) {
+    pna_gpu_ctx *c = sb.c; const FrameJob *fj = sb.fj; const hipStream_t st = sb.st; const size_t e0 = sb.e0, e1 = sb.e1;
+    if (fj && fj->solid && fj->srun) return store_solid_window(sb);
+    if (!fj || fj->solid) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (!launch_store || !launch_store_fold) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    const EntryRecords *recs = fj->recs;
+    const uint64_t CH = chunk_limit(fj->max_chunk);
+    const int mode = fj->cipher ? fj->cipher->cipher_mode : -1;
+    const bool cbc = mode == PNA_MODE_CBC, gcm = mode == PNA_MODE_GCM, ctr = mode == PNA_MODE_CTR;
+    const uint64_t G = gcm ? gcm_seg_size(fj->cipher) : 0;
+    // the form of an unencrypted sub-batch (option store_unfused; -1: by its longest data chunk, as measured -- profiles/store_rate.txt): chunks of one piece
+    // (10 000 x 1 MiB) are faster through the copy-only form and k_frame, 8.6 against 12.2 ms; a chunk of several pieces must not be CRC'd by one workgroup
+    // (one entry of 4 GiB: 4.6 against 839 ms), and at 4 KiB the fused form is ahead again (27.9 against 28.4 ms).  Sizes between 4 KiB and 1 MiB were not measured.
+    uint64_t longest = 0;
+    if (!fj->cipher && c->tun.store_unfused < 0)
+        for (size_t e = e0; e < e1; e++) if (!(recs && recs->len(e))) longest = std::max<uint64_t>(longest, std::min<uint64_t>(sb.src_len[e], CH));
+    const bool fused = !fj->cipher && (c->tun.store_unfused < 0 ? (longest > STORE_PIECE || longest <= 4096) : c->tun.store_unfused == 0);
+    GcmCallKeys gkeys{};
+    if (gcm) gkeys = gcm_call_keys(fj->cipher->key, fj->cipher->phsf, strlen(fj->cipher->phsf));
+    std::vector<uint8_t> blob, tmp;                          // the framing bytes; lits: where they go (src_off: in the blob)
+    std::vector<PlaceDescH> lits;
+    std::vector<StorePiece> pieces; std::vector<StoreChunk> chunks; std::vector<FrameDesc> units;
+    SubLayout L; GcmMaterial gm;
+    uint64_t pos = sb.out_base;
+    uint8_t fend[12] = {0, 0, 0, 0, 'F', 'E', 'N', 'D', 0, 0, 0, 0};
+    put_be32(fend + 8, frame_fend_crc());
+    auto lit = [&](const uint8_t *p, size_t n) {             // n framing bytes at `pos` (in pieces that fit a descriptor's 32-bit length)
+        for (size_t o = 0; o < n; o += 0x40000000u) lits.push_back(PlaceDescH{blob.size() + o, pos + o, (uint32_t)std::min<size_t>(0x40000000u, n - o), 0});
+        blob.insert(blob.end(), p, p + n); pos += n;
+    };
+    auto payload = [&](uint64_t src, uint64_t dst, uint64_t n) { for (uint64_t o = 0; o < n; o += STORE_PIECE) pieces.push_back(StorePiece{src + o, dst + o, (uint32_t)std::min<uint64_t>(STORE_PIECE, n - o), 0}); };
+    for (size_t e = e0; e < e1; e++) {
+        sb.dst_off[e] = pos;
+        if (recs && recs->len(e)) { lit(recs->at(e), (size_t)recs->len(e)); continue; }
+        const uint64_t len = sb.src_len[e], so = sb.src_off[e];
+        tmp.clear();
+        if (gcm) { gcm_entry_material(fj->cipher, gkeys, fj->ivs + 39 * e, (uint32_t)G, fj->names[e], PNA_ALGO_STORE, gm);
+                   frame_entry_prefix_enc(tmp, fj->names[e], PNA_ALGO_STORE, len, fj->cipher->encryption, PNA_MODE_GCM, fj->cipher->phsf, gm.header, 75); }
+        else if (fj->cipher) frame_entry_prefix_enc(tmp, fj->names[e], PNA_ALGO_STORE, len, fj->cipher->encryption, mode, fj->cipher->phsf, fj->ivs + 16 * e, 16);
+        else frame_entry_prefix(tmp, fj->names[e], PNA_ALGO_STORE, len, 0);
+        splice_meta(tmp, fj->meta, e);                       // (tmp ends in the first payload chunk's length and type)
+        if (len == 0 && !cbc && !gcm) { tmp.resize(tmp.size() - 8); tmp.insert(tmp.end(), fend, fend + 12); lit(tmp.data(), tmp.size()); continue; }
+        const uint64_t KG = gcm ? (len ? (len + G - 1) / G : 1) : 0;
+        const uint64_t plen = cbc ? (len / 16 + 1) * 16 : gcm ? len + 16 * KG : len;      // what the cipher makes of the payload
+        if (cbc && plen > CH) return fail(c, PNA_E_UNSUPPORTED, "CBC entry beyond one FDAT chunk");
+        if (gcm && KG > 0xFFFFFFFFull) return fail(c, PNA_E_INVAL, "GCM segment counter overflow");
+        if (gcm && plen > CH) return fail(c, PNA_E_UNSUPPORTED, "GCM entry beyond one FDAT chunk");
+        const uint64_t K = (plen + CH - 1) / CH;
+        if (chunks.size() + units.size() + K > 0x7FFFFFF0ull || pieces.size() + plen / STORE_PIECE + K > 0x7FFFFFF0ull) return fail(c, PNA_E_INVAL, "too many data chunks");
+        for (uint64_t k = 0; k < K; k++) {
+            const uint64_t cl = std::min<uint64_t>(CH, plen - k * CH);
+            if (k == 0) { put_be32(tmp.data() + tmp.size() - 8, (uint32_t)cl); lit(tmp.data(), tmp.size()); }
+            else { uint8_t h[8]; put_be32(h, (uint32_t)cl); memcpy(h + 4, "FDAT", 4); lit(h, 8); }
+            if (blob.size() > 0xFFFFFF00ull) return fail(c, PNA_E_INVAL, "the framing bytes of a sub-batch exceed 4 GiB");      // (FrameDesc::prefix_off; before the descriptor below takes the offset)
+            const uint64_t cstart = pos;                     // the chunk's data in the archive
+            if (fused) chunks.push_back(StoreChunk{cstart + cl, cl, (uint32_t)pieces.size(), (uint32_t)((cl + STORE_PIECE - 1) / STORE_PIECE), k + 1 == K ? 1u : 0u, 0});
+            else units.push_back(FrameDesc{cstart - 8, (uint32_t)cl, (uint32_t)(blob.size() - 8), 8u, k + 1 < K ? 2u : 0u});      // (k_frame puts the header down once more: the same bytes)
+            if (gcm) {
+                for (uint64_t q = 0; q < KG; q++) {          // segment q at cstart + q (G + 16), its tag behind it; the last one carries the final flag
+                    const uint64_t sl = std::min<uint64_t>(G, len - q * G), at = cstart + q * (G + 16);
+                    const uint32_t si = (uint32_t)(L.giv.size() / 16);
+                    GcmEntry ge{at, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+                    uint8_t iv[16];
+                    gcm_segment(gm, (uint32_t)q, q + 1 == KG, ge, iv);
+                    L.giv.insert(L.giv.end(), iv, iv + 16);
+                    L.gkeys.push(si, gm.key);
+                    for (uint64_t o = 0; o < sl; o += CTR_UNIT) L.cunits.push_back(CipherUnit{at + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
+                    L.gents.push_back(ge);
+                    payload(so + q * G, at, sl);
+                }
+            } else if (cbc) { L.cunits.push_back(CipherUnit{cstart, 0, (uint32_t)len, (uint32_t)(e - e0)}); payload(so, cstart, len); }
+            else {
+                payload(so + k * CH, cstart, cl);
+                if (ctr) for (uint64_t o = 0; o < cl; o += CTR_UNIT) L.cunits.push_back(CipherUnit{cstart + o, k * CH + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, cl - o), (uint32_t)(e - e0)});
+            }
+            pos += cl + 4;
+        }
+        pos += 12;                                           // FEND
+        if (blob.size() > 0xFFFFFF00ull) return fail(c, PNA_E_INVAL, "the framing bytes of a sub-batch exceed 4 GiB");      // (FrameDesc::prefix_off)
+    }
+    sb.dst_off[e1] = pos;
+    // the destination holds the sub-batch: nothing has been launched yet.  (k_frame reads whole 16-byte words below the capacity: the cipher forms keep the
+    // compressed paths' 16 bytes of room; the fused form touches its own bytes only and takes a destination of exactly the archive's size)
+    if (pos + (fused ? 0 : 16) > sb.dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
+    const size_t np = pieces.size(), nl = lits.size(), nc = chunks.size(), nu = units.size();
+    if (c->fr_blob.ensure(blob.size() + 16) || c->st_lits.ensure(nl * sizeof(PlaceDescH) + 16) || c->st_pieces.ensure(np * sizeof(StorePiece) + 16) ||
+        c->st_chunks.ensure(nc * sizeof(StoreChunk) + 16) || c->st_states.ensure(np * 4 + 16) || c->fr_desc.ensure(nu * sizeof(FrameDesc) + 16))
+        return fail(c, PNA_E_NOMEM, "stored workspace");
+    int rc = ensure_crc(c); if (rc) return rc;
+    for (auto &ev : c->st_ev) if (!ev) HIPCHK(c, hipEventCreate(&ev));
+    if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    if (nl) HIPCHK(c, hipMemcpyAsync(c->st_lits.p, lits.data(), nl * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
+    if (np) HIPCHK(c, hipMemcpyAsync(c->st_pieces.p, pieces.data(), np * sizeof(StorePiece), hipMemcpyHostToDevice, st));
+    if (nc) HIPCHK(c, hipMemcpyAsync(c->st_chunks.p, chunks.data(), nc * sizeof(StoreChunk), hipMemcpyHostToDevice, st));
+    if (nu) HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, units.data(), nu * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+    launch_gather(c->st_lits.p, (uint32_t)nl, (const uint8_t *)c->fr_blob.p, sb.d_dst, st);
+    HIPCHK(c, hipEventRecord(c->st_ev[0], st));
+    launch_store(c->st_pieces.p, (uint32_t)np, sb.d_src, sb.d_dst, (const CrcTabs *)c->crc_tabs.p, (uint32_t *)c->st_states.p, fused, st);
+    HIPCHK(c, hipEventRecord(c->st_ev[1], st));
+    if (fused) launch_store_fold(c->st_chunks.p, (uint32_t)nc, (const uint32_t *)c->st_states.p, c->st_pieces.p, "FDAT", frame_fend_crc(), sb.d_dst, st);
+    else {
+        if (fj->cipher) { rc = cipher_stage(sb, L); if (rc) return rc; }      // (no unit at all -- every entry empty -- is fine: GCM still writes its tags)
+        launch_frame((const FrameDesc *)c->fr_desc.p, (uint32_t)nu, (const uint8_t *)c->fr_blob.p, (const CrcTabs *)c->crc_tabs.p, sb.d_dst,
+                     (uint64_t)sb.dst_cap & ~(uint64_t)15, frame_fend_crc(), "FDAT", true, st, 0);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));                      // (the staging vectors are read by the copies; the caller's next sub-batch reuses the workspace)
+    float ms = 0; (void)hipEventElapsedTime(&ms, c->st_ev[0], c->st_ev[1]);
+    c->st_ms += ms; (fused ? c->st_fused : c->st_copy_only) += np; c->st_folded += nc;
+    return PNA_OK;
+}
+extern "C" int pna_gpu_debug_store_stats(pna_gpu_ctx *c, uint64_t *pieces_fused, uint64_t *pieces_copy_only, uint64_t *chunks_folded, double *ms_k_store) {
+    if (!c) return PNA_E_INVAL;
+    if (pieces_fused) *pieces_fused = c->st_fused;
+    if (pieces_copy_only) *pieces_copy_only = c->st_copy_only;
+    if (chunks_folded) *chunks_folded = c->st_folded;
+    if (ms_k_store) *ms_k_store = c->st_ms;
+    return PNA_OK;
+}
 // One sub-batch: entries [e0, e1) -> segments -> kernels; output appended at d_dst + out_base.
 int run_subbatch(pna_gpu_ctx *c, int algo, const uint8_t *d_src, const uint64_t *src_off, const uint64_t *src_len,
                  size_t e0, size_t e1, uint8_t *d_dst, size_t dst_cap, uint64_t out_base, uint64_t *dst_off,
                  hipStream_t st, bool timed, const FrameJob *fj) {
     const SubBatch sb{c, algo, d_src, src_off, src_len, e0, e1, d_dst, dst_cap, out_base, dst_off, st, timed, fj};
     HostMarks hm{c->tun.trace != 0};
+    if (algo == PNA_ALGO_STORE) return store_subbatch(sb);      // no codec: no plan, no LZ stage, no entropy stage
     SubPlan p;
     int rc = plan_subbatch(sb, hm, p);
     if (rc == PNA_OK && p.nseg == 0 && fj && fj->recs) return records_subbatch(sb);
@@ -1106,7 +1322,7 @@ int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, co
     EntryRecords recs;                                          // the tree form: the records of the entries that are not files
     { int rck = build_entry_records(c, n, names, src_len, kinds, meta, max_chunk, recs); if (rck) return rck; }
     if (!d_src && recs.count < n) return fail(c, PNA_E_INVAL, "null argument");
-    if (!encode_algo_ok(c, algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (!encode_algo_ok(c, algo, true)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     if ((uintptr_t)d_dst & 15) return fail(c, PNA_E_INVAL, "archive buffer must be 16-byte aligned");
     if (cipher && cipher->encryption == PNA_ENC_NONE) cipher = nullptr;
     const auto t_call0 = std::chrono::steady_clock::now();
@@ -1118,6 +1334,7 @@ int create_archive_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, co
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     c->timing = pna_gpu_timing{};
+    c->st_fused = c->st_copy_only = c->st_folded = 0; c->st_ms = 0;
     std::vector<uint8_t> head, tail;
     if (part_flags & PNA_PART_HEAD) frame_archive_head(head, 0);
     if (part_flags & PNA_PART_TAIL) frame_archive_tail(tail);
@@ -1210,7 +1427,9 @@ extern "C" size_t pna_gpu_solid_archive_tree_bound(int algo, size_t n, const cha
                                                    const pna_gpu_entry_meta *meta, uint32_t max_chunk_size, const pna_gpu_entry_kinds *kinds) {
     uint64_t plain = solid_plain_bound(n, names, src_len) + tree_bound_terms(n, meta, max_chunk_size, kinds);
     if (max_chunk_size) for (size_t i = 0; i < n; i++) plain += 12 * (src_len[i] / chunk_limit(max_chunk_size) + 1);      // a file's further FDAT chunks
-    return solid_enc_bound_of(solid_bound_of(algo, plain), cipher);
+    size_t b = solid_bound_of(algo, plain);
+    if (algo == PNA_ALGO_STORE) b += 12 * (size_t)(plain / chunk_limit(max_chunk_size) + 1);      // the stored stream itself is cut into SDAT chunks of max_chunk_size bytes
+    return solid_enc_bound_of(b, cipher);
 }
 extern "C" int pna_gpu_create_archive_tree_device(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                   const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
@@ -1249,6 +1468,123 @@ extern "C" int pna_gpu_create_solid_archive_enc_device(pna_gpu_ctx *c, int algo,
                                                        void *hip_stream) {
     return create_solid_device_impl(c, algo, level, n, names, d_src, src_off, src_len, cipher, nullptr, 0, nullptr, d_dst, dst_cap, archive_len, hip_stream);
 }
+// The stored solid stream (SHED compression 0): the serialised inner records ARE the stream, so nothing is compressed and nothing is copied twice -- the
+// framing bytes go from one blob to their places in the destination's SDAT bodies (k_gather), k_store puts every inner payload at its place there and
+// leaves its pieces' CRC registers, k_store_fold writes the inner FDAT CRCs and FEND.  The stream is cut into SDAT chunks of chunk_limit(max_chunk) bytes
+// (the default: one chunk up to 2^32 - 5 bytes); stream position p stands at base + p + 12 (p / SCH), and a cut may fall anywhere -- into a payload (its
+// pieces end there: the chunk folds by the piece list's lengths) or into a CRC field (the fold maps every byte).  With a cipher the stream is encrypted
+// where it stands -- CTR: one keystream over the SDAT bodies; GCM STREAM: one SDAT chunk per segment, its tag behind it (28 bytes between two segments) --,
+// and the SDAT CRCs are k_frame's over what stands there then.  For a stream of one chunk without a cipher the bytes are pna_create_archive's.
+static int create_solid_store(pna_gpu_ctx *c, size_t n, const char *const *names, const void *d_src, const uint64_t *src_off, const uint64_t *src_len,
+                              const pna_gpu_cipher *cipher, const uint8_t *ivs, const pna_gpu_entry_meta *meta, uint32_t max_chunk, const EntryRecords &recs,
+                              void *d_dst, size_t dst_cap, uint64_t *archive_len, hipStream_t st) {
+    const bool gcm = cipher && cipher->cipher_mode == PNA_MODE_GCM;
+    const uint64_t G = gcm ? gcm_seg_size(cipher) : 0, CHI = chunk_limit(max_chunk);
+    const uint64_t SCH = gcm ? G : chunk_limit(max_chunk), OVH = gcm ? 28 : 12;     // data bytes of an SDAT chunk, what stands between two chunks' data
+    std::vector<uint8_t> head, tail, blob, tmp;
+    solid_archive_head(head, PNA_ALGO_STORE, cipher, ivs);
+    frame_solid_tail(tail); frame_archive_tail(tail);
+    const uint64_t base = head.size() + 8;
+    auto at = [&](uint64_t p) { return base + p + OVH * (p / SCH); };
+    std::vector<PlaceDescH> lits; std::vector<StorePiece> pieces; std::vector<StoreChunk> chunks; std::vector<FrameDesc> units;
+    uint64_t pos = 0;
+    uint8_t fend[12] = {0, 0, 0, 0, 'F', 'E', 'N', 'D', 0, 0, 0, 0};
+    put_be32(fend + 8, frame_fend_crc());
+    auto lit = [&](const uint8_t *p, size_t nb) {            // framing bytes of the stream, cut where an SDAT chunk ends
+        const size_t b0 = blob.size();
+        blob.insert(blob.end(), p, p + nb);
+        for (size_t o = 0; o < nb;) {
+            const size_t k = (size_t)std::min<uint64_t>(std::min<uint64_t>(nb - o, SCH - pos % SCH), 0x40000000u);
+            lits.push_back(PlaceDescH{b0 + o, at(pos), (uint32_t)k, 0}); pos += k; o += k;
+        }
+    };
+    for (size_t i = 0; i < n; i++) {
+        if (recs.count && recs.len(i)) { lit(recs.at(i), (size_t)recs.len(i)); continue; }
+        const uint64_t len = src_len[i];
+        tmp.clear();
+        if (len == 0) { frame_inner_entry_empty(tmp, names[i]); splice_meta(tmp, meta, i); lit(tmp.data(), tmp.size()); continue; }
+        for (uint64_t o = 0; o < len; o += CHI) {
+            const uint64_t cl = std::min<uint64_t>(CHI, len - o);
+            const bool last = o + cl == len;
+            if (o == 0) { frame_entry_prefix(tmp, names[i], PNA_ALGO_STORE, len, (uint32_t)cl); splice_meta(tmp, meta, i); lit(tmp.data(), tmp.size()); }
+            else { uint8_t h[8]; put_be32(h, (uint32_t)cl); memcpy(h + 4, "FDAT", 4); lit(h, 8); }
+            if (pieces.size() + cl / STORE_PIECE + 2 > 0x7FFFFFF0ull || chunks.size() > 0x7FFFFFF0ull) return fail(c, PNA_E_INVAL, "too many data chunks");
+            StoreChunk ch{0, cl, (uint32_t)pieces.size(), 0, last ? 1u : 0u, 0};
+            bool regular = true;
+            for (uint64_t q = 0; q < cl;) {
+                const uint64_t k = std::min<uint64_t>(std::min<uint64_t>(cl - q, STORE_PIECE), SCH - pos % SCH);
+                if (k != STORE_PIECE && q + k != cl) regular = false;      // an SDAT cut inside the chunk
+                pieces.push_back(StorePiece{src_off[i] + o + q, at(pos), (uint32_t)k, 0}); pos += k; q += k;
+            }
+            ch.npieces = (uint32_t)pieces.size() - ch.first; ch.crc_off = pos; if (!regular) ch.flags |= 2u;
+            chunks.push_back(ch);
+            pos += last ? 16 : 4;                            // the CRC [and FEND]: k_store_fold's bytes
+        }
+    }
+    const uint64_t plain_len = pos;
+    const uint64_t K = gcm ? (plain_len ? (plain_len + G - 1) / G : 1) : (plain_len + SCH - 1) / SCH;
+    if (K > 0x7FFFFFF0ull) return fail(c, PNA_E_INVAL, gcm ? "GCM segment counter overflow" : "too many data chunks");
+    SubLayout L;
+    if (gcm) { L.gmat.resize(1); gcm_solid_material(cipher, ivs, PNA_ALGO_STORE, L.gmat[0]); }
+    for (uint64_t k = 0; k < K; k++) {                       // the SDAT chunks: header, cipher units, k_frame's descriptor
+        const uint64_t sl = std::min<uint64_t>(SCH, plain_len - k * SCH), hdr = base - 8 + k * (SCH + OVH), dl = sl + (gcm ? 16 : 0);
+        uint8_t h[8]; put_be32(h, (uint32_t)dl); memcpy(h + 4, "SDAT", 4);
+        lits.push_back(PlaceDescH{blob.size(), hdr, 8u, 0});
+        units.push_back(FrameDesc{hdr, (uint32_t)dl, (uint32_t)blob.size(), 8u, 0});
+        blob.insert(blob.end(), h, h + 8);
+        if (gcm) {
+            const uint32_t si = (uint32_t)(L.giv.size() / 16);
+            GcmEntry ge{hdr + 8, (uint32_t)sl, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+            uint8_t iv[16];
+            gcm_segment(L.gmat[0], (uint32_t)k, k + 1 == K, ge, iv);
+            L.giv.insert(L.giv.end(), iv, iv + 16);
+            L.gkeys.push(si, L.gmat[0].key);
+            for (uint64_t o = 0; o < sl; o += CTR_UNIT) L.cunits.push_back(CipherUnit{hdr + 8 + o, o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), si});
+            L.gents.push_back(ge);
+        } else if (cipher)
+            for (uint64_t o = 0; o < sl; o += CTR_UNIT) L.cunits.push_back(CipherUnit{hdr + 8 + o, k * SCH + o, (uint32_t)std::min<uint64_t>(CTR_UNIT, sl - o), 0u});
+    }
+    if (blob.size() > 0xFFFFFF00ull) return fail(c, PNA_E_INVAL, "the inner entries' framing exceeds 4 GiB");
+    const uint64_t end = head.size() + plain_len + OVH * K;
+    if (end + tail.size() + 16 > dst_cap) return fail(c, PNA_E_DSTSIZE, "device destination too small");
+    const size_t np = pieces.size(), nl = lits.size(), nc = chunks.size(), nu = units.size();
+    if (c->fr_blob.ensure(blob.size() + 16) || c->st_lits.ensure(nl * sizeof(PlaceDescH) + 16) || c->st_pieces.ensure(np * sizeof(StorePiece) + 16) ||
+        c->st_chunks.ensure(nc * sizeof(StoreChunk) + 16) || c->st_states.ensure(np * 4 + 16) || c->fr_desc.ensure(nu * sizeof(FrameDesc) + 16))
+        return fail(c, PNA_E_NOMEM, "stored workspace");
+    int rc = ensure_crc(c); if (rc) return rc;
+    for (auto &ev : c->st_ev) if (!ev) HIPCHK(c, hipEventCreate(&ev));
+    uint8_t *dst = (uint8_t *)d_dst;
+    c->timing = pna_gpu_timing{};
+    c->st_fused = c->st_copy_only = c->st_folded = 0; c->st_ms = 0;
+    HIPCHK(c, hipMemcpyAsync(dst, head.data(), head.size(), hipMemcpyHostToDevice, st));
+    if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(c->fr_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    if (nl) HIPCHK(c, hipMemcpyAsync(c->st_lits.p, lits.data(), nl * sizeof(PlaceDescH), hipMemcpyHostToDevice, st));
+    if (np) HIPCHK(c, hipMemcpyAsync(c->st_pieces.p, pieces.data(), np * sizeof(StorePiece), hipMemcpyHostToDevice, st));
+    if (nc) HIPCHK(c, hipMemcpyAsync(c->st_chunks.p, chunks.data(), nc * sizeof(StoreChunk), hipMemcpyHostToDevice, st));
+    if (nu) HIPCHK(c, hipMemcpyAsync(c->fr_desc.p, units.data(), nu * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
+    launch_gather(c->st_lits.p, (uint32_t)nl, (const uint8_t *)c->fr_blob.p, dst, st);
+    HIPCHK(c, hipEventRecord(c->st_ev[0], st));
+    launch_store(c->st_pieces.p, (uint32_t)np, (const uint8_t *)d_src, dst, (const CrcTabs *)c->crc_tabs.p, (uint32_t *)c->st_states.p, true, st);
+    HIPCHK(c, hipEventRecord(c->st_ev[1], st));
+    launch_store_fold(c->st_chunks.p, (uint32_t)nc, (const uint32_t *)c->st_states.p, c->st_pieces.p, "FDAT", frame_fend_crc(), dst, st, base, SCH, OVH);
+    if (cipher) {
+        const uint64_t zero = 0; uint64_t offs[2] = {0, 0};
+        const FrameJob fj{nullptr, 1, cipher, ivs};
+        const SubBatch sb{c, PNA_ALGO_STORE, (const uint8_t *)d_src, &zero, &plain_len, 0, 1, dst, dst_cap, head.size(), offs, st, false, &fj};
+        rc = cipher_stage(sb, L); if (rc) return rc;
+    }
+    launch_frame((const FrameDesc *)c->fr_desc.p, (uint32_t)nu, (const uint8_t *)c->fr_blob.p, (const CrcTabs *)c->crc_tabs.p, dst,
+                 (uint64_t)(dst_cap - tail.size()) & ~(uint64_t)15, frame_fend_crc(), "SDAT", false, st, 0);
+    HIPCHK(c, hipMemcpyAsync(dst + end, tail.data(), tail.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0; (void)hipEventElapsedTime(&ms, c->st_ev[0], c->st_ev[1]);
+    c->st_ms = ms; c->st_fused = np; c->st_folded = nc;
+    *archive_len = end + tail.size();
+    uint64_t in_total = 0; for (size_t i = 0; i < n; i++) in_total += src_len[i];
+    c->timing.in_bytes = in_total; c->timing.out_bytes = *archive_len;
+    return PNA_OK;
+}
 // (the tree form: inner entries that are not files are finished records between the file records -- blob spans, "without a data chunk" for k_frame --, files carry
 // their metadata chunks and are cut into FDAT chunks of max_chunk bytes: every inner entry of a solid stream is a stored record)
 int create_solid_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
@@ -1265,11 +1601,16 @@ int create_solid_device_impl(pna_gpu_ctx *c, int algo, int level, size_t n, cons
     EntryRecords recs;
     { int rck = build_entry_records(c, n, names, src_len, kinds, meta, max_chunk, recs); if (rck) return rck; }
     if (!d_src && recs.count < n) return fail(c, PNA_E_INVAL, "null argument");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
+    const bool stored = algo == PNA_ALGO_STORE && launch_store && launch_store_fold;
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !stored) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
     if ((uintptr_t)d_dst & 15) return fail(c, PNA_E_INVAL, "archive buffer must be 16-byte aligned");
     set_call_level(c, algo, level);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (stored) {
+        for (size_t i = 0; i < n; i++) if (!(recs.count && recs.len(i)) && (src_off[i] & 15)) return fail(c, PNA_E_INVAL, "entry offset not 16-byte aligned");
+        return create_solid_store(c, n, names, d_src, src_off, src_len, cipher, ivs, meta, max_chunk, recs, d_dst, dst_cap, archive_len, st);
+    }
     // ---- 1. layout of the serialised inner entries (all sizes are known up front)
     std::vector<FrameDesc> fds; std::vector<uint8_t> blob, tmp; std::vector<PlaceDescH> places;
     fds.reserve(n);

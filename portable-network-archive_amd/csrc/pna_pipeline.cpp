@@ -31,6 +31,7 @@ struct SolidWin { std::vector<FrameDesc> pieces; std::vector<uint32_t> piece_chu
 struct SolidRun {
     pna_gpu_ctx *c; int algo; const pna_gpu_cipher *cipher; const uint8_t *ivs; pna_sink_fn sink; void *user;
     SolidLayout L; SolidCipherRun crun;
+    uint32_t max_chunk = 0; SolidStoreRun srun;                                               // PNA_ALGO_STORE: the stream's SDAT cut, the window's place and the open chunk's CRC register
     uint64_t W = 0, nwin = 0, wcap_in = 0, wcap_out = 0, slot_in = 0, slot_out = 0;          // window bytes, windows, a window's room each way, the device slots' stride
     uint8_t *d_in(uint64_t k) const { return (uint8_t *)c->stage_in.p + (k & 1) * slot_in; }
     uint8_t *d_out(uint64_t k) const { return (uint8_t *)c->stage_out.p + (k & 1) * slot_out; }
@@ -119,10 +120,13 @@ static int solid_sizes(SolidRun &r) {
     const bool gcm = r.cipher && r.cipher->cipher_mode == PNA_MODE_GCM;
     const uint64_t G = gcm ? gcm_seg_size(r.cipher) : 0, plain_len = r.L.plain_len;
     r.W = std::max<uint64_t>(1, (uint64_t)c->tun.solid_win_mib) << 20;                        // a multiple of SEG_SIZE
+    const bool stored = r.algo == PNA_ALGO_STORE;
+    if (stored && gcm) r.W = std::max<uint64_t>(G, r.W - r.W % G);                            // stored GCM STREAM: windows of whole segments (the stream's length is known: no carry)
     r.nwin = (plain_len + r.W - 1) / r.W;
     r.wcap_in = std::min<uint64_t>(r.W, plain_len) + 8192;
     r.wcap_out = pna_gpu_bound(r.algo, (size_t)std::min<uint64_t>(r.W, plain_len)) + (std::min<uint64_t>(r.W, plain_len) / SEG_SIZE + 2) * 16 + 4096;
     if (gcm) r.wcap_out += G + 28 * ((r.wcap_out + G) / G + 2);    // GCM: the carry in front, a tag and SDAT framing per segment
+    if (stored && !gcm) r.wcap_out += 12 * (std::min<uint64_t>(r.W, plain_len) / chunk_limit(r.max_chunk) + 2);   // stored: SDAT framing per max_chunk bytes of the window
     int rc = ensure_crc(c); if (rc) return rc;
     r.slot_in = (r.wcap_in + 255) & ~(uint64_t)255; r.slot_out = (r.wcap_out + 255) & ~(uint64_t)255;   // the two device slots each way
     rc = Reserve{c}.add(c->stage_in, 2 * r.slot_in + 64).add(c->stage_out, 2 * r.slot_out + 64).add(c->hp_in, 2, r.wcap_in).add(c->hp_out, 2, r.wcap_out).done();
@@ -185,6 +189,7 @@ static int solid_window_compress(SolidRun &r, uint64_t k, const SolidWin &w, Sol
     FrameJob fj{nullptr, 1, r.cipher, r.ivs};
     fj.stream_len = r.L.plain_len;
     if (r.cipher) { r.crun.final_win = k + 1 == r.nwin; fj.crun = &r.crun; }
+    if (r.algo == PNA_ALGO_STORE) { fj.max_chunk = r.max_chunk; fj.srun = &r.srun; }
     if (r.algo == PNA_ALGO_DEFLATE) { fj.run = (k > 0 ? DRUN_CONT : 0u) | (k + 1 < r.nwin ? DRUN_OPEN : 0u); fj.adler_carry = (uint32_t *)c->solid_adler.p; }
     int rc = run_subbatch(c, r.algo, r.d_in(k), &off0, &len0, 0, 1, r.d_out(k), r.wcap_out, 0, offs, st, false, &fj);
     if (rc == PNA_OK && hipMemcpyAsync(c->hp_out[k & 1].p, r.d_out(k), offs[1], hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(c, PNA_E_HIP, "D2H copy failed");
@@ -199,6 +204,8 @@ static int solid_stream(pna_gpu_ctx *c, int algo, int level, size_t n, const cha
     set_call_level(c, algo, level);
     SolidRun r{c, algo, cipher, ivs, sink, user, solid_layout(n, names, src_len, tree.recs, tree.meta, tree.max_chunk), {}};
     if (r.L.chunks.size() > 0x7FFFFFF0u) return fail(c, PNA_E_INVAL, "too many data chunks");
+    r.max_chunk = tree.max_chunk;
+    c->st_fused = c->st_copy_only = c->st_folded = 0; c->st_ms = 0;
     // the fixed chunks around the stream (GCM: the stream header is the stream's first SDAT chunk, as in the device form)
     std::vector<uint8_t> head, tail;
     solid_archive_head(head, algo, cipher, ivs);
@@ -254,8 +261,10 @@ static int solid_one_shot(pna_gpu_ctx *c, int algo, int level, size_t n, const c
         rc = sink_put(c, sink, user, (const uint8_t *)c->hp_out[0].p + p, (size_t)std::min<uint64_t>(16u << 20, total - p));
     return rc;
 }
+// PNA_ALGO_STORE on the solid host forms: the stored stream travels in windows like the compressed ones (store_solid_window, pna_host.cpp); no entries: the one-shot form
+static bool solid_store_ok(int algo) { return algo == PNA_ALGO_STORE && launch_store && launch_store_fold; }
 static bool solid_windowed(const pna_gpu_ctx *c, int algo, size_t n) {
-    return n && c->tun.solid_win_mib > 0 && (algo == PNA_ALGO_DEFLATE || (algo == PNA_ALGO_ZSTD && !c->tun.single_frame));
+    return n && c->tun.solid_win_mib > 0 && (algo == PNA_ALGO_DEFLATE || solid_store_ok(algo) || (algo == PNA_ALGO_ZSTD && !c->tun.single_frame));
 }
 extern "C" int pna_gpu_create_solid_archive_host(pna_gpu_ctx *c, int algo, int level, size_t n, const char *const *names,
                                                  const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
@@ -277,7 +286,7 @@ extern "C" int pna_gpu_create_solid_archive_enc_host(pna_gpu_ctx *c, int algo, i
     const uint8_t *ivs = nullptr;
     int rc = resolve_ivs(c, cipher, 1, own_ivs, &ivs); if (rc) return rc;
     if (cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !solid_store_ok(algo)) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
     HIPCHK(c, hipSetDevice(c->device));
     pna_gpu_cipher ci = *cipher; ci.ivs = ivs;                  // (IVs drawn here: the one-shot form must not draw others)
     if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, &ci, ivs, sink, user);
@@ -302,7 +311,7 @@ extern "C" int pna_gpu_create_solid_archive_tree_host(pna_gpu_ctx *c, int algo, 
         if (cipher->cipher_mode == PNA_MODE_CBC) return fail(c, PNA_E_UNSUPPORTED, "solid archives: CTR and GCM on the device path (CBC encryption is one serial chain over the whole stream)");
         ci = *cipher; ci.ivs = ivs; cipher = &ci;               // (IVs drawn here: the one-shot form must not draw others)
     }
-    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
+    if (algo != PNA_ALGO_ZSTD && algo != PNA_ALGO_DEFLATE && !solid_store_ok(algo)) return fail(c, PNA_E_UNSUPPORTED, algo == PNA_ALGO_XZ ? "xz is written by the batch and the non-solid archive entry points only (option xz_encode)" : "algorithm not implemented on the device path");
     HIPCHK(c, hipSetDevice(c->device));
     const SolidTree tree{meta, max_chunk_size, kinds, recs.count ? &recs : nullptr};
     if (solid_windowed(c, algo, n)) return solid_stream(c, algo, level, n, names, src, src_len, cipher, ivs, sink, user, tree);
@@ -448,7 +457,7 @@ static int create_check(CreateCall &k, int level, std::vector<uint8_t> &own_ivs)
     { int rcm = check_meta(c, k.meta, k.n); if (rcm) return rcm; }
     if (!c || !k.sink || (k.n && (!k.names || !k.src || !k.src_len))) return fail(c, PNA_E_INVAL, "null argument");
     { int rck = build_entry_records(c, k.n, k.names, (const uint64_t *)k.src_len, k.kinds, k.meta, k.max_chunk, k.recs); if (rck) return rck; }
-    if (!encode_algo_ok(c, k.algo)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
+    if (!encode_algo_ok(c, k.algo, true)) return fail(c, PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");
     set_call_level(c, k.algo, level);
     if (k.cipher && k.cipher->encryption == PNA_ENC_NONE) k.cipher = nullptr;
     if (k.cipher) { int rc0 = resolve_ivs(c, k.cipher, k.n, own_ivs, &k.ivs); if (rc0) return rc0; }
@@ -593,6 +602,7 @@ static int create_archive_host_impl(pna_gpu_ctx *c, int algo, int level, size_t 
     std::vector<uint8_t> own_ivs;
     int rc = create_check(k, level, own_ivs); if (rc) return rc;
     c->timing = pna_gpu_timing{};
+    c->st_fused = c->st_copy_only = c->st_folded = 0; c->st_ms = 0;
     std::vector<uint8_t> head, tail;
     if (part_flags & PNA_PART_HEAD) frame_archive_head(head, 0);
     if (part_flags & PNA_PART_TAIL) frame_archive_tail(tail);
@@ -661,6 +671,7 @@ extern "C" int pna_gpu_create_archive_multi_host(pna_gpu_ctx *const *ctxs, size_
                                                  const void *const *src, const size_t *src_len, pna_sink_fn sink, void *user) {
     if (!ctxs || !n_ctx || !sink || (n && (!names || !src || !src_len))) return PNA_E_INVAL;
     for (size_t r = 0; r < n_ctx; r++) if (!ctxs[r]) return PNA_E_INVAL;
+    if (algo == PNA_ALGO_STORE) return fail(ctxs[0], PNA_E_UNSUPPORTED, "algorithm not implemented on the device path");   // (stored entries: the one-context entry points)
     if (n_ctx == 1) return pna_gpu_create_archive_host(ctxs[0], algo, level, n, names, src, src_len, sink, user);
     // contiguous ranges balanced by input bytes (shard.partition_entries)
     uint64_t total = 0; for (size_t i = 0; i < n; i++) total += src_len[i];
